@@ -1,9 +1,14 @@
 # coding=utf-8
 """Headline benchmark: trajectories/sec of the Multiverse forward on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run measures the headline workload only: set-up, W warm-up steps, K timed steps,
+the outputs of the last timed step written to DIR when --dump-outputs is given, one JSON
+line.  --full adds everything below (sub-workloads, host path, roofline, CPU baseline,
+fp32 reference).
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) bench.py starts the N ranks itself
 (torch.distributed.run on 127.0.0.1, a free port) and relays rank 0's JSON line.
@@ -17,7 +22,7 @@ inputs are resident in HBM when the timed region starts (`mv_upload_inputs` befo
 `mv_run_greedy_resident` inside).  Trajectories are independent, so N GPUs run N batch
 shards with no data-path collective ("scaling": "weak").
 
-Beside the headline the same run measures the other BASELINE configs, each as a
+With --full, beside the headline the same run measures the other BASELINE configs, each as a
 sub-object of the ONE JSON line with its own `value`, `ms_per_step`, `steps` and
 `roofline` (timed the same way: barrier + synchronize on both sides, max over ranks):
   greedy_b256     north_star's "batch 256" on one GPU (same forward, batch 256)
@@ -34,7 +39,7 @@ sub-object of the ONE JSON line with its own `value`, `ms_per_step`, `steps` and
                   compact feeds) next to the resident-input rate      [rank 0, N=1 only]
 (`--no-sub` skips them; `--workload beam|train` makes one of them the headline instead.)
 
-Extra objects on the line:
+Extra objects on the line (--full):
   roofline     -- dominant kernel (convlstm_step, >99 % of FLOPs): algorithmic FLOPs per
                   launch / average launch duration from hipEvents on the engine's stream,
                   against the dense MFMA peak of the arithmetic used.  The same sweep as a
@@ -212,9 +217,11 @@ LITERAL_GRIDS = dict(scene_h=72, scene_w=36, scene_grids=[(36, 18), (18, 9)])
 
 def measure(ctx, kind, batch, compute, steps, warmup, beam_size=20, graph=None,
             scene_conv_kernel=3, timed_seconds=None, fp32_ref=False, cpu_base=None,
-            cpu_batch=8, literal_grids=False):
+            cpu_batch=8, literal_grids=False, full=True, dump_dir=None):
   """One workload on this rank's GPU: build the engine, upload the batch, W untimed +
-  K timed steps between barriers, then one profiled step for the per-kernel roofline.
+  K timed steps between barriers, the outputs of the last timed step to `dump_dir` (if
+  given), then one profiled step for the per-kernel roofline (full) or for the gate-kernel
+  form that `dtype` names (f16x3).
   kind: greedy | beam | train.  steps None -> as many as fill `timed_seconds`."""
   from multiverse_amd import _lib, synth
   world, rank = ctx.world, ctx.rank
@@ -250,18 +257,19 @@ def measure(ctx, kind, batch, compute, steps, warmup, beam_size=20, graph=None,
     lib_allreduce = ctx.use_dist and parallel.init_engine_comm(eng)
 
   def one_step():
+    """-> the step's losses (training), else None (the outputs stay on the GPU)"""
     if not train:
       eng.run_resident(beam)
-      return
+      return None
     # Trainer.step on the resident batch: forward + loss + backward, all-reduce
     # (sum) of the flat gradient buffer over the ranks, clip + optimizer
     if lib_allreduce:
-      eng.train_step(None)       # buckets all-reduced during the backward pass, then 1/world
-      return
-    eng.train_forward_backward(None)
+      return eng.train_step(None)   # buckets all-reduced during the backward pass, then 1/world
+    losses = eng.train_forward_backward(None)
     if ctx.use_dist:
       parallel.allreduce_engine_grads(eng, ctx.local_rank)
     eng.train_apply(1.0 / world)
+    return losses
 
   for _ in range(warmup):
     one_step()
@@ -274,41 +282,251 @@ def measure(ctx, kind, batch, compute, steps, warmup, beam_size=20, graph=None,
     probe = ctx.max_over_ranks(time.perf_counter() - t0)
     steps = int(min(400, max(3, math.ceil((timed_seconds or SUB_TIMED_SECONDS) / probe))))
     ctx.barrier(eng)
+  last = None
   t0 = time.perf_counter()
   for _ in range(steps):
-    one_step()
+    last = one_step()
   eng.synchronize()
   ctx.barrier(eng)
   elapsed = ctx.max_over_ranks(time.perf_counter() - t0)
 
   ms_per_step = 1e3 * elapsed / steps
   value = world * batch * steps / elapsed
+  if dump_dir is not None:
+    dump_outputs(dump_dir, eng, kind, last, rank, world)
 
-  # ---- roofline of the dominant kernel, measured live with hipEvents
-  eng.set_profiling(True)
-  eng.reset_kernel_stats()
-  one_step()
-  eng.synchronize()
-  stats = eng.kernel_stats()
-  eng.set_profiling(False)
-  mfma_kernels = ["convlstm_step"] + (["convlstm_dgrad", "convlstm_wgrad"] if train else [])
-  if train and "convlstm_wgrad_x" in stats:      # f16x3: the x rows are a launch of their own
-    mfma_kernels.append("convlstm_wgrad_x")
-  conv = {k: sum(stats[n][k] for n in mfma_kernels)
-          for k in ("launches", "total_ms", "flops", "bytes", "flops_dense", "flops_mfma")}
-  conv_s = conv["total_ms"] * 1e-3
-  # achieved = algorithmic FLOPs the launches EXECUTED (zero-state steps skip the h half)
-  achieved_tf = conv["flops"] / conv_s / 1e12
+  f16 = compute == "f16x3"
+  bf16 = compute == "bf16"
   flops_traj, bytes_traj = algorithmic_counts(cfg, beam_size if beam else 1)
-  sparse_x = (not train and compute != "f32" and os.environ.get("MV_SPARSE_X", "1") != "0")
   flops_traj_exec, _ = algorithmic_counts(cfg, beam_size if beam else 1, executed=True,
-                                          sparse_x=sparse_x)
-  flops_traj_exec_dense_x, _ = algorithmic_counts(cfg, beam_size if beam else 1, executed=True)
+                                          sparse_x=(not train and compute != "f32" and
+                                                    os.environ.get("MV_SPARSE_X", "1") != "0"))
   if train:
     flops_traj *= 3.0   # forward + dgrad + wgrad of every gate convolution
     flops_traj_exec *= 3.0
+  roofline = None
+  f16_form = ""
+  if full or f16:
+    # one profiled step (hipEvents around every launch): the roofline of the dominant
+    # kernel (full) and, under f16x3, the gate-kernel form `dtype` names
+    eng.set_profiling(True)
+    eng.reset_kernel_stats()
+    one_step()
+    eng.synchronize()
+    stats = eng.kernel_stats()
+    eng.set_profiling(False)
+    mfma_kernels = ["convlstm_step"] + (["convlstm_dgrad", "convlstm_wgrad"] if train else [])
+    if train and "convlstm_wgrad_x" in stats:    # f16x3: the x rows are a launch of their own
+      mfma_kernels.append("convlstm_wgrad_x")
+    conv = {k: sum(stats[n][k] for n in mfma_kernels)
+            for k in ("launches", "total_ms", "flops", "bytes", "flops_dense", "flops_mfma")}
+    # the form the gate kernels of THESE launches ran in, from what the engine issued to the
+    # matrix pipe (3 fp16 MFMA products per fp32 product = direct 3x3; 2 = Winograd F(2,3)
+    # over rows; 1.67 = F(3,3) over rows; training mixes the forms of forward / dgrad / wgrad)
+    if f16:
+      step_pp = (stats["convlstm_step"]["flops_mfma"] / stats["convlstm_step"]["flops"]
+                 if stats["convlstm_step"]["flops"] else 3.0)
+      f16_form = "%s, %.2f fp16 MFMAs issued per fp32 product over the gate kernels" % (
+          gate_kernel_form(step_pp).split(" fp16 MFMA")[0].rsplit(",", 1)[0],
+          conv["flops_mfma"] / conv["flops"] if conv["flops"] else 3.0)
+  if full:
+    roofline = roofline_of(kind, compute, batch, beam_size, scene_conv_kernel, literal_grids,
+                           world, value, stats, mfma_kernels, conv, flops_traj_exec)
+
+  if beam:
+    metric = ("trajectories/sec (8-obs/12-pred, 18x32 grid, diverse beam-%d "
+              "multi-future decode)" % beam_size)
+    workload = ("BASELINE configs[3]: scale 0 (18x32, scene 36x64x11), beam %d "
+                "(diverse, gamma 0.01, fix_num_timestep 1), batch %d/GPU, fp32, "
+                "obs 8 / pred 12, %s" % (beam_size, batch,
+                                         "hipGraph replay" if graph else "stream launches"))
+  elif train:
+    metric = ("trajectories/sec (8-obs/12-pred, multi-scale 18x32+9x16 grid, "
+              "training step)")
+    workload = ("BASELINE configs[2]: multi-scale 18x32+9x16 (scene 36x64x11), "
+                "batch %d/GPU (global %d), fp32 training step = forward + CE/Huber/wd "
+                "loss + backward + %s + clip + Adadelta; gate convolutions: %s" % (
+                    batch, batch * world,
+                    "RCCL all-reduce of the 21.3M-float gradient buffer" if world > 1
+                    else "no all-reduce (1 rank)",
+                    "forward, dgrad and wgrad on the fp16 matrix pipe (f16x3 split, "
+                    "fp32-class error)" if f16 else
+                    "BASELINE configs[4]: forward and dgrad on bf16 operands, wgrad on the "
+                    "leading fp16 plane of each operand (one MFMA per product everywhere, "
+                    "fp32 accumulate, reduced precision; MV_BF16_BWD=0: backward on the "
+                    "f16x3 split)" if bf16
+                    else "fp32 matrix pipe"))
+  else:
+    metric = ("trajectories/sec (8-obs/12-pred, multi-scale %s grid, greedy forward)"
+              % ("36x18+18x9" if literal_grids else "18x32+9x16"))
+    workload = ("BASELINE configs[1]: multi-scale %s, "
+                "batch %d/GPU, fp32 forward-only, beam 1, obs 8 / pred 12%s; gate "
+                "convolution on %s"
+                % ("36x18+18x9 (scene 72x36x11) -- BASELINE.json's LITERAL grid wording; the "
+                   "reference's own grids are 18x32+9x16" if literal_grids else
+                   "18x32+9x16 (scene 36x64x11)",
+                   batch, (", hipGraph replay" if graph else "") +
+                   (", scene_conv_kernel 1 (dense 1x1 projections on MFMA)"
+                    if scene_conv_kernel == 1 else ""),
+                   "the fp16 matrix pipe (f16x3 split, fp32-class error)" if f16 else
+                   "the bf16 matrix pipe (BASELINE configs[4]: bf16 operands, fp32 accumulate; "
+                   "REDUCED precision, not the fp32 headline)" if bf16
+                   else "the fp32 matrix pipe"))
+  out = {
+      "metric": metric,
+      "value": round(value, 2),
+      "unit": "trajectories/sec",
+      "n_gpus": world,
+      "steps": steps,
+      "warmup": warmup,
+      "ms_per_step": round(ms_per_step, 3),
+      "timed_region_s": round(elapsed, 3),
+      "higher_is_better": True,
+      "scaling": "weak",
+      "vs_baseline": None,
+      "dtype": ("bf16 (gate-convolution operands in bf16, one MFMA per product, fp32 "
+                "accumulate; fp32 state and every other kernel; REDUCED precision: logits within "
+                "3e-2 of their range, tests/test_gpu_bf16.py)" + (
+                    "; dgrad on bf16 planes, wgrad on one fp16 plane per operand: gradient "
+                    "cosine vs the fp32 oracle > 0.999 asserted" if train else "") if bf16 else
+                "f16x3 (fp32 operands as two pre-scaled fp16 planes, fp32 accumulate and state; "
+                "%s; error vs fp64 within 2x of the fp32-MFMA path's -- asserted under "
+                "checkpoint-like dynamic range (tests/test_gpu_at_size.py) and measured equal "
+                "on trained weights (profiles/r6c_trained_weights_parity_and_metrics.log); "
+                "argmax / beam ids bit-exact)" % f16_form if (f16 and not train) else
+                "f16x3 gate convolutions (forward, dgrad, wgrad: fp32 operands as two "
+                "pre-scaled fp16 planes, fp32 accumulate; %s); fp32 "
+                "state, losses, gradients and optimizer" % f16_form if f16 else "f32"),
+      "data": "synthetic (seeded AR(1) trajectories, rectangle scene masks, "
+              "random-init weights with the reference's initialisers)",
+      "config": {"workload": workload,
+                 "batch_per_gpu": batch, "global_batch": batch * world,
+                 "obs_len": cfg.obs_len, "pred_len": cfg.pred_len,
+                 "parallelism": ("data-parallel x%d, gradient all-reduce (RCCL%s)" % (
+                                     world, ", in-library: one bucket per ConvLSTM kernel on a "
+                                     "side stream, overlapped with the backward pass"
+                                     if lib_allreduce else " via torch.distributed, one "
+                                     "blocking call after the backward pass")
+                                 if train else
+                                 "batch-sharded x%d, no data-path collective" % world),
+                 "alg_gflop_per_trajectory": round(flops_traj / 1e9, 2),
+                 "alg_gflop_per_trajectory_executed": round(flops_traj_exec / 1e9, 2),
+                 "alg_state_MB_per_trajectory": round(bytes_traj / 1e6, 2)},
+  }
+  if roofline is not None:
+    out["roofline"] = roofline
+
+  if train:
+    out["rccl_ranks"] = world if (ctx.use_dist and ctx.backend == "nccl") else 0
+    ci = eng.comm_info()
+    if ci:
+      out["allreduce"] = {"where": "libmultiverse_hip (RCCL)",
+                          "collectives_per_step": ci["buckets"],
+                          "MB_per_step": round(ci["bytes"] / 1e6, 1)}
+  if fp32_ref and (f16 or bf16) and not train:
+    # the same workload on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32), for reference
+    eng.set_compute_mode("f32")
+    one_step()
+    ctx.barrier(eng)
+    t1 = time.perf_counter()
+    nref = max(2, min(steps // 3, 12))
+    for _ in range(nref):
+      one_step()
+    eng.synchronize()
+    ctx.barrier(eng)
+    el = ctx.max_over_ranks(time.perf_counter() - t1)
+    flops_traj_exec_dense_x, _ = algorithmic_counts(cfg, beam_size if beam else 1, executed=True)
+    out["fp32_mfma_reference"] = {
+        "value": round(world * batch * nref / el, 2), "unit": "trajectories/sec",
+        "ms_per_step": round(1e3 * el / nref, 3), "steps": nref,
+        # the fp32 path multiplies the dense x operand (no sparse-x tables)
+        "mfma_frac_of_fp32_peak": round(
+            batch * nref / el * flops_traj_exec_dense_x / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)}
+    eng.set_compute_mode(compute)
+  eng.close()
+  if cpu_base and rank == 0 and world == 1 and not beam:
+    out["cpu_baseline"] = (cpu_baseline_train(min(cpu_batch, 4)) if train
+                           else cpu_baseline(cpu_batch))
+  return out
+
+
+DUMP_BYTES = 60 * 10 ** 6       # --dump-outputs: all arrays of all ranks together (< 64 MB)
+DUMP_SEED = 20240607            # the fixed sample of an array over its share of that
+
+
+def dump_outputs(out_dir, eng, kind, losses, rank, world):
+  """What the caller of the timed path receives from its last step, as <name>.npy (float32;
+  integer ids and the losses as float64): greedy -> the class and regression grids of every used scale;
+  beam -> best beam, regression grids, beam logits / ids / log-probs; train -> the losses
+  and the updated weights (every parameter, flattened and concatenated in the engine's
+  order).  An array larger than its share of DUMP_BYTES is replaced by a fixed sample: one
+  element at a seeded random position in each of n equal runs of its flat index (same
+  positions in every run), in order.
+  Several ranks: each writes its own arrays with a rank<r>_ prefix."""
+  import numpy as np
+  if kind == "greedy":
+    cls, reg = eng.download()
+    arrs = {}
+    for s in range(len(cls)):
+      if len(cls[s]):
+        arrs["grid_pred_class_s%d" % s] = cls[s]
+        arrs["grid_pred_reg_s%d" % s] = reg[s]
+  elif kind == "beam":
+    got, _ = eng.download_beam()
+    arrs = {"beam_" + k: v for k, v in got.items()}
+  else:
+    loss, wd, pgl = losses
+    arrs = {"losses": np.array([loss, wd] + list(pgl), dtype=np.float64),
+            "params": np.concatenate([eng.get_param(n).reshape(-1)
+                                      for n, _ in eng.param_specs()])}
+  arrs = {k: (v.astype(np.float64) if v.dtype.kind in "iu" or v.dtype == np.float64
+              else v.astype(np.float32, copy=False))
+          for k, v in arrs.items()}
+  # smallest first: an array that fits its share of what is left is written whole, and
+  # what it leaves unused goes to the larger ones; one that does not is sampled down to it
+  left = DUMP_BYTES // world
+  order = sorted(arrs, key=lambda k: arrs[k].nbytes)
+  for i, k in enumerate(order):
+    share = left // (len(order) - i)
+    a = arrs[k]
+    if a.nbytes > share:
+      a = a.reshape(-1)
+      n = share // a.itemsize          # < a.size, since a.nbytes > share
+      # one seeded position in each of n equal runs of the flat array: distinct, in
+      # order, and no index array the size of the whole output
+      edges = np.arange(n + 1, dtype=np.int64) * a.size // n
+      pick = edges[:-1] + (np.random.default_rng(DUMP_SEED).random(n) *
+                           np.diff(edges)).astype(np.int64)
+      del arrs[k]
+      arrs[k + "_sample"] = a = a[pick]
+    left -= a.nbytes
+  os.makedirs(out_dir, exist_ok=True)
+  prefix = "rank%d_" % rank if world > 1 else ""
+  for k, v in arrs.items():
+    np.save(os.path.join(out_dir, prefix + k + ".npy"), v)
+
+
+def gate_kernel_form(step_pp):
+  """The form of the f16x3 forward gate kernel from the fp16 MFMA products it issued per
+  algorithmic fp32 product (convlstm_step launches of a profiled step)."""
+  return ("winograd F(3,3) over image rows on pre-transformed operands, 5/3 fp16 MFMA products "
+          "per fp32 product" if step_pp < 1.9 else
+          "winograd F(2,3) over image rows, 2 fp16 MFMA products per fp32 product" if step_pp < 2.5
+          else "direct 3x3, 3 fp16 MFMA products per fp32 product")
+
+
+def roofline_of(kind, compute, batch, beam_size, scene_conv_kernel, literal_grids, world, value,
+                stats, mfma_kernels, conv, flops_traj_exec):
+  """The `roofline` object of a measured workload (--full) from the kernel stats of one
+  profiled step: the dominant kernel against the MFMA peak, the HBM-bound kernels, and the
+  HBM traffic of a committed PMC summary taken on these kernel sources."""
+  beam = kind == "beam"
+  train = kind == "train"
   f16 = compute == "f16x3"
   bf16 = compute == "bf16"
+  conv_s = conv["total_ms"] * 1e-3
+  # achieved = algorithmic FLOPs the launches EXECUTED (zero-state steps skip the h half)
+  achieved_tf = conv["flops"] / conv_s / 1e12
   peak = PEAK_FP16_MFMA_TFLOPS if (f16 or bf16) else PEAK_FP32_MFMA_TFLOPS
   other = {k: v for k, v in stats.items() if k not in mfma_kernels}
   roofline = {
@@ -364,11 +582,7 @@ def measure(ctx, kind, batch, compute, steps, warmup, beam_size=20, graph=None,
     per_product = conv["flops_mfma"] / conv["flops"] if conv["flops"] else 3.0
     step_pp = (stats["convlstm_step"]["flops_mfma"] / stats["convlstm_step"]["flops"]
                if stats["convlstm_step"]["flops"] else 3.0)
-    roofline["gate_kernel_form"] = (
-        "winograd F(3,3) over image rows on pre-transformed operands, 5/3 fp16 MFMA products per "
-        "fp32 product" if step_pp < 1.9 else
-        "winograd F(2,3) over image rows, 2 fp16 MFMA products per fp32 product" if step_pp < 2.5
-        else "direct 3x3, 3 fp16 MFMA products per fp32 product")
+    roofline["gate_kernel_form"] = gate_kernel_form(step_pp)
     roofline["note"] = ("f16x3: fp32 operands as two pre-scaled fp16 planes, fp32 accumulate; "
                         "%.2f fp16 MFMA products issued per algorithmic fp32 product over these "
                         "launches; ceiling of the method = peak / that" % per_product)
@@ -415,128 +629,7 @@ def measure(ctx, kind, batch, compute, steps, warmup, beam_size=20, graph=None,
       quote_sub_traffic(roofline, "train_bf16", stats, mfma_kernels)
     except Exception as ex:  # pylint: disable=broad-except
       roofline["traffic_note"] = "PMC summary not quoted: %s" % ex
-
-  if beam:
-    metric = ("trajectories/sec (8-obs/12-pred, 18x32 grid, diverse beam-%d "
-              "multi-future decode)" % beam_size)
-    workload = ("BASELINE configs[3]: scale 0 (18x32, scene 36x64x11), beam %d "
-                "(diverse, gamma 0.01, fix_num_timestep 1), batch %d/GPU, fp32, "
-                "obs 8 / pred 12, %s" % (beam_size, batch,
-                                         "hipGraph replay" if graph else "stream launches"))
-  elif train:
-    metric = ("trajectories/sec (8-obs/12-pred, multi-scale 18x32+9x16 grid, "
-              "training step)")
-    workload = ("BASELINE configs[2]: multi-scale 18x32+9x16 (scene 36x64x11), "
-                "batch %d/GPU (global %d), fp32 training step = forward + CE/Huber/wd "
-                "loss + backward + %s + clip + Adadelta; gate convolutions: %s" % (
-                    batch, batch * world,
-                    "RCCL all-reduce of the 21.3M-float gradient buffer" if world > 1
-                    else "no all-reduce (1 rank)",
-                    "forward, dgrad and wgrad on the fp16 matrix pipe (f16x3 split, "
-                    "fp32-class error)" if f16 else
-                    "BASELINE configs[4]: forward and dgrad on bf16 operands, wgrad on the "
-                    "leading fp16 plane of each operand (one MFMA per product everywhere, "
-                    "fp32 accumulate, reduced precision; MV_BF16_BWD=0: backward on the "
-                    "f16x3 split)" if bf16
-                    else "fp32 matrix pipe"))
-  else:
-    metric = ("trajectories/sec (8-obs/12-pred, multi-scale %s grid, greedy forward)"
-              % ("36x18+18x9" if literal_grids else "18x32+9x16"))
-    workload = ("BASELINE configs[1]: multi-scale %s, "
-                "batch %d/GPU, fp32 forward-only, beam 1, obs 8 / pred 12%s; gate "
-                "convolution on %s"
-                % ("36x18+18x9 (scene 72x36x11) -- BASELINE.json's LITERAL grid wording; the "
-                   "reference's own grids are 18x32+9x16" if literal_grids else
-                   "18x32+9x16 (scene 36x64x11)",
-                   batch, (", hipGraph replay" if graph else "") +
-                   (", scene_conv_kernel 1 (dense 1x1 projections on MFMA)"
-                    if scene_conv_kernel == 1 else ""),
-                   "the fp16 matrix pipe (f16x3 split, fp32-class error)" if f16 else
-                   "the bf16 matrix pipe (BASELINE configs[4]: bf16 operands, fp32 accumulate; "
-                   "REDUCED precision, not the fp32 headline)" if bf16
-                   else "the fp32 matrix pipe"))
-  # the form the gate kernels of THESE launches ran in, from what the engine issued to the
-  # matrix pipe (3 fp16 MFMA products per fp32 product = direct 3x3; 2 = Winograd F(2,3) over
-  # rows; 1.67 = F(3,3) over rows; training mixes the forms of forward / dgrad / wgrad)
-  f16_form = ""
-  if f16:
-    f16_form = "%s, %.2f fp16 MFMAs issued per fp32 product over the gate kernels" % (
-        roofline.get("gate_kernel_form", "gate kernel form n/a").split(" fp16 MFMA")[0].rsplit(",", 1)[0],
-        conv["flops_mfma"] / conv["flops"] if conv["flops"] else 3.0)
-  out = {
-      "metric": metric,
-      "value": round(value, 2),
-      "unit": "trajectories/sec",
-      "n_gpus": world,
-      "steps": steps,
-      "warmup": warmup,
-      "ms_per_step": round(ms_per_step, 3),
-      "timed_region_s": round(elapsed, 3),
-      "higher_is_better": True,
-      "scaling": "weak",
-      "vs_baseline": None,
-      "dtype": ("bf16 (gate-convolution operands in bf16, one MFMA per product, fp32 "
-                "accumulate; fp32 state and every other kernel; REDUCED precision: logits within "
-                "3e-2 of their range, tests/test_gpu_bf16.py)" + (
-                    "; dgrad on bf16 planes, wgrad on one fp16 plane per operand: gradient "
-                    "cosine vs the fp32 oracle > 0.999 asserted" if train else "") if bf16 else
-                "f16x3 (fp32 operands as two pre-scaled fp16 planes, fp32 accumulate and state; "
-                "%s; error vs fp64 within 2x of the fp32-MFMA path's -- asserted under "
-                "checkpoint-like dynamic range (tests/test_gpu_at_size.py) and measured equal "
-                "on trained weights (profiles/r6c_trained_weights_parity_and_metrics.log); "
-                "argmax / beam ids bit-exact)" % f16_form if (f16 and not train) else
-                "f16x3 gate convolutions (forward, dgrad, wgrad: fp32 operands as two "
-                "pre-scaled fp16 planes, fp32 accumulate; %s); fp32 "
-                "state, losses, gradients and optimizer" % f16_form if f16 else "f32"),
-      "data": "synthetic (seeded AR(1) trajectories, rectangle scene masks, "
-              "random-init weights with the reference's initialisers)",
-      "config": {"workload": workload,
-                 "batch_per_gpu": batch, "global_batch": batch * world,
-                 "obs_len": cfg.obs_len, "pred_len": cfg.pred_len,
-                 "parallelism": ("data-parallel x%d, gradient all-reduce (RCCL%s)" % (
-                                     world, ", in-library: one bucket per ConvLSTM kernel on a "
-                                     "side stream, overlapped with the backward pass"
-                                     if lib_allreduce else " via torch.distributed, one "
-                                     "blocking call after the backward pass")
-                                 if train else
-                                 "batch-sharded x%d, no data-path collective" % world),
-                 "alg_gflop_per_trajectory": round(flops_traj / 1e9, 2),
-                 "alg_gflop_per_trajectory_executed": round(flops_traj_exec / 1e9, 2),
-                 "alg_state_MB_per_trajectory": round(bytes_traj / 1e6, 2)},
-      "roofline": roofline,
-  }
-
-  if train:
-    out["rccl_ranks"] = world if (ctx.use_dist and ctx.backend == "nccl") else 0
-    ci = eng.comm_info()
-    if ci:
-      out["allreduce"] = {"where": "libmultiverse_hip (RCCL)",
-                          "collectives_per_step": ci["buckets"],
-                          "MB_per_step": round(ci["bytes"] / 1e6, 1)}
-  if fp32_ref and (f16 or bf16) and not train:
-    # the same workload on the fp32 matrix pipe (v_mfma_f32_32x32x2_f32), for reference
-    eng.set_compute_mode("f32")
-    one_step()
-    ctx.barrier(eng)
-    t1 = time.perf_counter()
-    nref = max(2, min(steps // 3, 12))
-    for _ in range(nref):
-      one_step()
-    eng.synchronize()
-    ctx.barrier(eng)
-    el = ctx.max_over_ranks(time.perf_counter() - t1)
-    out["fp32_mfma_reference"] = {
-        "value": round(world * batch * nref / el, 2), "unit": "trajectories/sec",
-        "ms_per_step": round(1e3 * el / nref, 3), "steps": nref,
-        # the fp32 path multiplies the dense x operand (no sparse-x tables)
-        "mfma_frac_of_fp32_peak": round(
-            batch * nref / el * flops_traj_exec_dense_x / 1e12 / PEAK_FP32_MFMA_TFLOPS, 4)}
-    eng.set_compute_mode(compute)
-  eng.close()
-  if cpu_base and rank == 0 and world == 1 and not beam:
-    out["cpu_baseline"] = (cpu_baseline_train(min(cpu_batch, 4)) if train
-                           else cpu_baseline(cpu_batch))
-  return out
+  return roofline
 
 
 def compact(sub):
@@ -699,10 +792,15 @@ def main():
                   help="--scene_conv_kernel of the reference (code/train.py:65): 3 = the published "
                        "3x3 stride-2 stack; 1 = the dense 1x1 projections, run as MFMA GEMMs "
                        "(BASELINE configs[4] names it)")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="write what the headline's last timed step computed to DIR/<name>.npy")
+  ap.add_argument("--full", action="store_true",
+                  help="besides the headline: its roofline, the fp32 reference and CPU "
+                       "baseline, the sub-workloads and host_path (the options below)")
   ap.add_argument("--no-sub", action="store_true",
-                  help="headline only: skip the sub-workloads and host_path")
+                  help="with --full: skip the sub-workloads and host_path")
   ap.add_argument("--only-sub", default=None,
-                  help="comma list of sub-workloads to run (default: all)")
+                  help="with --full: comma list of sub-workloads to run (default: all)")
   ap.add_argument("--no-cpu-baseline", action="store_true")
   ap.add_argument("--no-fp32-ref", action="store_true")
   ap.add_argument("--cpu-batch", type=int, default=8)
@@ -752,8 +850,10 @@ def main():
   head = measure(ctx, kind, batch, args.compute, args.steps, args.warmup,
                  beam_size=args.beam, graph=args.graph,
                  scene_conv_kernel=args.scene_conv_kernel,
-                 timed_seconds=DEFAULT_TIMED_SECONDS, fp32_ref=not args.no_fp32_ref,
-                 cpu_base=not args.no_cpu_baseline, cpu_batch=args.cpu_batch)
+                 timed_seconds=DEFAULT_TIMED_SECONDS,
+                 fp32_ref=args.full and not args.no_fp32_ref,
+                 cpu_base=args.full and not args.no_cpu_baseline, cpu_batch=args.cpu_batch,
+                 full=args.full, dump_dir=args.dump_outputs)
   out = head
 
   # A sub-workload that needs the in-library RCCL communicator (training) runs its bootstrap
@@ -772,7 +872,7 @@ def main():
   _par.deadline_hook = _emit_partial
 
   subs = []
-  with_subs = (not args.no_sub and kind == "greedy" and args.batch is None and
+  with_subs = (args.full and not args.no_sub and kind == "greedy" and args.batch is None and
                args.compute == "f16x3")
   if with_subs:
     subs = [("train_n32", dict(kind="train", batch=32, compute="f16x3")),

@@ -27,7 +27,13 @@ class FakeEngine(object):
 
   # -- set-up ----------------------------------------------------------------------------
   def set_params(self, params): self.nparams = len(params)
-  def upload(self, feed): self.feed_rows = int(feed["obs_scene"].shape[0])
+  def upload(self, feed):
+    import zlib
+    import numpy as np
+    self.feed_rows = int(feed["obs_scene"].shape[0])
+    # what the --dump-outputs arrays are made from: the uploaded inputs ...
+    self.feed_crc = zlib.crc32(np.ascontiguousarray(feed["obs_scene"]).tobytes())
+
   def upload_targets(self, feed): pass
   def set_graph_mode(self, on): pass
   def set_compute_mode(self, mode): self.mode = mode
@@ -44,8 +50,54 @@ class FakeEngine(object):
     self.steps += 1
 
   def run_resident(self, beam): self._work()
-  def train_forward_backward(self, feed): self._work()
-  def train_step(self, feed): self._work()
+
+  # -- --dump-outputs: arrays of the real shapes, made from the inputs and the step count ---
+  def _made(self, shape, dtype="float32"):
+    """... and the step count: same arguments, same arrays; another step, other arrays"""
+    import numpy as np
+    rng = np.random.default_rng([self.feed_crc, self.steps])
+    if np.dtype(dtype).kind == "i":
+      return rng.integers(0, 1000, shape).astype(dtype)
+    return rng.standard_normal(shape).astype(dtype)
+
+  def download(self):
+    """The class / regression grids of every used scale; the class grids hold the step
+    count, so a test sees which step they come from."""
+    import numpy as np
+    cfg, cls, reg = self.cfg, [], []
+    for s, (h, w) in enumerate(cfg.scene_grids):
+      if not cfg.use_grids[s]:
+        cls.append([])
+        reg.append([])
+        continue
+      shape = (cfg.batch_size, cfg.pred_len, h, w)
+      cls.append(np.full(shape + (1,), self.steps + s, dtype=np.float32))
+      reg.append(self._made(shape + (2,)))
+    return cls, reg
+
+  def download_beam(self):
+    cfg = self.cfg
+    N, B, T = cfg.batch_size, cfg.beam_size, cfg.pred_len
+    s = [i for i, u in enumerate(cfg.use_grids) if u][0]
+    h, w = cfg.scene_grids[s]
+    return {"best_beam": self._made((N, T, h, w, 1)), "grid_reg": self._made((N, T, h, w, 2)),
+            "logits": self._made((N, B, T, h * w)), "ids": self._made((N, B, T), "int32"),
+            "logprobs": self._made((N, B))}, s
+
+  def param_specs(self): return [("w", (3, 3, 8, 16)), ("b", (16,))]
+
+  def get_param(self, name):
+    return self._made(dict(self.param_specs())[name]) + (1.0 if name == "b" else 0.0)
+
+  def _losses(self): return (0.5 * self.steps, 0.25, [0.125, 0.0625])
+
+  def train_forward_backward(self, feed):
+    self._work()
+    return self._losses()
+
+  def train_step(self, feed):
+    self._work()
+    return self._losses()
   def train_apply(self, scale): self.scale = scale
 
   def kernel_stats(self):

@@ -71,7 +71,7 @@ def test_bench_gpus_8_training_step_control_flow(tmp_path):
 
 @pytest.mark.timeout(900)
 def test_stalled_rccl_bootstrap_in_a_sub_workload_keeps_the_headline_line(tmp_path):
-  """The default run measures the headline first and the sub-workloads after it.  If the
+  """The --full run measures the headline first and the sub-workloads after it.  If the
   in-library RCCL bootstrap of the training sub-workload never returns (here: a stand-in that
   sleeps), its deadline ends the ranks -- and rank 0 still emits ONE line carrying the measured
   headline and the reason, instead of the job dying without output or hanging."""
@@ -80,7 +80,7 @@ def test_stalled_rccl_bootstrap_in_a_sub_workload_keeps_the_headline_line(tmp_pa
   for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
     env.pop(k, None)
   r = subprocess.run([sys.executable, HARNESS, "--gpus", "2", "--steps", "2", "--warmup", "1",
-                      "--no-cpu-baseline", "--no-fp32-ref", "--only-sub", "train_n32"],
+                      "--full", "--no-cpu-baseline", "--no-fp32-ref", "--only-sub", "train_n32"],
                      env=env, capture_output=True, timeout=600)
   assert r.returncode != 0                       # the job failed, loudly ...
   assert b"FATAL: mv_allreduce_init" in r.stderr
@@ -89,3 +89,44 @@ def test_stalled_rccl_bootstrap_in_a_sub_workload_keeps_the_headline_line(tmp_pa
   line = json.loads(lines[0])
   assert line["n_gpus"] == 2 and line["value"] > 0 and "did not return" in line["aborted"]
   assert "train_n32" not in line
+
+
+@pytest.mark.timeout(900)
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+  """A plain run (no --full) carries the headline's contract fields and nothing that takes
+  runs of its own; --steps sets the timed steps; --dump-outputs writes the arrays of the
+  last timed step as float32 .npy, the same ones for the same arguments.  --full brings the
+  roofline back."""
+  import numpy as np
+  env = dict(os.environ, MV_BENCH_BACKEND="gloo", MV_HARNESS_DIR=str(tmp_path),
+             OMP_NUM_THREADS="1", MASTER_ADDR="127.0.0.1")
+  for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+    env.pop(k, None)
+
+  def run(*extra):
+    r = subprocess.run([sys.executable, HARNESS, "--gpus", "1", "--steps", "4", "--warmup", "1",
+                        "--batch", "2"] + list(extra), env=env, capture_output=True, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+  dumps = []
+  for k in range(2):
+    d = os.path.join(str(tmp_path), "dump%d" % k)
+    line = run("--dump-outputs", d)
+    assert line["steps"] == 4 and line["warmup"] == 1
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+      assert key in line, key
+    assert abs(line["value"] - 2 * 4 / (line["ms_per_step"] * 4e-3)) <= 0.02 * line["value"]
+    assert not set(line) & {"roofline", "cpu_baseline", "fp32_mfma_reference", "host_path",
+                            "train_n32", "beam_n128_b20", "greedy_b256", "bf16"}
+    names = sorted(os.listdir(d))
+    assert names == ["grid_pred_class_s0.npy", "grid_pred_class_s1.npy",
+                     "grid_pred_reg_s0.npy", "grid_pred_reg_s1.npy"]
+    dumps.append({n: np.load(os.path.join(d, n)) for n in names})
+  for n, a in dumps[0].items():
+    assert a.dtype == np.float32 and (a == dumps[1][n]).all(), n
+  # the stand-in's arrays carry its step count: warm-up 1 + timed 4 = the last timed step
+  assert (dumps[0]["grid_pred_class_s0.npy"] == 5).all()
+  assert "roofline" in run("--full", "--no-sub", "--no-cpu-baseline", "--no-fp32-ref")

@@ -1,17 +1,21 @@
 """The re-hosted command lines (scripts/train.py, scripts/test.py,
 scripts/multifuture_inference.py) against the reference's own argparse tables:
 every flag the reference declares exists here with the same type, default and
-action, read from the reference SOURCE with `ast` (nothing is imported or executed).
-Needs the /root/reference checkout; skipped elsewhere (the GPU box)."""
+action.  The tables were read from the reference SOURCE with `ast` (nothing imported
+or executed) and are recorded in tests/golden/reference_cli_flags.npz
+(tests/golden/make_reference_records.py)."""
 import ast
 import os
+import sys
 
 import pytest
 
 from multiverse_amd import cli
 
-REF = "/root/reference/code"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs /root/reference")
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import reference_records  # noqa: E402
+
+SCRIPTS = ("train.py", "test.py", "multifuture_inference.py")
 
 
 def _literal(node):
@@ -38,6 +42,11 @@ def reference_flags(path):
   return out
 
 
+def record(ref_code):
+  """{script: reference_flags(...)} of the reference checkout's code/ folder."""
+  return {script: reference_flags(os.path.join(ref_code, script)) for script in SCRIPTS}
+
+
 def ours(parser):
   out = {}
   for a in parser._actions:
@@ -50,7 +59,7 @@ def ours(parser):
 
 @pytest.mark.parametrize("script,kind", [("train.py", "t"), ("test.py", "T")])
 def test_model_scripts_declare_the_reference_flags(script, kind):
-  ref = reference_flags(os.path.join(REF, script))
+  ref = reference_records.load("cli_flags")[script]
   mine = ours(cli.model_parser(kind))
   assert len(ref) > 40
   missing = sorted(set(ref) - set(mine))
@@ -68,7 +77,7 @@ def test_model_scripts_declare_the_reference_flags(script, kind):
 
 
 def test_multifuture_inference_declares_the_reference_flags():
-  ref = reference_flags(os.path.join(REF, "multifuture_inference.py"))
+  ref = reference_records.load("cli_flags")["multifuture_inference.py"]
   mine = ours(cli.multifuture_inference_parser())
   missing = sorted(set(ref) - set(mine))
   assert not missing, missing

@@ -1,7 +1,9 @@
 """scripts/multifuture_eval_trajs.py and scripts/multifuture_eval_trajs_prob.py against
 the reference's own scripts, both executed as command lines on the same synthetic
 multi-future outputs (pure numpy scripts: no TensorFlow involved).  The printed
-metric lines must agree to the last digit.  Needs /root/reference; skipped elsewhere."""
+metric lines must agree to the last digit.  The reference scripts' lines on these inputs
+are recorded in tests/golden/reference_eval_scripts.npz
+(tests/golden/make_reference_records.py)."""
 import os
 import pickle
 import subprocess
@@ -10,9 +12,9 @@ import sys
 import numpy as np
 import pytest
 
-REF = "/root/reference/code"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs /root/reference")
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import reference_records  # noqa: E402
 
 
 def _make_case(tmp_path, seed=0, H=18, W=32):
@@ -53,9 +55,19 @@ def _run(script, *args):
   return [l for l in out.stdout.decode().splitlines() if l.strip()]
 
 
+def record(ref_code, tmp_path):
+  """The reference scripts' printed lines on the two cases below (tmp_path: a pathlib.Path)."""
+  (tmp_path / "a").mkdir(parents=True)
+  (tmp_path / "b").mkdir(parents=True)
+  gt, pred, _ = _make_case(tmp_path / "a", seed=1)
+  gt2, _, prob = _make_case(tmp_path / "b", seed=2)
+  return {"min_ade_fde": _run(os.path.join(ref_code, "multifuture_eval_trajs.py"), gt, pred),
+          "grid_nll": _run(os.path.join(ref_code, "multifuture_eval_trajs_prob.py"), gt2, prob)}
+
+
 def test_min_ade_fde_script_matches_the_reference(tmp_path):
   gt, pred, _ = _make_case(tmp_path, seed=1)
-  ref = _run(os.path.join(REF, "multifuture_eval_trajs.py"), gt, pred)
+  ref = reference_records.load("eval_scripts")["min_ade_fde"]
   mine = _run(os.path.join(ROOT, "scripts", "multifuture_eval_trajs.py"), gt, pred)
   assert ref[0] == mine[0] == "ADE/FDE:"
   assert ref[1] == mine[1]
@@ -65,7 +77,7 @@ def test_min_ade_fde_script_matches_the_reference(tmp_path):
 
 def test_grid_nll_script_matches_the_reference(tmp_path):
   gt, _, prob = _make_case(tmp_path, seed=2)
-  ref = _run(os.path.join(REF, "multifuture_eval_trajs_prob.py"), gt, prob)
+  ref = reference_records.load("eval_scripts")["grid_nll"]
   mine = _run(os.path.join(ROOT, "scripts", "multifuture_eval_trajs_prob.py"), gt, prob)
   assert ref[0] == mine[0]                       # sample counts per horizon
   assert ref[1] == mine[1] == "NLL:" and ref[2] == mine[2]

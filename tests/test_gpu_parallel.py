@@ -369,7 +369,7 @@ def test_bench_spawns_its_own_ranks(built_lib):
   env.pop("RANK", None)
   out = subprocess.check_output(
       [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3",
-       "--warmup", "1", "--no-fp32-ref", "--only-sub", "train_n32"],
+       "--warmup", "1", "--full", "--no-fp32-ref", "--only-sub", "train_n32"],
       env=env, timeout=900)
   lines = [l for l in out.decode().splitlines() if l.strip()]
   assert len(lines) == 1, lines

@@ -2,8 +2,9 @@
 npy + id map -> observed trajectories, grid classes, regression targets, one-hot scene
 masks, T_pred per sample) against the functions of the reference's own
 `code/multifuture_inference.py`, imported unmodified (TensorFlow = the eager shim, not
-called on this path) and run on the same synthetic on-disk dataset.  Needs
-/root/reference; skipped elsewhere."""
+called on this path) and run on the same synthetic on-disk dataset.  What the reference's
+functions returned there is recorded in tests/golden/reference_multifuture_inputs.npz
+(tests/golden/make_reference_records.py)."""
 import argparse
 import copy
 import importlib
@@ -19,13 +20,13 @@ from multiverse_amd import multifuture as mf
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "oracle", "tf1_shim"))
+sys.path.insert(0, os.path.join(HERE, "golden"))
 import mf_fixture  # noqa: E402
-import run_reference as rr  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not rr.available(), reason="needs the /root/reference checkout")
+import reference_records  # noqa: E402
 
 
 def _reference_module():
+  import run_reference as rr
   rr.import_reference()
   sys.path.insert(0, rr.REFERENCE_CODE)
   argv = sys.argv
@@ -49,22 +50,45 @@ def _args(ds):
       scene_h=36, scene_w=64, scene_class=11, video_h=1080, video_w=1920)
 
 
-def test_get_inputs_matches_the_reference(tmp_path):
-  ref = _reference_module()
-  ds = mf_fixture.make_dataset(str(tmp_path), n_traj=5)
+def _case(root, n_traj):
+  ds = mf_fixture.make_dataset(root, n_traj=n_traj)
   files = sorted(glob(os.path.join(ds["traj_path"], "*.txt")))
   ids = [os.path.splitext(os.path.basename(f))[0] for f in files]
-  gt = mf.load_gt(ds["multifuture_path"], ids)
+  return ds, files, mf.load_gt(ds["multifuture_path"], ids)
 
+
+def record(tmp_dir):
+  """What the reference's functions return on the datasets of the two tests below."""
+  ref = _reference_module()
+  ds, files, gt = _case(os.path.join(tmp_dir, "inputs"), 5)
   a_ref = copy.deepcopy(_args(ds))
   ref.add_grid(a_ref)                                # the reference mutates args in place
+  out = {"add_grid": {"scene_grids": a_ref.scene_grids,
+                      "scene_grid_strides": a_ref.scene_grid_strides,
+                      "scene_grid_centers": [np.asarray(c) for c in a_ref.scene_grid_centers]},
+         "get_inputs": ref.get_inputs(a_ref, files, gt)}
+  ds, files, gt = _case(os.path.join(tmp_dir, "feed"), 4)
+  args = mf.add_grid(copy.deepcopy(_args(ds)))
+  args.use_soft_grid_class = False
+  inputs = mf.get_inputs(args, files, gt)
+  ph = _Placeholders(len(args.scene_grids))
+  out["feed_dicts"] = [ref.PredictionModelInference.get_feed_dict(ph, inputs, args, idx)
+                       for idx in range(len(files))]
+  return out
+
+
+def test_get_inputs_matches_the_reference(tmp_path):
+  rec = reference_records.load("multifuture_inputs")
+  ds, files, gt = _case(str(tmp_path), 5)
+
+  a_ref = rec["add_grid"]
   a_me = mf.add_grid(copy.deepcopy(_args(ds)))
-  assert a_ref.scene_grids == a_me.scene_grids
-  assert a_ref.scene_grid_strides == a_me.scene_grid_strides
-  for c0, c1 in zip(a_ref.scene_grid_centers, a_me.scene_grid_centers):
+  assert a_ref["scene_grids"] == a_me.scene_grids
+  assert a_ref["scene_grid_strides"] == a_me.scene_grid_strides
+  for c0, c1 in zip(a_ref["scene_grid_centers"], a_me.scene_grid_centers):
     assert (np.asarray(c0) == np.asarray(c1)).all()
 
-  r = ref.get_inputs(a_ref, files, gt)
+  r = rec["get_inputs"]
   m = mf.get_inputs(a_me, files, gt)
   assert sorted(r) == sorted(m)
   assert r["max_pred_lengths"] == m["max_pred_lengths"]
@@ -92,17 +116,14 @@ class _Placeholders(object):
 
 
 def test_inference_feed_matches_the_reference(tmp_path):
-  ref = _reference_module()
-  ds = mf_fixture.make_dataset(str(tmp_path), n_traj=4)
-  files = sorted(glob(os.path.join(ds["traj_path"], "*.txt")))
-  ids = [os.path.splitext(os.path.basename(f))[0] for f in files]
-  gt = mf.load_gt(ds["multifuture_path"], ids)
+  feed_dicts = reference_records.load("multifuture_inputs")["feed_dicts"]
+  ds, files, gt = _case(str(tmp_path), 4)
   args = mf.add_grid(copy.deepcopy(_args(ds)))
   args.use_soft_grid_class = False
   inputs = mf.get_inputs(args, files, gt)
-  ph = _Placeholders(len(args.scene_grids))
+  assert len(feed_dicts) == len(files)
   for idx in range(len(files)):
-    want = ref.PredictionModelInference.get_feed_dict(ph, inputs, args, idx)
+    want = feed_dicts[idx]
     feed, n_real = mf.inference_feed(inputs, args, [idx])
     assert n_real == 1
     assert feed["pred_length"] == int(want["pred_length"][0])

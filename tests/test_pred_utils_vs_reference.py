@@ -2,7 +2,8 @@
 scene-table compaction) and `evaluate` (grid accuracy, ADE/FDE from class + offset) --
 against the reference's own `code/pred_utils.py`, imported UNMODIFIED (its `import
 tensorflow` resolves to the eager shim, which this path never calls).  The same
-deterministic fake Tester feeds both.  Needs /root/reference; skipped elsewhere."""
+deterministic fake Tester feeds both.  What the reference's functions returned is recorded
+in tests/golden/reference_pred_utils.npz (tests/golden/make_reference_records.py)."""
 import argparse
 import importlib
 import os
@@ -15,12 +16,16 @@ from multiverse_amd import pred_utils, synth
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                 "oracle", "tf1_shim"))
-import run_reference as rr  # noqa: E402
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+import reference_records  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not rr.available(), reason="needs the /root/reference checkout")
+BATCH_KEYS = ("obs_traj", "pred_traj", "obs_grid_class", "pred_grid_class",
+              "obs_grid_target_all_0")
+SCENE_KEY = "VIRAT_S_040003_02_000197_000552_F_00001234_P_12"
 
 
 def _reference_pred_utils():
+  import run_reference as rr
   rr.import_reference()                      # puts the TF shim in place
   sys.path.insert(0, rr.REFERENCE_CODE)
   try:
@@ -78,32 +83,77 @@ def _config(tmp_path, use_grids, batch_size):
   return cfg
 
 
-@pytest.mark.parametrize("use_grids", [(1, 1), (1, 0)])
-def test_read_data_batcher_and_evaluate_match_the_reference(tmp_path, use_grids):
-  ref_pu = _reference_pred_utils()
+def _batcher_case(tmp_path, use_grids):
   cfg = _config(tmp_path, use_grids, batch_size=4)
   data = synth.make_npz_data(cfg, 10, seed=21, float32_traj=True)
   np.savez(os.path.join(str(tmp_path), "data_test.npz"), **data)
+  return cfg
 
-  ref_ds = ref_pu.read_data(cfg, "test")
+
+def _per_scene_case(tmp_path):
+  cfg = _config(tmp_path, (0, 1), batch_size=4)
+  cfg.per_scene_eval = True
+  data = synth.make_npz_data(cfg, 10, seed=23, float32_traj=True)
+  cams = ["0000", "0002", "0400", "0401"]                      # "0500" stays empty
+  keys = ["VIRAT_S_%s0%d_0%d_000197_000552_F_%08d_P_%d" % (cams[i % 4], i % 7, i % 3, 100 + i, i)
+          for i in range(10)]
+  n = len(data["obs_traj"])
+  data["obs_boxid"] = np.arange(n * cfg.obs_len, dtype="int64").reshape(n, cfg.obs_len)
+  data["person_boxid2key"] = {int(data["obs_boxid"][i][0]): keys[i] for i in range(n)}
+  np.savez(os.path.join(str(tmp_path), "data_test.npz"), **data)
+  return cfg, cams, keys
+
+
+def record(tmp_dir):
+  """What the reference's read_data / batcher / evaluate / get_scene return in the tests
+  below."""
+  ref_pu = _reference_pred_utils()
+  out = {}
+  for use_grids in ((1, 1), (1, 0)):
+    d = os.path.join(tmp_dir, "grids%d%d" % use_grids)
+    os.makedirs(d)
+    cfg = _batcher_case(d, use_grids)
+    ds = ref_pu.read_data(cfg, "test")
+    batches = []
+    for idx, b in ds.get_batches(4, full=True, shuffle=False):
+      bd = {k: np.asarray(b.data[k]) for k in ("batch_obs_scene", "batch_scene_feat") + BATCH_KEYS}
+      bd["original_batch_size"] = b.data["original_batch_size"]
+      batches.append([tuple(int(i) for i in idx), bd])
+    out["grids%d%d" % use_grids] = {"num_examples": ds.num_examples, "batches": batches,
+                                    "evaluate": ref_pu.evaluate(ds, cfg, None,
+                                                                _NoisyGtTester(cfg))}
+  d = os.path.join(tmp_dir, "per_scene")
+  os.makedirs(d)
+  cfg, _, _ = _per_scene_case(d)
+  ds = ref_pu.read_data(cfg, "test")
+  out["per_scene"] = {"get_scene": ref_pu.get_scene(SCENE_KEY),
+                      "traj_key": list(ds.data["traj_key"]),
+                      "evaluate": ref_pu.evaluate(ds, cfg, None, _NoisyGtTester(cfg))}
+  return out
+
+
+@pytest.mark.parametrize("use_grids", [(1, 1), (1, 0)])
+def test_read_data_batcher_and_evaluate_match_the_reference(tmp_path, use_grids):
+  rec = reference_records.load("pred_utils")["grids%d%d" % use_grids]
+  cfg = _batcher_case(tmp_path, use_grids)
+
   my_ds = pred_utils.read_data(cfg, "test")
-  assert ref_ds.num_examples == my_ds.num_examples == 10
+  assert rec["num_examples"] == my_ds.num_examples == 10
 
   # the batcher: same indices, same padded content, same compacted scene table
-  rb = list(ref_ds.get_batches(4, full=True, shuffle=False))
+  rb = rec["batches"]
   mb = list(my_ds.get_batches(4, full=True, shuffle=False))
   assert len(rb) == len(mb) == 3
   for (ri, r), (mi, m) in zip(rb, mb):
     assert tuple(ri) == tuple(mi)
-    assert r.data["original_batch_size"] == m.data["original_batch_size"]
-    assert (np.asarray(r.data["batch_obs_scene"]) == np.asarray(m.data["batch_obs_scene"])).all()
-    assert (np.asarray(r.data["batch_scene_feat"]) == np.asarray(m.data["batch_scene_feat"])).all()
-    for key in ("obs_traj", "pred_traj", "obs_grid_class", "pred_grid_class",
-                "obs_grid_target_all_0"):
-      assert (np.asarray(r.data[key]) == np.asarray(m.data[key])).all(), key
+    assert r["original_batch_size"] == m.data["original_batch_size"]
+    assert (r["batch_obs_scene"] == np.asarray(m.data["batch_obs_scene"])).all()
+    assert (r["batch_scene_feat"] == np.asarray(m.data["batch_scene_feat"])).all()
+    for key in BATCH_KEYS:
+      assert (r[key] == np.asarray(m.data[key])).all(), key
 
   tester = _NoisyGtTester(cfg)
-  ref_p = ref_pu.evaluate(ref_ds, cfg, None, tester)
+  ref_p = rec["evaluate"]
   my_p = pred_utils.evaluate(my_ds, cfg, None, tester)
   assert sorted(ref_p) == sorted(my_p)
   assert len(ref_p) >= 3
@@ -117,24 +167,13 @@ def test_read_data_batcher_and_evaluate_match_the_reference(tmp_path, use_grids)
 def test_per_scene_eval_matches_the_reference(tmp_path):
   """--per_scene_eval (code/pred_utils.py:374-378, 514-517, 569-578): ADE / FDE per ActEV
   camera, keyed by the scene part of the trajectory key; a camera without samples reports 0."""
-  ref_pu = _reference_pred_utils()
-  assert pred_utils.get_scene("VIRAT_S_040003_02_000197_000552_F_00001234_P_12") == \
-      ref_pu.get_scene("VIRAT_S_040003_02_000197_000552_F_00001234_P_12") == "0400"
-  cfg = _config(tmp_path, (0, 1), batch_size=4)
-  cfg.per_scene_eval = True
-  data = synth.make_npz_data(cfg, 10, seed=23, float32_traj=True)
-  cams = ["0000", "0002", "0400", "0401"]                      # "0500" stays empty
-  keys = ["VIRAT_S_%s0%d_0%d_000197_000552_F_%08d_P_%d" % (cams[i % 4], i % 7, i % 3, 100 + i, i)
-          for i in range(10)]
-  n = len(data["obs_traj"])
-  data["obs_boxid"] = np.arange(n * cfg.obs_len, dtype="int64").reshape(n, cfg.obs_len)
-  data["person_boxid2key"] = {int(data["obs_boxid"][i][0]): keys[i] for i in range(n)}
-  np.savez(os.path.join(str(tmp_path), "data_test.npz"), **data)
-  ref_ds = ref_pu.read_data(cfg, "test")
+  rec = reference_records.load("pred_utils")["per_scene"]
+  assert pred_utils.get_scene(SCENE_KEY) == rec["get_scene"] == "0400"
+  cfg, cams, keys = _per_scene_case(tmp_path)
   my_ds = pred_utils.read_data(cfg, "test")
-  assert list(my_ds.data["traj_key"]) == list(ref_ds.data["traj_key"]) == keys
+  assert list(my_ds.data["traj_key"]) == rec["traj_key"] == keys
   tester = _NoisyGtTester(cfg)
-  ref_p = ref_pu.evaluate(ref_ds, cfg, None, tester)
+  ref_p = rec["evaluate"]
   my_p = pred_utils.evaluate(my_ds, cfg, None, tester)
   assert sorted(ref_p) == sorted(my_p)
   for cam in cams + ["0500"]:

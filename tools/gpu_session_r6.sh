@@ -7,8 +7,8 @@
 #   parallel  tests/test_gpu_parallel.py -s (two ranks on one GPU: gloo, the in-library all-reduce
 #             over tests/fake_rccl in both modes, the dropped-event-wait negative controls)
 #   wino      tests/test_gpu_wino.py -s (kernel-level parity of the gate kernel forms)
-#   bench     the default `python bench.py` line (headline + every sub-workload)
-#   headline  `python bench.py --no-sub` x 2 (same-box repeatability of the headline)
+#   bench     the `python bench.py --full` line (headline + every sub-workload)
+#   headline  `python bench.py --full --no-sub` x 2 (same-box repeatability of the headline)
 #   pmcgreedy rocprofv3 trace + PMC of the greedy workload only
 #   profiles  rocprofv3 traces + PMC of greedy / beam / train / bf16 training (tools/profile_workload.sh)
 #   smoke     __graft_entry__.smoke()
@@ -23,7 +23,7 @@ cd ${GRAFT_REPO_ROOT:-$(pwd)}
 T=$1; shift
 O=gpurun_out/$T
 mkdir -p $O
-BQ="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+BQ="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 line() { python - "$1" <<'PY'
 import json, sys
 try:
@@ -50,7 +50,7 @@ for stage in "$@"; do
       (time timeout 900 python -m pytest tests/test_gpu_wino.py -m gpu -q -s) > $O/wino_tests.log 2>&1
       echo "wino rc $?"; grep -E "passed|failed|error" $O/wino_tests.log | tail -3 ;;
     bench)
-      (time timeout 900 python bench.py) > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+      (time timeout 900 python bench.py --full) > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
       line $O/bench_default.json ;;
     headline)
       for i in 1 2; do timeout 300 $BQ --steps 100 > $O/headline_$i.json 2> $O/headline_$i.err; line $O/headline_$i.json; done ;;

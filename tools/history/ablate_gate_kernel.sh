@@ -15,7 +15,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in "$@"; do
   export MV_LIB_PATH=$ROOT/build/variants/libmv_$v.so
   [ -f $MV_LIB_PATH ] || { echo "missing $MV_LIB_PATH"; continue; }
-  B="python $ROOT/bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+  B="python $ROOT/bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
   timeout 300 $B --steps 30 --warmup 3 > $OUT/$v.bench.json 2> $OUT/$v.bench.err
   rm -rf $OUT/pmc_$v
   timeout 300 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_ANY -d $OUT/pmc_$v -o pmc -- $B --steps 2 --warmup 1 > /dev/null 2> $OUT/$v.pmc.err

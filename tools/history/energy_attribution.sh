@@ -14,7 +14,7 @@ TAG=${1:-r5a}
 STEPS=${2:-500}
 O=gpurun_out/$TAG
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --steps $STEPS --warmup 20"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --steps $STEPS --warmup 20"
 sample() {   # $1 = log; runs until the file $O/stop appears
   while [ ! -e $O/stop ]; do rocm-smi -c -P 2>/dev/null | grep -E "sclk|Power" >> $1; sleep 0.2; done
 }

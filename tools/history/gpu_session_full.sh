@@ -16,9 +16,9 @@ timeout 900 python -m pytest tests -m gpu -q > $O/gpu_tests.log 2>&1; rc=$?
 echo "gpu tests rc $rc"; tail -4 $O/gpu_tests.log
 if [ $rc -ne 0 ]; then grep -E "^(FAILED|ERROR)" $O/gpu_tests.log; fi     # measurements follow either way
 for v in ${AB_GNN:-v2 v3}; do      # AB_GNN=" " skips the A/B
-  MV_GNN=$v timeout 200 python bench.py --workload beam --no-sub --no-cpu-baseline --no-fp32-ref \
+  MV_GNN=$v timeout 200 python bench.py --full --workload beam --no-sub --no-cpu-baseline --no-fp32-ref \
     > $O/beam_gnn_$v.json 2> $O/beam_gnn_$v.err
-  MV_GNN=$v timeout 200 python bench.py --no-sub --no-cpu-baseline --no-fp32-ref \
+  MV_GNN=$v timeout 200 python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref \
     > $O/greedy_gnn_$v.json 2> $O/greedy_gnn_$v.err
 done
 python - <<PY
@@ -38,7 +38,7 @@ bash tools/profile_workload.sh r3_beam --workload beam > $O/prof_beam.log 2>&1
 bash tools/profile_workload.sh r3_train --workload train > $O/prof_train.log 2>&1
 bash tools/profile_workload.sh r3_greedy_bf16 --compute bf16 > $O/prof_bf16.log 2>&1
 grep -h "gnn_attend" gpurun_out/prof_r3_*/kernel_trace_stats.md
-timeout 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+timeout 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))

@@ -10,11 +10,11 @@ timeout 600 python -m pytest tests/test_gpu_wino.py -q -x -s > $O/wino_tests.log
 echo "wino tests rc $rc"; grep -E "winograd|direct|dynamic|passed|failed" $O/wino_tests.log | tail -30
 if [ $rc -ne 0 ]; then tail -60 $O/wino_tests.log; fi
 for w in 0 1; do
-  MV_WINO=$w timeout 300 python bench.py --no-sub --no-cpu-baseline --no-fp32-ref \
+  MV_WINO=$w timeout 300 python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref \
     > $O/greedy_wino$w.json 2> $O/greedy_wino$w.err
-  MV_WINO=$w timeout 300 python bench.py --workload beam --no-sub --no-cpu-baseline --no-fp32-ref \
+  MV_WINO=$w timeout 300 python bench.py --full --workload beam --no-sub --no-cpu-baseline --no-fp32-ref \
     > $O/beam_wino$w.json 2> $O/beam_wino$w.err
-  MV_WINO=$w timeout 300 python bench.py --workload train --no-sub --no-cpu-baseline --no-fp32-ref \
+  MV_WINO=$w timeout 300 python bench.py --full --workload train --no-sub --no-cpu-baseline --no-fp32-ref \
     > $O/train_wino$w.json 2> $O/train_wino$w.err
 done
 python - <<PY

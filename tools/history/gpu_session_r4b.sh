@@ -12,7 +12,7 @@ for v in "4 0" "8 1" "4 1"; do
 done
 timeout 600 python -m pytest tests/test_gpu_parallel.py -q -x -s -k "two_ranks" > $O/parallel.log 2>&1
 echo "parallel rc $?"; grep -E "reduced|parameters after|passed|failed|Error" $O/parallel.log | tail
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for v in "8 0 0" "4 0 0" "8 1 0" "4 1 0" "8 0 1" "8 0 2" "4 0 2"; do
   set -- $v
   MV_WINO_WAVES=$1 MV_WINO_PIPE=$2 MV_WINO_ABL=$3 timeout 300 $B > $O/greedy_w$1_p$2_a$3.json 2> $O/greedy_w$1_p$2_a$3.err

@@ -5,7 +5,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4c
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for v in "8 0 0" "4 0 0" "4 30 0" "4 50 0" "4 70 0" "4 50 1" "4 0 1" "8 0 1"; do
   set -- $v
   MV_WINO_WAVES=$1 MV_WINO_STAGGER=$2 MV_WINO_MAP=$3 timeout 300 $B > $O/greedy_w$1_s$2_m$3.json 2> $O/greedy_w$1_s$2_m$3.err

@@ -5,7 +5,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4d
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --steps 40"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --steps 40"
 for w in 8 4; do
 for a in 0 2 4 8 16 32 12 28 60; do
   MV_WINO_WAVES=$w MV_WINO_ABL=$a timeout 300 $B > $O/greedy_w${w}_a$a.json 2> $O/greedy_w${w}_a$a.err

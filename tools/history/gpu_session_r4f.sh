@@ -7,7 +7,7 @@ O=gpurun_out/r4f
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_f16x3.py -q -x -s > $O/train_tests.log 2>&1
 echo "train tests rc $?"; grep -E "passed|failed|Error|assert" $O/train_tests.log | tail -8
-B="python bench.py --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
 for v in v1 v2; do
   MV_WGRAD=$v timeout 300 $B > $O/train_wgrad_$v.json 2> $O/train_wgrad_$v.err
 done

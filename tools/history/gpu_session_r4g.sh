@@ -6,7 +6,7 @@ O=gpurun_out/r4g
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_f16x3.py -q -x > $O/train_tests.log 2>&1
 echo "train tests rc $?"; tail -3 $O/train_tests.log
-B="python bench.py --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
 timeout 300 $B > $O/train.json 2> $O/train.err
 python - <<PY
 import json

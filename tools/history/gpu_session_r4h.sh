@@ -9,7 +9,7 @@ for w in 8 4; do
   MV_WINO_WAVES=$w timeout 300 python -m pytest tests/test_gpu_wino.py -q -x > $O/wino_tests_w$w.log 2>&1
   echo "wino tests waves $w rc $?"; tail -2 $O/wino_tests_w$w.log
 done
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --steps 40"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --steps 40"
 for v in "8 0" "4 0" "8 4" "8 2"; do
   set -- $v
   MV_WINO_WAVES=$1 MV_WINO_ABL=$2 timeout 300 $B > $O/greedy_w$1_a$2.json 2> $O/greedy_w$1_a$2.err

@@ -8,7 +8,7 @@ T=${1:-r4j}
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train_variants.py -q -x -k "emb128 or hidden" > $O/variants.log 2>&1
 echo "shape variants rc $?"; tail -2 $O/variants.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))

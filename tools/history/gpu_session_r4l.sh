@@ -6,7 +6,7 @@ O=gpurun_out/r4l
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_f16x3.py -q -x -s > $O/train_tests.log 2>&1
 echo "train tests rc $?"; grep -E "passed|failed|Error|assert" $O/train_tests.log | tail -6
-B="python bench.py --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
 for v in 0 1; do
   MV_WINO_DGRAD=$v timeout 300 $B > $O/train_wd$v.json 2> $O/train_wd$v.err
 done

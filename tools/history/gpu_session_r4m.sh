@@ -8,7 +8,7 @@ timeout 900 python -m pytest tests/test_gpu_train.py tests/test_gpu_f16x3.py -q 
 echo "train tests rc $?"; tail -2 $O/train_tests.log
 timeout 600 python -m pytest tests/test_gpu_edge.py -q -x -k "hidden_size or emb_size" > $O/shapes.log 2>&1
 echo "shape tests rc $?"; tail -2 $O/shapes.log
-B="python bench.py --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --workload train --no-sub --no-cpu-baseline --no-fp32-ref"
 for v in 0 1; do
   MV_WINO_DGRAD=$v timeout 300 $B > $O/train_wd$v.json 2> $O/train_wd$v.err
 done

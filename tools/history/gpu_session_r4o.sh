@@ -5,7 +5,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4o
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for w in 8 4; do
   MV_WINO_WAVES=$w timeout 300 $B --steps 60 > $O/greedy_w$w.json 2> $O/greedy_w$w.err
   MV_WINO_WAVES=$w timeout 300 $B --workload beam > $O/beam_w$w.json 2> $O/beam_w$w.err

@@ -8,7 +8,7 @@ O=gpurun_out/r4r
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_forward.py tests/test_gpu_dropin.py tests/test_gpu_f16x3.py tests/test_gpu_reference_pin.py -q -x -m gpu > $O/tests.log 2>&1
 echo "tests rc $?"; tail -3 $O/tests.log
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for rep in 1 2; do
 for v in 0 1; do
   MV_POST_GATE=$v timeout 300 $B --steps 80 > $O/greedy_pg${v}_$rep.json 2> $O/greedy_pg${v}_$rep.err

@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_forward.py tests/test_gpu_f16x3.py t
 echo "tests rc $?"; tail -3 $O/tests.log
 timeout 600 python -m pytest tests/test_gpu_train_variants.py -q -x -m gpu -k "hidden or emb128" > $O/tests_train.log 2>&1
 echo "train variant tests rc $?"; tail -2 $O/tests_train.log
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for rep in 1 2; do
   MV_LIB_PATH=build/variants/libmv_head.so timeout 300 $B --steps 80 > $O/greedy_head_$rep.json 2> $O/greedy_head_$rep.err
   timeout 300 $B --steps 80 > $O/greedy_new_$rep.json 2> $O/greedy_new_$rep.err

@@ -5,7 +5,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4smi2
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 sample() { while [ ! -e $O/stop ]; do rocm-smi -c -P 2>/dev/null | grep -E "sclk|Power" >> $1; sleep 0.25; done; }
 run() {   # $1 = tag, rest = bench args
   T=$1; shift

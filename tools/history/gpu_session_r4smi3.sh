@@ -4,7 +4,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4smi3
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 sample() { while [ ! -e $O/stop ]; do rocm-smi -c -P 2>/dev/null | grep -E "sclk|Power" >> $1; sleep 0.25; done; }
 run() { T=$1; shift; rm -f $O/stop; sample $O/smi_$T.log & SP=$!; timeout 100 $B "$@" > $O/$T.json 2> $O/$T.err; touch $O/stop; wait $SP; }
 run bf16 --compute bf16 --scene-conv-kernel 1 --steps 600

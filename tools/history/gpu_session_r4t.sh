@@ -11,7 +11,7 @@ MV_BF16_BWD=0 timeout 600 python -m pytest tests/test_gpu_bf16.py -q -x -m gpu -
 echo "bf16 tests (f16x3 backward) rc $?"; grep -E "passed|failed|error|cosine|bf16 train" $O/tests_bf16_old.log | tail -4
 timeout 600 python -m pytest tests/test_gpu_train.py tests/test_gpu_edge.py -q -x -m gpu -k "bf16 or mode" > $O/tests_more.log 2>&1
 echo "more tests rc $?"; tail -2 $O/tests_more.log
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --workload train --batch 64 --compute bf16 --scene-conv-kernel 1"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --workload train --batch 64 --compute bf16 --scene-conv-kernel 1"
 MV_BF16_BWD=0 timeout 300 $B > $O/train_bf16_bwd0.json 2> $O/train_bf16_bwd0.err
 timeout 300 $B > $O/train_bf16_bwd1.json 2> $O/train_bf16_bwd1.err
 python - <<PY

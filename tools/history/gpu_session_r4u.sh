@@ -7,7 +7,7 @@ O=gpurun_out/r4u
 mkdir -p $O
 timeout 600 python -m pytest tests/test_gpu_bf16.py -q -x -m gpu -s -k training > $O/tests_bf16.log 2>&1
 echo "bf16 training test rc $?"; grep -E "passed|failed|error|cosine|bf16 train" $O/tests_bf16.log | tail -4
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --workload train --batch 64 --compute bf16 --scene-conv-kernel 1"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --workload train --batch 64 --compute bf16 --scene-conv-kernel 1"
 for k in 4 2 1; do
   MV_DGRAD_KSLICES=$k timeout 300 $B > $O/train_bf16_ks$k.json 2> $O/train_bf16_ks$k.err
 done

@@ -8,7 +8,7 @@ O=gpurun_out/$T
 mkdir -p $O
 timeout 1200 python -m pytest tests -q -x -m gpu > $O/gpu_tests.log 2>&1
 echo "gpu tests rc $?"; tail -3 $O/gpu_tests.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))

@@ -5,7 +5,7 @@ set -u
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 O=gpurun_out/r4w
 mkdir -p $O
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --workload train"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --workload train"
 for k in 24 8 16 32 48; do
   MV_WGRAD_SPLITS=$k timeout 200 $B > $O/train_f16x3_s$k.json 2> $O/train_f16x3_s$k.err
 done

@@ -9,7 +9,7 @@ O=gpurun_out/r4x
 mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_wino.py tests/test_gpu_forward.py tests/test_gpu_f16x3.py tests/test_gpu_at_size.py tests/test_gpu_reference_pin.py tests/test_gpu_bf16.py -q -x -m gpu > $O/tests.log 2>&1
 echo "tests rc $?"; tail -3 $O/tests.log
-B="python bench.py --no-sub --no-cpu-baseline --no-fp32-ref"
+B="python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref"
 for rep in 1 2; do
   MV_LIB_PATH=build/variants/libmv_head.so timeout 300 $B --steps 80 > $O/greedy_head_$rep.json 2> $O/greedy_head_$rep.err
   timeout 300 $B --steps 80 > $O/greedy_new_$rep.json 2> $O/greedy_new_$rep.err

@@ -8,7 +8,7 @@ mkdir -p $O
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc $?"; tail -2 $O/smoke.log
 timeout 600 python -m pytest tests/test_gpu_wino.py tests/test_gpu_kernels.py tests/test_gpu_forward.py -q -x -m gpu > $O/tests.log 2>&1
 echo "tests rc $?"; tail -2 $O/tests.log
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; echo "bench rc $?"
 python - <<PY
 import json
 d = json.load(open("$O/bench_default.json"))

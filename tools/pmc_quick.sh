@@ -16,7 +16,7 @@ mkdir -p $OUT
 i=0
 for ctrs in "$@"; do
   i=$((i + 1))
-  rocprofv3 --kernel-trace --pmc $ctrs -d $OUT -o p$i -- python bench.py --no-sub --no-cpu-baseline --no-fp32-ref "${BA[@]}" --steps 1 --warmup 1 > /dev/null 2> $OUT/p$i.err
+  rocprofv3 --kernel-trace --pmc $ctrs -d $OUT -o p$i -- python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref "${BA[@]}" --steps 1 --warmup 1 > /dev/null 2> $OUT/p$i.err
   python - $OUT/p${i}_results.db "$K" <<'PY'
 import sqlite3, sys
 try:

@@ -11,8 +11,8 @@ i=0
 for kv in "$@"; do
   i=$((i + 1))
   f=$O/train_$i.json
-  if [ "$kv" = "-" ]; then timeout 300 python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --workload train > $f 2> $O/train_$i.err
-  else env $kv timeout 300 python bench.py --no-sub --no-cpu-baseline --no-fp32-ref --workload train > $f 2> $O/train_$i.err; fi
+  if [ "$kv" = "-" ]; then timeout 300 python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --workload train > $f 2> $O/train_$i.err
+  else env $kv timeout 300 python bench.py --full --no-sub --no-cpu-baseline --no-fp32-ref --workload train > $f 2> $O/train_$i.err; fi
   python - $f "$kv" <<'PY'
 import json, sys
 try:
