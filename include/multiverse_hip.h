@@ -48,6 +48,13 @@ typedef struct mv_config {
   int32_t obs_len;           /* T_o */
   int32_t max_pred_len;      /* upper bound of the run-time T_pred */
   int32_t scene_h, scene_w, scene_class;        /* 36, 64, 11 */
+  /* scene_conv_dim 0 = a model built WITHOUT the scene encoder (--use_scene_enc off, the
+   * reference's default graph, code/pred_models.py:146-165, 218-229): no scene stack; the class
+   * encoders take grid_emb(one_hot(labels)) through ONE person_pred/grid_emb/{W [3,3,1,E], b [E]}
+   * shared by the scales, their kernels [k,k,E+C,4C]; the graph attention sees h alone.
+   * scene_conv_kernel and simaug_graph then have no effect; mv_inputs.obs_scene / scene_feat and
+   * mv_inputs_compact.obs_scene / scene_feat_u8 may be NULL and are never read; mv_attack_*,
+   * mv_set/get_scene_feat, mv_get_scene_grad, mv_scene_mix and mv_set_label_mixup fail. */
   int32_t scene_conv_dim, scene_conv_kernel;    /* 64 (a multiple of 32 up to 128), 3 */
   int32_t emb_size;          /* 32 */
   int32_t hidden_size;       /* enc_hidden_size == dec_hidden_size, 256 */

@@ -294,6 +294,11 @@ def activation_code(act):
   return ACTIVATIONS[name]
 
 
+def uses_scene(cfg):
+  """--use_scene_enc: the scene stack feeds the class encoders and the graph attention."""
+  return bool(getattr(cfg, "use_scene_enc", True))
+
+
 def make_config(cfg):
   """argparse.Namespace (after process_args) -> mv_config."""
   c = mv_config()
@@ -303,7 +308,9 @@ def make_config(cfg):
   c.max_pred_len = int(getattr(cfg, "max_pred_len", None) or cfg.pred_len)
   c.scene_h, c.scene_w, c.scene_class = int(cfg.scene_h), int(cfg.scene_w), \
       int(cfg.scene_class)
-  c.scene_conv_dim = int(cfg.scene_conv_dim)
+  # a model built without the scene encoder (--use_scene_enc off, the reference's default
+  # graph, code/pred_models.py:146-165, 218-229) is scene_conv_dim 0 on the C ABI
+  c.scene_conv_dim = int(cfg.scene_conv_dim) if uses_scene(cfg) else 0
   c.scene_conv_kernel = int(cfg.scene_conv_kernel)
   c.emb_size = int(cfg.emb_size)
   if int(cfg.enc_hidden_size) != int(cfg.dec_hidden_size):
@@ -461,13 +468,17 @@ class Engine(object):
     N, T = cfg.batch_size, cfg.obs_len
     inp = mv_inputs()
     keep = []
-    obs_scene = i32(feed["obs_scene"]).reshape(N, T)
-    scene_feat = f32(feed["scene_feat"])
-    keep += [obs_scene, scene_feat]
-    inp.obs_scene = iptr(obs_scene)
-    inp.scene_feat = fptr(scene_feat)
-    inp.num_scene_frames = int(scene_feat.shape[0])
-    self._num_frames = int(scene_feat.shape[0])
+    if uses_scene(cfg):
+      obs_scene = i32(feed["obs_scene"]).reshape(N, T)
+      scene_feat = f32(feed["scene_feat"])
+      keep += [obs_scene, scene_feat]
+      inp.obs_scene = iptr(obs_scene)
+      inp.scene_feat = fptr(scene_feat)
+      inp.num_scene_frames = int(scene_feat.shape[0])
+      self._num_frames = int(scene_feat.shape[0])
+    else:     # no scene encoder: nothing reads the scene arrays, none is handed over
+      inp.num_scene_frames = 0
+      self._num_frames = 0
     inp.pred_len = int(feed.get("pred_length", cfg.pred_len))
     for s, (h, w) in enumerate(cfg.scene_grids):
       if not cfg.use_grids[s]:
@@ -576,18 +587,22 @@ class Engine(object):
     N, T = cfg.batch_size, cfg.obs_len
     if not self._centers_current(feed["grid_centers"]):
       self.set_grid_centers(feed["grid_centers"])
-    scene_any = np.asarray(feed["scene_feat"])
-    if scene_any.dtype != np.uint8 and not ((scene_any == 0) | (scene_any == 1)).all():
-      raise MvError("upload_compact: scene_feat must be 0/1 masks (it is handed over as "
-                    "uint8); use the dense upload for real-valued scene features")
     inp = mv_inputs_compact()
-    obs_scene = i32(feed["obs_scene"]).reshape(N, T)
-    scene = np.ascontiguousarray(np.asarray(feed["scene_feat"]).astype(np.uint8, copy=False))
     xy = np.ascontiguousarray(np.asarray(feed["obs_xy"], dtype=np.float64).reshape(N, T, 2))
-    keep = [obs_scene, scene, xy]
-    inp.obs_scene = iptr(obs_scene)
-    inp.scene_feat_u8 = scene.ctypes.data_as(_u8p)
-    inp.num_scene_frames = int(scene.shape[0])
+    keep = [xy]
+    if uses_scene(cfg):
+      scene_any = np.asarray(feed["scene_feat"])
+      if scene_any.dtype != np.uint8 and not ((scene_any == 0) | (scene_any == 1)).all():
+        raise MvError("upload_compact: scene_feat must be 0/1 masks (it is handed over as "
+                      "uint8); use the dense upload for real-valued scene features")
+      obs_scene = i32(feed["obs_scene"]).reshape(N, T)
+      scene = np.ascontiguousarray(np.asarray(feed["scene_feat"]).astype(np.uint8, copy=False))
+      keep += [obs_scene, scene]
+      inp.obs_scene = iptr(obs_scene)
+      inp.scene_feat_u8 = scene.ctypes.data_as(_u8p)
+      inp.num_scene_frames = int(scene.shape[0])
+    else:
+      inp.num_scene_frames = 0
     inp.pred_len = int(feed.get("pred_length", cfg.pred_len))
     inp.obs_xy = xy.ctypes.data_as(_dp)
     inp.num_rows = int(feed.get("num_rows", N))

@@ -495,6 +495,8 @@ int mv_allreduce_info(mv_handle h, int32_t* rank, int32_t* world, int32_t* bucke
 int mv_attack_begin(mv_handle h) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_attack_begin: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(h->train, "mv_train_init has not been called");
     MV_REQUIRE(h->inputs_ready, "no inputs uploaded");
     TrainState& t = TS(h);
@@ -517,6 +519,8 @@ int mv_attack_end(mv_handle h) {
 int mv_set_scene_feat(mv_handle h, const float* scene_feat) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_set_scene_feat: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(scene_feat && h->inputs_ready, "mv_set_scene_feat: NULL / no inputs uploaded");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
     HIP_CHECK(hipMemcpy(h->scene_feat.p, scene_feat, n * sizeof(float), hipMemcpyHostToDevice));
@@ -526,6 +530,8 @@ int mv_set_scene_feat(mv_handle h, const float* scene_feat) {
 int mv_get_scene_feat(mv_handle h, float* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_get_scene_feat: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(out && h->inputs_ready, "mv_get_scene_feat: NULL / no inputs uploaded");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
     HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -536,6 +542,8 @@ int mv_get_scene_feat(mv_handle h, float* out) {
 int mv_get_scene_grad(mv_handle h, float* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_get_scene_grad: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(h->train && TS(h).have_dscene, "no input gradient (mv_attack_begin, then "
                "mv_train_forward_backward)");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
@@ -547,6 +555,8 @@ int mv_get_scene_grad(mv_handle h, float* out) {
 int mv_attack_step(mv_handle h, float epsilon, float step) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_attack_step: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(h->train && TS(h).have_dscene && TS(h).scene_clean.p,
                "mv_attack_step: mv_attack_begin + mv_train_forward_backward first");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
@@ -559,6 +569,8 @@ int mv_attack_step(mv_handle h, float epsilon, float step) {
 int mv_scene_mix(mv_handle h, const float* other, float weight) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_scene_mix: the model has no scene encoder (scene_conv_dim 0): "
+               "there are no scene features");
     MV_REQUIRE(h->train && h->inputs_ready, "mv_scene_mix: training engine with inputs");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
     TrainState& t = TS(h);
@@ -596,6 +608,8 @@ int mv_set_label_mixup(mv_handle h, const int32_t* const* obs_labels2,
                        const float* sample_weight) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->no_scene(), "mv_set_label_mixup: not built for a model without the scene encoder "
+               "(scene_conv_dim 0)");
     MV_REQUIRE(h->train, "mv_train_init has not been called");
     MV_REQUIRE(obs_labels2 && pred_labels2, "mv_set_label_mixup: NULL argument");
     MV_REQUIRE(weight >= 0.f && weight <= 1.f, "mv_set_label_mixup: weight %g not in [0, 1]",

@@ -383,7 +383,22 @@ void run_encoders(mv_engine* e, Cursors& cur) {
       const size_t total = (size_t)N * S.K * D;
       const bool sparse = sparse_x_on(e, S);
       const size_t nc = (size_t)N * 9 * 4 * c.hidden_size;   // table of one step
-      if (sparse) {
+      if (e->no_scene()) {
+        // x = grid_emb(one_hot(labels[:, t])): table terms of the weights alone (built with
+        // the decoder's, ensure_params), or the dense embedding of this step
+        if (!sparse) {
+          const int E = S.enc_cls.Cx;
+          const size_t tx = (size_t)N * S.K * E;
+          launch(e, "enc_grid_emb_onehot", (double)tx, 4.0 * tx, [&] {
+            size_t pst = 0;
+            _Float16* p16 = e->plane_out(S.xbuf_cls.p, &pst);
+            hipLaunchKernelGGL(mv::enc_grid_emb_onehot_kernel, dim3(cdiv(tx, 256)), dim3(256),
+                               0, e->stream, S.labels.p, T, t, 1, e->enc_emb_W->dev.p,
+                               e->enc_emb_b->dev.p, S.xbuf_cls.p, N, S.H, S.W, E, p16, pst,
+                               c.activation);
+          });
+        }
+      } else if (sparse) {
         if (t == 0)      // the tables of all T_o steps in one launch
           launch(e, "sx_encoder_corr", 2.0 * nc * D * T, 4.0 * nc * T, [&] {
             hipLaunchKernelGGL(mv::sx_encoder_corr_kernel,
@@ -415,7 +430,11 @@ void run_encoders(mv_engine* e, Cursors& cur) {
       // regression encoder's never
       probs.back().skip_h32 =
           (t + 1 < T || (!c.use_gnn && (c.beam_size == 1 || beam_shared_first()))) ? 1 : 0;
-      if (sparse) {
+      if (sparse && e->no_scene()) {   // the decoder's by-class form, radius 2
+        set_sparse_x(e, S, probs.back(), true, S.labels.p + t, T, 1);
+        probs.back().sx_bias = S.sx_enc_bias.p;
+        probs.back().sx_corr = S.sx_enc_tab.p;
+      } else if (sparse) {
         set_sparse_x(e, S, probs.back(), false, S.labels.p + t, T, 1);
         probs.back().sx_corr = S.sx_enc_corr.p + (size_t)t * nc;
       }
@@ -991,7 +1010,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
 void enqueue_forward(mv_engine* e, bool beam) {
   const mv_config& c = e->cfg;
   const int Tp = e->pred_len;
-  run_scene(e);
+  if (!e->no_scene()) run_scene(e);
   Cursors cur;
   run_encoders(e, cur);
   if (beam) {

@@ -7,23 +7,26 @@ namespace {
 void upload_inputs(mv_engine* e, const mv_inputs* in) {
   const mv_config& c = e->cfg;
   const size_t N = c.batch_size, T = c.obs_len;
-  MV_REQUIRE(in->obs_scene && in->scene_feat, "obs_scene / scene_feat is NULL");
-  MV_REQUIRE(in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T,
+  const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
+  MV_REQUIRE(!scene || (in->obs_scene && in->scene_feat), "obs_scene / scene_feat is NULL");
+  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
              "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
   MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
              "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
-  for (size_t i = 0; i < N * T; ++i)
+  for (size_t i = 0; scene && i < N * T; ++i)
     MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
                "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
                in->num_scene_frames);
-  e->num_frames = in->num_scene_frames;
+  e->num_frames = scene ? in->num_scene_frames : 0;
   e->pred_len = in->pred_len;
-  HIP_CHECK(hipMemcpyAsync(e->obs_scene.p, in->obs_scene, N * T * sizeof(int32_t),
-                           hipMemcpyHostToDevice, e->stream));
-  HIP_CHECK(hipMemcpyAsync(e->scene_feat.p, in->scene_feat,
-                           (size_t)e->num_frames * c.scene_h * c.scene_w *
-                               c.scene_class * sizeof(float),
-                           hipMemcpyHostToDevice, e->stream));
+  if (scene) {
+    HIP_CHECK(hipMemcpyAsync(e->obs_scene.p, in->obs_scene, N * T * sizeof(int32_t),
+                             hipMemcpyHostToDevice, e->stream));
+    HIP_CHECK(hipMemcpyAsync(e->scene_feat.p, in->scene_feat,
+                             (size_t)e->num_frames * c.scene_h * c.scene_w *
+                                 c.scene_class * sizeof(float),
+                             hipMemcpyHostToDevice, e->stream));
+  }
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
@@ -47,28 +50,31 @@ void upload_inputs(mv_engine* e, const mv_inputs* in) {
 void upload_inputs_compact(mv_engine* e, const mv_inputs_compact* in) {
   const mv_config& c = e->cfg;
   const size_t N = c.batch_size, T = c.obs_len;
-  MV_REQUIRE(in->obs_scene && in->scene_feat_u8 && in->obs_xy,
+  const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
+  MV_REQUIRE(in->obs_xy && (!scene || (in->obs_scene && in->scene_feat_u8)),
              "obs_scene / scene_feat_u8 / obs_xy is NULL");
-  MV_REQUIRE(in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T,
+  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
              "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
   MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
              "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
   MV_REQUIRE(in->num_rows >= 0 && (size_t)in->num_rows <= N, "num_rows %d not in [0, N=%zu]",
              in->num_rows, N);
-  for (size_t i = 0; i < N * T; ++i)
+  for (size_t i = 0; scene && i < N * T; ++i)
     MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
                "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
                in->num_scene_frames);
-  e->num_frames = in->num_scene_frames;
+  e->num_frames = scene ? in->num_scene_frames : 0;
   e->pred_len = in->pred_len;
-  HIP_CHECK(hipMemcpyAsync(e->obs_scene.p, in->obs_scene, N * T * sizeof(int32_t),
-                           hipMemcpyHostToDevice, e->stream));
-  const size_t nscene = (size_t)e->num_frames * c.scene_h * c.scene_w * c.scene_class;
-  e->scene_u8.alloc(N * T * c.scene_h * c.scene_w * c.scene_class);
-  HIP_CHECK(hipMemcpyAsync(e->scene_u8.p, in->scene_feat_u8, nscene, hipMemcpyHostToDevice,
-                           e->stream));
-  hipLaunchKernelGGL(mv::u8_to_f32_kernel, dim3(cdiv(nscene, 256)), dim3(256), 0, e->stream,
-                     e->scene_u8.p, e->scene_feat.p, nscene);
+  if (scene) {
+    HIP_CHECK(hipMemcpyAsync(e->obs_scene.p, in->obs_scene, N * T * sizeof(int32_t),
+                             hipMemcpyHostToDevice, e->stream));
+    const size_t nscene = (size_t)e->num_frames * c.scene_h * c.scene_w * c.scene_class;
+    e->scene_u8.alloc(N * T * c.scene_h * c.scene_w * c.scene_class);
+    HIP_CHECK(hipMemcpyAsync(e->scene_u8.p, in->scene_feat_u8, nscene, hipMemcpyHostToDevice,
+                             e->stream));
+    hipLaunchKernelGGL(mv::u8_to_f32_kernel, dim3(cdiv(nscene, 256)), dim3(256), 0,
+                       e->stream, e->scene_u8.p, e->scene_feat.p, nscene);
+  }
   e->xy_dev.alloc(2 * N * std::max<size_t>(T, c.max_pred_len));
   HIP_CHECK(hipMemcpyAsync(e->xy_dev.p, in->obs_xy, 2 * N * T * sizeof(double),
                            hipMemcpyHostToDevice, e->stream));
@@ -130,7 +136,8 @@ static PipeLayout pipe_layout(const mv_engine* e) {
   PipeLayout L;
   size_t o = 0;
   L.obs_scene = o; o = al(o + N * T * sizeof(int32_t));
-  L.scene_feat = o; o = al(o + N * T * c.scene_h * c.scene_w * c.scene_class * sizeof(float));
+  const size_t frames = e->no_scene() ? 0 : N * T;     // no scene encoder: no scene block
+  L.scene_feat = o; o = al(o + frames * c.scene_h * c.scene_w * c.scene_class * sizeof(float));
   for (int s = 0; s < c.num_scales; ++s) {
     if (!e->sc[s].use) continue;
     const size_t K = e->sc[s].K;
@@ -187,21 +194,24 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
   mv_engine::PipeSlot& sl = e->pipe[e->pipe_head % e->pipe.size()];
   MV_REQUIRE(!sl.busy, "pipeline full: %zu submissions not collected (mv_collect_greedy)",
              e->pipe.size());
-  MV_REQUIRE(in->obs_scene && in->scene_feat, "obs_scene / scene_feat is NULL");
-  MV_REQUIRE(in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T,
+  const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
+  MV_REQUIRE(!scene || (in->obs_scene && in->scene_feat), "obs_scene / scene_feat is NULL");
+  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
              "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
   MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
              "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
-  for (size_t i = 0; i < N * T; ++i)
+  for (size_t i = 0; scene && i < N * T; ++i)
     MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
                "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
                in->num_scene_frames);
   const PipeLayout L = pipe_layout(e);
   char* pin = static_cast<char*>(sl.pin);
-  const size_t sf_bytes = (size_t)in->num_scene_frames * c.scene_h * c.scene_w *
-                          c.scene_class * sizeof(float);
-  memcpy(pin + L.obs_scene, in->obs_scene, N * T * sizeof(int32_t));
-  memcpy(pin + L.scene_feat, in->scene_feat, sf_bytes);
+  const size_t sf_bytes = scene ? (size_t)in->num_scene_frames * c.scene_h * c.scene_w *
+                                      c.scene_class * sizeof(float) : 0;
+  if (scene) {
+    memcpy(pin + L.obs_scene, in->obs_scene, N * T * sizeof(int32_t));
+    memcpy(pin + L.scene_feat, in->scene_feat, sf_bytes);
+  }
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
@@ -214,7 +224,7 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
     memcpy(pin + L.labels[s], in->grid_obs_labels[s], N * T * sizeof(int32_t));
     memcpy(pin + L.obs_reg[s], in->grid_obs_regress[s], N * T * S.K * 2 * sizeof(float));
   }
-  sl.num_frames = in->num_scene_frames; sl.pred_len = in->pred_len;
+  sl.num_frames = scene ? in->num_scene_frames : 0; sl.pred_len = in->pred_len;
   // copy stream: the whole input block in one transfer (it must not start before the
   // slot's previous fetch has left the same pinned / staging buffers: collect waited d2h)
   HIP_CHECK(hipMemcpyAsync(sl.dev, sl.pin, L.in_bytes, hipMemcpyHostToDevice, e->copy_stream));
@@ -224,8 +234,10 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
   auto d2d = [&](void* dst, const void* src, size_t n) {
     HIP_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, e->stream));
   };
-  d2d(e->obs_scene.p, sl.dev + L.obs_scene, N * T * sizeof(int32_t));
-  d2d(e->scene_feat.p, sl.dev + L.scene_feat, sf_bytes);
+  if (scene) {
+    d2d(e->obs_scene.p, sl.dev + L.obs_scene, N * T * sizeof(int32_t));
+    d2d(e->scene_feat.p, sl.dev + L.scene_feat, sf_bytes);
+  }
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;

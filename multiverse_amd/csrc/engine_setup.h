@@ -101,7 +101,13 @@ void build_param_table(mv_engine* e) {
                 k = c.convlstm_kernel, sk = c.scene_conv_kernel;
   int64_t cin = c.scene_class;
   char nm[256];
-  for (int i = 0; i < c.num_scales; ++i) {
+  if (e->no_scene()) {
+    // no scene stack; the class encoders embed the one-hot map through ONE grid_emb shared by
+    // the scales (scope "grid_emb" under person_pred, AUTO_REUSE: code/pred_models.py:218-229)
+    e->enc_emb_W = e->add_param("person_pred/grid_emb/W", {3, 3, 1, E});
+    e->enc_emb_b = e->add_param("person_pred/grid_emb/b", {E});
+  }
+  for (int i = 0; i < c.num_scales && !e->no_scene(); ++i) {
     snprintf(nm, sizeof(nm), "person_pred/scene_conv%d/W", i + 1);
     e->scene_W.push_back(e->add_param(nm, {sk, sk, cin, D}));
     snprintf(nm, sizeof(nm), "person_pred/scene_conv%d/b", i + 1);
@@ -121,7 +127,7 @@ void build_param_table(mv_engine* e) {
                                {k, k, Cx + C, 4 * C});
       cc.biases = e->add_param(std::string("person_pred/") + base + "/biases", {4 * C});
     };
-    cell(S.enc_cls, "encoder_grid_class_%d/enc_grid_%d", D);
+    cell(S.enc_cls, "encoder_grid_class_%d/enc_grid_%d", e->no_scene() ? E : D);
     cell(S.enc_reg, "encoder_grid_reg_%d/enc_grid_regress_%d", 2);
     cell(S.dec_cls, "decoder_grid_class_%d/decoder_rnn/dec_grid_%d", E);
     snprintf(nm, sizeof(nm), "person_pred/decoder_grid_class_%d/decoder_rnn/grid_emb/W", s);
@@ -178,9 +184,12 @@ void validate_config(const mv_config& c) {
   // --scene_conv_dim (code/train.py:69): whole 32-channel chunks of the class encoder's x
   // operand; above 64 the graph attention takes its one-wave-per-cell form (two scene
   // channels per lane) and the class encoder its dense x operand
-  MV_REQUIRE(c.scene_conv_dim > 0 && c.scene_conv_dim <= 128 &&
-             mv::convlstm_cx_supported(c.scene_conv_dim),
-             "scene_conv_dim %d unsupported (a multiple of 32 up to 128)", c.scene_conv_dim);
+  // (0: a model built without the scene encoder, the reference's default graph)
+  MV_REQUIRE(c.scene_conv_dim == 0 ||
+             (c.scene_conv_dim > 0 && c.scene_conv_dim <= 128 &&
+              mv::convlstm_cx_supported(c.scene_conv_dim)),
+             "scene_conv_dim %d unsupported (0 = no scene encoder, or a multiple of 32 up to "
+             "128)", c.scene_conv_dim);
   // the decoders' x operand: whole 32-channel chunks of the gate GEMM, 16-byte plane vectors
   // and the decode tail's LDS (decode_tail.h) -- checked here, not at the first decode step
   MV_REQUIRE(c.emb_size >= 32 && c.emb_size % 32 == 0 && c.emb_size <= 512 &&
@@ -211,20 +220,24 @@ void alloc_buffers(mv_engine* e) {
   const size_t N = c.batch_size, T = c.obs_len, Tp = c.max_pred_len,
                C = c.hidden_size, D = c.scene_conv_dim, B = c.beam_size;
   const size_t maxU = N * T;
+  const bool scene = !e->no_scene();     // no scene encoder: no scene inputs, no scene stack
   e->obs_scene.alloc(N * T);
-  e->scene_feat.alloc(maxU * c.scene_h * c.scene_w * c.scene_class);
+  if (scene) e->scene_feat.alloc(maxU * c.scene_h * c.scene_w * c.scene_class);
   int hh = c.scene_h, ww = c.scene_w;
   for (int i = 0; i < c.num_scales; ++i) {
     hh = (hh + 1) / 2; ww = (ww + 1) / 2;
     e->conv_h.push_back(hh); e->conv_w.push_back(ww);
-    e->scene_conv[i].alloc(maxU * hh * ww * D);
+    if (scene) e->scene_conv[i].alloc(maxU * hh * ww * D);
   }
   const size_t xc = (size_t)std::max((int)D, c.emb_size);
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
     const size_t K = S.K, R = N * B;
-    S.scene_mean.alloc(N * K * D);
+    // (no scene encoder: the graph attention reads no scene channels; one zeroed channel
+    // keeps its scene-mean pointer valid)
+    S.scene_mean.alloc(N * K * std::max<size_t>(D, 1));
+    if (!scene) HIP_CHECK(hipMemset(S.scene_mean.p, 0, N * K * sizeof(float)));
     S.labels.alloc(N * T);
     S.obs_reg.alloc(N * T * K * 2);
     for (int i = 0; i < 2; ++i) {
@@ -242,7 +255,8 @@ void alloc_buffers(mv_engine* e) {
     S.wq_cls.alloc(C * 32); S.wq_reg.alloc(C * 32);
     S.sx_cellyx.alloc(K);
     S.sx_dec_bias.alloc(9 * 4 * C); S.sx_dec_corr.alloc(9 * 25 * 4 * C);
-    S.sx_enc_corr.alloc(T * N * 9 * 4 * C);
+    if (scene) S.sx_enc_corr.alloc(T * N * 9 * 4 * C);
+    else { S.sx_enc_bias.alloc(9 * 4 * C); S.sx_enc_tab.alloc(9 * 25 * 4 * C); }
     if (B > 1) {
       e->bm_logits.alloc(Tp * R * K);
       e->bm_ids.alloc(Tp * R);
@@ -514,6 +528,12 @@ void ensure_params(mv_engine* e) {
                          S.dec_cls.kernel->dev.p, S.dec_cls.biases->dev.p, S.emb_cls_W->dev.p,
                          S.emb_cls_b->dev.p, S.dec_cls.Cx, C, S.sx_dec_bias.p, S.sx_dec_corr.p,
                          e->cfg.activation);
+      if (e->no_scene())   // the class encoder's x is grid_emb(one_hot) too: the same tables
+        hipLaunchKernelGGL(mv::sx_decoder_tables_kernel,
+                           dim3(cdiv((size_t)(9 + 9 * 25) * 4 * C, 256)), dim3(256), 0,
+                           e->stream, S.enc_cls.kernel->dev.p, S.enc_cls.biases->dev.p,
+                           e->enc_emb_W->dev.p, e->enc_emb_b->dev.p, S.enc_cls.Cx, C,
+                           S.sx_enc_bias.p, S.sx_enc_tab.p, e->cfg.activation);
       S.sx_valid = true;
     }
   }

@@ -137,6 +137,9 @@ struct ScaleState {
   DevBuf<uint32_t> sx_cellyx;               // [K] y << 16 | x
   DevBuf<float> sx_dec_bias, sx_dec_corr;   // [9][4C], [9][25][4C]: functions of the weights
   DevBuf<float> sx_enc_corr;                // [T_o][N][9][4C]: every encoder step
+  // no scene encoder (scene_conv_dim 0): the class encoder's x is grid_emb(one_hot) as the
+  // decoder's -- by-class tables of the encoder kernel and the shared person_pred/grid_emb
+  DevBuf<float> sx_enc_bias, sx_enc_tab;    // [9][4C], [9][25][4C]
   bool sx_valid = false;
 };
 
@@ -151,6 +154,10 @@ struct mv_engine {
   Param* decode_reg_W = nullptr;   // --use_single_decoder: the offset kernel shared by the scales
   std::map<std::string, Param*> by_name;
   std::vector<Param*> scene_W, scene_b;
+  // no scene encoder (mv_config.scene_conv_dim == 0): the class encoders' input embedding
+  // person_pred/grid_emb/{W,b}, ONE pair shared by the scales (code/pred_models.py:218-229)
+  Param *enc_emb_W = nullptr, *enc_emb_b = nullptr;
+  bool no_scene() const { return cfg.scene_conv_dim == 0; }
   ScaleState sc[MV_MAX_SCALES];
   // inputs
   DevBuf<int32_t> obs_scene;       // [N, T_o]

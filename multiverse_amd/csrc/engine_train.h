@@ -173,7 +173,7 @@ void train_alloc(mv_engine* e) {
     if (c.use_gnn) {
       R.hg.alloc(Tp * NK * C, mv::kWgradPad);
       R.gnn_a.alloc(NK * 9); R.gnn_de.alloc(NK * 9); R.gnn_n.alloc(NK);
-      R.dsmean.alloc(NK * D);
+      R.dsmean.alloc(NK * std::max<size_t>(D, 1));   // (no scene encoder: no scene channels)
     }
     R.logits.alloc(Tp * NK); R.regio.alloc((Tp + 1) * NK * 2);
     R.ids.alloc(Tp * N); R.onehot.alloc(Tp * NK);
@@ -189,7 +189,7 @@ void train_alloc(mv_engine* e) {
     max_partial = std::max(max_partial, (size_t)1088 * 4 * C);   // run_colsum: 1024 + 32 fold rows
     (void)E;
   }
-  for (int i = 0; i < c.num_scales; ++i) {
+  for (int i = 0; i < c.num_scales && !e->no_scene(); ++i) {
     const size_t n = (size_t)N * To * e->conv_h[i] * e->conv_w[i] * D;
     t.dys[i].alloc(n); t.dpre_sc[i].alloc(n);
   }
@@ -552,7 +552,22 @@ void train_forward(mv_engine* e) {
   const bool reg_tf = t.tc.reg_teacher_forcing != 0;
   const int nb = c.use_single_decoder ? 1 : 2;   // branches run: class (+ regression)
   train_prepare_targets(e);
-  run_scene(e);
+  if (!e->no_scene()) run_scene(e);
+  else {
+    // no scene encoder: the class encoders' x of all T_o steps, time-major, in one launch per
+    // scale (the shared person_pred/grid_emb; dropout below, per step)
+    for (int s = 0; s < c.num_scales; ++s) {
+      ScaleState& S = e->sc[s];
+      if (!S.use) continue;
+      const size_t tx = (size_t)To * N * S.K * E;
+      launch(e, "enc_grid_emb_onehot", (double)tx, 4.0 * tx, [&] {
+        hipLaunchKernelGGL(mv::enc_grid_emb_onehot_kernel, dim3(cdiv(tx, 256)), dim3(256), 0,
+                           e->stream, S.labels.p, To, 0, To, e->enc_emb_W->dev.p,
+                           e->enc_emb_b->dev.p, t.sc[s].enc[0].xs.p, N, S.H, S.W, E,
+                           (_Float16*)nullptr, (size_t)0, c.activation);
+      });
+    }
+  }
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
@@ -571,8 +586,10 @@ void train_forward(mv_engine* e) {
       if (!S.use) continue;
       TrainScale& R = t.sc[s];
       const size_t NKC = (size_t)N * S.K * C;
-      float* xc = R.enc[0].xs.p + (size_t)ts * N * S.K * D;
-      const size_t total = (size_t)N * S.K * D;
+      const int Cx = R.enc[0].Cx;          // D, or E without the scene encoder
+      float* xc = R.enc[0].xs.p + (size_t)ts * N * S.K * Cx;
+      const size_t total = (size_t)N * S.K * Cx;
+      if (!e->no_scene())
       launch(e, "enc_class_input", 0, 4.0 * total, [&] {
         hipLaunchKernelGGL(mv::enc_class_input_kernel, dim3(cdiv(total, 256)), dim3(256),
                            0, e->stream, e->scene_conv[s].p, e->obs_scene.p, S.labels.p,
@@ -1417,7 +1434,8 @@ void train_backward(mv_engine* e) {
         slots.push_back(gs);
         ConvLstmArgs a;
         mv::convlstm_dgrad_args(a, G, R.enc[b].wdpack.p, dh_b[s][b],
-                                need_dx ? R.enc[b].dxs.p + (size_t)ts * NK * D : nullptr,
+                                need_dx ? R.enc[b].dxs.p + (size_t)ts * NK * R.enc[b].Cx
+                                        : nullptr,
                                 N, S.H, S.W, R.enc[b].Cx, C, need_dh, need_dx);
         probs.push_back(a);
         flops.push_back(2.0 * NK * 9 * ((need_dx ? R.enc[b].Cx : 0) + C) * 4.0 * C);
@@ -1427,12 +1445,14 @@ void train_backward(mv_engine* e) {
     for (int s = 0; s < c.num_scales; ++s) {
       if (!e->sc[s].use) continue;
       for (int b = 0; b < 2; ++b) std::swap(dh_a[s][b], dh_b[s][b]);
-      run_dropout(e, t.sc[s].enc[0].dxs.p + (size_t)ts * N * e->sc[s].K * D,
-                  (size_t)N * e->sc[s].K * D, s, 0, ts);
+      const int Cx = t.sc[s].enc[0].Cx;
+      run_dropout(e, t.sc[s].enc[0].dxs.p + (size_t)ts * N * e->sc[s].K * Cx,
+                  (size_t)N * e->sc[s].K * Cx, s, 0, ts);
     }
   }
   // ---- parameter gradients
   bool single_first_done = false;
+  bool enc_emb_done = false;       // no scene encoder: the shared grid_emb's first scale
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
@@ -1444,6 +1464,40 @@ void train_backward(mv_engine* e) {
       const float* hin = (b == 0 && c.use_gnn) ? R.hg.p : R.hs[b].p + (size_t)To * NKC;
       run_wgrad(e, R.dec[b], hin, Tp, S.H, S.W, (2 * s + b) * 64);
       comm_reduce_cell(e, *R.dec[b].cell);
+    }
+    if (e->no_scene()) {
+      // class-encoder grid_emb (shared by the scales): d x -> d pre-activation in place (xs
+      // holds the DROPPED embedding: the scaled form recovers the output where the mask
+      // kept it), then dW from the 9 cells around each hot cell and db = column sums.
+      // Scale 0 writes, scale 1 adds: a fixed order, bitwise reproducible.  The pair rides
+      // in the closing "rest" all-reduce group, after both scales (comm_reduce_rest_and_join)
+      const int E2 = R.enc[0].Cx;
+      const size_t tot = (size_t)To * NK * E2;
+      float* dx = R.enc[0].dxs.p;
+      launch(e, "tanh_bwd", 3.0 * tot, 12.0 * tot, [&] {
+        if (t.tc.keep_prob < 1.0f)
+          hipLaunchKernelGGL(mv::tanh_bwd_scaled_kernel, dim3(cdiv(tot, 256)), dim3(256), 0,
+                             e->stream, dx, R.enc[0].xs.p, dx, tot, t.tc.keep_prob,
+                             e->cfg.activation);
+        else
+          hipLaunchKernelGGL(mv::tanh_bwd_kernel, dim3(cdiv(tot, 256)), dim3(256), 0,
+                             e->stream, dx, R.enc[0].xs.p, dx, tot, e->cfg.activation);
+      });
+      const bool first = !enc_emb_done;
+      launch(e, "grid_emb_onehot_wgrad", 9.0 * To * N * E2, 4.0 * 9 * To * N * E2, [&] {
+        hipLaunchKernelGGL(mv::grid_emb_onehot_wgrad_kernel, dim3(9, E2 / 32), dim3(256), 0,
+                           e->stream, dx, S.labels.p, N, To, S.H, S.W, E2,
+                           grad_of(e, e->enc_emb_W), first ? 0 : 1);
+      });
+      if (first) {
+        run_colsum(e, dx, (size_t)To * NK, E2, grad_of(e, e->enc_emb_b), t.partial.p);
+      } else {      // (single_w: scratch of >= 9 C 2 floats)
+        run_colsum(e, dx, (size_t)To * NK, E2, t.single_w.p, t.partial.p);
+        hipLaunchKernelGGL(mv::add_scaled_kernel, dim3(cdiv((size_t)E2, 256)), dim3(256), 0,
+                           e->stream, grad_of(e, e->enc_emb_b), t.single_w.p, 1.0f,
+                           (size_t)E2);
+      }
+      enc_emb_done = true;
     }
     // class-decoder grid_emb: its input maps of all steps, [Tp][N][K] -- slot 0 the
     // one-hot of the last observed cell, slot t the one-hot argmax / the logits of step
@@ -1495,8 +1549,8 @@ void train_backward(mv_engine* e) {
       }
     }
   }
-  // ---- scene stack
-  const int U = e->num_frames, L = c.num_scales, k = c.scene_conv_kernel;
+  // ---- scene stack (none without the scene encoder)
+  const int U = e->num_frames, L = e->no_scene() ? 0 : c.num_scales, k = c.scene_conv_kernel;
   for (int i = L - 1; i >= 0; --i) {
     const int Ho = e->conv_h[i], Wo = e->conv_w[i];
     const int Hi = i == 0 ? c.scene_h : e->conv_h[i - 1];

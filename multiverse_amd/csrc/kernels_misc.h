@@ -251,6 +251,74 @@ __global__ void grid_emb_onehot_kernel(const int32_t* __restrict__ ids,
   emit_planes(p16, p16_stride, idx, E, v);
 }
 
+// Class-encoder input of a model built WITHOUT the scene encoder (code/pred_models.py:218-229):
+// x_t = act(grid_emb(one_hot(labels[:, t])) + b) through the ONE person_pred/grid_emb shared by
+// the scales, in the closed form of grid_emb_onehot_kernel, for the steps t0 .. t0 + nsteps - 1
+// in one launch: out [nsteps][N][H][W][E] time-major (the training chain's x of every step, or
+// one step of the inference x buffer with its operand planes through p16).  labels [N][T].
+__global__ void enc_grid_emb_onehot_kernel(const int32_t* __restrict__ labels, int T, int t0,
+                                           int nsteps, const float* __restrict__ w,
+                                           const float* __restrict__ b,
+                                           float* __restrict__ out, int N, int H, int W, int E,
+                                           _Float16* p16 = nullptr, size_t p16_stride = 0,
+                                           int act = 0) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = H * W;
+  const size_t total = (size_t)nsteps * N * K * E;
+  if (idx >= total) return;
+  const int e = idx % E;
+  size_t r = idx / E;
+  const int cell = r % K; r /= K;
+  const int n = r % N;
+  const int ts = r / N;
+  const int id = labels[(size_t)n * T + t0 + ts];
+  const int py = id / W, px = id - py * W;
+  const int yy = cell / W, xx = cell - yy * W;
+  const int dy = yy - py, dx = xx - px;
+  float acc = 0.f;
+  if (dy >= -1 && dy <= 1 && dx >= -1 && dx <= 1)
+    acc = w[((1 - dy) * 3 + (1 - dx)) * E + e];
+  const float v = act_apply(act, acc + b[e]);
+  out[idx] = v;
+  emit_planes(p16, p16_stride, idx, E, v);
+}
+
+// Weight gradient of that embedding: a 3x3 conv whose input is one-hot sees tap (ky, kx) only
+// at the cell hot - (ky - 1, kx - 1), so
+//   dW[ky][kx][e] = sum over (t, n) of dpre[t][n][hot(n, t) - (ky - 1, kx - 1)][e]
+// (cells outside the image skipped): 9 cells per map instead of the whole grid.  dpre
+// [T][N][H][W][E] time-major (d pre-activation), labels [N][T].  One workgroup per (tap, 32
+// columns): 8 row groups of 32 lanes sum rows m = g, g + 8, .. in order, then the 8 partials
+// are added in a fixed order -- bitwise reproducible.  accumulate: dw += the sum (the second
+// scale onto the first: the encoders of both scales share the variable).
+constexpr int kEmbWgradGroups = 8;
+__global__ __launch_bounds__(256)
+void grid_emb_onehot_wgrad_kernel(const float* __restrict__ dpre,
+                                  const int32_t* __restrict__ labels, int N, int T, int H,
+                                  int W, int E, float* __restrict__ dw, int accumulate) {
+  __shared__ float part[kEmbWgradGroups][32];
+  const int tap = blockIdx.x, ky = tap / 3, kx = tap - ky * 3;
+  const int lane = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const int e = blockIdx.y * 32 + lane;      // E is a multiple of 32 (validate_config)
+  const int K = H * W, M = T * N;
+  float s = 0.f;
+  for (int m = g; m < M; m += kEmbWgradGroups) {
+    const int t = m / N, n = m - t * N;
+    const int id = labels[(size_t)n * T + t];
+    const int py = id / W, px = id - py * W;
+    const int y = py - (ky - 1), x = px - (kx - 1);
+    if (y < 0 || y >= H || x < 0 || x >= W) continue;
+    s += dpre[((size_t)m * K + (size_t)y * W + x) * E + e];
+  }
+  part[g][lane] = s;
+  __syncthreads();
+  if (g != 0) return;
+  float tot = part[0][lane];
+  for (int i = 1; i < kEmbWgradGroups; ++i) tot += part[i][lane];
+  float* dst = dw + (size_t)tap * E + e;
+  *dst = accumulate ? *dst + tot : tot;
+}
+
 // ---------------------------------------------------------------- graph attention
 // h_out = h + sum_j softmax_j(<f_i, f_j>) h_j over the <= 9 in-bounds 3x3
 // neighbours, f = l2_normalize([h ; scene_mean]).  The reference builds the

@@ -243,8 +243,7 @@ class Model(object):
     """Same unsupported-combination asserts as the reference graph builder
     (code/pred_models.py:261-262) plus the engine's own scope limits."""
     _lib.activation_code(getattr(config, "activation_func", "tanh"))   # tanh / relu / lrelu
-    if not getattr(config, "use_scene_enc", True):
-      raise _lib.MvError("only the published --use_scene_enc wiring is built")
+    # (--use_scene_enc off builds the reference's default graph: scene_conv_dim 0 on the ABI)
     if getattr(config, "use_beam_search", False):
       assert not getattr(config, "is_train", False)
       assert sum(config.use_grids) == 1, "only one scale test at a time"

@@ -95,11 +95,20 @@ def param_shapes(cfg):
   D = cfg.scene_conv_dim
   E = cfg.emb_size
   shapes = {}
-  cin = cfg.scene_class
-  for i in range(len(cfg.scene_grid_strides)):
-    shapes["person_pred/scene_conv%d/W" % (i + 1)] = (sk, sk, cin, D)
-    shapes["person_pred/scene_conv%d/b" % (i + 1)] = (D,)
-    cin = D
+  if getattr(cfg, "use_scene_enc", True):
+    cin = cfg.scene_class
+    for i in range(len(cfg.scene_grid_strides)):
+      shapes["person_pred/scene_conv%d/W" % (i + 1)] = (sk, sk, cin, D)
+      shapes["person_pred/scene_conv%d/b" % (i + 1)] = (D,)
+      cin = D
+  else:
+    # no scene encoder (code/pred_models.py:146-165 skipped): the class encoders embed the
+    # one-hot map with ONE grid_emb shared by the scales (scope "grid_emb" under person_pred
+    # with AUTO_REUSE, :218-229) -- not the decoders' grid_emb -- and their kernels take
+    # emb_size input channels
+    shapes["person_pred/grid_emb/W"] = (3, 3, 1, E)
+    shapes["person_pred/grid_emb/b"] = (E,)
+    D = E
   for s, use in enumerate(cfg.use_grids):
     if not use:
       continue
