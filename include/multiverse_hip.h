@@ -253,6 +253,25 @@ int  mv_run_beam_resident(mv_handle h);
 int  mv_synchronize(mv_handle h);
 int  mv_download_outputs(mv_handle h, mv_outputs* out);
 int  mv_download_beam_outputs(mv_handle h, mv_beam_outputs* out);
+/* Multi-future decode of the LAST forward, on the device (code/multifuture_inference.py:475-517,
+ * code/multifuture_eval_trajs_prob.py:19-34, 88-93): what a caller wants from a decode is
+ * [N, B, T_p, 2] trajectories and, for the grid-NLL evaluation, one [N, T_p, K] occupancy map,
+ * not every beam's logits.  Both calls run on the handle's stream behind whatever forward was
+ * queued (mv_run_*_resident, mv_forward_*), copy their result to `out` and synchronise.
+ * mv_decode_trajectories: out[n, b, t, :] = centre[id] (+ offset[n, t, id, :] unless
+ *   center_only), doubles, B = beam_size; id = the beam's cell on a beam handle (its single
+ *   active scale; `scale` is ignored), argmax_k of the class logits of `scale` (first index of
+ *   the maximum) on a greedy handle (B = 1).  The centres are those of mv_set_grid_centers;
+ *   double centre + widened float offset is the reference's own operation: bit-identical.
+ * mv_beam_occupancy (beam handles): out[n, t, k] = sum_b softmax_b(logprobs[n, :])[b] *
+ *   softmax_k(logits[n, b, t, :])[k], float32 throughout, bitwise reproducible.
+ * Errors: no forward has run; the centres of the scale were never set; mv_beam_occupancy on
+ * a greedy handle; either call on a use_single_decoder beam handle (host decode only). */
+int  mv_decode_trajectories(mv_handle h, int32_t scale, int32_t center_only, double* out);
+int  mv_beam_occupancy(mv_handle h, float* out /* [N, T_p, K] */);
+/* the small members of mv_download_beam_outputs on their own (beam handles, after a forward):
+ * ids [N, B, T_p], logprobs [N, B]; either may be NULL */
+int  mv_download_beam_ids(mv_handle h, int32_t* ids, float* logprobs);
 
 /* -- training: one call == sess.run([loss, train_op, wd_loss, pred_grid_loss]) */
 int  mv_train_init(mv_handle h, const mv_train_config* tc);

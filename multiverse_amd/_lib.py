@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = [
     "mv_op_convlstm_bwd", "mv_op_gnn_bwd",
     "mv_set_grid_centers", "mv_upload_inputs_compact", "mv_upload_targets_compact",
     "mv_pipeline_create", "mv_submit_greedy", "mv_collect_greedy",
+    "mv_decode_trajectories", "mv_beam_occupancy", "mv_download_beam_ids",
 ]
 
 
@@ -202,6 +203,9 @@ def load():
   lib.mv_synchronize.argtypes = [h]
   lib.mv_download_outputs.argtypes = [h, C.POINTER(mv_outputs)]
   lib.mv_download_beam_outputs.argtypes = [h, C.POINTER(mv_beam_outputs)]
+  lib.mv_decode_trajectories.argtypes = [h, C.c_int32, C.c_int32, _dp]
+  lib.mv_beam_occupancy.argtypes = [h, _fp]
+  lib.mv_download_beam_ids.argtypes = [h, _ip, _fp]
   lib.mv_set_profiling.argtypes = [h, C.c_int32]
   lib.mv_set_graph_mode.argtypes = [h, C.c_int32]
   lib.mv_set_compute_mode.argtypes = [h, C.c_int32]
@@ -489,6 +493,7 @@ class Engine(object):
       inp.grid_obs_labels[s] = iptr(lab)
       inp.grid_obs_regress[s] = fptr(reg)
     self._keep = keep
+    self._pred_len = inp.pred_len
     return inp
 
   def _alloc_outputs(self, Tp):
@@ -698,6 +703,77 @@ class Engine(object):
     out, arrs, s = self._alloc_beam(self._pred_len)
     check(self.lib.mv_download_beam_outputs(self.handle, C.byref(out)), self.handle)
     return arrs, s
+
+  # ---- multi-future decode of the last forward, on the device (csrc/multifuture_decode.h)
+  def _beam_scale(self):
+    return [i for i, u in enumerate(self.cfg.use_grids) if u][0]
+
+  def _last_pred_len(self):
+    return int(getattr(self, "_pred_len", self.cfg.pred_len))
+
+  def decode_trajectories(self, scale=None, center_only=False):
+    """Pixel trajectories of the last forward -> float64 [N, B, T_pred, 2] (B = beam_size,
+    1 for a greedy engine, whose `scale` picks the grid): centre of the decoded cell plus
+    its offset, bit-identical to multifuture.decode_trajectories on the downloaded outputs.
+    Needs set_grid_centers."""
+    c = self.c_cfg
+    if scale is None:
+      scale = self._beam_scale()
+    Tp = self._last_pred_len()
+    buf = np.empty(c.batch_size * c.beam_size * max(c.max_pred_len, Tp) * 2, dtype=np.float64)
+    check(self.lib.mv_decode_trajectories(self.handle, int(scale), 1 if center_only else 0,
+                                          buf.ctypes.data_as(_dp)), self.handle)
+    return buf[:c.batch_size * c.beam_size * Tp * 2].reshape(c.batch_size, c.beam_size, Tp, 2)
+
+  def beam_occupancy(self):
+    """Occupancy map of the last beam decode -> float32 [N, T_pred, K]: every beam's
+    per-step softmax over the grid, mixed with softmax(beam log-probabilities) -- the map
+    multifuture.eval_grid_nll builds from the downloaded logits."""
+    c = self.c_cfg
+    h, w = self.cfg.scene_grids[self._beam_scale()]
+    Tp = self._last_pred_len()
+    buf = np.empty(c.batch_size * max(c.max_pred_len, Tp) * h * w, dtype=np.float32)
+    check(self.lib.mv_beam_occupancy(self.handle, fptr(buf)), self.handle)
+    return buf[:c.batch_size * Tp * h * w].reshape(c.batch_size, Tp, h * w)
+
+  def beam_ids(self):
+    """(ids int32 [N, B, T_pred], logprobs float32 [N, B]) of the last beam decode -- the
+    small members of download_beam, without its logits / best_beam / offsets."""
+    c = self.c_cfg
+    Tp = self._last_pred_len()
+    ids = np.empty(c.batch_size * c.beam_size * max(c.max_pred_len, Tp), dtype=np.int32)
+    lp = np.empty((c.batch_size, c.beam_size), dtype=np.float32)
+    check(self.lib.mv_download_beam_ids(self.handle, iptr(ids), fptr(lp)), self.handle)
+    return ids[:c.batch_size * c.beam_size * Tp].reshape(c.batch_size, c.beam_size, Tp), lp
+
+  def forward_beam_decoded(self, feed, center_only=False, occupancy=False, logits=False):
+    """One beam decode whose fetch is what a caller uses: upload (the compact form when
+    feed["compact"]), run_resident(beam=True), then {"trajs" float64 [N, B, T, 2], "ids"
+    [N, B, T], "logprobs" [N, B][, "occupancy" float32 [N, T, K]]} -- every beam's logits,
+    the offsets maps and best_beam stay in HBM (logits=True fetches "logits" [N, B, T, K] as
+    well, for callers that store them).  The grid centres are those of set_grid_centers
+    (feed["grid_centers"] when the feed carries them)."""
+    if feed.get("compact", False):
+      self.upload_compact(feed)
+    else:
+      if feed.get("grid_centers") is not None and \
+          not self._centers_current(feed["grid_centers"]):
+        self.set_grid_centers(feed["grid_centers"])
+      self.upload(feed)
+    self.run_resident(True)
+    c = self.c_cfg
+    Tp = self._last_pred_len()
+    arrs = {"trajs": self.decode_trajectories(center_only=center_only)}
+    arrs["ids"], arrs["logprobs"] = self.beam_ids()
+    if occupancy:
+      arrs["occupancy"] = self.beam_occupancy()
+    if logits:
+      arrs["logits"] = self.download_beam()[0]["logits"]
+    return arrs, self._beam_scale()
+
+  def forward_beam_decoded_compact(self, feed, center_only=False, occupancy=False,
+                                   logits=False):
+    return self.forward_beam_decoded(dict(feed, compact=True), center_only, occupancy, logits)
 
   # ---- training (Trainer.step)
   def train_init(self, cfg=None, world=None):

@@ -209,6 +209,9 @@ _MF_FLAGS = [
     ("--scene_conv_kernel", int, 3), ("--video_h", int, 1080), ("--video_w", int, 1920),
     # not in the reference: samples with equal T_pred are decoded together
     ("--batch_size", int, 1),
+    # not in the reference: trajectories (and the occupancy map of the grid-NLL evaluation,
+    # traj_id -> float32 [T, h*w]) decoded on the GPU; the beams' logits stay there
+    ("--device_decode", B, None), ("--save_occupancy_file", str, None),
 ]
 
 
@@ -230,6 +233,8 @@ def multifuture_inference_main(argv=None):
   """code/multifuture_inference.py:387-530."""
   from multiverse_amd import multifuture as mf, pred_models, pred_utils
   args = multifuture_inference_parser().parse_args(argv)
+  if args.save_occupancy_file is not None:
+    args.device_decode = True
   mf.add_grid(args)
   assert sum(args.use_grids) == 1
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
@@ -240,8 +245,12 @@ def multifuture_inference_main(argv=None):
                         max_pred_len=max(inputs["max_pred_lengths"] + [12]))
   model = pred_models.Model(cfg, cfg.modelname, gpuid=args.gpuid)
   model.load_params(pred_utils.load_weights(args.model_path, scope="person_pred"))
-  output_data, beam_prob = mf.run_inference(args, model, inputs, traj_ids)
+  res = mf.run_inference(args, model, inputs, traj_ids)
+  output_data, beam_prob = res[0], res[1]
   model.close()
+  if args.save_occupancy_file is not None:
+    with open(args.save_occupancy_file, "wb") as f:
+      pickle.dump(res[2], f)
   with open(args.output_file, "wb") as f:
     pickle.dump(output_data, f)
   if args.save_prob_file is not None:

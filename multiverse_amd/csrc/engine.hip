@@ -32,6 +32,7 @@
 #include "kernels_misc.h"
 #include "decode_tail.h"
 #include "sparse_x.h"
+#include "multifuture_decode.h"
 #include "train_kernels.h"
 #include "comm.h"
 
@@ -258,6 +259,30 @@ int mv_download_beam_outputs(mv_handle h, mv_beam_outputs* out) {
   return guarded(h, [&] {
     MV_REQUIRE(out, "NULL outputs");
     download_beam(h, out);
+  });
+}
+
+int mv_decode_trajectories(mv_handle h, int32_t scale, int32_t center_only, double* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    decode_trajectories(h, scale, center_only != 0, out);
+    drain_events(h);
+  });
+}
+
+int mv_beam_occupancy(mv_handle h, float* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    beam_occupancy(h, out);
+    drain_events(h);
+  });
+}
+
+int mv_download_beam_ids(mv_handle h, int32_t* ids, float* logprobs) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    download_beam_ids(h, ids, logprobs);
+    drain_events(h);
   });
 }
 

@@ -1033,6 +1033,7 @@ void run_forward(mv_engine* e, bool beam) {
     MV_REQUIRE(e->cfg.beam_size > 1, "engine was created with beam_size 1");
   if (!e->graph_mode || e->profiling) {
     enqueue_forward(e, beam);
+    e->last_forward = beam ? 2 : 1;
     return;
   }
   const auto key = std::make_tuple(beam ? 1 : 0, e->pred_len, e->num_frames);
@@ -1055,6 +1056,7 @@ void run_forward(mv_engine* e, bool beam) {
     it = e->graphs.emplace(key, ex).first;
   }
   HIP_CHECK(hipGraphLaunch(it->second, e->stream));
+  e->last_forward = beam ? 2 : 1;
 }
 
 }  // namespace

@@ -319,6 +319,95 @@ void download_beam(mv_engine* e, mv_beam_outputs* out) {
   HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 
+// ---- multi-future decode of the last forward, on the device (multifuture_decode.h).  Both
+// run on the handle's stream behind whatever forward was queued, copy their small result to
+// the caller's buffer and synchronise.
+static int mf_beam_scale(const mv_engine* e) {
+  int s = 0;
+  for (int i = 0; i < e->cfg.num_scales; ++i) if (e->sc[i].use) s = i;
+  return s;
+}
+
+static void mf_require_forward(const mv_engine* e, const char* who) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(!(c.beam_size > 1 && c.use_single_decoder),
+             "%s: use_single_decoder with beam search decodes on the host (the offsets come "
+             "per beam, and the reference's own reshape of them mixes beams)", who);
+  MV_REQUIRE(e->last_forward != 0, "%s: no forward has run on this handle", who);
+  MV_REQUIRE(e->last_forward == (c.beam_size > 1 ? 2 : 1),
+             "%s: the last forward of this beam handle was a greedy one", who);
+}
+
+void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(out, "mv_decode_trajectories: NULL out");
+  mf_require_forward(e, "mv_decode_trajectories");
+  const bool beam = c.beam_size > 1;
+  if (beam) scale = mf_beam_scale(e);
+  MV_REQUIRE(scale >= 0 && scale < c.num_scales && e->sc[scale].use,
+             "mv_decode_trajectories: scale %d is not an enabled scale", scale);
+  ScaleState& S = e->sc[scale];
+  MV_REQUIRE(S.centers.p, "mv_set_grid_centers(%d) has not been called", scale);
+  const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
+  const size_t rows = (size_t)N * B * Tp;
+  e->mf_traj.alloc((size_t)N * B * c.max_pred_len * 2);
+  const size_t grid = beam ? cdiv(rows, (size_t)mv::kMfBlock) : cdiv(rows, (size_t)mv::kMfWaves);
+  const double bytes = beam ? rows * (4.0 + 16.0 + (center_only ? 16.0 : 24.0))
+                            : rows * (4.0 * K + 16.0 + (center_only ? 16.0 : 24.0));
+  launch(e, "decode_traj", center_only ? 0.0 : 2.0 * rows, bytes, [&] {
+    hipLaunchKernelGGL(mv::decode_traj_kernel, dim3(grid), dim3(mv::kMfBlock), 0, e->stream,
+                       beam ? e->bm_out_ids.p : nullptr, S.out_cls.p, S.out_reg.p, S.centers.p,
+                       e->mf_traj.p, (int)rows, B, Tp, K, center_only);
+  });
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(out, e->mf_traj.p, rows * 2 * sizeof(double), hipMemcpyDeviceToHost,
+                           e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
+void beam_occupancy(mv_engine* e, float* out) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(out, "mv_beam_occupancy: NULL out");
+  MV_REQUIRE(c.beam_size > 1, "mv_beam_occupancy: engine was created with beam_size 1 (the "
+             "occupancy map mixes the beams of a beam-search decode)");
+  mf_require_forward(e, "mv_beam_occupancy");
+  const ScaleState& S = e->sc[mf_beam_scale(e)];
+  const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
+  const size_t cells = (size_t)N * Tp * K;
+  e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
+  // HBM-bound: every beam's logits row read once, the map written once
+  launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
+    const dim3 grid(N * Tp), block(mv::kMfBlock);
+    if (K <= mv::kMfBlock)
+      hipLaunchKernelGGL(mv::beam_occupancy_kernel<1>, grid, block, 0, e->stream,
+                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+    else if (K <= 3 * mv::kMfBlock)
+      hipLaunchKernelGGL(mv::beam_occupancy_kernel<3>, grid, block, 0, e->stream,
+                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+    else
+      hipLaunchKernelGGL(mv::beam_occupancy_anyk_kernel, grid, block, 0, e->stream,
+                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+  });
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipMemcpyAsync(out, e->mf_occ.p, cells * sizeof(float), hipMemcpyDeviceToHost,
+                           e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
+void download_beam_ids(mv_engine* e, int32_t* ids, float* logprobs) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(c.beam_size > 1, "mv_download_beam_ids: engine was created with beam_size 1");
+  MV_REQUIRE(e->last_forward == 2, "mv_download_beam_ids: no beam forward has run on this handle");
+  const size_t R = (size_t)c.batch_size * c.beam_size;
+  if (ids)
+    HIP_CHECK(hipMemcpyAsync(ids, e->bm_out_ids.p, R * e->pred_len * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, e->stream));
+  if (logprobs)
+    HIP_CHECK(hipMemcpyAsync(logprobs, e->bm_lp[0].p, R * sizeof(float), hipMemcpyDeviceToHost,
+                             e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
 template <typename F>
 int guarded(mv_engine* e, F&& fn) {
   try {

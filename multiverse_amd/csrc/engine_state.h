@@ -183,6 +183,10 @@ struct mv_engine {
   DevBuf<float> bm_reg_steps;      // [T, N*B, K, 2]   per step, in the step's own row order
   DevBuf<float> bm_out_reg;        // [N*B, T, K, 2]   traced back
   DevBuf<int32_t> bm_out_ids;      // [N, B, T]
+  // multi-future decode of the last forward (multifuture_decode.h): 0 none yet, 1 greedy, 2 beam
+  int last_forward = 0;
+  DevBuf<double> mf_traj;          // [N, B, T, 2] pixel trajectories
+  DevBuf<float> mf_occ;            // [N, T, K] occupancy map of the beams
   // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = f16x3 split on the fp16 matrix pipe,
   // 2 = bf16 operands / fp32 accumulate (one plane, one MFMA per product)
   int compute_mode = 0;

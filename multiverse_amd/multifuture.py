@@ -239,6 +239,8 @@ def run_inference(args, model, inputs, traj_ids):
   """The per-sample loop of code/multifuture_inference.py:458-523 ->
   (output_data {traj_id: [num_out][T][2]}, beam_prob {traj_id: (logits
   [1,B,T,K], logprobs [1,B])}).  `model.run_forward(feed)` is one sess.run."""
+  if getattr(args, "device_decode", False):
+    return run_inference_device(args, model, inputs, traj_ids)
   use_grid_idx = list(args.use_grids).index(True)
   N = model.config.batch_size
   by_len = {}
@@ -266,6 +268,48 @@ def run_inference(args, model, inputs, traj_ids):
           beam_prob[traj_ids[i]] = (b[0][None], b[2][None])
   ordered = {t: output_data[t] for t in traj_ids}
   return ordered, ({t: beam_prob[t] for t in traj_ids if t in beam_prob})
+
+
+def run_inference_device(args, model, inputs, traj_ids):
+  """`run_inference` with the decode on the device (`args.device_decode`):
+  `model.run_forward_decoded(feed, ...)` returns the trajectories themselves -- centre +
+  offset in float64, the operation of `decode_trajectories`, so the same values -- and only
+  the beams' ids / log-probabilities besides.  Same first two return values; with
+  `args.save_occupancy_file` a third, {traj_id: float32 [T, K]} (the map `eval_grid_nll`
+  builds from the logits).  `args.save_prob_file` still needs every beam's logits: they are
+  then fetched as well."""
+  use_grid_idx = list(args.use_grids).index(True)
+  N = model.config.batch_size
+  greedy = bool(args.greedy)
+  want_occ = getattr(args, "save_occupancy_file", None) is not None and not greedy
+  want_prob = getattr(args, "save_prob_file", None) is not None and not greedy
+  by_len = {}
+  for i in range(len(traj_ids)):
+    by_len.setdefault(inputs["max_pred_lengths"][i], []).append(i)
+  output_data, beam_prob, occupancy = {}, {}, {}
+  for T_pred in sorted(by_len):
+    group = by_len[T_pred]
+    for lo in range(0, len(group), N):
+      idxs = group[lo:lo + N]
+      feed, n_real = inference_feed(inputs, args, idxs, batch_size=N)
+      dec = model.run_forward_decoded(feed, center_only=bool(args.center_only),
+                                      occupancy=want_occ,
+                                      grid_centers=args.scene_grid_centers,
+                                      logits=want_prob)
+      trajs = dec["trajs"]                                   # [N, B, T, 2]
+      for r in range(n_real):
+        i = idxs[r]
+        rows = [trajs[r, 0]] * args.num_out if greedy else trajs[r, :args.num_out]
+        output_data[traj_ids[i]] = [[row[t] for t in range(T_pred)] for row in rows]
+        if want_occ:
+          occupancy[traj_ids[i]] = dec["occupancy"][r]
+        if want_prob:
+          beam_prob[traj_ids[i]] = (dec["logits"][r][None], dec["logprobs"][r][None])
+  ordered = {t: output_data[t] for t in traj_ids}
+  ret = (ordered, {t: beam_prob[t] for t in traj_ids if t in beam_prob})
+  if getattr(args, "save_occupancy_file", None) is not None:
+    ret += ({t: occupancy[t] for t in traj_ids if t in occupancy},)
+  return ret
 
 
 # ------------------------------------------------------------------ metrics
@@ -320,16 +364,23 @@ def eval_grid_nll(gt_by_traj, predictions, scene_h=18, scene_w=32, video_h=1080,
   nlls = {"T=%d" % (t + 1): [] for t in time_list}
   for traj_id in predictions:
     gt = gt_by_traj[traj_id]
-    beams, logprobs = predictions[traj_id]
-    probs = _softmax(np.squeeze(logprobs))
-    beams = _softmax(np.squeeze(beams), axis=-1)          # [B, T, K]
-    assert beams.shape[-1] == scene_h * scene_w
+    entry = predictions[traj_id]
+    occ = None
+    if isinstance(entry, np.ndarray):     # already the mixture: float32 [T, K] (device decode)
+      occ = entry
+      assert occ.ndim == 2 and occ.shape[-1] == scene_h * scene_w
+    else:
+      beams, logprobs = entry
+      probs = _softmax(np.squeeze(logprobs))
+      beams = _softmax(np.squeeze(beams), axis=-1)          # [B, T, K]
+      assert beams.shape[-1] == scene_h * scene_w
     for t in time_list:
       xys = [gt[fid]["x_agent_traj"][t][2:] for fid in gt
              if len(gt[fid]["x_agent_traj"]) > t]
       if not xys:
         continue
-      grid = (beams[:, t, :].astype("float32") * probs[:, None].astype("float32")).sum(0)
+      grid = occ[t] if occ is not None else \
+          (beams[:, t, :].astype("float32") * probs[:, None].astype("float32")).sum(0)
       idx = xy_to_grid_class(np.asarray(xys), scene_h, scene_w, video_h, video_w)
       nll = float(np.mean([-np.log(grid[k] + np.finfo(float).eps) for k in idx]))
       nlls["T=%d" % (t + 1)].append(nll)

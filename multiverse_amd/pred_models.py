@@ -306,6 +306,36 @@ class Model(object):
     return cls, reg, None
 
 
+  def run_forward_decoded(self, feed, center_only=False, occupancy=False, grid_centers=None,
+                          logits=False):
+    """One decode whose fetch is what a multi-future caller uses, decoded on the device:
+    {"trajs": float64 [N, B, T, 2]} (B = 1 for a greedy model) and, for a beam-search model,
+    "ids" [N, B, T], "logprobs" [N, B] and -- with occupancy -- "occupancy" float32
+    [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
+    [N, B, T, K] is fetched as well, for a caller that stores them).  grid_centers: list over
+    scales of [H, W, 2] cell centres (default: the feed's, else those already resident)."""
+    cfg = self.config
+    eng = self.engine
+    compact = bool(feed.get("compact", False))
+    centers = grid_centers if grid_centers is not None else feed.get("grid_centers")
+    if centers is not None and not compact and not eng._centers_current(centers):  # pylint: disable=protected-access
+      eng.set_grid_centers(centers)
+    if getattr(cfg, "use_beam_search", False):
+      arrs, _ = (eng.forward_beam_decoded_compact if compact
+                 else eng.forward_beam_decoded)(feed, center_only, occupancy, logits)
+      return arrs
+    if occupancy:
+      raise _lib.MvError("run_forward_decoded: the occupancy map mixes the beams of a "
+                         "beam-search decode; this model decodes greedily")
+    if compact:
+      eng.upload_compact(feed)
+    else:
+      eng.upload(feed)
+    eng.run_resident(False)
+    s = list(cfg.use_grids).index(True)
+    return {"trajs": eng.decode_trajectories(scale=s, center_only=center_only)}
+
+
 class Tester(object):
   """code/pred_models.py:1745-1790."""
 
