@@ -821,15 +821,6 @@ __device__ __forceinline__ void convlstm16_lds_body(const ConvLstm16Args& p, int
   }
 }
 
-// SHIFT form of the step kernels: every problem's W divides 32 (MV_CONV_SHIFT=0: never)
-static inline bool conv_group_shift(const ConvLstm16Args* probs, int n) {
-  static const bool off = getenv("MV_CONV_SHIFT") && atoi(getenv("MV_CONV_SHIFT")) == 0;
-  if (off) return false;
-  for (int i = 0; i < n; ++i)
-    if (probs[i].f.W <= 0 || 32 % probs[i].f.W != 0) return false;
-  return true;
-}
-
 // block -> (column block cb, row tile mt) of the forward step.  A workgroup reads the
 // operand planes of its 256 cells and ONE column block's weights.
 //   mode 0  cb = block % 8: a column block per XCD -- its L2 keeps that block's 1.3 MB of
@@ -1040,11 +1031,7 @@ static inline unsigned convlstm16_blocks(const ConvLstmArgs& a) {
   const size_t M = (size_t)a.rows * a.H * a.W;
   return (unsigned)((M + kBlockRows16 - 1) / kBlockRows16) * (unsigned)a.n_colblocks;
 }
-// MV_CONV_MAP=1: row tile per XCD (step_block_map); grid padded to 8 row tiles
-static inline int conv_step_map_mode() {
-  static const int m = getenv("MV_CONV_MAP") ? atoi(getenv("MV_CONV_MAP")) : 0;
-  return m;
-}
+// map mode 1: row tile per XCD (step_block_map); grid padded to 8 row tiles
 static inline unsigned convlstm16_step_blocks(const ConvLstmArgs& a, int mode) {
   if (mode == 0) return convlstm16_blocks(a);
   const size_t M = (size_t)a.rows * a.H * a.W;
@@ -1052,8 +1039,9 @@ static inline unsigned convlstm16_step_blocks(const ConvLstmArgs& a, int mode) {
   return (unsigned)(((mt + 7) / 8) * 8) * (unsigned)a.n_colblocks;
 }
 
-static inline void launch_convlstm16_dgrads(const ConvLstm16Args* probs, int n,
-                                            hipStream_t stream, bool bf16 = false) {
+// (shift, and map_mode / xf16 below: the caller's plan, gate_plan.h)
+static inline void launch_convlstm16_dgrads(const ConvLstm16Args* probs, int n, bool bf16,
+                                            bool shift, hipStream_t stream) {
   ConvLstm16Group g{};
   g.n = n;
   unsigned total = 0;
@@ -1063,7 +1051,6 @@ static inline void launch_convlstm16_dgrads(const ConvLstm16Args* probs, int n,
     g.block_end[i] = (int32_t)total;
   }
   for (int i = n; i < kMaxGroup; ++i) g.block_end[i] = (int32_t)total;
-  const bool shift = conv_group_shift(probs, n);
   if (bf16 && shift)
     hipLaunchKernelGGL(convlstm_dgrad_bf16_kernel<true>, dim3(total), dim3(kThreads16), 0, stream, g);
   else if (bf16)
@@ -1220,11 +1207,12 @@ __global__ void split_planes_dyn_kernel(const float* __restrict__ in, _Float16* 
   *reinterpret_cast<f16x8*>(p1 + o) = b;
 }
 
-static inline void launch_convlstm_bf16_steps(const ConvLstm16Args* probs, int n,
-                                              hipStream_t stream) {
+// xf16: unbounded-activation models (a problem carries an x exponent): the three-pass x kernel
+static inline void launch_convlstm_bf16_steps(const ConvLstm16Args* probs, int n, bool shift,
+                                              int map_mode, bool xf16, hipStream_t stream) {
   ConvLstm16Group g{};
   g.n = n;
-  g.map_mode = conv_step_map_mode();
+  g.map_mode = map_mode;
   unsigned total = 0;
   for (int i = 0; i < n; ++i) {
     g.p[i] = probs[i];
@@ -1232,10 +1220,6 @@ static inline void launch_convlstm_bf16_steps(const ConvLstm16Args* probs, int n
     g.block_end[i] = (int32_t)total;
   }
   for (int i = n; i < kMaxGroup; ++i) g.block_end[i] = (int32_t)total;
-  // unbounded-activation models (a problem carries an x exponent): the three-pass x kernel
-  bool xf16 = false;
-  for (int i = 0; i < n; ++i) xf16 = xf16 || probs[i].x_exp != nullptr;
-  const bool shift = conv_group_shift(probs, n);
   if (xf16) {
     if (shift)
       hipLaunchKernelGGL((convlstm_step_bf16_kernel<true, true>), dim3(total), dim3(kThreads16), 0, stream, g);
@@ -1248,11 +1232,11 @@ static inline void launch_convlstm_bf16_steps(const ConvLstm16Args* probs, int n
   }
 }
 
-static inline void launch_convlstm16_steps(const ConvLstm16Args* probs, int n,
-                                           hipStream_t stream) {
+static inline void launch_convlstm16_steps(const ConvLstm16Args* probs, int n, bool shift,
+                                           int map_mode, hipStream_t stream) {
   ConvLstm16Group g{};
   g.n = n;
-  g.map_mode = conv_step_map_mode();
+  g.map_mode = map_mode;
   unsigned total = 0;
   for (int i = 0; i < n; ++i) {
     g.p[i] = probs[i];
@@ -1260,7 +1244,7 @@ static inline void launch_convlstm16_steps(const ConvLstm16Args* probs, int n,
     g.block_end[i] = (int32_t)total;
   }
   for (int i = n; i < kMaxGroup; ++i) g.block_end[i] = (int32_t)total;
-  if (conv_group_shift(probs, n))
+  if (shift)
     hipLaunchKernelGGL(convlstm_step_f16x3_lds_kernel<true>, dim3(total), dim3(kThreads16), 0, stream, g);
   else
     hipLaunchKernelGGL(convlstm_step_f16x3_lds_kernel<false>, dim3(total), dim3(kThreads16), 0, stream, g);

@@ -378,13 +378,14 @@ void convlstm_wgrad_fast_kernel(const WgradArgs a) {
 
 static inline bool wgrad_fast_ok(const WgradArgs& a) { return (a.W % (2 * kWgUnroll)) == 0; }
 
-static inline void wgrad_plan(WgradArgs& a, int target_blocks) {
+// forced_splits: the MV_WGRAD_SPLITS tuning knob (gate_plan.h), NULL = unset
+static inline void wgrad_plan(WgradArgs& a, int target_blocks, const int* forced_splits) {
   a.n_xblocks = (a.Cx + kWgTile - 1) / kWgTile;
   a.n_ciblocks = a.n_xblocks + a.C / kWgTile;
   if (wgrad_fast_ok(a)) {      // splits are ranges of whole images
     const int per_split = 9 * a.n_ciblocks * ((4 * a.C) / (4 * kWgTile));
     int nsplit = target_blocks / per_split;
-    if (const char* ev = getenv("MV_WGRAD_SPLITS")) nsplit = atoi(ev);   // tuning knob
+    if (forced_splits) nsplit = *forced_splits;
     if (nsplit > 256) nsplit = 256;
     nsplit = (nsplit + 7) & ~7;
     if (nsplit < 8) nsplit = 8;

@@ -904,21 +904,17 @@ void convlstm_wgrad_f16x3_wide_kernel(const Wgrad16Args a) {
       }
 }
 
-static inline bool wgrad16_wide_ok(int W, int C) {
-  static const bool on = !(getenv("MV_WGRAD_WIDE") && atoi(getenv("MV_WGRAD_WIDE")) == 0);
-  return on && (W % 16) == 0 && (C % 256) == 0;
-}
+// (the switches and overrides named below are read in gate_plan.h and handed in)
+static inline bool wgrad16_wide_ok(int W, int C) { return (W % 16) == 0 && (C % 256) == 0; }
 // Split count of the wide kernel: 9 taps x nsplit workgroups per XCD and (channel, column) group
 // on 64 slots -- 7 splits = one full round, 14 = two, 21 = three -- never more than the planned count
 // (the partial buffer), and at least ~64 k-steps per split.
-static inline int wgrad16_wide_map_mode(int C) {
-  static const int m = getenv("MV_WGRAD_WIDE_MAP") ? atoi(getenv("MV_WGRAD_WIDE_MAP")) : 0;
+static inline int wgrad16_wide_map_mode(int C, int m) {        // m: MV_WGRAD_WIDE_MAP
   if (m == 2 && C != 2 * kWgwA) return 0;
   return m >= 0 && m <= 2 ? m : 0;
 }
-static inline int wgrad16_wide_splits(long long Mtot, int planned, int map_mode) {
-  int v = 0;
-  if (const char* ev = getenv("MV_WGRAD_WIDE_SPLITS")) v = atoi(ev);
+static inline int wgrad16_wide_splits(long long Mtot, int planned, int map_mode, int v) {
+  // v: MV_WGRAD_WIDE_SPLITS (0 = unset)
   const int mult = map_mode == 1 ? 8 : (map_mode == 2 ? 4 : 1);
   if (v >= 1 && v <= planned && v % mult == 0) return v;
   if (map_mode == 1) return planned;                 // a multiple of 8 by construction
@@ -942,22 +938,14 @@ static inline unsigned wgrad16_wide_blocks(const Wgrad16Args& a, bool xrows = fa
 // The x rows on the wide tile measured the same as on the 128 x 128 tile (2.59 vs 2.56 ms per
 // training step, profiles/r5wg_wgrad_wide_tile_ab.md: 20 fat workgroups per split fill the chip
 // worse than 40 small ones, which eats the tile's gain): off unless MV_WGRAD_WIDE_X=1.
-static inline bool wgrad16_wide_x_enabled() {
-  static const bool on = getenv("MV_WGRAD_WIDE_X") && atoi(getenv("MV_WGRAD_WIDE_X")) == 1;
-  return on;
-}
 
 constexpr size_t kWg16LdsBytes = (size_t)2 * 2 * kWg16Tile * sizeof(_Float16);   // 80 KB
 constexpr size_t kWg16LdsBytes1 = (size_t)2 * 2 * wg16_tile<1>() * sizeof(_Float16);   // NP = 1: 40 KB
 
 static inline bool wgrad16_ok(int W, int C) { return (W % 16) == 0 && (C % 128) == 0; }
 // the row-triple form: whole triples only; MV_WGRAD_WINO=0 keeps the direct form
-// (one_plane: the reduced-precision mode's single fp16 plane per operand, MV_WGRAD_WINO_BF16=0)
-static inline bool wgrad16_wino3_ok(int H, bool one_plane) {
-  static const bool on = !(getenv("MV_WGRAD_WINO") && atoi(getenv("MV_WGRAD_WINO")) == 0);
-  static const bool on1 = !(getenv("MV_WGRAD_WINO_BF16") && atoi(getenv("MV_WGRAD_WINO_BF16")) == 0);
-  return on && (on1 || !one_plane) && H >= 3 && H % 3 == 0;
-}
+// (MV_WGRAD_WINO_BF16=0: in the reduced-precision mode's single fp16 plane per operand)
+static inline bool wgrad16_wino3_ok(int H) { return H >= 3 && H % 3 == 0; }
 
 static inline void wgrad16_plan(Wgrad16Args& a, long long Mtot, int nsplit) {
   a.ksteps_total = (int32_t)(Mtot / 16);
@@ -972,9 +960,7 @@ static inline void wgrad16_plan(Wgrad16Args& a, long long Mtot, int nsplit) {
 // 480 / 960 workgroups fill one / two rounds to 94 % (the h rows' 21: 1.64 / 3.28 rounds).
 // Measured: 1.94 against 2.17 - 2.28 ms per training step (profiles/r6t, MV_WGRAD_WIDE_SPLITS
 // sweep).  MV_WGRAD_X_SPLITS overrides; never more than the h rows' count (the partial buffer).
-static inline int wgrad16_x_splits(long long Mgemm, int nsplit_h) {
-  int v = 12;
-  if (const char* ev = getenv("MV_WGRAD_X_SPLITS")) v = atoi(ev);
+static inline int wgrad16_x_splits(long long Mgemm, int nsplit_h, int v = 12) {
   if (v < 1 || v > nsplit_h || Mgemm / 16 < (long long)v * 32) return nsplit_h;
   return v;
 }

@@ -697,15 +697,7 @@ static inline unsigned convlstm_wino_blocks(const ConvLstmArgs& a, int waves) {
 }
 
 // The Winograd form serves a group when every problem's W divides 32 (the DPP column shift)
-// and C is a multiple of 16.  MV_WINO=0 keeps the direct kernel (A/B runs).
-static inline bool wino_enabled() {
-  static const bool off = getenv("MV_WINO") && atoi(getenv("MV_WINO")) == 0;
-  return !off;
-}
-static inline bool wino_dgrad_enabled() {
-  static const bool off = getenv("MV_WINO_DGRAD") && atoi(getenv("MV_WINO_DGRAD")) == 0;
-  return !off;
-}
+// and C is a multiple of 16.
 static inline bool wino_geometry_ok(const ConvLstmArgs& a) {
   return a.W > 0 && 32 % a.W == 0 && a.C % kWnCh == 0 && (a.Cx % 16 == 0 || a.x_small) &&
          a.H >= 2;
@@ -722,15 +714,12 @@ static inline void wino_init_attributes() {
   (void)done;
 }
 
-static inline void launch_convlstm_wino_steps(const ConvLstmWinoArgs* probs, int n,
+static inline void launch_convlstm_wino_steps(const ConvLstmWinoArgs* probs, int n, int map_mode,
                                               hipStream_t stream) {
   ConvLstmWinoGroup g{};
   g.n = n;
   const int waves = wino_waves();
-  // MV_WINO_MAP: block -> column block map (1, default: the two halves of a 128-byte state
-  // line on one XCD)
-  static const int map_mode = getenv("MV_WINO_MAP") ? atoi(getenv("MV_WINO_MAP")) : 1;
-  g.map_mode = map_mode;
+  g.map_mode = map_mode;       // block -> column block map (gate_plan.h: MV_WINO_MAP)
   unsigned total = 0;
   for (int i = 0; i < n; ++i) {
     g.p[i] = probs[i];

@@ -911,11 +911,6 @@ static inline unsigned convlstm_wino3_blocks(const ConvLstmArgs& a, bool halo, i
   return (unsigned)mtiles * ncb;
 }
 
-// MV_WINO3=0 keeps the F(2,3) row-pair kernel (A/B runs).
-static inline bool wino3_enabled() {
-  static const bool off = getenv("MV_WINO3") && atoi(getenv("MV_WINO3")) == 0;
-  return !off;
-}
 // The F(3,3) form serves a problem when C is a multiple of the channel block, the x operand
 // comes as 16-channel planes (or is the 2-channel fp32 chunk) under the FIXED 2^8 scale -- the
 // per-tensor exponent of unbounded activations leaves one bit of headroom, the components here
@@ -928,11 +923,12 @@ static inline bool wino3_geometry_ok(const ConvLstmArgs& a, const ConvLstm16Args
 static inline bool wino3_needs_halo(const ConvLstmArgs& a) { return 32 % a.W != 0; }
 // The HALO tiling addresses the pre-transformed operands with ONE 32-bit byte offset per lane
 // from the buffer's start (a wave's 32 triple-cells start anywhere) and sends the lanes outside
-// the sequence to offset 2^31, which must lie BEYOND the buffer: a problem whose x or h operand
-// holds 2 GiB or more (36 x 18 grid, 128 rows x 20 beams, 256 channels: 2.8 GB) takes the
-// F(2,3) form instead.  The exact tiling rebases its descriptor per wave tile: no such limit.
+// the sequence to offset 2^31, which must lie BEYOND the buffer: a launch in the halo tiling must
+// not hold a problem whose x or h operand has 2 GiB or more (36 x 18 grid, 128 rows x 20 beams,
+// 256 channels: 2.8 GB).  The exact tiling rebases its descriptor per wave tile: no such limit.
+// The tiling is ONE per launch, so the bound concerns every problem of a halo group, whatever
+// its own width (gate_plan.h decides).
 static inline bool wino3_halo_addressable(const ConvLstmArgs& a) {
-  if (!wino3_needs_halo(a)) return true;
   const size_t lim = (size_t)1 << 31;
   const int cx16 = a.x_small ? 0 : (a.Cx + 15) / 16 * 16;
   return wino3_v_elems(a.rows, a.H, a.W, a.C) * 2 < lim &&
@@ -950,33 +946,6 @@ static inline void wino3_init_attributes() {
     return true;
   }();
   (void)done;
-}
-
-static inline void launch_convlstm_wino3_steps(const ConvLstmWinoArgs* probs, int n,
-                                               hipStream_t stream) {
-  ConvLstmWinoGroup g{};
-  g.n = n;
-  // MV_WINO_MAP: 2 (default here): an XCD holds four column blocks and every second row tile --
-  // a row tile's pre-transformed operands then come through 4 of the 8 L2s (+0.7 % greedy and
-  // beam-20 against 1 = two column blocks per XCD, same box; 3 = eight: no better)
-  static const int map_mode = getenv("MV_WINO_MAP") ? atoi(getenv("MV_WINO_MAP")) : 2;
-  g.map_mode = map_mode;
-  bool halo = false;                       // one tiling per launch: any problem that needs it
-  for (int i = 0; i < n; ++i) halo = halo || wino3_needs_halo(probs[i].b.f);
-  unsigned total = 0;
-  for (int i = 0; i < n; ++i) {
-    g.p[i] = probs[i];
-    total += convlstm_wino3_blocks(probs[i].b.f, halo, map_mode);
-    g.block_end[i] = (int32_t)total;
-  }
-  for (int i = n; i < kMaxGroup; ++i) g.block_end[i] = (int32_t)total;
-  wino3_init_attributes();
-  if (halo)
-    hipLaunchKernelGGL((convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, true>), dim3(total),
-                       dim3(kW3Waves * 64), wino3_lds_bytes(), stream, g);
-  else
-    hipLaunchKernelGGL((convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, false>), dim3(total),
-                       dim3(kW3Waves * 64), wino3_lds_bytes(), stream, g);
 }
 
 // ------------------------------------------------------------------ bf16 mode on this tile
@@ -1010,35 +979,37 @@ static inline size_t bf16t_lds_bytes() {
   return (size_t)2 * (3 * 3 * kW3Nrb * 64 * 16) + (size_t)kW3Waves * Wn3<kW3Nrb>::kTileFloats * 4 +
          (size_t)kW3Waves * 192 * 4;
 }
-// MV_BF16T=0 keeps the 32-cell bf16 body of convlstm_f16x3.h (A/B runs).
-static inline bool bf16t_enabled() {
-  static const bool off = getenv("MV_BF16T") && atoi(getenv("MV_BF16T")) == 0;
-  return !off;
-}
 static inline bool bf16t_geometry_ok(const ConvLstmArgs& a, const ConvLstm16Args& q) {
   return a.W > 0 && a.C % Wn3<kW3Nrb>::kCh == 0 && (a.Cx % 16 == 0 || a.x_small) && a.H >= 3 &&
          q.x_exp == nullptr;
 }
-template <bool HALO>
-static inline void bf16t_launch_one(const ConvLstmWinoGroup& g, unsigned total, hipStream_t stream) {
-  static const bool attr = [] {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, HALO, true>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, (int)bf16t_lds_bytes());
-    return true;
-  }();
-  (void)attr;
-  hipLaunchKernelGGL((convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, HALO, true>), dim3(total),
-                     dim3(kW3Waves * 64), bf16t_lds_bytes(), stream, g);
+// One launcher for both kernels of the row-triple tile: F(3,3) on the f16x3 split and, with
+// BF16D, the direct bf16 form.  The caller's plan (gate_plan.h) has chosen the tiling -- ONE per
+// launch: halo if any problem needs it -- and the block map.  (The F(3,3) attributes are also set
+// when the weights are packed, i.e. outside any graph capture.)
+template <bool HALO, bool BF16D>
+static inline void tile3_launch_one(const ConvLstmWinoGroup& g, unsigned total, hipStream_t stream) {
+  const size_t lds = BF16D ? bf16t_lds_bytes() : wino3_lds_bytes();
+  if constexpr (BF16D) {
+    static const bool attr = [lds] {
+      (void)hipFuncSetAttribute(
+          reinterpret_cast<const void*>(convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, HALO, true>),
+          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      return true;
+    }();
+    (void)attr;
+  } else {
+    wino3_init_attributes();
+  }
+  hipLaunchKernelGGL((convlstm_step_wino3_kernel<kW3Waves, kW3Nrb, HALO, BF16D>), dim3(total),
+                     dim3(kW3Waves * 64), lds, stream, g);
 }
-static inline void launch_convlstm_bf16t_steps(const ConvLstmWinoArgs* probs, int n,
-                                               hipStream_t stream) {
+template <bool BF16D>
+static inline void launch_convlstm_tile3_steps(const ConvLstmWinoArgs* probs, int n, bool halo,
+                                               int map_mode, hipStream_t stream) {
   ConvLstmWinoGroup g{};
   g.n = n;
-  static const int map_mode = getenv("MV_WINO_MAP") ? atoi(getenv("MV_WINO_MAP")) : 2;
   g.map_mode = map_mode;
-  bool halo = false;
-  for (int i = 0; i < n; ++i) halo = halo || wino3_needs_halo(probs[i].b.f);
   unsigned total = 0;
   for (int i = 0; i < n; ++i) {
     g.p[i] = probs[i];
@@ -1046,8 +1017,16 @@ static inline void launch_convlstm_bf16t_steps(const ConvLstmWinoArgs* probs, in
     g.block_end[i] = (int32_t)total;
   }
   for (int i = n; i < kMaxGroup; ++i) g.block_end[i] = (int32_t)total;
-  if (halo) bf16t_launch_one<true>(g, total, stream);
-  else bf16t_launch_one<false>(g, total, stream);
+  if (halo) tile3_launch_one<true, BF16D>(g, total, stream);
+  else tile3_launch_one<false, BF16D>(g, total, stream);
+}
+static inline void launch_convlstm_wino3_steps(const ConvLstmWinoArgs* probs, int n, bool halo,
+                                               int map_mode, hipStream_t stream) {
+  launch_convlstm_tile3_steps<false>(probs, n, halo, map_mode, stream);
+}
+static inline void launch_convlstm_bf16t_steps(const ConvLstmWinoArgs* probs, int n, bool halo,
+                                               int map_mode, hipStream_t stream) {
+  launch_convlstm_tile3_steps<true>(probs, n, halo, map_mode, stream);
 }
 
 }  // namespace mv

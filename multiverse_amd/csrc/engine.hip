@@ -37,6 +37,7 @@
 #include "comm.h"
 
 #include "engine_state.h"
+#include "gate_plan.h"
 #include "engine_setup.h"
 #include "engine_forward.h"
 #include "engine_io.h"
@@ -742,12 +743,12 @@ int mv_set_compute_mode(mv_handle h, int32_t mode) {
         h->ph16[i].alloc(2 * (rows * K * c.hidden_size + mv::kPlaneSlack + mv::kPlanePad));
         HIP_CHECK(hipMemset(h->px16[i].p, 0, h->px16[i].n * sizeof(_Float16)));
         if (c.activation != 0) h->xexp[i].alloc(65);    // never inside a graph capture
-        if (mode == 1 && mv::wino_enabled() && mv::wino3_enabled() && c.activation == 0) {
+        if (wino3_possible(mode, c.activation)) {    // F(3,3): the pre-transformed operands
           size_t vx = 0, vh = 0;
           for (int s = 0; s < c.num_scales; ++s) {
-            if (!h->sc[s].use || h->sc[s].H < 3) continue;
-            vx = std::max(vx, mv::wino3_v_elems((int)rows, h->sc[s].H, h->sc[s].W, (int)((xc + 15) / 16 * 16)));
-            vh = std::max(vh, mv::wino3_v_elems((int)rows, h->sc[s].H, h->sc[s].W, c.hidden_size));
+            if (!h->sc[s].use) continue;
+            vx = std::max(vx, wino3_scratch_elems((int)rows, h->sc[s].H, h->sc[s].W, (int)xc));
+            vh = std::max(vh, wino3_scratch_elems((int)rows, h->sc[s].H, h->sc[s].W, c.hidden_size));
           }
           if (vx) h->pv3x[i].alloc(vx);
           if (vh) h->pv3h[i].alloc(vh);

@@ -62,20 +62,26 @@ ConvCell* cell_of_pack(mv_engine* e, const float* wpack) {
   throw HipError{"internal: unknown weight pack"};
 }
 
-// f16x3 compute mode: split the fp32 operands of every problem into two scaled
-// fp16 planes (HBM-bound, ~2 % of the step), then one grouped launch of the
-// fp16-MFMA kernel.
-void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
-                          double flops, double bytes, double dense) {
-  std::vector<mv::ConvLstm16Args> p16(probs.size());
+// ---- f16x3 / bf16 compute modes: prepare the operand planes, plan the launch (gate_plan.h),
+// queue the F(3,3) input transforms, launch.
+
+// Operand planes of every problem of a group: the planes a producer left, or a split of the fp32
+// operand into the slot's scratch (one grouped launch; unbounded x operands one by one, under
+// their own exponent).  Fills p16[i] up to the weight packs.
+void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
+                           const std::vector<ConvCell*>& cells,
+                           std::vector<mv::ConvLstm16Args>& p16) {
   struct SplitItem { const float* in; _Float16* p0; _Float16* p1; int cells, C; };
   std::vector<SplitItem> splits;
   struct DynItem { const float* in; _Float16* p0; _Float16* p1; int cells, C; int32_t* bits; };
   std::vector<DynItem> dyn_splits;
   const bool bf16 = e->compute_mode == 2;
+  auto ready = [&](const float* src) -> const mv_engine::PlaneBuf* {
+    auto it = e->planes.find(src);
+    return (it != e->planes.end() && it->second.valid) ? &it->second : nullptr;
+  };
   for (size_t i = 0; i < probs.size(); ++i) {
     const ConvLstmArgs& a = probs[i];
-    ConvCell* cc = cell_of_pack(e, a.wpack);
     mv::ConvLstm16Args& q = p16[i];
     // the kernel's epilogue lets a 32-cell wave tile span at most two images
     MV_REQUIRE(a.H * a.W >= 32, "f16x3 / bf16 compute modes need grids of at least 32 cells "
@@ -88,15 +94,14 @@ void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
                "f16x3 / bf16 training forward: gate tensor of %d rows exceeds 4 GB "
                "(lower the per-GPU batch or use compute mode f32)", a.rows);
     q.f = a;
-    q.wp16 = bf16 ? cc->wpb.p : cc->wp16.p;
-    q.wx32 = bf16 ? cc->wx32u.p : cc->wx32.p;
-    const size_t cells = (size_t)a.rows * a.H * a.W;
+    q.wp16 = bf16 ? cells[i]->wpb.p : cells[i]->wp16.p;
+    q.wx32 = bf16 ? cells[i]->wx32u.p : cells[i]->wx32.p;
+    const size_t ncell = (size_t)a.rows * a.H * a.W;
     // bf16 mode, unbounded activations: three x passes (convlstm_f16x3.h xpasses)
-    const int xpass = (bf16 && e->dyn_x() && !a.x_small) ? 3 : 1;
+    const int xpass = bf16_x_passes(e->compute_mode, e->dyn_x(), a.x_small);
     q.n_xk = a.x_small ? 0 : xpass * mv::f16x3_xksteps(a.Cx);
     q.n_hk = a.zero_state ? 0 : 9 * (a.C / 16);
-    q.w_ksteps = xpass * mv::f16x3_xksteps(a.Cx) + 9 * (a.C / 16);
-    if (a.x_small) q.w_ksteps = 9 * (a.C / 16);
+    q.w_ksteps = (a.x_small ? 0 : xpass * mv::f16x3_xksteps(a.Cx)) + 9 * (a.C / 16);
     if (bf16)       // an LDS stage of the bf16 kernel holds MV_BF16_UNITS row units of 3 k-steps
       MV_REQUIRE((q.n_xk / 3) % MV_BF16_UNITS == 0 && (q.n_hk / 3) % MV_BF16_UNITS == 0,
                  "bf16 mode: %d x / %d h k-steps do not fill whole LDS stages (emb_size and "
@@ -106,11 +111,10 @@ void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
     // The conv epilogue emits the operand planes of h' (assembled per wave in LDS,
     // 16-byte stores) when the next consumer of h' is a gate convolution; MV_EPI_PLANES=0
     // falls back to the separate split pass over the fp32 h'.
-    static const bool epi = !(getenv("MV_EPI_PLANES") && atoi(getenv("MV_EPI_PLANES")) == 0);
     q.h16_out = nullptr;
     q.h16_out_stride = 0;
     e->plane_invalidate(a.h_out);
-    if (epi && a.want_h16 && !a.gates_out) {
+    if (gate_knobs().epi_planes && a.want_h16 && !a.gates_out) {
       size_t pst = 0;
       if (_Float16* po = e->plane_out(a.h_out, &pst)) {   // marks the planes valid
         q.h16_out = po;
@@ -118,40 +122,38 @@ void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
       }
     }
     q.f.skip_h32 = (a.skip_h32 && q.h16_out && !e->train) ? 1 : 0;
-    auto ready = [&](const float* src) -> const mv_engine::PlaneBuf* {
-      auto it = e->planes.find(src);
-      return (it != e->planes.end() && it->second.valid) ? &it->second : nullptr;
-    };
-    if (!a.x_small && a.Cx > 0 && !a.sx_corr) {
+    if (has_dense_x(a)) {
       MV_REQUIRE((size_t)a.x_row_stride == (size_t)a.H * a.W * a.Cx,
                  "internal: f16x3 needs a contiguous x operand");
-      const size_t n = cells * a.Cx;
       if (const auto* pb = ready(a.x)) {
         q.x16 = pb->p; q.x_plane_stride = (int64_t)pb->n;
       } else {
-      const size_t pst = n + mv::kPlaneSlack + mv::kPlanePad;
-      MV_REQUIRE(e->px16[i].n >= 2 * pst, "internal: f16x3 x plane scratch");
-      _Float16* p0 = e->px16[i].p + mv::kPlanePad;
-      q.x16 = p0; q.x_plane_stride = (int64_t)pst;
-      if (e->dyn_x()) {       // unbounded activations: planes of 2^e x, e from max |x|
-        MV_REQUIRE(e->xexp[i].p, "internal: x exponent scratch");
-        q.x_exp = e->xexp[i].p + 64;
-        dyn_splits.push_back(DynItem{a.x, p0, p0 + pst, (int)cells, a.Cx, e->xexp[i].p});
-      } else {
-      splits.push_back(SplitItem{a.x, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)cells, a.Cx});
+        const size_t pst = ncell * a.Cx + mv::kPlaneSlack + mv::kPlanePad;
+        MV_REQUIRE(e->px16[i].n >= 2 * pst, "internal: f16x3 x plane scratch");
+        _Float16* p0 = e->px16[i].p + mv::kPlanePad;
+        q.x16 = p0; q.x_plane_stride = (int64_t)pst;
+        if (e->dyn_x()) {       // unbounded activations: planes of 2^e x, e from max |x|
+          MV_REQUIRE(e->xexp[i].p, "internal: x exponent scratch");
+          q.x_exp = e->xexp[i].p + 64;
+          dyn_splits.push_back(DynItem{a.x, p0, p0 + pst, (int)ncell, a.Cx, e->xexp[i].p});
+        } else {
+          splits.push_back(SplitItem{a.x, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)ncell, a.Cx});
+        }
       }
-      }
+      // the three-pass x kernel of the bf16 mode is chosen per launch from the problems' x
+      // exponents, the weight packs per cell from dyn_x(): they must agree
+      MV_REQUIRE(!(bf16 && e->dyn_x()) || q.x_exp, "internal: bf16 mode, unbounded activations: "
+                 "a dense x operand came as producer planes, without its exponent");
     }
-    if (!a.zero_state) {
-      const size_t n = cells * a.C;     // source rows == rows (beam: permuted, same count)
+    if (!a.zero_state) {      // source rows == rows (beam: permuted, same count)
       if (const auto* pb = ready(a.h)) {
         q.h16 = pb->p; q.h_plane_stride = (int64_t)pb->n;
       } else {
-      const size_t pst = n + mv::kPlaneSlack + mv::kPlanePad;
-      MV_REQUIRE(e->ph16[i].n >= 2 * pst, "internal: f16x3 h plane scratch");
-      _Float16* p0 = e->ph16[i].p + mv::kPlanePad;
-      q.h16 = p0; q.h_plane_stride = (int64_t)pst;
-      splits.push_back(SplitItem{a.h, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)cells, a.C});
+        const size_t pst = ncell * a.C + mv::kPlaneSlack + mv::kPlanePad;
+        MV_REQUIRE(e->ph16[i].n >= 2 * pst, "internal: f16x3 h plane scratch");
+        _Float16* p0 = e->ph16[i].p + mv::kPlanePad;
+        q.h16 = p0; q.h_plane_stride = (int64_t)pst;
+        splits.push_back(SplitItem{a.h, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)ncell, a.C});
       }
     }
   }
@@ -182,99 +184,81 @@ void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
       hipLaunchKernelGGL(mv::split_planes_group_kernel, dim3(nb), dim3(256), 0, e->stream, g);
     });
   }
-  // f16x3: the Winograd F(2,3) form of the same step (two thirds of the MFMAs,
-  // convlstm_wino.h) whenever every problem of the group fits its tiling
-  const bool wino_mode = e->compute_mode == 1 && mv::wino_enabled();
-  bool wino = wino_mode;
-  std::vector<mv::ConvLstmWinoArgs> pw(p16.size());
-  for (size_t i = 0; i < p16.size(); ++i) {
-    ConvCell* cc = cell_of_pack(e, probs[i].wpack);
-    if (!mv::wino_geometry_ok(p16[i].f) || !cc->wpw.p) wino = false;
+}
+
+// F(3,3): the input transform of every operand of the group runs ONCE, in a pre-pass into `out`,
+// instead of in every one of the C / 16 column-block workgroups of the gate kernel.
+double queue_wino3_transform(std::vector<mv::Wn3TransformItem>& tr, const mv::Wn3TransformItem& it) {
+  tr.push_back(it);
+  return (double)it.rows * it.H * it.W * it.Cc * 4.0 * (1.0 + 5.0 / 3.0);     // bytes moved
+}
+
+// The grouped gate launch in the planned form.  p16: the prepared problems; packs: per problem
+// the pack of that form; v3x / v3h: per problem the pre-transformed operands (Wino3), or NULL.
+void launch_gate_group(const ForwardPlan& pl, const mv::ConvLstm16Args* p16,
+                       const _Float16* const* packs, const float* const* w_hwio,
+                       _Float16* const* v3x, _Float16* const* v3h, int n, hipStream_t stream) {
+  if (pl.form == GateForm::Direct16)
+    return mv::launch_convlstm16_steps(p16, n, pl.shift, pl.map_mode, stream);
+  if (pl.form == GateForm::Bf16)
+    return mv::launch_convlstm_bf16_steps(p16, n, pl.shift, pl.map_mode, pl.x_passes == 3, stream);
+  mv::ConvLstmWinoArgs pw[mv::kMaxGroup] = {};
+  for (int i = 0; i < n; ++i) {
     pw[i].b = p16[i];
-    pw[i].wpw = cc->wpw.p;
-    pw[i].w_hwio = cc->kernel->dev.p;
+    pw[i].wpw = packs[i];
+    pw[i].w_hwio = w_hwio[i];
     pw[i].n_xc = p16[i].f.x_small ? 0 : p16[i].f.Cx / 16;
+    pw[i].v3x = v3x ? v3x[i] : nullptr;
+    pw[i].v3h = v3h ? v3h[i] : nullptr;
   }
-  // ... and its F(3,3) form (five ninths, convlstm_wino3.h) when every problem fits THAT tiling
-  // (any grid width: widths that do not divide 32 take its halo tiling) and the slots' buffers
-  // hold the pre-transformed operands.  The input transform runs ONCE per operand, in a
-  // pre-pass, instead of in every one of the C / 16 column-block workgroups of the gate kernel.
-  bool wino3 = wino_mode && mv::wino3_enabled();
-  for (size_t i = 0; i < p16.size() && wino3; ++i) {
-    const ConvLstmArgs& a = p16[i].f;
-    ConvCell* cc = cell_of_pack(e, probs[i].wpack);
-    if (!mv::wino3_geometry_ok(a, p16[i]) || !cc->wpw3.p) wino3 = false;
-    else if (!mv::wino3_halo_addressable(a)) wino3 = false;   // 32-bit lane offsets (HALO)
-    else if (!a.zero_state && e->pv3h[i].n < mv::wino3_v_elems(a.rows, a.H, a.W, a.C)) wino3 = false;
-    else if (!a.x_small && a.Cx > 0 && !a.sx_corr &&
-             e->pv3x[i].n < mv::wino3_v_elems(a.rows, a.H, a.W, a.Cx)) wino3 = false;
-  }
+  if (pl.form == GateForm::Wino2) mv::launch_convlstm_wino_steps(pw, n, pl.map_mode, stream);
+  else if (pl.form == GateForm::Wino3)
+    mv::launch_convlstm_wino3_steps(pw, n, pl.halo, pl.map_mode, stream);
+  else mv::launch_convlstm_bf16t_steps(pw, n, pl.halo, pl.map_mode, stream);
+}
+
+void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
+                          double flops, double bytes, double dense) {
+  const int n = (int)probs.size();
+  MV_REQUIRE(n <= mv::kMaxGroup, "internal: gate group of %d problems", n);
+  std::vector<ConvCell*> cells(n);
+  for (int i = 0; i < n; ++i) cells[i] = cell_of_pack(e, probs[i].wpack);
+  std::vector<mv::ConvLstm16Args> p16(n);
+  prepare_gate_operands(e, probs, cells, p16);
+  ForwardProblem fp[mv::kMaxGroup];
+  for (int i = 0; i < n; ++i) fp[i] = ForwardProblem{&p16[i], cells[i], e->pv3x[i].n, e->pv3h[i].n};
+  const ForwardPlan pl = plan_forward_group(e->compute_mode, fp, n);
+  const _Float16* packs[mv::kMaxGroup] = {};
+  const float* w_hwio[mv::kMaxGroup] = {};
+  _Float16 *v3x[mv::kMaxGroup] = {}, *v3h[mv::kMaxGroup] = {};
   std::vector<mv::Wn3TransformItem> tr3;
   double tr3_bytes = 0;
-  if (wino3) {
-    for (size_t i = 0; i < p16.size(); ++i) {
-      const mv::ConvLstm16Args& q = p16[i];
-      const ConvLstmArgs& a = q.f;
-      const double cells = (double)a.rows * a.H * a.W;
-      pw[i].wpw = cell_of_pack(e, probs[i].wpack)->wpw3.p;
-      if (!a.zero_state) {
-        tr3.push_back(mv::Wn3TransformItem{q.h16, q.h_plane_stride, e->pv3h[i].p, a.src_row_h,
-                                           a.rows, a.H, a.W, a.C});
-        pw[i].v3h = e->pv3h[i].p;
-        tr3_bytes += cells * a.C * 4.0 * (1.0 + 5.0 / 3.0);
-      }
-      if (!a.x_small && a.Cx > 0 && !a.sx_corr) {
-        tr3.push_back(mv::Wn3TransformItem{q.x16, q.x_plane_stride, e->pv3x[i].p, nullptr,
-                                           a.rows, a.H, a.W, a.Cx});
-        pw[i].v3x = e->pv3x[i].p;
-        tr3_bytes += cells * a.Cx * 4.0 * (1.0 + 5.0 / 3.0);
-      }
+  for (int i = 0; i < n; ++i) {
+    const mv::ConvLstm16Args& q = p16[i];
+    const ConvLstmArgs& a = q.f;
+    w_hwio[i] = cells[i]->kernel->dev.p;
+    packs[i] = pl.form == GateForm::Wino2 ? cells[i]->wpw.p
+             : pl.form == GateForm::Wino3 ? cells[i]->wpw3.p
+             : pl.form == GateForm::Bf16T ? cells[i]->wpbt.p : nullptr;
+    if (pl.form != GateForm::Wino3) continue;
+    if (!a.zero_state) {
+      v3h[i] = e->pv3h[i].p;
+      tr3_bytes += queue_wino3_transform(tr3, {q.h16, q.h_plane_stride, v3h[i], a.src_row_h,
+                                               a.rows, a.H, a.W, a.C});
+    }
+    if (has_dense_x(a)) {
+      v3x[i] = e->pv3x[i].p;
+      tr3_bytes += queue_wino3_transform(tr3, {q.x16, q.x_plane_stride, v3x[i], nullptr,
+                                               a.rows, a.H, a.W, a.Cx});
     }
   }
   if (!tr3.empty())
     launch(e, "wino3_transform", 0, tr3_bytes, [&] {
       mv::launch_wino3_transforms(tr3.data(), (int)tr3.size(), e->stream);
     });
-  // fp16 MFMA products ISSUED per executed fp32 product: 3 in the direct form; in a Winograd
-  // form 3 * (components * row tiles) / (3 * H) -- partial tiles count (9 rows = 5 pairs: 2.22,
-  // not 2), weighted over the group by executed FLOPs
-  double factor = e->compute_mode == 2 ? 1.0 : 3.0;
-  if (wino || wino3) {
-    double num = 0, den = 0;
-    for (const auto& a : probs) {
-      const double cx = a.sx_corr ? 0.0 : (double)a.Cx;
-      const double fl = (double)a.rows * a.H * a.W * (cx + (a.zero_state ? 0 : a.C));
-      // (the halo tiling issues 32 lanes for 30 owned triple-cells)
-      const double per = wino3 ? 5.0 * ((a.H + 2) / 3) / a.H * (mv::wino3_needs_halo(a) ? 32.0 / 30.0 : 1.0)
-                               : 4.0 * ((a.H + 1) / 2) / a.H;
-      num += fl * per; den += fl;
-    }
-    factor = den > 0 ? num / den : (wino3 ? 5.0 / 3.0 : 2.0);
-  }
-  // bf16 mode: the row-triple tile (convlstm_wino3.h BF16D) when every problem fits it
-  bool bf16t = bf16 && mv::bf16t_enabled();
-  for (size_t i = 0; i < p16.size() && bf16t; ++i) {
-    ConvCell* cc = cell_of_pack(e, probs[i].wpack);
-    if (!mv::bf16t_geometry_ok(p16[i].f, p16[i]) || !cc->wpbt.p) bf16t = false;
-  }
-  if (bf16t)
-    for (size_t i = 0; i < p16.size(); ++i) {
-      pw[i].b = p16[i];
-      pw[i].wpw = cell_of_pack(e, probs[i].wpack)->wpbt.p;
-      pw[i].v3x = pw[i].v3h = nullptr;
-    }
   launch(e, "convlstm_step", flops, bytes, [&] {
-    if (bf16t)
-      mv::launch_convlstm_bf16t_steps(pw.data(), (int)pw.size(), e->stream);
-    else if (e->compute_mode == 2)
-      mv::launch_convlstm_bf16_steps(p16.data(), (int)p16.size(), e->stream);
-    else if (wino3)
-      mv::launch_convlstm_wino3_steps(pw.data(), (int)pw.size(), e->stream);
-    else if (wino)
-      mv::launch_convlstm_wino_steps(pw.data(), (int)pw.size(), e->stream);
-    else
-      mv::launch_convlstm16_steps(p16.data(), (int)p16.size(), e->stream);
-  }, dense, factor);
+    launch_gate_group(pl, p16.data(), packs, w_hwio, v3x, v3h, n, e->stream);
+  }, dense, pl.mfma_factor);
 }
 
 // One launch for up to four independent ConvLSTM steps (class / regression

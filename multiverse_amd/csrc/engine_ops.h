@@ -77,11 +77,11 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
     MV_REQUIRE(H * W >= 32, "grids of at least 32 cells");
     OpCtx ctx(device);
     const size_t cells = (size_t)M * H * W;
-    const bool small = Cx > 0 && 9 * Cx <= mv::kBK;
-    const int Cx16 = small ? 0 : Cx;
+    const bool small = x_is_small(Cx);
+    const int Cx16 = x_chunk16(Cx);
     const int Cin = Cx + C, N4 = 4 * C;
     DevBuf<float> dx, dc, dh, dw, db, dco, dho, dk, dwx, dplanes;
-    DevBuf<_Float16> px, ph, pho, wp;
+    DevBuf<_Float16> px, ph, pho, wp, v3x, v3h;
     ctx.up(dx, x, cells * Cx);
     ctx.up(db, biases, (size_t)4 * C);
     ctx.up(dk, kernel, (size_t)9 * Cin * N4);
@@ -124,76 +124,59 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
     q.n_xk = small ? 0 : mv::f16x3_xksteps(Cx);
     q.n_hk = zero ? 0 : 9 * (C / 16);
     q.w_ksteps = small ? 9 * (C / 16) : mv::f16x3_xksteps(Cx) + 9 * (C / 16);
+    // the variant forces its form: the engine's packs and launcher, under an explicit plan
+    // (block maps and shift as the engine would choose them)
+    ForwardPlan pl;
+    pl.shift = gate_knobs().conv_shift && 32 % W == 0;
+    pl.map_mode = gate_knobs().conv_map;
+    _Float16 *v3xp = nullptr, *v3hp = nullptr;
     if (variant == 1) {
       std::vector<_Float16> p16(mv::f16x3_wpack_elems(Cx16, C));
       if (small) {
-        std::vector<float> wh((size_t)9 * C * N4);
-        for (int t = 0; t < 9; ++t)
-          memcpy(&wh[(size_t)t * C * N4], &kernel[((size_t)t * Cin + Cx) * N4],
-                 (size_t)C * N4 * sizeof(float));
-        mv::pack_f16x3_weights(wh.data(), 0, C, p16.data());
-        const int nch = mv::convlstm_xchunks(Cx) + 9 * (C / mv::kBK);
-        std::vector<float> wx((size_t)(C / mv::kChBlock) * mv::kBN * mv::kBK);
-        for (int cb = 0; cb < C / mv::kChBlock; ++cb)
-          for (int i = 0; i < mv::kBN * mv::kBK; ++i)
-            wx[(size_t)cb * mv::kBN * mv::kBK + i] =
-                packed[((size_t)cb * nch + 0) * mv::kBN * mv::kBK + i] * 65536.0f;
-        ctx.up(dwx, wx.data(), wx.size());
+        mv::pack_f16x3_weights(kernel_h_rows(kernel, Cx, C).data(), 0, C, p16.data());
+        upload(dwx, small_x_chunk(kernel, Cx, C, 65536.0f));
         q.wx32 = dwx.p;
       } else {
         mv::pack_f16x3_weights(kernel, Cx, C, p16.data());
       }
-      ctx.up(wp, p16.data(), p16.size());
+      upload(wp, p16);
       q.wp16 = wp.p;
-      mv::launch_convlstm16_steps(&q, 1, ctx.stream);
     } else if (variant == 4) {
       MV_REQUIRE(mv::bf16t_geometry_ok(a, q), "bf16 row-triple tile: H %d >= 3", H);
-      const size_t halves = mv::bf16t_wpack_elems(Cx16, C, mv::kW3Nrb);
-      wp.alloc(halves);
-      hipLaunchKernelGGL(mv::pack_bf16t_kernel, dim3(cdiv(halves, 256)), dim3(256), 0,
-                         ctx.stream, dk.p, wp.p, Cx, Cx16, C, mv::kW3Nrb, halves);
-      mv::ConvLstmWinoArgs wq{};
+      pack_bf16t(ctx.stream, dk.p, Cx, C, wp);
       q.x_plane_stride = q.h_plane_stride = q.h16_out_stride = 0;     // single planes
-      wq.b = q; wq.wpw = wp.p; wq.w_hwio = dk.p; wq.n_xc = Cx16 / 16;
-      mv::launch_convlstm_bf16t_steps(&wq, 1, ctx.stream);
+      pl.form = GateForm::Bf16T;
+      pl.halo = mv::wino3_needs_halo(a);
+      pl.map_mode = gate_knobs().wino_map_bf16t;
     } else if (variant == 3) {
       MV_REQUIRE(mv::wino3_geometry_ok(a, q), "Winograd F(3,3) form: H %d >= 3", H);
-      MV_REQUIRE(mv::wino3_halo_addressable(a), "Winograd F(3,3) form, halo tiling (W %d does "
+      MV_REQUIRE(!mv::wino3_needs_halo(a) || mv::wino3_halo_addressable(a),
+                 "Winograd F(3,3) form, halo tiling (W %d does "
                  "not divide 32): an operand of 2 GiB or more is not addressable", W);
-      const size_t halves = mv::wino3_wpack_elems(Cx16, C, mv::kW3Nrb);
-      wp.alloc(halves);
-      hipLaunchKernelGGL(mv::pack_wino3_kernel, dim3(cdiv(halves / 2, 256)), dim3(256), 0,
-                         ctx.stream, dk.p, wp.p, Cx, Cx16, C, mv::kW3Nrb, halves / 2);
-      mv::ConvLstmWinoArgs wq{};
-      wq.b = q; wq.wpw = wp.p; wq.w_hwio = dk.p; wq.n_xc = Cx16 / 16;
+      pack_wino3(ctx.stream, dk.p, Cx, C, wp);
+      pl.form = GateForm::Wino3;
+      pl.halo = mv::wino3_needs_halo(a);
+      pl.map_mode = gate_knobs().wino_map_f33;
       // the pre-transformed operands, as the engine hands them over
-      DevBuf<_Float16> v3x, v3h;
-      {
-        std::vector<mv::Wn3TransformItem> tr;
-        if (!zero) {
-          v3h.alloc(mv::wino3_v_elems(M, H, W, C));
-          tr.push_back(mv::Wn3TransformItem{q.h16, q.h_plane_stride, v3h.p, nullptr, M, H, W, C});
-          wq.v3h = v3h.p;
-        }
-        if (Cx16 > 0) {
-          v3x.alloc(mv::wino3_v_elems(M, H, W, Cx16));
-          tr.push_back(mv::Wn3TransformItem{q.x16, q.x_plane_stride, v3x.p, nullptr, M, H, W, Cx16});
-          wq.v3x = v3x.p;
-        }
-        mv::launch_wino3_transforms(tr.data(), (int)tr.size(), ctx.stream);
+      std::vector<mv::Wn3TransformItem> tr;
+      if (!zero) {
+        v3h.alloc(mv::wino3_v_elems(M, H, W, C));
+        queue_wino3_transform(tr, {q.h16, q.h_plane_stride, v3hp = v3h.p, nullptr, M, H, W, C});
       }
-      mv::launch_convlstm_wino3_steps(&wq, 1, ctx.stream);
-      HIP_CHECK(hipStreamSynchronize(ctx.stream));    // v3x / v3h die with this scope
+      if (Cx16 > 0) {
+        v3x.alloc(mv::wino3_v_elems(M, H, W, Cx16));
+        queue_wino3_transform(tr, {q.x16, q.x_plane_stride, v3xp = v3x.p, nullptr, M, H, W, Cx16});
+      }
+      mv::launch_wino3_transforms(tr.data(), (int)tr.size(), ctx.stream);
     } else {
       MV_REQUIRE(mv::wino_geometry_ok(a), "Winograd form: W %d must divide 32, H >= 2", W);
-      const size_t halves = mv::wino_wpack_elems(Cx16, C);
-      wp.alloc(halves);
-      hipLaunchKernelGGL(mv::pack_wino_kernel, dim3(cdiv(halves / 2, 256)), dim3(256), 0,
-                         ctx.stream, dk.p, wp.p, Cx, Cx16, C, halves / 2);
-      mv::ConvLstmWinoArgs wq{};
-      wq.b = q; wq.wpw = wp.p; wq.w_hwio = dk.p; wq.n_xc = Cx16 / 16;
-      mv::launch_convlstm_wino_steps(&wq, 1, ctx.stream);
+      pack_wino(ctx.stream, dk.p, Cx, C, wp);
+      pl.form = GateForm::Wino2;
+      pl.map_mode = gate_knobs().wino_map_f23;
     }
+    const _Float16* pack = wp.p;
+    const float* hwio = dk.p;
+    launch_gate_group(pl, &q, &pack, &hwio, &v3xp, &v3hp, 1, ctx.stream);
     HIP_CHECK(hipGetLastError());
     if (h16_out) {
       dplanes.alloc(cells * C);
@@ -347,11 +330,10 @@ int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* 
     mv::convlstm_dgrad_args(d, dg.p, dwd.p, dho2.p, dxo.p, M, H, W, Cx, C, true, Cx > 0);
     mv::launch_convlstm_dgrads(&d, 1, ctx.stream);
     // wgrad (device-side packs are checked against the host packs on the way)
-    mv::WgradArgs wa{};
+    const WgradPlan wpl = plan_wgrad(0, 3, M, H, W, Cx, C);
+    mv::WgradArgs wa = wpl.fp32;
     wa.x = Cx ? dx_.p : nullptr; wa.h = dh_.p; wa.g = dg.p;
-    wa.R = M; wa.H = H; wa.W = W; wa.Cx = Cx; wa.C = C;
-    mv::wgrad_plan(wa, 3072);
-    part.alloc(mv::wgrad_partial_elems(wa));
+    part.alloc(wpl.partial_elems);
     wa.partial = part.p;
     mv::launch_convlstm_wgrad(wa, ctx.stream);
     const size_t ncols = (size_t)9 * (Cx + C) * 4 * C;
@@ -369,8 +351,8 @@ int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* 
       const int nx = mv::convlstm_xchunks(Cx), nch = nx + 9 * (C / mv::kBK);
       p1.alloc(packed.size()); p2.alloc(packedT.size());
       hipLaunchKernelGGL(mv::pack_fwd_kernel, dim3(cdiv(packed.size(), 256)), dim3(256), 0,
-                         ctx.stream, wsrc.p, p1.p, Cx, C, nx, nch,
-                         (Cx > 0 && 9 * Cx <= mv::kBK) ? 1 : 0, packed.size());
+                         ctx.stream, wsrc.p, p1.p, Cx, C, nx, nch, x_is_small(Cx) ? 1 : 0,
+                         packed.size());
       hipLaunchKernelGGL(mv::pack_dgrad_kernel, dim3(cdiv(packedT.size(), 256)), dim3(256),
                          0, ctx.stream, wsrc.p, p2.p, Cx, C, 9 * (4 * C / mv::kBK),
                          packedT.size());

@@ -289,21 +289,53 @@ void ensure_packed(mv_engine* e, ConvCell& cc) {
                       hipMemcpyHostToDevice));
 }
 
-static bool C_multiple_ok(const mv_engine* e, const ConvCell& cc) {
-  return e->cfg.hidden_size % mv::kWnCh == 0 &&
-         (cc.Cx % 16 == 0 || (cc.Cx > 0 && 9 * cc.Cx <= mv::kBK));
+CellPacks packs_of(const mv_engine* e, const ConvCell& cc) {
+  return cell_packs(e->compute_mode, e->cfg.activation, cc.Cx, e->cfg.hidden_size,
+                    cc.wino_numerics_ok);
 }
+
+// A small x operand (gate_plan.h x_is_small) is one fp32 chunk of the gate GEMM: the matrix-pipe
+// packs then hold the h rows alone ...
+std::vector<float> kernel_h_rows(const float* kernel, int Cx, int C) {
+  const int Cin = Cx + C, N4 = 4 * C;
+  std::vector<float> wh((size_t)9 * C * N4);
+  for (int t = 0; t < 9; ++t)
+    memcpy(&wh[(size_t)t * C * N4], &kernel[((size_t)t * Cin + Cx) * N4],
+           (size_t)C * N4 * sizeof(float));
+  return wh;
+}
+// ... and the x chunk travels beside them: chunk 0 of every column block of the fp32 pack,
+// scaled (f16x3: 2^16, bf16: 1)
+std::vector<float> small_x_chunk(const float* kernel, int Cx, int C, float scale) {
+  std::vector<float> packed(mv::convlstm_wpack_elems(Cx, C));
+  mv::pack_convlstm_weights(kernel, Cx, C, packed.data());
+  const int nch = mv::convlstm_xchunks(Cx) + 9 * (C / mv::kBK);
+  std::vector<float> wx((size_t)(C / mv::kChBlock) * mv::kBN * mv::kBK);
+  for (int cb = 0; cb < C / mv::kChBlock; ++cb)
+    for (int i = 0; i < mv::kBN * mv::kBK; ++i)
+      wx[(size_t)cb * mv::kBN * mv::kBK + i] =
+          packed[((size_t)cb * nch + 0) * mv::kBN * mv::kBK + i] * scale;
+  return wx;
+}
+template <typename T>
+void upload(DevBuf<T>& dst, const std::vector<T>& src) {
+  dst.alloc(src.size());
+  HIP_CHECK(hipMemcpy(dst.p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+}
+void refresh_host_copy(ConvCell& cc) {
+  if (!cc.host_stale) return;
+  HIP_CHECK(hipMemcpy(cc.kernel->host.data(), cc.kernel->dev.p,
+                      cc.kernel->elems() * sizeof(float), hipMemcpyDeviceToHost));
+  cc.host_stale = false;
+}
+
 // f16x3 packs (two scaled fp16 planes in fragment order; the fp32 x chunk of the
 // 2-channel regression-encoder input scaled by 2^16), from the CURRENT weights.
 void ensure_packed16(mv_engine* e, ConvCell& cc) {
   if (cc.wp16.p) return;
   const int C = e->cfg.hidden_size;
   MV_REQUIRE(mv::f16x3_cx_supported(cc.Cx), "f16x3: Cx %d unsupported", cc.Cx);
-  if (cc.host_stale) {
-    HIP_CHECK(hipMemcpy(cc.kernel->host.data(), cc.kernel->dev.p,
-                        cc.kernel->elems() * sizeof(float), hipMemcpyDeviceToHost));
-    cc.host_stale = false;
-  }
+  refresh_host_copy(cc);
   {   // 256 w must stay inside fp16 (|w| < 255): true of any sane checkpoint, checked anyway
     float mx = 0.f;
     for (float v : cc.kernel->host) mx = std::max(mx, std::fabs(v));
@@ -312,7 +344,7 @@ void ensure_packed16(mv_engine* e, ConvCell& cc) {
     // same of the flipped rows -- which reach up to 1.5 max |w| when three taps of one column
     // share a sign: the bound is taken on THOSE values, column by column
     float reach = mx;
-    if (mv::wino_enabled() && C_multiple_ok(e, cc)) {
+    if (cell_packs(1, e->cfg.activation, cc.Cx, C, true).wpw) {   // whatever the outlier test says
       const size_t Cin = (size_t)cc.Cx + C, N4 = 4 * (size_t)C;
       const float* w = cc.kernel->host.data();
       for (size_t dxc = 0; dxc < 3 * Cin; ++dxc) {          // (dx, input channel) pairs
@@ -346,89 +378,54 @@ void ensure_packed16(mv_engine* e, ConvCell& cc) {
     if (ok != cc.wino_numerics_ok) { cc.wpw.release(); cc.wpw3.release(); }
     cc.wino_numerics_ok = ok;
   }
-  const bool small = cc.Cx > 0 && 9 * cc.Cx <= mv::kBK;
   // the h part (and an x part that is a multiple of 16 channels) as fp16 planes
-  const int Cx16 = small ? 0 : cc.Cx;
-  std::vector<_Float16> p16(mv::f16x3_wpack_elems(Cx16, C));
-  if (small) {   // drop the x channels: pack a view of the kernel without them
-    const int Cin = cc.Cx + C, N4 = 4 * C;
-    std::vector<float> wh((size_t)9 * C * N4);
-    for (int t = 0; t < 9; ++t)
-      memcpy(&wh[(size_t)t * C * N4], &cc.kernel->host[((size_t)t * Cin + cc.Cx) * N4],
-             (size_t)C * N4 * sizeof(float));
-    mv::pack_f16x3_weights(wh.data(), 0, C, p16.data());
-    std::vector<float> packed(mv::convlstm_wpack_elems(cc.Cx, C));
-    mv::pack_convlstm_weights(cc.kernel->host.data(), cc.Cx, C, packed.data());
-    const int nch = mv::convlstm_xchunks(cc.Cx) + 9 * (C / mv::kBK);
-    std::vector<float> wx((size_t)(C / mv::kChBlock) * mv::kBN * mv::kBK);
-    for (int cb = 0; cb < C / mv::kChBlock; ++cb)
-      for (int i = 0; i < mv::kBN * mv::kBK; ++i)
-        wx[(size_t)cb * mv::kBN * mv::kBK + i] =
-            packed[((size_t)cb * nch + 0) * mv::kBN * mv::kBK + i] * 65536.0f;
-    cc.wx32.alloc(wx.size());
-    HIP_CHECK(hipMemcpy(cc.wx32.p, wx.data(), wx.size() * sizeof(float),
-                        hipMemcpyHostToDevice));
+  std::vector<_Float16> p16(mv::f16x3_wpack_elems(x_chunk16(cc.Cx), C));
+  if (x_is_small(cc.Cx)) {
+    mv::pack_f16x3_weights(kernel_h_rows(cc.kernel->host.data(), cc.Cx, C).data(), 0, C, p16.data());
+    upload(cc.wx32, small_x_chunk(cc.kernel->host.data(), cc.Cx, C, 65536.0f));
   } else {
     mv::pack_f16x3_weights(cc.kernel->host.data(), cc.Cx, C, p16.data());
   }
-  cc.wp16.alloc(p16.size());
-  HIP_CHECK(hipMemcpy(cc.wp16.p, p16.data(), p16.size() * sizeof(_Float16),
-                      hipMemcpyHostToDevice));
+  upload(cc.wp16, p16);
 }
 
-// Winograd F(2,3) pack of the f16x3 forward (convlstm_wino.h), from the CURRENT device
-// weights; the transform of the kernel rows runs in fp64 on the device.
-void pack_wino(mv_engine* e, ConvCell& cc) {
-  const int C = e->cfg.hidden_size;
-  const bool small = cc.Cx > 0 && 9 * cc.Cx <= mv::kBK;
-  const int Cx16 = small ? 0 : cc.Cx;
-  const size_t halves = mv::wino_wpack_elems(Cx16, C);
+// Device-side packs of the kernel `w` (HWIO, fp32, on the device) into `dst`: Winograd F(2,3) of
+// the f16x3 forward (convlstm_wino.h; the transform of the kernel rows runs in fp64), Winograd
+// F(3,3) (convlstm_wino3.h), and the bf16 mode's row-triple tile (convlstm_wino3.h BF16D).  The
+// first two also raise their kernels' dynamic-LDS limit: packing never runs inside a graph capture.
+void pack_wino(hipStream_t stream, const float* w, int Cx, int C, DevBuf<_Float16>& dst) {
+  const size_t halves = mv::wino_wpack_elems(x_chunk16(Cx), C);
   mv::wino_init_attributes();
-  cc.wpw.alloc(halves);
-  const size_t threads = halves / 2;
-  hipLaunchKernelGGL(mv::pack_wino_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, e->stream,
-                     cc.kernel->dev.p, cc.wpw.p, cc.Cx, Cx16, C, threads);
+  dst.alloc(halves);
+  hipLaunchKernelGGL(mv::pack_wino_kernel, dim3(cdiv(halves / 2, 256)), dim3(256), 0, stream, w,
+                     dst.p, Cx, x_chunk16(Cx), C, halves / 2);
 }
-// Winograd F(3,3) pack (convlstm_wino3.h), likewise from the CURRENT device weights.
-void pack_wino3(mv_engine* e, ConvCell& cc) {
-  const int C = e->cfg.hidden_size;
-  const bool small = cc.Cx > 0 && 9 * cc.Cx <= mv::kBK;
-  const int Cx16 = small ? 0 : cc.Cx;
-  const size_t halves = mv::wino3_wpack_elems(Cx16, C, mv::kW3Nrb);
+void pack_wino3(hipStream_t stream, const float* w, int Cx, int C, DevBuf<_Float16>& dst) {
+  const size_t halves = mv::wino3_wpack_elems(x_chunk16(Cx), C, mv::kW3Nrb);
   mv::wino3_init_attributes();
-  cc.wpw3.alloc(halves);
-  const size_t threads = halves / 2;
-  hipLaunchKernelGGL(mv::pack_wino3_kernel, dim3(cdiv(threads, 256)), dim3(256), 0, e->stream,
-                     cc.kernel->dev.p, cc.wpw3.p, cc.Cx, Cx16, C, mv::kW3Nrb, threads);
+  dst.alloc(halves);
+  hipLaunchKernelGGL(mv::pack_wino3_kernel, dim3(cdiv(halves / 2, 256)), dim3(256), 0, stream, w,
+                     dst.p, Cx, x_chunk16(Cx), C, mv::kW3Nrb, halves / 2);
 }
-// every weight-mutating path comes through here (or releases both packs): a non-null pack is by
-// construction a pack of the CURRENT weights -- re-packed in place when its form is enabled (no
-// hipFree / hipMalloc per training step: they synchronise the device), released otherwise
-void pack_wino_forms(mv_engine* e, ConvCell& cc) {
-  const bool on = mv::wino_enabled() && C_multiple_ok(e, cc) && cc.wino_numerics_ok;
-  if (on) pack_wino(e, cc); else cc.wpw.release();
-  if (on && mv::wino3_enabled()) pack_wino3(e, cc); else cc.wpw3.release();
+void pack_bf16t(hipStream_t stream, const float* w, int Cx, int C, DevBuf<_Float16>& dst) {
+  const size_t halves = mv::bf16t_wpack_elems(x_chunk16(Cx), C, mv::kW3Nrb);
+  dst.alloc(halves);
+  hipLaunchKernelGGL(mv::pack_bf16t_kernel, dim3(cdiv(halves, 256)), dim3(256), 0, stream, w,
+                     dst.p, Cx, x_chunk16(Cx), C, mv::kW3Nrb, halves);
 }
-void ensure_packed_wino(mv_engine* e, ConvCell& cc) {
-  if (cc.wpw.p) return;
-  pack_wino_forms(e, cc);
-}
-
-// bf16 mode on the row-triple tile (convlstm_wino3.h BF16D): the pack of the CURRENT device
-// weights, or none (tanh models only -- unbounded activations keep the three-pass x path of the
-// 32-cell body; MV_BF16T=0: A/B runs)
-void pack_bf16t(mv_engine* e, ConvCell& cc) {
+// every weight-mutating path comes through here (or releases the packs): a non-null pack is by
+// construction a pack of the CURRENT device weights -- re-packed in place when the cell carries
+// the form (no hipFree / hipMalloc per training step: they synchronise the device), released
+// otherwise
+void pack_tile_forms(mv_engine* e, ConvCell& cc) {
+  const CellPacks p = packs_of(e, cc);
   const int C = e->cfg.hidden_size;
-  const bool small = cc.Cx > 0 && 9 * cc.Cx <= mv::kBK;
-  const int Cx16 = small ? 0 : cc.Cx;
-  if (!(mv::bf16t_enabled() && C_multiple_ok(e, cc) && e->cfg.activation == 0)) {
-    cc.wpbt.release();
-    return;
+  if (e->compute_mode == 1) {      // (another mode's packs stay: they are of the same weights)
+    if (p.wpw) pack_wino(e->stream, cc.kernel->dev.p, cc.Cx, C, cc.wpw); else cc.wpw.release();
+    if (p.wpw3) pack_wino3(e->stream, cc.kernel->dev.p, cc.Cx, C, cc.wpw3); else cc.wpw3.release();
+  } else if (e->compute_mode == 2) {
+    if (p.wpbt) pack_bf16t(e->stream, cc.kernel->dev.p, cc.Cx, C, cc.wpbt); else cc.wpbt.release();
   }
-  const size_t halves = mv::bf16t_wpack_elems(Cx16, C, mv::kW3Nrb);
-  cc.wpbt.alloc(halves);
-  hipLaunchKernelGGL(mv::pack_bf16t_kernel, dim3(cdiv(halves, 256)), dim3(256), 0, e->stream,
-                     cc.kernel->dev.p, cc.wpbt.p, cc.Cx, Cx16, C, mv::kW3Nrb, halves);
 }
 
 // bf16 packs (one unscaled plane; the 2-channel regression-encoder input keeps its fp32
@@ -437,33 +434,12 @@ void ensure_packed_bf16(mv_engine* e, ConvCell& cc) {
   if (cc.wpb.p) return;
   const int C = e->cfg.hidden_size;
   MV_REQUIRE(mv::f16x3_cx_supported(cc.Cx), "bf16: Cx %d unsupported", cc.Cx);
-  if (cc.host_stale) {
-    HIP_CHECK(hipMemcpy(cc.kernel->host.data(), cc.kernel->dev.p,
-                        cc.kernel->elems() * sizeof(float), hipMemcpyDeviceToHost));
-    cc.host_stale = false;
-  }
-  const bool small = cc.Cx > 0 && 9 * cc.Cx <= mv::kBK;
-  const int Cx16 = small ? 0 : cc.Cx;
-  const bool xf16 = e->cfg.activation != 0 && !small;     // engine_state.h dyn_x
-  std::vector<_Float16> pb(mv::bf16_wpack_elems(Cx16, C, xf16));
-  if (small) {
-    const int Cin = cc.Cx + C, N4 = 4 * C;
-    std::vector<float> wh((size_t)9 * C * N4);
-    for (int t = 0; t < 9; ++t)
-      memcpy(&wh[(size_t)t * C * N4], &cc.kernel->host[((size_t)t * Cin + cc.Cx) * N4],
-             (size_t)C * N4 * sizeof(float));
-    mv::pack_bf16_weights(wh.data(), 0, C, pb.data());
-    std::vector<float> packed(mv::convlstm_wpack_elems(cc.Cx, C));
-    mv::pack_convlstm_weights(cc.kernel->host.data(), cc.Cx, C, packed.data());
-    const int nch = mv::convlstm_xchunks(cc.Cx) + 9 * (C / mv::kBK);
-    std::vector<float> wx((size_t)(C / mv::kChBlock) * mv::kBN * mv::kBK);
-    for (int cb = 0; cb < C / mv::kChBlock; ++cb)
-      memcpy(&wx[(size_t)cb * mv::kBN * mv::kBK],
-             &packed[((size_t)cb * nch + 0) * mv::kBN * mv::kBK],
-             (size_t)mv::kBN * mv::kBK * sizeof(float));
-    cc.wx32u.alloc(wx.size());
-    HIP_CHECK(hipMemcpy(cc.wx32u.p, wx.data(), wx.size() * sizeof(float),
-                        hipMemcpyHostToDevice));
+  refresh_host_copy(cc);
+  const bool xf16 = bf16_x_passes(2, e->dyn_x(), x_is_small(cc.Cx)) == 3;
+  std::vector<_Float16> pb(mv::bf16_wpack_elems(x_chunk16(cc.Cx), C, xf16));
+  if (x_is_small(cc.Cx)) {
+    mv::pack_bf16_weights(kernel_h_rows(cc.kernel->host.data(), cc.Cx, C).data(), 0, C, pb.data());
+    upload(cc.wx32u, small_x_chunk(cc.kernel->host.data(), cc.Cx, C, 1.0f));
   } else {
     if (xf16) {        // the x rows travel as fp16 of 256 w there: same range bound as f16x3
       const int Cin = cc.Cx + C, N4 = 4 * C;
@@ -478,10 +454,8 @@ void ensure_packed_bf16(mv_engine* e, ConvCell& cc) {
     }
     mv::pack_bf16_weights(cc.kernel->host.data(), cc.Cx, C, pb.data(), xf16);
   }
-  cc.wpb.alloc(pb.size());
-  HIP_CHECK(hipMemcpy(cc.wpb.p, pb.data(), pb.size() * sizeof(_Float16),
-                      hipMemcpyHostToDevice));
-  pack_bf16t(e, cc);
+  upload(cc.wpb, pb);
+  pack_tile_forms(e, cc);
 }
 
 // scene channels the graph attention sees: all of them, except in the greedy decoder of the
@@ -507,8 +481,9 @@ void ensure_params(mv_engine* e) {
     for (ConvCell* cc : active_cells(e, S)) ensure_packed(e, *cc);
     if (e->compute_mode == 1)
       for (ConvCell* cc : active_cells(e, S)) ensure_packed16(e, *cc);
-    if (e->compute_mode == 1 && mv::wino_enabled())
-      for (ConvCell* cc : active_cells(e, S)) ensure_packed_wino(e, *cc);
+    if (e->compute_mode == 1)     // (after ensure_packed16: it runs the outlier test)
+      for (ConvCell* cc : active_cells(e, S))
+        if (packs_of(e, *cc).wpw && !cc->wpw.p) pack_tile_forms(e, *cc);
     if (e->compute_mode == 2)
       for (ConvCell* cc : active_cells(e, S)) ensure_packed_bf16(e, *cc);
     if (!S.wq_valid) {     // hidden2grid tap packs, from the CURRENT device weights

@@ -37,10 +37,7 @@ struct TrainChain {               // one ConvLSTM cell over its T steps
 // models: 0.99997).  Since round 6 the x k-steps of such models run as an f16x3 split of the x
 // part alone in the FORWARD (convlstm_f16x3.h xpasses; engine_state.h dyn_x): cosine 0.99995
 // (tests/test_gpu_bf16.py::test_bf16_with_unbounded_activations).
-static bool bf16_bwd_enabled(const mv_engine*) {
-  static const bool on = !(getenv("MV_BF16_BWD") && atoi(getenv("MV_BF16_BWD")) == 0);
-  return on;
-}
+static bool bf16_bwd_enabled(const mv_engine*) { return gate_knobs().bf16_bwd; }
 
 struct TrainScale {
   DevBuf<float> hs[2], cs[2];     // branch 0 = class, 1 = regression: [To+Tp+1][N][K][C]
@@ -158,11 +155,10 @@ void train_alloc(mv_engine* e) {
       if (need_dx) ch.dxs.alloc(T * NK * cell->Cx);
       ch.gates.alloc(T * NK * 4 * C, mv::kWgradPad);
       ch.wdpack.alloc(mv::convlstm_dgrad_wpack_elems(cell->Cx, (int)C));
-      mv::WgradArgs wa{};
-      wa.R = (int)(T * N); wa.H = S.H; wa.W = S.W; wa.Cx = cell->Cx; wa.C = (int)C;
-      mv::wgrad_plan(wa, 3072);
-      // (the row-triple form of the f16x3 wgrad keeps 15 partial taps per split instead of 9)
-      max_partial = std::max(max_partial, (mv::wgrad_partial_elems(wa) * 15 + 8) / 9);
+      for (int mode = 0; mode <= 2; ++mode)     // the compute mode may change after this
+        max_partial = std::max(max_partial,
+                               plan_wgrad(mode, c.convlstm_kernel, (int)(T * N), S.H, S.W, cell->Cx,
+                                          (int)C).partial_elems);
     };
     chain(R.enc[0], &S.enc_cls, To, true);
     chain(R.dec[0], &S.dec_cls, Tp, true);
@@ -353,7 +349,7 @@ void run_pack(mv_engine* e, TrainChain& ch) {
     cc.wpack.alloc(total);
     hipLaunchKernelGGL(mv::pack_fwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
                        e->stream, cc.kernel->dev.p, cc.wpack.p, Cx, C, nx, nch,
-                       (Cx > 0 && 9 * Cx <= mv::kBK) ? 1 : 0, total);
+                       x_is_small(Cx) ? 1 : 0, total);
   }
   {
     const size_t total = mv::convlstm_dgrad_wpack_elems(Cx, C);
@@ -363,27 +359,26 @@ void run_pack(mv_engine* e, TrainChain& ch) {
   }
   cc.host_stale = true;     // the host copy no longer matches the device weights
   if (e->compute_mode != 0) {   // matrix-pipe planes of the updated kernel, on the device
-    const bool small = Cx > 0 && 9 * Cx <= mv::kBK;
-    const int Cx16 = small ? 0 : Cx;
-    if (e->compute_mode == 1) {
+    const int Cx16 = x_chunk16(Cx);
+    const CellPacks pk = packs_of(e, cc);
+    if (pk.wp16) {
       const size_t halves = mv::f16x3_wpack_elems(Cx16, C);
       cc.wp16.alloc(halves);
       const size_t threads = halves / 2;
       hipLaunchKernelGGL(mv::pack_f16x3_kernel, dim3(cdiv(threads, 256)), dim3(256), 0,
                          e->stream, cc.kernel->dev.p, cc.wp16.p, Cx, Cx16, C, threads);
-      pack_wino_forms(e, cc);     // releases both Winograd packs, re-packs what is enabled
       cc.wpb.release(); cc.wpbt.release(); cc.wx32u.release();
     } else {                    // bf16 forward (the backward's packs: below)
-      const bool xf16 = e->cfg.activation != 0 && Cx16 > 0;
+      const bool xf16 = bf16_x_passes(2, e->dyn_x(), x_is_small(Cx)) == 3;
       const size_t halves = mv::bf16_wpack_elems(Cx16, C, xf16);
       cc.wpb.alloc(halves);
       hipLaunchKernelGGL(mv::pack_bf16_kernel, dim3(cdiv(halves, 256)), dim3(256), 0,
                          e->stream, cc.kernel->dev.p, cc.wpb.p, Cx, Cx16, C, halves,
                          xf16 ? 1 : 0);
-      pack_bf16t(e, cc);
       cc.wp16.release(); cc.wx32.release(); cc.wpw.release(); cc.wpw3.release();
     }
-    if (e->compute_mode == 2 && bf16_bwd_enabled(e)) {
+    pack_tile_forms(e, cc);     // re-packs the forms the cell carries, releases the others
+    if (pk.wdb) {
       const size_t db = mv::bf16_dgrad_wpack_elems(Cx, C);
       ch.wdb.alloc(db);
       hipLaunchKernelGGL(mv::pack_bf16_dgrad_kernel, dim3(cdiv(db, 256)), dim3(256), 0,
@@ -395,7 +390,7 @@ void run_pack(mv_engine* e, TrainChain& ch) {
       ch.wd16.alloc(dh);
       hipLaunchKernelGGL(mv::pack_f16x3_dgrad_kernel, dim3(cdiv(dh / 2, 256)), dim3(256), 0,
                          e->stream, cc.kernel->dev.p, ch.wd16.p, Cx, C, dh / 2);
-      if (e->compute_mode == 1 && mv::wino_enabled() && mv::wino_dgrad_enabled()) {
+      if (pk.wdw) {
         const size_t dw = mv::wino_dgrad_wpack_elems(Cx, C);
         ch.wdw.alloc(dw);
         hipLaunchKernelGGL(mv::pack_wino_dgrad_kernel, dim3(cdiv(dw / 2, 256)), dim3(256), 0,
@@ -404,7 +399,7 @@ void run_pack(mv_engine* e, TrainChain& ch) {
         ch.wdw.release();
       }
     }
-    if (small) {
+    if (x_is_small(Cx)) {
       const size_t n = (size_t)(C / mv::kChBlock) * mv::kBN * mv::kBK;
       const int nch = mv::convlstm_xchunks(Cx) + 9 * (C / mv::kBK);
       DevBuf<float>& dst = e->compute_mode == 1 ? cc.wx32 : cc.wx32u;
@@ -794,9 +789,8 @@ void run_gate_bwd(mv_engine* e, float* gates, const float* c_prev, const float* 
                   const float* dh, float* dc, size_t cells, int C,
                   int32_t* gmax_bits = nullptr, int group_slot = -1) {
   const size_t total = cells * C;
-  static const bool fuse_on = !(getenv("MV_BF16_FUSED_SPLIT") && atoi(getenv("MV_BF16_FUSED_SPLIT")) == 0);
   _Float16* plane = nullptr;
-  if (fuse_on && group_slot >= 0 && group_slot < mv::kMaxGroup && C % 32 == 0 &&
+  if (gate_knobs().bf16_fused_split && group_slot >= 0 && group_slot < mv::kMaxGroup && C % 32 == 0 &&
       e->compute_mode == 2 && bf16_bwd_enabled(e)) {
     TrainState& t = TS(e);
     const size_t n = cells * 4 * (size_t)C;
@@ -820,120 +814,95 @@ void run_gate_bwd(mv_engine* e, float* gates, const float* c_prev, const float* 
   });
 }
 
-// f16x3 compute mode: G of every problem -> two fp16 planes under its own
-// power-of-two scale, then the grouped dgrad launch on the fp16 matrix pipe.
+// f16x3 / bf16 compute modes: plan the group (gate_plan.h), G of every problem -> two fp16 planes
+// under its own power-of-two scale (or one bf16 plane), the grouped dgrad launch on the matrix
+// pipe, then the sum over the k slices.
 void run_dgrad_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
                            const std::vector<TrainChain*>& chains,
                            const std::vector<int>& slots, double fl, double by) {
   TrainState& t = TS(e);
-  std::vector<mv::ConvLstm16Args> p16(probs.size());
-  // the Winograd F(2,3) form of the same convolution (two thirds of the MFMAs) when every
-  // problem of the group fits its tiling; MV_WINO_DGRAD=0 keeps the direct kernel
-  const bool bf = e->compute_mode == 2 && bf16_bwd_enabled(e);
-  bool wino = e->compute_mode == 1 && mv::wino_enabled() && mv::wino_dgrad_enabled();
-  for (size_t i = 0; i < probs.size() && wino; ++i) {
-    const ConvLstmArgs& a = probs[i];
-    if (!(a.W > 0 && 32 % a.W == 0 && a.H >= 2 && a.out0_cols % 64 == 0 && (a.C / 16) % 8 == 0) ||
-        !chains[i]->wdw.p)
-      wino = false;
-  }
-  std::vector<mv::ConvLstmWinoArgs> pw(wino ? probs.size() : 0);
-  for (size_t i = 0; i < probs.size(); ++i) {
+  const int n = (int)probs.size();
+  bool has_wdw[mv::kMaxGroup] = {};
+  for (int i = 0; i < n; ++i) has_wdw[i] = chains[i]->wdw.p != nullptr;
+  const DgradPlan pl = plan_dgrad_group(e->compute_mode, probs.data(), has_wdw, n);
+  const bool bf = pl.bf16;
+  std::vector<mv::ConvLstm16Args> p16(n);
+  std::vector<mv::ConvLstmWinoArgs> pw(pl.wino ? n : 0);
+  for (int i = 0; i < n; ++i) {
     const ConvLstmArgs& a = probs[i];
     mv::ConvLstm16Args& q = p16[i];
     q = mv::ConvLstm16Args{};
     q.f = a;
-    const size_t n = (size_t)a.rows * a.H * a.W * a.C;      // a.C == 4C here
-    const size_t pst = n + mv::kPlaneSlack + mv::kPlanePad;
-    const size_t gcells = (size_t)a.rows * a.H * a.W;
+    const size_t M = (size_t)a.rows * a.H * a.W;
+    const size_t nel = M * a.C;                               // a.C == 4C here
+    const size_t pst = nel + mv::kPlaneSlack + mv::kPlanePad;
     MV_REQUIRE(t.g16[i].n >= 2 * pst, "internal: G plane scratch");
     _Float16* p0 = t.g16[i].p + mv::kPlanePad;
     const bool fused = bf && t.g16_fused[i];       // the plane came out of lstm_gate_bwd
     t.g16_fused[i] = false;
     if (!fused)
-    launch(e, "split_planes", 0, (bf ? 6.0 : 8.0) * n, [&] {
-      if (bf)
-        hipLaunchKernelGGL(mv::split_plane_bf16_kernel, dim3(mv::split_planes_blocks(gcells, a.C)),
-                           dim3(256), 0, e->stream, a.h, p0, (int)gcells, a.C);
-      else
-      hipLaunchKernelGGL(mv::split_planes_dyn_kernel, dim3(mv::split_planes_blocks(gcells, a.C)),
-                         dim3(256), 0, e->stream, a.h, p0, p0 + pst, (int)gcells, a.C,
-                         t.gmax.p + (size_t)slots[i] * 64, t.gexp.p + slots[i]);
-    });
+      launch(e, "split_planes", 0, (bf ? 6.0 : 8.0) * nel, [&] {
+        if (bf)
+          hipLaunchKernelGGL(mv::split_plane_bf16_kernel, dim3(mv::split_planes_blocks(M, a.C)),
+                             dim3(256), 0, e->stream, a.h, p0, (int)M, a.C);
+        else
+          hipLaunchKernelGGL(mv::split_planes_dyn_kernel, dim3(mv::split_planes_blocks(M, a.C)),
+                             dim3(256), 0, e->stream, a.h, p0, p0 + pst, (int)M, a.C,
+                             t.gmax.p + (size_t)slots[i] * 64, t.gexp.p + slots[i]);
+      });
     q.h16 = p0; q.h_plane_stride = (int64_t)pst;
     q.x16 = nullptr; q.x_plane_stride = 0;
     q.wp16 = bf ? chains[i]->wdb.p : chains[i]->wd16.p;
     MV_REQUIRE(q.wp16, "internal: dgrad weight pack of the compute mode is missing");
     q.n_xk = 0; q.n_hk = 9 * (a.C / 16); q.w_ksteps = q.n_hk;
     q.g_exp = bf ? nullptr : t.gexp.p + slots[i];
-    const size_t M = (size_t)a.rows * a.H * a.W;
-    if (wino) {
-      // split-K of the Winograd form: (d h column block, slice) combos = 8 = the XCDs, the d x
-      // blocks a region of their own with eight slices (convlstm_dgrad_wino_kernel)
-      const int ncm = a.out0_cols / 64;
-      const bool need_dx = a.out1 && a.out1_cols > 0;
-      int nkm = std::max(1, 8 / ncm);
-      while ((a.C / 16) % nkm != 0) nkm /= 2;
-      const int nkx = need_dx ? 8 : 1;
+    // partial sums of the k slices
+    const DgradPlan::Slices& ks = pl.s[i];
+    const int ns0 = pl.wino ? ks.nks_main : ks.n_kslice, ns1 = pl.wino ? ks.nks_x : ks.n_kslice;
+    const bool need_dx = pl.wino ? ns1 > 1 : a.out1_cols > 0;
+    q.n_kslice = ks.n_kslice;
+    if (ns0 > 1) { t.dpart0[i].alloc((size_t)ns0 * M * a.out0_cols); q.part0 = t.dpart0[i].p; }
+    if (ns1 > 1 && need_dx) {
+      t.dpart1[i].alloc((size_t)ns1 * M * ((a.out1_cols + 3) / 4 * 4));
+      q.part1 = t.dpart1[i].p;
+    }
+    if (pl.wino) {
       mv::ConvLstmWinoArgs& w = pw[i];
-      w.nks_main = nkm; w.nks_x = nkx;
-      if (nkm > 1) { t.dpart0[i].alloc((size_t)nkm * M * a.out0_cols); q.part0 = t.dpart0[i].p; }
-      if (need_dx) {
-        t.dpart1[i].alloc((size_t)nkx * M * ((a.out1_cols + 3) / 4 * 4));
-        q.part1 = t.dpart1[i].p;
-      }
+      w.nks_main = ks.nks_main; w.nks_x = ks.nks_x;
       w.b = q;
-      w.b.f.n_colblocks = need_dx ? mv::wino_dgrad_colblocks(a.out1_cols, a.out0_cols) : ncm;
+      w.b.f.n_colblocks = ns1 > 1 ? mv::wino_dgrad_colblocks(a.out1_cols, a.out0_cols)
+                                  : a.out0_cols / 64;
       w.wpw = chains[i]->wdw.p;
       w.n_xc = 0;
-      continue;
-    }
-    // split-K over four channel-group ranges (see convlstm16_dgrad_dispatch)
-    const int nstages = q.n_hk / 3;
-    // (the bf16 dgrad is a third as long: whole-K tiles, no partial sums -- 1 208 vs 1 202 /
-    // 1 178 traj/s with 2 / 4 slices at batch 64, profiles/r4u_*)
-    static const int ks_set = getenv("MV_DGRAD_KSLICES") ? atoi(getenv("MV_DGRAD_KSLICES")) : 0;
-    const int ks_env = ks_set > 0 ? ks_set : (bf ? 1 : 4);
-    if (bf)
-      MV_REQUIRE(nstages % MV_BF16_UNITS == 0, "internal: bf16 dgrad stage count %d", nstages);
-    if (ks_env > 1 && nstages % (2 * ks_env) == 0) {
-      q.n_kslice = ks_env;
-      t.dpart0[i].alloc((size_t)ks_env * M * a.out0_cols);
-      q.part0 = t.dpart0[i].p;
-      if (a.out1_cols > 0) {
-        t.dpart1[i].alloc((size_t)ks_env * M * ((a.out1_cols + 3) / 4 * 4));
-        q.part1 = t.dpart1[i].p;
-      }
     }
   }
   launch(e, "convlstm_dgrad", fl, by, [&] {
-    if (wino)
-      mv::launch_convlstm_wino_dgrads(pw.data(), (int)pw.size(), e->stream);
+    if (pl.wino)
+      mv::launch_convlstm_wino_dgrads(pw.data(), n, e->stream);
     else
-      mv::launch_convlstm16_dgrads(p16.data(), (int)p16.size(), e->stream, bf);
-  }, -1.0, wino ? 2.0 : (bf ? 1.0 : 3.0));
+      mv::launch_convlstm16_dgrads(p16.data(), n, bf, pl.shift, e->stream);
+  }, -1.0, pl.mfma_factor);
   mv::SumSlicesArgs sa{};
   unsigned blocks = 0;
   double sbytes = 0;
-  for (size_t i = 0; i < p16.size(); ++i) {
+  for (int i = 0; i < n; ++i) {
     const mv::ConvLstm16Args& q = p16[i];
-    const int ns0 = wino ? pw[i].nks_main : q.n_kslice, ns1 = wino ? pw[i].nks_x : q.n_kslice;
     const size_t M = (size_t)q.f.rows * q.f.H * q.f.W;
     sa.nslice = 1;
     for (int o = 0; o < 2; ++o) {
-      const int ns = o ? ns1 : ns0;
+      const int ns = pl.wino ? (o ? pl.s[i].nks_x : pl.s[i].nks_main) : pl.s[i].n_kslice;
       if (ns <= 1) continue;
       float* out = o ? q.f.out1 : q.f.out0;
-      const size_t n = M * (size_t)(o ? q.f.out1_cols : q.f.out0_cols);
-      if (!out || n == 0) continue;
-      MV_REQUIRE(n % 4 == 0, "internal: dgrad slice sum needs a multiple of 4 elements");
+      const size_t nel = M * (size_t)(o ? q.f.out1_cols : q.f.out0_cols);
+      if (!out || nel == 0) continue;
+      MV_REQUIRE(nel % 4 == 0, "internal: dgrad slice sum needs a multiple of 4 elements");
       sa.part[sa.nseg] = o ? q.part1 : q.part0;
       sa.out[sa.nseg] = out;
-      sa.n[sa.nseg] = n;
+      sa.n[sa.nseg] = nel;
       sa.nslice_seg[sa.nseg] = ns;
-      blocks += cdiv(n / 4, 256);
+      blocks += cdiv(nel / 4, 256);
       sa.block_end[sa.nseg] = blocks;
-      sbytes += 4.0 * n * (ns + 1);
+      sbytes += 4.0 * nel * (ns + 1);
       ++sa.nseg;
     }
   }
@@ -1061,55 +1030,104 @@ void comm_reduce_rest_and_join(mv_engine* e) {
   if (!(comm_fault() & 2)) HIP_CHECK(hipStreamWaitEvent(e->stream, c->done, 0));
 }
 
+// f16x3 wgrad: one operand [Mtot][Cc] of a chain -> its transposed, column-shifted fp16 planes
+// dst[0..2] (row-triple form: the five components of each).  Scale 2^exp[0], or 2^fixed_exp.
+void wgrad_transpose_operand(mv_engine* e, const WgradPlan& pl, const float* src,
+                             DevBuf<_Float16>* dst, int Cc, int H, int W, const int32_t* exp,
+                             int fixed_exp, int npl) {
+  if (pl.wino) {
+    hipLaunchKernelGGL(mv::wino3_transpose_a3_kernel,
+                       dim3((unsigned)(pl.Mrow3 / 64), (unsigned)((Cc + 31) / 32)), dim3(256), 0,
+                       e->stream, src, dst[0].p, dst[1].p, dst[2].p, pl.Mtot3, Cc, pl.Mrow3, H, W,
+                       exp, fixed_exp, (long long)2 * Cc * pl.Mrow3, npl);
+    return;
+  }
+  const dim3 grid((unsigned)(pl.Mrow / 64), Cc / 64);
+  if (Cc % 64 == 0 && pl.transpose3) {     // the three column-shifted copies from one read
+    hipLaunchKernelGGL(mv::transpose_split3_kernel, grid, dim3(256), 0, e->stream, src, dst[0].p,
+                       dst[1].p, dst[2].p, pl.Mtot, Cc, pl.Mrow, W, exp, fixed_exp, npl);
+    return;
+  }
+  for (int d = 0; d < 3; ++d) {
+    if (Cc % 64 == 0)
+      hipLaunchKernelGGL(mv::transpose_split_kernel, grid, dim3(256), 0, e->stream, src, dst[d].p,
+                         pl.Mtot, Cc, pl.Mrow, W, d - 1, exp, fixed_exp, (float*)nullptr, npl);
+    else      // any width up to 64
+      hipLaunchKernelGGL(mv::transpose_split_narrow_kernel, dim3((unsigned)(pl.Mrow / 64)),
+                         dim3(256), 0, e->stream, src, dst[d].p, pl.Mtot, Cc, pl.Mrow, W, d - 1, exp,
+                         npl);
+  }
+}
+
+// f16x3 wgrad GEMM of the h rows (xrows false) or the x rows of one chain: the kernel instance
+// for {narrow, wide tile} x {1, 3 planes}.  (The narrow three-plane tile needs its dynamic-LDS
+// limit raised, once per training state.)
+void wgrad16_init_attributes(TrainState& t) {
+  if (t.wgrad16_attr) return;
+  HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<false, 3>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
+  HIP_CHECK(hipFuncSetAttribute(
+      reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<true, 3>),
+      hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
+  t.wgrad16_attr = true;
+}
+void launch_wgrad16(mv_engine* e, const mv::Wgrad16Args& q, bool wide, bool one, bool xrows) {
+  const dim3 grid(wide ? mv::wgrad16_wide_blocks(q, xrows) : mv::wgrad16_blocks(q, xrows));
+  const size_t lds = wide ? 0 : (one ? mv::kWg16LdsBytes1 : mv::kWg16LdsBytes);
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, e->stream, q); };
+  if (!xrows) {
+    if (wide && one) go(mv::convlstm_wgrad_f16x3_wide_kernel<1>);
+    else if (wide) go(mv::convlstm_wgrad_f16x3_wide_kernel<3>);
+    else if (one) go(mv::convlstm_wgrad_f16x3_kernel<false, 1>);
+    else go(mv::convlstm_wgrad_f16x3_kernel<false, 3>);
+  } else {
+    if (wide && one) go(mv::convlstm_wgrad_f16x3_wide_kernel<1, true>);
+    else if (wide) go(mv::convlstm_wgrad_f16x3_wide_kernel<3, true>);
+    else if (one) go(mv::convlstm_wgrad_f16x3_kernel<true, 1>);
+    else go(mv::convlstm_wgrad_f16x3_kernel<true, 3>);
+  }
+}
+
 // gslot: first gmax slot of the chain's steps (f16x3 mode), see train_backward
 void run_wgrad(mv_engine* e, TrainChain& ch, const float* hin, int Tsteps, int H, int W,
                int gslot) {
   TrainState& t = TS(e);
-  const int N = e->cfg.batch_size, C = e->cfg.hidden_size;
-  mv::WgradArgs wa{};
-  wa.x = ch.Cx ? ch.xs.p : nullptr; wa.h = hin; wa.g = ch.gates.p;
-  wa.partial = t.partial.p;
-  wa.R = Tsteps * N; wa.H = H; wa.W = W; wa.Cx = ch.Cx; wa.C = C;
-  mv::wgrad_plan(wa, 3072);
-  MV_REQUIRE(mv::wgrad_partial_elems(wa) <= t.partial.n, "internal: wgrad partial buffer");
-  const double cells = (double)wa.R * H * W;
-  if (e->cfg.convlstm_kernel != 3) {       // generic taps: one deterministic pass, no split
+  const int N = e->cfg.batch_size, C = e->cfg.hidden_size, Cx = ch.Cx;
+  const WgradPlan pl = plan_wgrad(e->compute_mode, e->cfg.convlstm_kernel, Tsteps * N, H, W, Cx, C);
+  MV_REQUIRE(pl.partial_elems <= t.partial.n && pl.nsplit_x <= pl.nsplit,
+             "internal: wgrad partial buffer (%zu floats planned, %zu allocated; %d x splits of "
+             "%d)", pl.partial_elems, t.partial.n, pl.nsplit_x, pl.nsplit);
+  const double cells = (double)pl.Mtot;
+  if (pl.generic) {                        // generic taps: one deterministic pass, no split
     const int k = e->cfg.convlstm_kernel;
-    launch(e, "convlstm_wgrad", 2.0 * cells * k * k * (ch.Cx + C) * 4.0 * C,
-           cells * (ch.Cx + 5.0 * C) * 4.0, [&] {
+    launch(e, "convlstm_wgrad", 2.0 * cells * k * k * (Cx + C) * 4.0 * C,
+           cells * (Cx + 5.0 * C) * 4.0, [&] {
       mv::ConvGenericWgradArgs ga{};
-      ga.x = wa.x; ga.h = wa.h; ga.g = wa.g; ga.dw = grad_of(e, ch.cell->kernel);
-      ga.R = wa.R; ga.H = H; ga.W = W; ga.Cx = ch.Cx; ga.C = C; ga.ksize = k;
+      ga.x = Cx ? ch.xs.p : nullptr; ga.h = hin; ga.g = ch.gates.p;
+      ga.dw = grad_of(e, ch.cell->kernel);
+      ga.R = Tsteps * N; ga.H = H; ga.W = W; ga.Cx = Cx; ga.C = C; ga.ksize = k;
       mv::launch_convlstm_generic_wgrad(ga, e->stream);
-    }, -1.0, 0.0);
+    }, -1.0, pl.mfma_factor);
     launch(e, "bias_colsum", 0, cells * 4.0 * C * 4.0, [&] {
       run_colsum(e, ch.gates.p, (size_t)cells, (size_t)4 * C, grad_of(e, ch.cell->biases),
                  t.partial.p);
     });
     return;
   }
-  const size_t ncols = (size_t)9 * (ch.Cx + C) * 4 * C;
-  const bool f16 = e->compute_mode != 0 && mv::wgrad16_ok(W, C);
-  bool wino_form = false;                  // f16x3: the row-triple form (15 partial taps)
-  int nsplit_x = 0;                        // ... and the split count of its x rows
-  size_t bias_blocks = (size_t)(((long long)cells + 63) / 64);
-  if (f16) {
+  const size_t ncols = (size_t)9 * (Cx + C) * 4 * C;
+  size_t bias_blocks = (size_t)((pl.Mtot + 63) / 64);
+  if (pl.f16) {
     // both operands as cell-contiguous fp16 plane pairs, then the f16x3 GEMMs
-    // (convlstm_wgrad_f16x3.h): h rows, x rows; bias partials fall out of the G pass
-    const long long Mtot = (long long)wa.R * H * W;
-    const long long Mrow = (Mtot + 63) / 64 * 64;
-    const int Cx = ch.Cx;
+    // (convlstm_wgrad_f16x3.h): h rows, x rows; bias partials fall out of the G pass.
     // compute mode 2: one fp16 plane per operand (see bf16_bwd_enabled); the lower planes are
     // neither written by the transposes nor read by the GEMMs
-    const bool one = e->compute_mode == 2 && bf16_bwd_enabled(e);
-    const int npl = one ? 1 : 2;
-    MV_REQUIRE((size_t)Mrow <= t.mrow_max, "internal: wgrad plane scratch");
-    // Winograd F(3,3) over row triples (convlstm_wgrad_f16x3.h, "the row-triple form"): 5/9 of
-    // the MFMAs on operands of 5/3 the size; both planes only (fp32-class mode)
-    const bool wino = mv::wgrad16_wino3_ok(H, one);
-    const long long Mtot3 = Mtot / 3, Mrow3 = (Mtot3 + 63) / 64 * 64;
+    const int npl = pl.one ? 1 : 2;
+    MV_REQUIRE((size_t)pl.Mrow <= t.mrow_max, "internal: wgrad plane scratch");
+    // the row-triple form (Winograd F(3,3) over row triples: 5/9 of the MFMAs) works on
+    // operands of 5/3 the size
     const size_t mrow3_max = (t.mrow_max / 3 + 63) / 64 * 64 + 64;
-    const size_t pl_cells = wino ? 5 * mrow3_max : t.mrow_max;   // plane pairs x cells per channel
+    const size_t pl_cells = pl.wino ? 5 * mrow3_max : t.mrow_max;   // plane pairs x cells per channel
     t.gt16.alloc((size_t)2 * 4 * C * pl_cells);
     t.bias_part.alloc(t.mrow_max / 64 * 4 * C);
     for (int d = 0; d < 3; ++d) t.at16[d].alloc((size_t)2 * C * pl_cells);
@@ -1118,163 +1136,83 @@ void run_wgrad(mv_engine* e, TrainChain& ch, const float* hin, int Tsteps, int H
     // x rows: any width up to 64 (narrow transpose), or whole 64-channel column groups
     // (--emb_size 128: the transpose of the h operand, one grid row per group)
     MV_REQUIRE(Cx <= 64 || Cx % 64 == 0, "internal: f16x3 wgrad x operand of %d channels", Cx);
-    if (!t.wgrad16_attr) {
-      HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<false, 3>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
-      HIP_CHECK(hipFuncSetAttribute(
-          reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<true, 3>),
-          hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
-      t.wgrad16_attr = true;
-    }
-
-    if (wino)
-      launch(e, "wgrad_transpose", 0,
-             cells * (4.0 * C * (4.0 + 4.0 * 5 / 3) + (C + Cx) * (4.0 + 3.0 * 4.0 * 5 / 3)), [&] {
-        hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, e->stream,
-                           t.gmax.p + (size_t)gslot * 64, Tsteps, 64, t.chain_exp.p);
-        hipLaunchKernelGGL(mv::wino3_transpose_g_kernel, dim3((unsigned)(Mrow3 / 64), 4 * C / 32),
-                           dim3(256), 0, e->stream, ch.gates.p, t.gt16.p, Mtot3, 4 * C, Mrow3, W,
-                           t.chain_exp.p, t.bias_part.p, (long long)2 * 4 * C * Mrow3, npl);
-        hipLaunchKernelGGL(mv::wino3_transpose_a3_kernel, dim3((unsigned)(Mrow3 / 64), C / 32),
-                           dim3(256), 0, e->stream, hin, t.at16[0].p, t.at16[1].p, t.at16[2].p,
-                           Mtot3, C, Mrow3, H, W, (const int32_t*)nullptr, 8,
-                           (long long)2 * C * Mrow3, npl);
-        if (Cx) {   // x operand: exponent from max |x| of the chain
-          HIP_CHECK(hipMemsetAsync(t.chain_exp.p + 64, 0, 64 * sizeof(int32_t), e->stream));
-          hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, e->stream,
-                             ch.xs.p, (size_t)Mtot * Cx, t.chain_exp.p + 64);
-          // |V| <= 6 max|x|: three more bits of headroom than the direct form's 2^13
-          hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, e->stream,
-                             t.chain_exp.p + 64, 1, 64, t.chain_exp.p + 2, 10);
-          hipLaunchKernelGGL(mv::wino3_transpose_a3_kernel,
-                             dim3((unsigned)(Mrow3 / 64), (unsigned)((Cx + 31) / 32)), dim3(256), 0,
-                             e->stream, ch.xs.p, t.xt16[0].p, t.xt16[1].p, t.xt16[2].p, Mtot3, Cx,
-                             Mrow3, H, W, t.chain_exp.p + 2, 0, (long long)2 * Cx * Mrow3, npl);
-        }
-      });
-    else
-    launch(e, "wgrad_transpose", 0, cells * (4.0 * C + (C + Cx) * 3.0) * (4.0 + 2.0 * npl), [&] {
+    wgrad16_init_attributes(t);
+    const double tr_bytes =
+        pl.wino ? cells * (4.0 * C * (4.0 + 4.0 * 5 / 3) + (C + Cx) * (4.0 + 3.0 * 4.0 * 5 / 3))
+                : cells * (4.0 * C + (C + Cx) * 3.0) * (4.0 + 2.0 * npl);
+    launch(e, "wgrad_transpose", 0, tr_bytes, [&] {
       hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, e->stream,
                          t.gmax.p + (size_t)gslot * 64, Tsteps, 64, t.chain_exp.p);
-      hipLaunchKernelGGL(mv::transpose_split_kernel, dim3((unsigned)(Mrow / 64), 4 * C / 64),
-                         dim3(256), 0, e->stream, ch.gates.p, t.gt16.p, Mtot, 4 * C, Mrow, W,
-                         0, t.chain_exp.p, 0, t.bias_part.p, npl);
-      static const bool fused3 = !(getenv("MV_TRANSPOSE3") && atoi(getenv("MV_TRANSPOSE3")) == 0);
-      if (fused3)     // the three column-shifted copies of h from one read
-        hipLaunchKernelGGL(mv::transpose_split3_kernel, dim3((unsigned)(Mrow / 64), C / 64),
-                           dim3(256), 0, e->stream, hin, t.at16[0].p, t.at16[1].p, t.at16[2].p,
-                           Mtot, C, Mrow, W, (const int32_t*)nullptr, 8, npl);
+      if (pl.wino)
+        hipLaunchKernelGGL(mv::wino3_transpose_g_kernel, dim3((unsigned)(pl.Mrow3 / 64), 4 * C / 32),
+                           dim3(256), 0, e->stream, ch.gates.p, t.gt16.p, pl.Mtot3, 4 * C, pl.Mrow3,
+                           W, t.chain_exp.p, t.bias_part.p, (long long)2 * 4 * C * pl.Mrow3, npl);
       else
-      for (int d = 0; d < 3; ++d)
-        hipLaunchKernelGGL(mv::transpose_split_kernel, dim3((unsigned)(Mrow / 64), C / 64),
-                           dim3(256), 0, e->stream, hin, t.at16[d].p, Mtot, C, Mrow, W,
-                           d - 1, (const int32_t*)nullptr, 8, (float*)nullptr, npl);
+        hipLaunchKernelGGL(mv::transpose_split_kernel, dim3((unsigned)(pl.Mrow / 64), 4 * C / 64),
+                           dim3(256), 0, e->stream, ch.gates.p, t.gt16.p, pl.Mtot, 4 * C, pl.Mrow, W,
+                           0, t.chain_exp.p, 0, t.bias_part.p, npl);
+      wgrad_transpose_operand(e, pl, hin, t.at16, C, H, W, nullptr, 8, npl);
       if (Cx) {   // x operand: exponent from max |x| of the chain
         HIP_CHECK(hipMemsetAsync(t.chain_exp.p + 64, 0, 64 * sizeof(int32_t), e->stream));
         hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, e->stream,
-                           ch.xs.p, (size_t)Mtot * Cx, t.chain_exp.p + 64);
+                           ch.xs.p, (size_t)pl.Mtot * Cx, t.chain_exp.p + 64);
+        // (row-triple form: |V| <= 6 max|x|, three more bits of headroom than the direct 2^13)
         hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, e->stream,
-                           t.chain_exp.p + 64, 1, 64, t.chain_exp.p + 2);
-      }
-      if (Cx && Cx % 64 == 0 && fused3)
-        hipLaunchKernelGGL(mv::transpose_split3_kernel, dim3((unsigned)(Mrow / 64), Cx / 64),
-                           dim3(256), 0, e->stream, ch.xs.p, t.xt16[0].p, t.xt16[1].p,
-                           t.xt16[2].p, Mtot, Cx, Mrow, W, t.chain_exp.p + 2, 0, npl);
-      else
-      for (int d = 0; d < 3 && Cx; ++d) {
-        if (Cx % 64 == 0)
-          hipLaunchKernelGGL(mv::transpose_split_kernel, dim3((unsigned)(Mrow / 64), Cx / 64),
-                             dim3(256), 0, e->stream, ch.xs.p, t.xt16[d].p, Mtot, Cx, Mrow, W,
-                             d - 1, t.chain_exp.p + 2, 0, (float*)nullptr, npl);
-        else
-          hipLaunchKernelGGL(mv::transpose_split_narrow_kernel, dim3((unsigned)(Mrow / 64)),
-                             dim3(256), 0, e->stream, ch.xs.p, t.xt16[d].p, Mtot, Cx, Mrow, W,
-                             d - 1, t.chain_exp.p + 2, npl);
+                           t.chain_exp.p + 64, 1, 64, t.chain_exp.p + 2, pl.wino ? 10 : 13);
+        wgrad_transpose_operand(e, pl, ch.xs.p, t.xt16, Cx, H, W, t.chain_exp.p + 2, 0, npl);
       }
     });
     mv::Wgrad16Args q{};
     for (int d = 0; d < 3; ++d) q.at[d] = t.at16[d].p;
     q.gt = t.gt16.p; q.partial = t.partial.p; q.g_exp = t.chain_exp.p;
     q.a_exp = t.chain_exp.p + 1;
-    q.Mrow = Mrow; q.H = H; q.W = W; q.Cx = Cx; q.C = C; q.Ca = C;
-    if (wino) {
-      q.ntaps = 15; q.Mrow = Mrow3; q.H = H / 3;
-      q.a_comp_stride = (int64_t)2 * C * Mrow3; q.g_comp_stride = (int64_t)2 * 4 * C * Mrow3;
+    q.Mrow = pl.Mrow; q.H = H; q.W = W; q.Cx = Cx; q.C = C; q.Ca = C;
+    if (pl.wino) {
+      q.ntaps = 15; q.Mrow = pl.Mrow3; q.H = H / 3;
+      q.a_comp_stride = (int64_t)2 * C * pl.Mrow3; q.g_comp_stride = (int64_t)2 * 4 * C * pl.Mrow3;
+      bias_blocks = (size_t)(pl.Mrow3 / 64);
     }
-    const long long Mgemm = wino ? Mtot3 : Mtot;          // cells of the GEMMs' reduction
-    wino_form = wino;
-    if (wino) bias_blocks = (size_t)(Mrow3 / 64);
-    // the wide tile (convlstm_wgrad_f16x3.h) balances on 7 / 14 splits; the x rows and the
-    // reduction follow its count
-    const bool wide = mv::wgrad16_wide_ok(W, C);
-    if (wide) {
-      q.map_mode = mv::wgrad16_wide_map_mode(C);
-      wa.nsplit = mv::wgrad16_wide_splits(Mgemm, wa.nsplit, q.map_mode);
-    }
-    mv::wgrad16_plan(q, Mgemm, wa.nsplit);
+    if (pl.wide) q.map_mode = pl.map_mode;
+    mv::wgrad16_plan(q, pl.Mgemm, pl.nsplit);
     launch(e, "convlstm_wgrad", 2.0 * cells * 9 * C * 4.0 * C, cells * 5.0 * C * 4.0, [&] {
-      if (wide && one)
-        hipLaunchKernelGGL(mv::convlstm_wgrad_f16x3_wide_kernel<1>,
-                           dim3(mv::wgrad16_wide_blocks(q)), dim3(256), 0, e->stream, q);
-      else if (wide)
-        hipLaunchKernelGGL(mv::convlstm_wgrad_f16x3_wide_kernel<3>,
-                           dim3(mv::wgrad16_wide_blocks(q)), dim3(256), 0, e->stream, q);
-      else if (one)
-        hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_kernel<false, 1>),
-                           dim3(mv::wgrad16_blocks(q, false)), dim3(256), mv::kWg16LdsBytes1,
-                           e->stream, q);
-      else
-      hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_kernel<false, 3>),
-                         dim3(mv::wgrad16_blocks(q, false)), dim3(256), mv::kWg16LdsBytes,
-                         e->stream, q);
-    }, -1.0, (one ? 1.0 : 3.0) * (wino ? 5.0 / 9.0 : 1.0));
+      launch_wgrad16(e, q, pl.wide, pl.one, false);
+    }, -1.0, pl.mfma_factor);
     if (Cx > 0) {
       mv::Wgrad16Args qx = q;
       for (int d = 0; d < 3; ++d) qx.at[d] = t.xt16[d].p;
       qx.Ca = Cx; qx.a_exp = t.chain_exp.p + 2;
-      if (wino) {
-        qx.a_comp_stride = (int64_t)2 * Cx * Mrow3;
-        nsplit_x = mv::wgrad16_x_splits(Mgemm, wa.nsplit);
-        mv::wgrad16_plan(qx, Mgemm, nsplit_x);
+      if (pl.wino) {
+        qx.a_comp_stride = (int64_t)2 * Cx * pl.Mrow3;
+        mv::wgrad16_plan(qx, pl.Mgemm, pl.nsplit_x);
       }
       launch(e, "convlstm_wgrad_x", 2.0 * cells * 9 * Cx * 4.0 * C,
              cells * (Cx + 4.0 * C) * 4.0, [&] {
-        if (wide && mv::wgrad16_wide_x_enabled() && one)
-          hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_wide_kernel<1, true>),
-                             dim3(mv::wgrad16_wide_blocks(qx, true)), dim3(256), 0, e->stream, qx);
-        else if (wide && mv::wgrad16_wide_x_enabled())
-          hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_wide_kernel<3, true>),
-                             dim3(mv::wgrad16_wide_blocks(qx, true)), dim3(256), 0, e->stream, qx);
-        else if (one)
-          hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_kernel<true, 1>),
-                             dim3(mv::wgrad16_blocks(qx, true)), dim3(256), mv::kWg16LdsBytes1,
-                             e->stream, qx);
-        else
-        hipLaunchKernelGGL((mv::convlstm_wgrad_f16x3_kernel<true, 3>),
-                           dim3(mv::wgrad16_blocks(qx, true)), dim3(256), mv::kWg16LdsBytes,
-                           e->stream, qx);
-      }, -1.0, (one ? 1.0 : 3.0) * (wino ? 5.0 / 9.0 : 1.0));
+        launch_wgrad16(e, qx, pl.wide_x, pl.one, true);
+      }, -1.0, pl.mfma_factor);
     }
   } else {
-  launch(e, "convlstm_wgrad", 2.0 * cells * 9 * (ch.Cx + C) * 4.0 * C,
-         cells * (ch.Cx + 5.0 * C) * 4.0, [&] {
-    mv::launch_convlstm_wgrad(wa, e->stream);
-  }, -1.0, 1.0);
+    mv::WgradArgs wa = pl.fp32;
+    wa.x = Cx ? ch.xs.p : nullptr; wa.h = hin; wa.g = ch.gates.p;
+    wa.partial = t.partial.p;
+    launch(e, "convlstm_wgrad", 2.0 * cells * 9 * (Cx + C) * 4.0 * C,
+           cells * (Cx + 5.0 * C) * 4.0, [&] {
+      mv::launch_convlstm_wgrad(wa, e->stream);
+    }, -1.0, pl.mfma_factor);
   }
-  launch(e, "wgrad_reduce", 0, 4.0 * ncols * ((wino_form ? 15.0 / 9 : 1.0) * wa.nsplit + 1), [&] {
+  const bool wino_form = pl.f16 && pl.wino;
+  launch(e, "wgrad_reduce", 0, 4.0 * ncols * ((wino_form ? 15.0 / 9 : 1.0) * pl.nsplit + 1), [&] {
     if (wino_form)
       hipLaunchKernelGGL(mv::wgrad_wino3_reduce_kernel, dim3(cdiv(ncols / 3, 256)), dim3(256), 0,
-                         e->stream, t.partial.p, wa.nsplit, nsplit_x > 0 ? nsplit_x : wa.nsplit,
-                         (size_t)ch.Cx * 4 * C, ncols / 9, grad_of(e, ch.cell->kernel));
+                         e->stream, t.partial.p, pl.nsplit, pl.nsplit_x,
+                         (size_t)Cx * 4 * C, ncols / 9, grad_of(e, ch.cell->kernel));
     else
-    hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(ncols, 256)), dim3(256), 0,
-                       e->stream, t.partial.p, grad_of(e, ch.cell->kernel),
-                       (size_t)wa.nsplit, ncols, (size_t)wa.nsplit);
+      hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(ncols, 256)), dim3(256), 0,
+                         e->stream, t.partial.p, grad_of(e, ch.cell->kernel),
+                         (size_t)pl.nsplit, ncols, (size_t)pl.nsplit);
   });
   // biases: column sums of G
   launch(e, "bias_colsum", 0, cells * 4.0 * C * 4.0, [&] {
-    if (f16)
+    if (pl.f16)
       run_colsum(e, t.bias_part.p, bias_blocks, (size_t)4 * C,
                  grad_of(e, ch.cell->biases), t.partial.p);
     else

@@ -1,0 +1,146 @@
+# coding=utf-8
+"""Which gate-kernel launches a fixed list of configurations issues (GPU).
+
+For every configuration: build an engine, run one step to settle the weight packs and the operand
+planes, then one step with profiling on, and record `Engine.kernel_stats()` without the timings:
+per kernel name the launch count and the host-computed flops / bytes / flops_dense / flops_mfma.
+Those are exact functions of the kernel form the host chose (csrc/gate_plan.h), the halo flag,
+the split counts and the x pass count, so two builds that print the same document issue the same
+launches.  The document goes to stdout (or to the file named as the first argument) as ONE JSON
+object with sorted keys.
+
+  python tools/launch_table.py profiles/launch_table.json [f16x3,bf16]
+
+(second argument: only the configurations of these compute modes).  A configuration the engine
+refuses is recorded with the error text instead of a table.
+
+The list reaches every form: the published shapes greedy and beam-20 in the three compute modes;
+a training step in each mode, with and without the scene encoder; relu models (per-tensor x
+exponent: F(2,3) forward, three-pass bf16 x); the literal 36 x 18 / 18 x 9 grids (halo tiling,
+fp32 wgrad on the 9-wide grid); --convlstm_kernel 5 (generic loops); hidden sizes 128 and 512
+(every hidden size the engine accepts is a multiple of the Winograd channel block, so none can
+fail the packs' channel-block test); emb_size 128 (x rows of the wgrad in whole 64-channel
+groups); and weights with outliers (no Winograd form).  Environment switches are inherited: run
+it under MV_WINO3=0 etc. to table what a switch selects."""
+
+from __future__ import annotations
+
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+LITERAL = dict(scene_h=72, scene_w=36, scene_grids=[(36, 18), (18, 9)])
+MODES = ("f32", "f16x3", "bf16")
+
+
+def configurations():
+  """-> [(name, kind, compute mode, config overrides, weights)]; kind greedy | beam | train"""
+  out = []
+  for m in MODES:
+    out.append(("published/greedy", "greedy", m, dict(batch_size=4, use_grids=(1, 1)), None))
+    out.append(("published/beam20", "beam", m,
+                dict(batch_size=2, use_grids=(1, 0), beam_size=20), None))
+    out.append(("published/train", "train", m, dict(batch_size=2, use_grids=(1, 1)), None))
+    out.append(("noscene/train", "train", m,
+                dict(batch_size=2, use_grids=(1, 1), use_scene_enc=False), None))
+  for m in ("f16x3", "bf16"):
+    relu = dict(batch_size=2, use_grids=(1, 1), activation_func="relu")
+    out.append(("relu/greedy", "greedy", m, relu, None))
+    out.append(("relu/train", "train", m, relu, None))
+    lit = dict(batch_size=2, use_grids=(1, 1), **LITERAL)
+    out.append(("literal/greedy", "greedy", m, lit, None))
+    out.append(("literal/train", "train", m, lit, None))
+    out.append(("literal/beam20", "beam", m,
+                dict(batch_size=2, use_grids=(1, 0), beam_size=20, **LITERAL), None))
+    e128 = dict(batch_size=2, use_grids=(1, 1), emb_size=128)
+    out.append(("emb128/train", "train", m, e128, None))
+    for ch in (128, 512):
+      hid = dict(batch_size=2, use_grids=(1, 1), enc_hidden_size=ch, dec_hidden_size=ch)
+      out.append(("hidden%d/greedy" % ch, "greedy", m, hid, None))
+      out.append(("hidden%d/train" % ch, "train", m, hid, None))
+  ck5 = dict(batch_size=2, use_grids=(0, 1), convlstm_kernel=5)
+  out.append(("ck5/greedy", "greedy", "f32", ck5, None))
+  out.append(("ck5/train", "train", "f32", ck5, None))
+  out.append(("outliers/greedy", "greedy", "f16x3", dict(batch_size=2, use_grids=(0, 1)),
+              "outliers"))
+  return out
+
+
+def outlier_params(cfg, params):
+  """+-230 entries in the h rows of kernels of median |w| ~3e-3 (tests/test_gpu_at_size.py):
+  max |w| > 4096 x median |w|, the engine keeps such a cell on the direct 3x3 form"""
+  rng = np.random.default_rng(77)
+  for name in list(params):
+    if not name.endswith("/kernel"):
+      continue
+    w = params[name].copy()
+    cx = w.shape[2] - cfg.enc_hidden_size
+    flat = w[:, :, cx:, :].reshape(-1).copy()
+    idx = rng.integers(0, flat.size, size=200)
+    flat[idx] = (rng.choice([-1.0, 1.0], size=200) * 230.0).astype(np.float32)
+    w[:, :, cx:, :] = flat.reshape(w[:, :, cx:, :].shape)
+    params[name] = np.ascontiguousarray(w, dtype=np.float32)
+  return params
+
+
+def table_of(kind, mode, overrides, weights):
+  from multiverse_amd import _lib, synth
+  over = dict(overrides)
+  cfg = synth.default_config(batch_size=over.pop("batch_size"), use_grids=over.pop("use_grids"),
+                             beam_size=over.pop("beam_size", 1), is_train=kind == "train",
+                             **over)
+  params = synth.make_params(cfg, seed=synth.SEED_BASE + 2)
+  if weights == "outliers":
+    params = outlier_params(cfg, params)
+  feed = synth.make_feed(cfg, seed=synth.SEED_BASE + 3)
+  eng = _lib.Engine(cfg, device=0)
+  try:
+    eng.set_params(params)
+    eng.set_graph_mode(False)        # per-launch events need eager launches
+    eng.set_compute_mode(mode)
+    if kind == "train":
+      eng.train_init()
+    step = {"greedy": lambda: eng.forward_greedy(feed), "beam": lambda: eng.forward_beam(feed),
+            "train": lambda: eng.train_step(feed)}[kind]
+    step()
+    eng.synchronize()
+    eng.set_profiling(True)
+    eng.reset_kernel_stats()
+    step()
+    eng.synchronize()
+    stats = eng.kernel_stats()
+  finally:
+    eng.close()
+  return {name: {k: v for k, v in st.items() if k != "total_ms"} for name, st in stats.items()}
+
+
+def main(argv):
+  from multiverse_amd import _lib
+  modes = argv[2].split(",") if len(argv) > 2 else MODES
+  doc = {}
+  for name, kind, mode, overrides, weights in configurations():
+    if mode not in modes:
+      continue
+    key = "%s/%s" % (name, mode)
+    print("[launch_table] %s" % key, file=sys.stderr, flush=True)
+    try:
+      doc[key] = table_of(kind, mode, overrides, weights)
+    except _lib.MvError as err:
+      doc[key] = {"error": str(err)}
+  text = json.dumps(doc, sort_keys=True, indent=1) + "\n"
+  if len(argv) > 1:
+    os.makedirs(os.path.dirname(os.path.abspath(argv[1])), exist_ok=True)
+    with open(argv[1], "w") as f:
+      f.write(text)
+  else:
+    sys.stdout.write(text)
+  return 0
+
+
+if __name__ == "__main__":
+  sys.exit(main(sys.argv))
