@@ -99,6 +99,8 @@ int mv_create(const mv_config* cfg, int device, mv_handle* out) {
     e->cfg = *cfg;
     e->device = device;
     HIP_CHECK(hipStreamCreate(&e->stream));
+    e->issue = e->stream;
+    create_chain_streams(e);
     build_param_table(e);
     alloc_buffers(e);
     if (cfg->beam_size > 1) {
@@ -108,7 +110,15 @@ int mv_create(const mv_config* cfg, int device, mv_handle* out) {
       ensure_beam_step_lds(device, ((size_t)2 * cfg->beam_size * K + 512) * sizeof(float));
     }
   });
-  if (rc != 0) { delete e; return rc; }
+  if (rc != 0) {
+    if (e) {
+      if (e->fork_ev) (void)hipEventDestroy(e->fork_ev);
+      if (e->join_ev) (void)hipEventDestroy(e->join_ev);
+      if (e->stream_b) (void)hipStreamDestroy(e->stream_b);
+    }
+    delete e;
+    return rc;
+  }
   *out = e;
   return 0;
 }
@@ -117,6 +127,7 @@ int mv_destroy(mv_handle h) {
   if (!h) return 0;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->stream_b) (void)hipStreamSynchronize(h->stream_b);
   if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
   if (h->fetch_stream) (void)hipStreamSynchronize(h->fetch_stream);
   pipeline_destroy(h);
@@ -130,6 +141,9 @@ int mv_destroy(mv_handle h) {
     delete h->comm;
   }
   delete h->train;
+  if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
+  if (h->join_ev) (void)hipEventDestroy(h->join_ev);
+  if (h->stream_b) (void)hipStreamDestroy(h->stream_b);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
   return 0;
@@ -730,7 +744,8 @@ int mv_set_compute_mode(mv_handle h, int32_t mode) {
                h->cfg.convlstm_kernel);
     if (mode != 0) {
       // operand-plane scratch per group slot: even slots class-sized (N*B rows),
-      // odd slots regression-sized (N rows), largest enabled grid
+      // odd slots regression-sized (N rows), largest enabled grid.  The chain pairs of the
+      // greedy forward (beam_size 1: every slot N rows) use slots {0, 1} and {2, 3}.
       const mv_config& c = h->cfg;
       size_t K = 0;
       for (int s = 0; s < c.num_scales; ++s)

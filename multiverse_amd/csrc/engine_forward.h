@@ -83,6 +83,7 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
   for (size_t i = 0; i < probs.size(); ++i) {
     const ConvLstmArgs& a = probs[i];
     mv::ConvLstm16Args& q = p16[i];
+    const size_t sl = (size_t)e->slot0 + i;      // the group slot of the pair being issued
     // the kernel's epilogue lets a 32-cell wave tile span at most two images
     MV_REQUIRE(a.H * a.W >= 32, "f16x3 / bf16 compute modes need grids of at least 32 cells "
                "(%d x %d); use compute mode f32", a.H, a.W);
@@ -129,13 +130,13 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
         q.x16 = pb->p; q.x_plane_stride = (int64_t)pb->n;
       } else {
         const size_t pst = ncell * a.Cx + mv::kPlaneSlack + mv::kPlanePad;
-        MV_REQUIRE(e->px16[i].n >= 2 * pst, "internal: f16x3 x plane scratch");
-        _Float16* p0 = e->px16[i].p + mv::kPlanePad;
+        MV_REQUIRE(e->px16[sl].n >= 2 * pst, "internal: f16x3 x plane scratch");
+        _Float16* p0 = e->px16[sl].p + mv::kPlanePad;
         q.x16 = p0; q.x_plane_stride = (int64_t)pst;
         if (e->dyn_x()) {       // unbounded activations: planes of 2^e x, e from max |x|
-          MV_REQUIRE(e->xexp[i].p, "internal: x exponent scratch");
-          q.x_exp = e->xexp[i].p + 64;
-          dyn_splits.push_back(DynItem{a.x, p0, p0 + pst, (int)ncell, a.Cx, e->xexp[i].p});
+          MV_REQUIRE(e->xexp[sl].p, "internal: x exponent scratch");
+          q.x_exp = e->xexp[sl].p + 64;
+          dyn_splits.push_back(DynItem{a.x, p0, p0 + pst, (int)ncell, a.Cx, e->xexp[sl].p});
         } else {
           splits.push_back(SplitItem{a.x, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)ncell, a.Cx});
         }
@@ -150,8 +151,8 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
         q.h16 = pb->p; q.h_plane_stride = (int64_t)pb->n;
       } else {
         const size_t pst = ncell * a.C + mv::kPlaneSlack + mv::kPlanePad;
-        MV_REQUIRE(e->ph16[i].n >= 2 * pst, "internal: f16x3 h plane scratch");
-        _Float16* p0 = e->ph16[i].p + mv::kPlanePad;
+        MV_REQUIRE(e->ph16[sl].n >= 2 * pst, "internal: f16x3 h plane scratch");
+        _Float16* p0 = e->ph16[sl].p + mv::kPlanePad;
         q.h16 = p0; q.h_plane_stride = (int64_t)pst;
         splits.push_back(SplitItem{a.h, p0, bf16 ? (_Float16*)nullptr : p0 + pst, (int)ncell, a.C});
       }
@@ -159,12 +160,12 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
   }
   for (const DynItem& it : dyn_splits) {
     launch(e, "split_planes", 0, 12.0 * (double)it.cells * it.C, [&] {
-      HIP_CHECK(hipMemsetAsync(it.bits, 0, 64 * sizeof(int32_t), e->stream));
-      hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, e->stream, it.in,
+      HIP_CHECK(hipMemsetAsync(it.bits, 0, 64 * sizeof(int32_t), e->issue));
+      hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, e->issue, it.in,
                          (size_t)it.cells * it.C, it.bits);
       hipLaunchKernelGGL(mv::split_planes_dyn_kernel,
                          dim3(mv::split_planes_blocks((size_t)it.cells, it.C)), dim3(256), 0,
-                         e->stream, it.in, it.p0, it.p1, it.cells, it.C, it.bits, it.bits + 64);
+                         e->issue, it.in, it.p0, it.p1, it.cells, it.C, it.bits, it.bits + 64);
     });
   }
   // operands no producer left as planes: one grouped split launch in front of the gate kernel
@@ -181,7 +182,7 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
       sbytes += (bf16 ? 6.0 : 8.0) * (double)it.cells * it.C;
     }
     launch(e, "split_planes", 0, sbytes, [&] {
-      hipLaunchKernelGGL(mv::split_planes_group_kernel, dim3(nb), dim3(256), 0, e->stream, g);
+      hipLaunchKernelGGL(mv::split_planes_group_kernel, dim3(nb), dim3(256), 0, e->issue, g);
     });
   }
 }
@@ -217,69 +218,112 @@ void launch_gate_group(const ForwardPlan& pl, const mv::ConvLstm16Args* p16,
   else mv::launch_convlstm_bf16t_steps(pw, n, pl.halo, pl.map_mode, stream);
 }
 
-void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
-                          double flops, double bytes, double dense) {
-  const int n = (int)probs.size();
-  MV_REQUIRE(n <= mv::kMaxGroup, "internal: gate group of %d problems", n);
-  std::vector<ConvCell*> cells(n);
-  for (int i = 0; i < n; ++i) cells[i] = cell_of_pack(e, probs[i].wpack);
-  std::vector<mv::ConvLstm16Args> p16(n);
-  prepare_gate_operands(e, probs, cells, p16);
-  ForwardProblem fp[mv::kMaxGroup];
-  for (int i = 0; i < n; ++i) fp[i] = ForwardProblem{&p16[i], cells[i], e->pv3x[i].n, e->pv3h[i].n};
-  const ForwardPlan pl = plan_forward_group(e->compute_mode, fp, n);
-  const _Float16* packs[mv::kMaxGroup] = {};
-  const float* w_hwio[mv::kMaxGroup] = {};
-  _Float16 *v3x[mv::kMaxGroup] = {}, *v3h[mv::kMaxGroup] = {};
-  std::vector<mv::Wn3TransformItem> tr3;
-  double tr3_bytes = 0;
-  for (int i = 0; i < n; ++i) {
-    const mv::ConvLstm16Args& q = p16[i];
-    const ConvLstmArgs& a = q.f;
-    w_hwio[i] = cells[i]->kernel->dev.p;
-    packs[i] = pl.form == GateForm::Wino2 ? cells[i]->wpw.p
-             : pl.form == GateForm::Wino3 ? cells[i]->wpw3.p
-             : pl.form == GateForm::Bf16T ? cells[i]->wpbt.p : nullptr;
-    if (pl.form != GateForm::Wino3) continue;
-    if (!a.zero_state) {
-      v3h[i] = e->pv3h[i].p;
-      tr3_bytes += queue_wino3_transform(tr3, {q.h16, q.h_plane_stride, v3h[i], a.src_row_h,
-                                               a.rows, a.H, a.W, a.C});
-    }
-    if (has_dense_x(a)) {
-      v3x[i] = e->pv3x[i].p;
-      tr3_bytes += queue_wino3_transform(tr3, {q.x16, q.x_plane_stride, v3x[i], nullptr,
-                                               a.rows, a.H, a.W, a.Cx});
-    }
-  }
-  if (!tr3.empty())
-    launch(e, "wino3_transform", 0, tr3_bytes, [&] {
-      mv::launch_wino3_transforms(tr3.data(), (int)tr3.size(), e->stream);
-    });
-  launch(e, "convlstm_step", flops, bytes, [&] {
-    launch_gate_group(pl, p16.data(), packs, w_hwio, v3x, v3h, n, e->stream);
-  }, dense, pl.mfma_factor);
-}
-
-// One launch for up to four independent ConvLSTM steps (class / regression
-// chain of each scale advance in lockstep).
-void run_conv_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
-  if (probs.empty()) return;
+// A gate group with its operands prepared: the problems, their cells, the group slots they use.
+struct GatePrep {
+  std::vector<ConvCell*> cells;
+  std::vector<mv::ConvLstm16Args> p16;
+  int slot0 = 0;
   double flops = 0, bytes = 0, dense = 0;
+  int n() const { return (int)p16.size(); }
+};
+
+// dense: the step as the reference computes it; executed: a zero-state step
+// (first encoder step) never multiplies the h half and never reads h, c
+void gate_group_cost(const std::vector<ConvLstmArgs>& probs, double& flops, double& bytes,
+                     double& dense) {
+  flops = bytes = dense = 0;
   for (const auto& a : probs) {
     const double M = (double)a.rows * a.H * a.W;
-    // dense: the step as the reference computes it; executed: a zero-state step
-    // (first encoder step) never multiplies the h half and never reads h, c
     dense += 2.0 * M * 9.0 * (a.Cx + a.C) * 4.0 * a.C;
     // sparse x: the x k-steps are not executed (table terms in the epilogue)
     const double cx = a.sx_corr ? 0.0 : (double)a.Cx;
     flops += 2.0 * M * 9.0 * (cx + (a.zero_state ? 0 : a.C)) * 4.0 * a.C;
     bytes += M * (cx + (a.zero_state ? 2.0 : 4.0) * a.C) * 4.0;   // x,(h,c) in; h,c out
   }
+}
+
+GatePrep prepare_gate_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
+  GatePrep g;
+  const int n = (int)probs.size();
+  MV_REQUIRE(e->slot0 + n <= mv::kMaxGroup, "internal: gate group of %d problems from slot %d",
+             n, e->slot0);
+  g.slot0 = e->slot0;
+  g.cells.resize(n);
+  for (int i = 0; i < n; ++i) g.cells[i] = cell_of_pack(e, probs[i].wpack);
+  g.p16.resize(n);
+  prepare_gate_operands(e, probs, g.cells, g.p16);
+  gate_group_cost(probs, g.flops, g.bytes, g.dense);
+  return g;
+}
+
+// ONE plan for the gate launches of a step: the groups of both chain pairs take the form, the
+// tiling and the block map that the step's single grouped launch would take, so a chain's
+// kernel does not depend on how the step's problems are spread over launches.
+ForwardPlan plan_gate_groups(mv_engine* e, const GatePrep* const* groups, int ngroups) {
+  ForwardProblem fp[mv::kMaxGroup];
+  int n = 0;
+  for (int g = 0; g < ngroups; ++g)
+    for (int i = 0; i < groups[g]->n(); ++i) {
+      MV_REQUIRE(n < mv::kMaxGroup, "internal: more than %d gate problems in a step", mv::kMaxGroup);
+      const int sl = groups[g]->slot0 + i;
+      fp[n++] = ForwardProblem{&groups[g]->p16[i], groups[g]->cells[i], e->pv3x[sl].n, e->pv3h[sl].n};
+    }
+  return plan_forward_group(e->compute_mode, fp, n);
+}
+
+// Input transforms (F(3,3)) and the grouped gate launch of a prepared group, on e->issue.
+void issue_gate_group(mv_engine* e, const GatePrep& g, const ForwardPlan& pl) {
+  const int n = g.n();
+  const _Float16* packs[mv::kMaxGroup] = {};
+  const float* w_hwio[mv::kMaxGroup] = {};
+  _Float16 *v3x[mv::kMaxGroup] = {}, *v3h[mv::kMaxGroup] = {};
+  std::vector<mv::Wn3TransformItem> tr3;
+  double tr3_bytes = 0;
+  for (int i = 0; i < n; ++i) {
+    const mv::ConvLstm16Args& q = g.p16[i];
+    const ConvLstmArgs& a = q.f;
+    const int sl = g.slot0 + i;
+    w_hwio[i] = g.cells[i]->kernel->dev.p;
+    packs[i] = pl.form == GateForm::Wino2 ? g.cells[i]->wpw.p
+             : pl.form == GateForm::Wino3 ? g.cells[i]->wpw3.p
+             : pl.form == GateForm::Bf16T ? g.cells[i]->wpbt.p : nullptr;
+    if (pl.form != GateForm::Wino3) continue;
+    if (!a.zero_state) {
+      v3h[i] = e->pv3h[sl].p;
+      tr3_bytes += queue_wino3_transform(tr3, {q.h16, q.h_plane_stride, v3h[i], a.src_row_h,
+                                               a.rows, a.H, a.W, a.C});
+    }
+    if (has_dense_x(a)) {
+      v3x[i] = e->pv3x[sl].p;
+      tr3_bytes += queue_wino3_transform(tr3, {q.x16, q.x_plane_stride, v3x[i], nullptr,
+                                               a.rows, a.H, a.W, a.Cx});
+    }
+  }
+  if (!tr3.empty())
+    launch(e, "wino3_transform", 0, tr3_bytes, [&] {
+      mv::launch_wino3_transforms(tr3.data(), (int)tr3.size(), e->issue);
+    });
+  launch(e, "convlstm_step", g.flops, g.bytes, [&] {
+    launch_gate_group(pl, g.p16.data(), packs, w_hwio, v3x, v3h, n, e->issue);
+  }, g.dense, pl.mfma_factor);
+}
+
+void run_conv_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
+  const GatePrep g = prepare_gate_group(e, probs);
+  const GatePrep* gp = &g;
+  issue_gate_group(e, g, plan_gate_groups(e, &gp, 1));
+}
+
+// One launch for up to four independent ConvLSTM steps (class / regression
+// chain of each scale advance in lockstep).
+void run_conv_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
+  if (probs.empty()) return;
   if (e->compute_mode != 0) {
-    run_conv_group_f16x3(e, probs, flops, bytes, dense);
+    run_conv_group_f16x3(e, probs);
     return;
   }
+  double flops = 0, bytes = 0, dense = 0;
+  gate_group_cost(probs, flops, bytes, dense);
   if (e->cfg.convlstm_kernel != 3) {            // --convlstm_kernel 1 / 5 / ...: plain fp32 loops
     const double kk = (double)e->cfg.convlstm_kernel * e->cfg.convlstm_kernel / 9.0;
     launch(e, "convlstm_step", flops * kk, bytes, [&] {
@@ -288,14 +332,37 @@ void run_conv_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
         ga.f = a;
         ga.w = cell_of_bias(e, a.bias)->kernel->dev.p;
         ga.ksize = e->cfg.convlstm_kernel;
-        mv::launch_convlstm_generic_step(ga, e->stream);
+        mv::launch_convlstm_generic_step(ga, e->issue);
       }
     }, dense * kk, 0.0);
     return;
   }
   launch(e, "convlstm_step", flops, bytes, [&] {
-    mv::launch_convlstm_steps(probs.data(), (int)probs.size(), e->stream);
+    mv::launch_convlstm_steps(probs.data(), (int)probs.size(), e->issue);
   }, dense, 1.0);
+}
+
+// The gate launches of a step whose chains run as two pairs: group `a` (class chains) on the
+// engine's stream, group `b` (regression chains) on the second one, each with its own group
+// slots, both in the form planned for the step's problems together.
+void run_conv_pairs(mv_engine* e, const std::vector<ConvLstmArgs>& a,
+                    const std::vector<ConvLstmArgs>& b) {
+  if (e->compute_mode == 0 || a.empty() || b.empty()) {
+    { IssueOn on(e, 0); run_conv_group(e, a); }
+    { IssueOn on(e, 1); run_conv_group(e, b); }
+    return;
+  }
+  MV_REQUIRE(a.size() <= 2 && b.size() <= 2, "internal: chain pairs of %zu / %zu problems",
+             a.size(), b.size());
+  GatePrep ga, gb;
+  { IssueOn on(e, 0); ga = prepare_gate_group(e, a); }
+  { IssueOn on(e, 1); gb = prepare_gate_group(e, b); }
+  // (the step's single launch dispatches the dense-x problems first: same order here; it
+  // weights nothing but the profile's MFMA factor)
+  const GatePrep* both[2] = {&gb, &ga};
+  const ForwardPlan pl = plan_gate_groups(e, both, 2);
+  { IssueOn on(e, 0); issue_gate_group(e, ga, pl); }
+  { IssueOn on(e, 1); issue_gate_group(e, gb, pl); }
 }
 
 void run_scene(mv_engine* e) {
@@ -316,13 +383,13 @@ void run_scene(mv_engine* e) {
       launch(e, "scene_proj1x1_mfma", 2.0 * M * Ci * Co,
              4.0 * (total + (double)M * Ci), [&] {
         hipLaunchKernelGGL(mv::scene_proj1x1_mfma_kernel, dim3(cdiv(M, 128)), dim3(256), 0,
-                           e->stream, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, c.activation);
+                           e->issue, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, c.activation);
       });
     } else {
     launch(e, "scene_conv_s2_tanh", 2.0 * total * k * k * Ci,
            4.0 * (total + (double)U * Hi * Wi * Ci), [&] {
       hipLaunchKernelGGL(mv::scene_conv_s2_tanh_kernel, dim3(cdiv(total, 256)),
-                         dim3(256), 0, e->stream, in, w, b, out, U, Hi, Wi, Ci,
+                         dim3(256), 0, e->issue, in, w, b, out, U, Hi, Wi, Ci,
                          Ho, Wo, Co, k, pad_h / 2, pad_w / 2, c.activation);
     });
     }
@@ -335,7 +402,7 @@ void run_scene(mv_engine* e) {
     launch(e, "scene_mean", (double)total * c.obs_len,
            4.0 * total * (c.obs_len + 1), [&] {
       hipLaunchKernelGGL(mv::scene_mean_kernel, dim3(cdiv(total, 256)), dim3(256),
-                         0, e->stream, e->scene_conv[s].p, e->obs_scene.p,
+                         0, e->issue, e->scene_conv[s].p, e->obs_scene.p,
                          S.scene_mean.p, c.batch_size, c.obs_len, S.K,
                          c.scene_conv_dim);
     });
@@ -355,15 +422,19 @@ static bool beam_shared_first() {
 }
 
 // Encoders of every enabled scale (dynamic_rnn from the zero state, T_o steps;
-// code/pred_models.py:212-215, 232-234), all chains advanced in lockstep.
-void run_encoders(mv_engine* e, Cursors& cur) {
+// code/pred_models.py:212-215, 232-234), all chains advanced in lockstep: step t's input
+// launches (on e->issue) and gate problems for the chains in `chains`.
+enum : int { kChainCls = 1, kChainReg = 2, kChainAll = 3 };
+
+void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
+                           std::vector<ConvLstmArgs>& probs) {
   const mv_config& c = e->cfg;
   const int N = c.batch_size, T = c.obs_len, D = c.scene_conv_dim;
-  for (int t = 0; t < T; ++t) {
-    std::vector<ConvLstmArgs> probs;
-    for (int s = 0; s < c.num_scales; ++s) {
+  for (int s = 0; s < c.num_scales; ++s) {
+    {
       ScaleState& S = e->sc[s];
       if (!S.use) continue;
+      if (chains & kChainCls) {
       const size_t total = (size_t)N * S.K * D;
       const bool sparse = sparse_x_on(e, S);
       const size_t nc = (size_t)N * 9 * 4 * c.hidden_size;   // table of one step
@@ -377,7 +448,7 @@ void run_encoders(mv_engine* e, Cursors& cur) {
             size_t pst = 0;
             _Float16* p16 = e->plane_out(S.xbuf_cls.p, &pst);
             hipLaunchKernelGGL(mv::enc_grid_emb_onehot_kernel, dim3(cdiv(tx, 256)), dim3(256),
-                               0, e->stream, S.labels.p, T, t, 1, e->enc_emb_W->dev.p,
+                               0, e->issue, S.labels.p, T, t, 1, e->enc_emb_W->dev.p,
                                e->enc_emb_b->dev.p, S.xbuf_cls.p, N, S.H, S.W, E, p16, pst,
                                c.activation);
           });
@@ -388,7 +459,7 @@ void run_encoders(mv_engine* e, Cursors& cur) {
             hipLaunchKernelGGL(mv::sx_encoder_corr_kernel,
                                dim3(cdiv((size_t)4 * c.hidden_size, 256), 9,
                                     cdiv((size_t)N, mv::kSxRows) * T),
-                               dim3(256), 0, e->stream, S.enc_cls.kernel->dev.p,
+                               dim3(256), 0, e->issue, S.enc_cls.kernel->dev.p,
                                e->scene_conv[s].p, e->obs_scene.p, S.labels.p, N, T, -1, S.K, D,
                                c.hidden_size, S.sx_enc_corr.p);
           });
@@ -397,14 +468,12 @@ void run_encoders(mv_engine* e, Cursors& cur) {
         size_t pst = 0;
         _Float16* p16 = e->plane_out(S.xbuf_cls.p, &pst);
         hipLaunchKernelGGL(mv::enc_class_input_kernel, dim3(cdiv(total, 256)),
-                           dim3(256), 0, e->stream, e->scene_conv[s].p,
+                           dim3(256), 0, e->issue, e->scene_conv[s].p,
                            e->obs_scene.p, S.labels.p, S.xbuf_cls.p, N, T, t, S.K, D, p16,
                            pst);
       });
       }
-      // x = grid_obs_regress[:, t] is read in place through the row stride
-      const size_t row = (size_t)S.K * 2;
-      const int cc = cur.cls[s], cr = cur.reg[s];
+      const int cc = cur.cls[s];
       probs.push_back(conv_problem(e, S.enc_cls, S.xbuf_cls.p, S.cls_h[cc].p,
                                    S.cls_c[cc].p, nullptr, nullptr, S.cls_h[cc ^ 1].p,
                                    S.cls_c[cc ^ 1].p, N, S.H, S.W, t == 0, 0,
@@ -422,15 +491,35 @@ void run_encoders(mv_engine* e, Cursors& cur) {
         set_sparse_x(e, S, probs.back(), false, S.labels.p + t, T, 1);
         probs.back().sx_corr = S.sx_enc_corr.p + (size_t)t * nc;
       }
+      cur.cls[s] ^= 1;
+      }
+      if (!(chains & kChainReg)) continue;
+      // x = grid_obs_regress[:, t] is read in place through the row stride
+      const size_t row = (size_t)S.K * 2;
+      const int cr = cur.reg[s];
       if (!c.use_single_decoder)     // single decoder: the regression encoder feeds nothing
         probs.push_back(conv_problem(e, S.enc_reg, S.obs_reg.p + (size_t)t * row,
                                      S.reg_h[cr].p, S.reg_c[cr].p, nullptr, nullptr,
                                      S.reg_h[cr ^ 1].p, S.reg_c[cr ^ 1].p, N, S.H, S.W,
                                      t == 0, (size_t)T * row));
       if (!c.use_single_decoder) probs.back().skip_h32 = 1;
-      cur.cls[s] ^= 1; cur.reg[s] ^= 1;
+      cur.reg[s] ^= 1;
     }
-    run_conv_group(e, probs);
+  }
+}
+
+void run_encoders(mv_engine* e, Cursors& cur, bool pairs) {
+  for (int t = 0; t < e->cfg.obs_len; ++t) {
+    if (!pairs) {
+      std::vector<ConvLstmArgs> probs;
+      encoder_step_problems(e, cur, t, kChainAll, probs);
+      run_conv_group(e, probs);
+      continue;
+    }
+    std::vector<ConvLstmArgs> pa, pb;
+    { IssueOn on(e, 0); encoder_step_problems(e, cur, t, kChainCls, pa); }
+    { IssueOn on(e, 1); encoder_step_problems(e, cur, t, kChainReg, pb); }
+    run_conv_pairs(e, pa, pb);
   }
 }
 
@@ -498,9 +587,9 @@ void run_gnn_jobs(mv_engine* e, const std::vector<GnnJob>& jobs) {
     launch(e, "gnn_attend", flops, bytes, [&] {
       if (tiled && ver >= 3) {
         hipLaunchKernelGGL(mv::gnn_attend_v3_kernel, dim3(nblocks), dim3(mv::kGnn3Threads), 0,
-                           e->stream, grp, c.hidden_size, gnn_scene_dim(e));
+                           e->issue, grp, c.hidden_size, gnn_scene_dim(e));
       } else if (tiled) {
-        hipLaunchKernelGGL(mv::gnn_attend_v2_kernel, dim3(nblocks), dim3(mv::kGnnThreads), 0, e->stream,
+        hipLaunchKernelGGL(mv::gnn_attend_v2_kernel, dim3(nblocks), dim3(mv::kGnnThreads), 0, e->issue,
                            grp, c.hidden_size, gnn_scene_dim(e));
       } else {
         const size_t cells = (size_t)A.rows * A.S->K;
@@ -508,11 +597,11 @@ void run_gnn_jobs(mv_engine* e, const std::vector<GnnJob>& jobs) {
         _Float16* p16 = e->plane_out(A.out, &pst);
         if (c.hidden_size <= 256)
           hipLaunchKernelGGL(mv::gnn_attend_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                             e->stream, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
+                             e->issue, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
                              A.S->H, A.S->W, c.hidden_size, gnn_scene_dim(e), A.sm_div, p16, pst);
         else
           hipLaunchKernelGGL(mv::gnn_attend_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                             e->stream, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
+                             e->issue, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
                              A.S->H, A.S->W, c.hidden_size, gnn_scene_dim(e), A.sm_div, p16, pst);
       }
     });
@@ -532,7 +621,7 @@ void run_hidden2grid(mv_engine* e, ScaleState& S, const float* h, const float* w
   const int C = e->cfg.hidden_size;
   launch(e, "hidden2grid", cells * 2.0 * 9 * C * P, 4.0 * cells * (C + P), [&] {
     hipLaunchKernelGGL(mv::hidden2grid_kernel<P>, dim3(cdiv(cells, 4)), dim3(256),
-                       0, e->stream, h, w, out, out_row_stride, rows, S.H, S.W, C);
+                       0, e->issue, h, w, out, out_row_stride, rows, S.H, S.W, C);
   });
 }
 
@@ -552,11 +641,11 @@ void run_emb_onehot(mv_engine* e, ScaleState& S, const int32_t* ids, int stride,
     _Float16* p16 = e->plane_out(out, &pst);
     if (tail_v2() && E % 8 == 0)
       hipLaunchKernelGGL(mv::grid_emb_onehot8_kernel, dim3(cdiv(total / 8, 256)), dim3(256), 0,
-                         e->stream, ids, stride, ids_div, S.emb_cls_W->dev.p,
+                         e->issue, ids, stride, ids_div, S.emb_cls_W->dev.p,
                          S.emb_cls_b->dev.p, out, rows, S.H, S.W, E, p16, pst, e->cfg.activation);
     else
       hipLaunchKernelGGL(mv::grid_emb_onehot_kernel, dim3(cdiv(total, 256)),
-                         dim3(256), 0, e->stream, ids, stride, ids_div, S.emb_cls_W->dev.p,
+                         dim3(256), 0, e->issue, ids, stride, ids_div, S.emb_cls_W->dev.p,
                          S.emb_cls_b->dev.p, out, rows, S.H, S.W, E, p16, pst, e->cfg.activation);
   });
 }
@@ -573,7 +662,7 @@ void run_emb_dense(mv_engine* e, ScaleState& S, const float* x, size_t row_strid
     size_t pst = 0;
     _Float16* p16 = e->plane_out(out, &pst);
     hipLaunchKernelGGL(mv::grid_emb_dense_kernel, dim3(cdiv(total, 256)), dim3(256),
-                       0, e->stream, x, row_stride, W->dev.p, b->dev.p, out, rows, S.H, S.W,
+                       0, e->issue, x, row_stride, W->dev.p, b->dev.p, out, rows, S.H, S.W,
                        P, E, p16, pst, e->cfg.activation);
   });
 }
@@ -620,6 +709,9 @@ struct TailPlan {
   // inference buffers S.ids / S.xbuf_cls / S.xbuf_reg with their operand planes)
   int32_t* cls_ids_out = nullptr; float* cls_x_out = nullptr; float* reg_x_out = nullptr;
   bool cls_embed = true;   // false: ids only (the embedding is made elsewhere)
+  // the chains of this scale that the launch carries (the chain pairs of the greedy forward
+  // run the class chains' tail and the regression chains' tail as launches of their own)
+  bool do_cls = true, do_reg = true;
 };
 
 void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
@@ -634,10 +726,17 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
                "decode tail: K %d / emb_size %d", S.K, E);
     const int reg_rows = pl.reg_rows ? pl.reg_rows : N;
     const size_t cc = (size_t)pl.cls_rows * S.K, cr = (size_t)reg_rows * S.K;
-    qp.push_back(mv::H2gQProblem{pl.cls_h, S.wq_cls.p, S.q_cls.p, (int32_t)cc, 1});
-    qp.push_back(mv::H2gQProblem{pl.reg_h, S.wq_reg.p, S.q_reg.p, (int32_t)cr, 2});
-    qbytes += 4.0 * (cc * (C + 9.0) + cr * (C + 18.0));
-    qflops += 2.0 * 9 * C * (cc + 2.0 * cr);
+    if (pl.do_cls) {
+      qp.push_back(mv::H2gQProblem{pl.cls_h, S.wq_cls.p, S.q_cls.p, (int32_t)cc, 1});
+      qbytes += 4.0 * cc * (C + 9.0);
+      qflops += 2.0 * 9 * C * cc;
+    }
+    if (pl.do_reg) {
+      qp.push_back(mv::H2gQProblem{pl.reg_h, S.wq_reg.p, S.q_reg.p, (int32_t)cr, 2});
+      qbytes += 4.0 * cr * (C + 18.0);
+      qflops += 2.0 * 9 * C * 2.0 * cr;
+    }
+    if (pl.do_cls) {
     mv::TailProblem a{};
     a.q = S.q_cls.p; a.out = pl.cls_out; a.out_row_stride = pl.cls_stride;
     a.rows = pl.cls_rows; a.H = S.H; a.W = S.W; a.P = 1; a.E = E; a.onehot = 1;
@@ -660,6 +759,8 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
       }
     }
     tp.push_back(a);
+    }
+    if (!pl.do_reg) continue;
     mv::TailProblem b{};
     b.q = S.q_reg.p; b.out = pl.reg_out; b.out_row_stride = pl.reg_stride;
     b.rows = reg_rows; b.H = S.H; b.W = S.W; b.P = 2; b.E = E; b.onehot = 0;
@@ -680,66 +781,75 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
     tp.push_back(b);
   }
   MV_REQUIRE(qp.size() <= (size_t)mv::kTailMax, "decode tail: too many chains");
+  if (qp.empty()) return;
   launch(e, "hidden2grid", qflops, qbytes, [&] {
-    mv::launch_h2g_q(qp.data(), (int)qp.size(), C, e->stream);
+    mv::launch_h2g_q(qp.data(), (int)qp.size(), C, e->issue);
   });
   launch(e, "decode_tail", 0, tbytes, [&] {
-    mv::launch_decode_tail(tp.data(), (int)tp.size(), e->stream);
+    mv::launch_decode_tail(tp.data(), (int)tp.size(), e->issue);
   });
 }
 
 // Greedy decoders of every enabled scale in lockstep: class decoder
 // (grid_decoder with input_onehot, use_gnn; code/pred_models.py:311-471) and
-// regression decoder.
-void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp) {
+// regression decoder.  `pairs`: the class chains and the regression chains are issued as two
+// chain pairs (enqueue_forward) instead of sharing every launch.
+void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
   const mv_config& c = e->cfg;
   const int N = c.batch_size, T = c.obs_len;
   const bool v2 = tail_v2();
+  MV_REQUIRE(!pairs || (v2 && !c.use_single_decoder), "internal: chain pairs need the grouped "
+             "decoder tail and a regression decoder");
   for (int t = 0; t < Tp; ++t) {
-    std::vector<ConvLstmArgs> probs;
-    if (c.use_gnn) {
-      std::vector<GnnJob> jobs;
-      for (int s = 0; s < c.num_scales; ++s)
-        if (e->sc[s].use)
-          jobs.push_back(GnnJob{&e->sc[s], e->sc[s].cls_h[cur.cls[s]].p, nullptr,
-                                e->sc[s].cls_hg.p, N, 1});
-      run_gnn_jobs(e, jobs);
-    }
-    for (int s = 0; s < c.num_scales; ++s) {
-      ScaleState& S = e->sc[s];
-      if (!S.use) continue;
-      const int cc = cur.cls[s];
-      const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
-      // sparse x: the embedding of a one-hot map enters the gate kernel as table terms
-      const bool sparse = sparse_x_on(e, S) && (t == 0 || !c.class_feedback_dense);
-      if (sparse)
-        ;
-      else if (t == 0)  // one_hot(last observed cell)
-        run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, N);
-      else if (c.class_feedback_dense)   // raw logits of the previous step (:388-406)
-        run_emb_dense(e, S, S.out_cls.p + (size_t)(t - 1) * S.K, (size_t)Tp * S.K,
-                      S.xbuf_cls.p, N, S.emb_cls_W, S.emb_cls_b, 1);
-      else if (!v2)
-        run_emb_onehot(e, S, S.ids.p, 1, S.xbuf_cls.p, N);
-      probs.push_back(conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p,
-                                   nullptr, nullptr, S.cls_h[cc ^ 1].p,
-                                   S.cls_c[cc ^ 1].p, N, S.H, S.W, false, 0,
-                                   /*want_h16=*/!c.use_gnn));
-      if (sparse) {
-        if (t == 0) set_sparse_x(e, S, probs.back(), true, S.labels.p + (T - 1), T, 1);
-        else set_sparse_x(e, S, probs.back(), true, S.ids.p, 1, 1);
+    // input launches (on e->issue) and gate problems of step t for the chains in `chains`
+    auto step_problems = [&](int chains, std::vector<ConvLstmArgs>& probs) {
+      if ((chains & kChainCls) && c.use_gnn) {
+        std::vector<GnnJob> jobs;
+        for (int s = 0; s < c.num_scales; ++s)
+          if (e->sc[s].use)
+            jobs.push_back(GnnJob{&e->sc[s], e->sc[s].cls_h[cur.cls[s]].p, nullptr,
+                                  e->sc[s].cls_hg.p, N, 1});
+        run_gnn_jobs(e, jobs);
       }
-      cur.cls[s] ^= 1;
-      if (!c.use_single_decoder) probs.push_back(reg_decoder_problem(e, s, cur, t, Tp, !v2));
-    }
-    // longest tiles first: the dense-x problems (162 k-steps per tile) are dispatched
-    // before the sparse-x ones (144), so the last, partly filled round of workgroups is
-    // made of the short ones
-    std::stable_sort(probs.begin(), probs.end(), [](const ConvLstmArgs& a, const ConvLstmArgs& b) {
-      return (a.sx_corr == nullptr) > (b.sx_corr == nullptr);
-    });
-    run_conv_group(e, probs);
-    if (v2) {
+      for (int s = 0; s < c.num_scales; ++s) {
+        ScaleState& S = e->sc[s];
+        if (!S.use) continue;
+        if (chains & kChainCls) {
+          const int cc = cur.cls[s];
+          const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
+          // sparse x: the embedding of a one-hot map enters the gate kernel as table terms
+          const bool sparse = sparse_x_on(e, S) && (t == 0 || !c.class_feedback_dense);
+          if (sparse)
+            ;
+          else if (t == 0)  // one_hot(last observed cell)
+            run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, N);
+          else if (c.class_feedback_dense)   // raw logits of the previous step (:388-406)
+            run_emb_dense(e, S, S.out_cls.p + (size_t)(t - 1) * S.K, (size_t)Tp * S.K,
+                          S.xbuf_cls.p, N, S.emb_cls_W, S.emb_cls_b, 1);
+          else if (!v2)
+            run_emb_onehot(e, S, S.ids.p, 1, S.xbuf_cls.p, N);
+          probs.push_back(conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p,
+                                       nullptr, nullptr, S.cls_h[cc ^ 1].p,
+                                       S.cls_c[cc ^ 1].p, N, S.H, S.W, false, 0,
+                                       /*want_h16=*/!c.use_gnn));
+          if (sparse) {
+            if (t == 0) set_sparse_x(e, S, probs.back(), true, S.labels.p + (T - 1), T, 1);
+            else set_sparse_x(e, S, probs.back(), true, S.ids.p, 1, 1);
+          }
+          cur.cls[s] ^= 1;
+        }
+        if ((chains & kChainReg) && !c.use_single_decoder)
+          probs.push_back(reg_decoder_problem(e, s, cur, t, Tp, !v2));
+      }
+      // longest tiles first: the dense-x problems (162 k-steps per tile) are dispatched
+      // before the sparse-x ones (144), so the last, partly filled round of workgroups is
+      // made of the short ones
+      std::stable_sort(probs.begin(), probs.end(), [](const ConvLstmArgs& a, const ConvLstmArgs& b) {
+        return (a.sx_corr == nullptr) > (b.sx_corr == nullptr);
+      });
+    };
+    // the grouped decoder tail of step t for the chains in `chains`
+    auto step_tail = [&](int chains) {
       std::vector<TailPlan> plans;
       for (int s = 0; s < c.num_scales; ++s) {
         ScaleState& S = e->sc[s];
@@ -756,9 +866,26 @@ void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp) {
           pl.reg_h = pl.cls_h;
           pl.reg_next = false;
         }
+        pl.do_cls = (chains & kChainCls) != 0;
+        pl.do_reg = (chains & kChainReg) != 0;
         plans.push_back(pl);
       }
       run_tail(e, plans);
+    };
+    if (pairs) {
+      std::vector<ConvLstmArgs> pa, pb;
+      { IssueOn on(e, 0); step_problems(kChainCls, pa); }
+      { IssueOn on(e, 1); step_problems(kChainReg, pb); }
+      run_conv_pairs(e, pa, pb);
+      { IssueOn on(e, 0); step_tail(kChainCls); }
+      { IssueOn on(e, 1); step_tail(kChainReg); }
+      continue;
+    }
+    std::vector<ConvLstmArgs> probs;
+    step_problems(kChainAll, probs);
+    run_conv_group(e, probs);
+    if (v2) {
+      step_tail(kChainAll);
       continue;
     }
     for (int s = 0; s < c.num_scales; ++s) {
@@ -769,7 +896,7 @@ void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp) {
       run_hidden2grid<1>(e, S, S.cls_h[cur.cls[s]].p, S.out_cls_W->dev.p, logits, orow, N);
       if (t + 1 < Tp && !c.class_feedback_dense) {
         launch(e, "argmax_rows", 0, 4.0 * N * S.K, [&] {
-          hipLaunchKernelGGL(mv::argmax_rows_kernel, dim3(N), dim3(64), 0, e->stream,
+          hipLaunchKernelGGL(mv::argmax_rows_kernel, dim3(N), dim3(64), 0, e->issue,
                              logits, orow, S.ids.p, N, S.K);
         });
       }
@@ -853,14 +980,14 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
     const size_t row4 = (size_t)K * C / 4, total4 = (size_t)R * row4;
     launch(e, "beam_tile_state", 0, 8.0 * total4 * 16, [&] {
       hipLaunchKernelGGL(tile_rows_kernel, dim3(cdiv(total4, 256)), dim3(256), 0,
-                         e->stream, S.cls_h[cc].p, S.cls_h[cc ^ 1].p, row4, B, total4);
+                         e->issue, S.cls_h[cc].p, S.cls_h[cc ^ 1].p, row4, B, total4);
       hipLaunchKernelGGL(tile_rows_kernel, dim3(cdiv(total4, 256)), dim3(256), 0,
-                         e->stream, S.cls_c[cc].p, S.cls_c[cc ^ 1].p, row4, B, total4);
+                         e->issue, S.cls_c[cc].p, S.cls_c[cc ^ 1].p, row4, B, total4);
     });
     e->plane_invalidate(S.cls_h[cc ^ 1].p);   // fp32 copy only: planes are re-split
     cur.cls[s] ^= 1;
   }
-  HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->stream));
+  HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
   int lpi = 0;
   const int32_t* src = nullptr;  // state row indirection for the next cell step
   const bool sparse = sparse_x_on(e, S);
@@ -928,17 +1055,17 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
       if (one_per_sample) {
         const size_t total = (size_t)R * K;
         hipLaunchKernelGGL(tile_beam0_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                           e->stream, logits, K, B, total);
+                           e->issue, logits, K, B, total);
         if (single)
           hipLaunchKernelGGL(tile_beam0_kernel, dim3(cdiv(total * 2, 256)), dim3(256), 0,
-                             e->stream, regstep, K * 2, B, total * 2);
+                             e->issue, regstep, K * 2, B, total * 2);
       }
       int32_t* ids = e->bm_ids.p + (size_t)(time - 1) * R;
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
-        HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)R * sizeof(int32_t), e->stream));
+        HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)R * sizeof(int32_t), e->issue));
       launch(e, "beam_step", 0, 4.0 * R * K, [&] {
-        launch_beam_step(e->stream, logits, e->bm_lp[lpi].p, e->bm_cand.p, N, B, K, time,
+        launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, N, B, K, time,
                          c.diverse_beam, logf(c.diverse_gamma), c.fix_num_timestep,
                          e->bm_lp[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
                          one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr);
@@ -973,36 +1100,63 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
   }
   // back-trace (:689-806)
   hipLaunchKernelGGL(beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0,
-                     e->stream, e->bm_ids.p, e->bm_parents.p, e->bm_out_ids.p,
+                     e->issue, e->bm_ids.p, e->bm_parents.p, e->bm_out_ids.p,
                      e->bm_trace.p, N, B, Tp);
   const size_t total = (size_t)R * Tp * K;
   hipLaunchKernelGGL(beam_gather_logits_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                     e->stream, e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p,
+                     e->issue, e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p,
                      N, B, Tp, K);
   if (c.use_single_decoder) {       // offsets along every beam: the same gather, 2K per row
     const size_t tot2 = (size_t)R * Tp * K * 2;
     hipLaunchKernelGGL(beam_gather_logits_kernel, dim3(cdiv(tot2, 256)), dim3(256), 0,
-                       e->stream, e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p,
+                       e->issue, e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p,
                        N, B, Tp, K * 2);
   }
   // final logprobs are in bm_lp[lpi]
   if (lpi != 0)
     HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, e->bm_lp[1].p, (size_t)R * sizeof(float),
-                             hipMemcpyDeviceToDevice, e->stream));
+                             hipMemcpyDeviceToDevice, e->issue));
 }
 
-void enqueue_forward(mv_engine* e, bool beam) {
+// The four chains of a greedy forward (class / regression x two scales) exchange nothing between
+// the scene stage and the end of the decode, and want different things from the chip: a gate
+// launch the matrix pipe, the attention / transform / tail kernels HBM and L2.  So the greedy
+// inference forward issues them as two chain pairs -- the class chains on the engine's stream,
+// the regression chains on a second one -- that meet once per forward: the second stream starts
+// after everything queued before the forward (uploads, weight packs), the engine's stream
+// continues after both.  The regression pair does not read the scene stage, which thereby runs
+// under its first encoder steps.  One stream, in the order of before: MV_CHAIN_STREAMS=1;
+// profiling (event brackets around overlapped launches time nothing); hipGraph capture (a
+// captured fork / join becomes parallel branches of the graph); beam search; a model with one
+// decoder (no regression chains); MV_TAIL=v1; batches above kChainPairMaxBatch -- measured on one
+// box, alternating fresh processes: batch 64 +0.7 % (bf16 mode +2.1 %), batch 256 -2.6 % (the
+// two gate launches of a step run side by side rather than against the other pair's small
+// kernels, and at 256 rows a launch of its own per pair costs more than the small kernels
+// hide); sizes in between are unmeasured and stay on one stream.
+constexpr int kChainPairMaxBatch = 64;
+
+void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
   const mv_config& c = e->cfg;
   const int Tp = e->pred_len;
-  if (!e->no_scene()) run_scene(e);
+  const bool pairs = !beam && e->stream_b && !e->profiling && !capturing && c.beam_size == 1 &&
+                     !c.use_single_decoder && tail_v2() && c.batch_size <= kChainPairMaxBatch;
   Cursors cur;
-  run_encoders(e, cur);
+  if (pairs) {
+    ChainFork fork(e);
+    if (!e->no_scene()) { IssueOn on(e, 0); run_scene(e); }
+    run_encoders(e, cur, true);
+    run_decoders_greedy(e, cur, Tp, true);
+    HIP_CHECK(hipGetLastError());
+    return;
+  }
+  if (!e->no_scene()) run_scene(e);
+  run_encoders(e, cur, false);
   if (beam) {
     int s = 0;
     for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
     run_decoders_beam(e, s, cur, Tp);
   } else {
-    run_decoders_greedy(e, cur, Tp);
+    run_decoders_greedy(e, cur, Tp, false);
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -1026,7 +1180,7 @@ void run_forward(mv_engine* e, bool beam) {
     hipGraph_t g = nullptr;
     HIP_CHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     try {
-      enqueue_forward(e, beam);
+      enqueue_forward(e, beam, /*capturing=*/true);
     } catch (...) {
       (void)hipStreamEndCapture(e->stream, &g);
       if (g) (void)hipGraphDestroy(g);

@@ -58,6 +58,66 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   HIP_CHECK(hipGetLastError());
 }
 
+// MV_CHAIN_STREAMS=1 keeps the whole greedy forward on one stream (the order before the chain
+// pairs, for A/B runs); default 2.  MV_CHAIN_PRIORITY=1 creates the regression pair's stream at
+// the lowest priority, so that the class pair (attention + transform + gate + tail: the longer
+// critical path of a step) is dispatched first; default 0, plain streams.
+static int chain_streams() {
+  static const int n = (getenv("MV_CHAIN_STREAMS") && atoi(getenv("MV_CHAIN_STREAMS")) == 1) ? 1 : 2;
+  return n;
+}
+static bool chain_priority() {
+  static const bool on = getenv("MV_CHAIN_PRIORITY") && atoi(getenv("MV_CHAIN_PRIORITY")) == 1;
+  return on;
+}
+
+void create_chain_streams(mv_engine* e) {
+  if (chain_streams() != 2) return;
+  if (chain_priority()) {
+    int least = 0, greatest = 0;
+    HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_CHECK(hipStreamCreateWithPriority(&e->stream_b, hipStreamDefault, least));
+  } else {
+    HIP_CHECK(hipStreamCreate(&e->stream_b));
+  }
+  HIP_CHECK(hipEventCreateWithFlags(&e->fork_ev, hipEventDisableTiming));
+  HIP_CHECK(hipEventCreateWithFlags(&e->join_ev, hipEventDisableTiming));
+}
+
+// The chain pair whose launches are being issued (mv_engine::issue / slot0), for a scope.
+struct IssueOn {
+  mv_engine* e;
+  hipStream_t prev;
+  int prev_slot0;
+  IssueOn(mv_engine* e_, int pair) : e(e_), prev(e_->issue), prev_slot0(e_->slot0) {
+    e->issue = pair ? e->stream_b : e->stream;
+    e->slot0 = pair ? 2 : 0;
+  }
+  ~IssueOn() { e->issue = prev; e->slot0 = prev_slot0; }
+  IssueOn(const IssueOn&) = delete;
+  IssueOn& operator=(const IssueOn&) = delete;
+};
+
+// Fork / join of the two chain pairs: stream_b starts after everything queued on `stream` so
+// far, and `stream` continues after everything queued on stream_b -- on every way out of the
+// forward (a failed check throws between the two).
+struct ChainFork {
+  mv_engine* e;
+  explicit ChainFork(mv_engine* e_) : e(e_) {
+    HIP_CHECK(hipEventRecord(e->fork_ev, e->stream));
+    HIP_CHECK(hipStreamWaitEvent(e->stream_b, e->fork_ev, 0));
+  }
+  ~ChainFork() {
+    e->issue = e->stream;
+    e->slot0 = 0;
+    if (hipEventRecord(e->join_ev, e->stream_b) != hipSuccess ||
+        hipStreamWaitEvent(e->stream, e->join_ev, 0) != hipSuccess)
+      (void)hipStreamSynchronize(e->stream_b);
+  }
+  ChainFork(const ChainFork&) = delete;
+  ChainFork& operator=(const ChainFork&) = delete;
+};
+
 // Launch wrapper: optional hipEvent bracket per launch for the roofline figure.
 template <typename F>
 void launch(mv_engine* e, const char* name, double flops, double bytes, F&& fn,
@@ -70,9 +130,9 @@ void launch(mv_engine* e, const char* name, double flops, double bytes, F&& fn,
   PendingEvent pe{si, nullptr, nullptr};
   HIP_CHECK(hipEventCreate(&pe.a));
   HIP_CHECK(hipEventCreate(&pe.b));
-  HIP_CHECK(hipEventRecord(pe.a, e->stream));
+  HIP_CHECK(hipEventRecord(pe.a, e->issue));
   fn();
-  HIP_CHECK(hipEventRecord(pe.b, e->stream));
+  HIP_CHECK(hipEventRecord(pe.b, e->issue));
   e->stats[si].launches += 1;
   e->stats[si].flops += flops;
   e->stats[si].flops_dense += flops_dense >= 0 ? flops_dense : flops;

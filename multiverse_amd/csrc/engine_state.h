@@ -149,6 +149,16 @@ struct mv_engine {
   mv_config cfg{};
   int device = 0;
   hipStream_t stream = nullptr;
+  // Two launch streams of the greedy inference forward (engine_forward.h enqueue_forward): the
+  // class chains (pair 0) stay on `stream`, the regression chains (pair 1) run on `stream_b`
+  // between one fork and one join per forward.  Every launch of the forward goes to `issue`, and
+  // a gate group takes its scratch from the group slots slot0, slot0 + 1 (pair 0: {0, 1}, pair
+  // 1: {2, 3}); outside a forward that has forked, issue == stream and slot0 == 0.  Host issue is
+  // single-threaded, so the pair being issued is engine state (IssueOn sets and restores it).
+  hipStream_t stream_b = nullptr;
+  hipEvent_t fork_ev = nullptr, join_ev = nullptr;
+  hipStream_t issue = nullptr;
+  int slot0 = 0;
   std::string err;
   std::vector<std::unique_ptr<Param>> params;
   Param* decode_reg_W = nullptr;   // --use_single_decoder: the offset kernel shared by the scales
