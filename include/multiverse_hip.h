@@ -272,6 +272,23 @@ int  mv_beam_occupancy(mv_handle h, float* out /* [N, T_p, K] */);
 /* the small members of mv_download_beam_outputs on their own (beam handles, after a forward):
  * ids [N, B, T_p], logprobs [N, B]; either may be NULL */
 int  mv_download_beam_ids(mv_handle h, int32_t* ids, float* logprobs);
+/* Per-row prediction lengths: one forward decodes samples of different lengths.  lengths[n] =
+ * L[n] in [0, pred_len] (checked at the forward; pred_len is the forward's mv_inputs.pred_len);
+ * NULL clears.  Sticky until cleared; applies to mv_forward_*, mv_run_*_resident, the downloads
+ * and the three multi-future decode calls above.  Every output keeps its shape (time dimension
+ * pred_len).  For t < L[n], row n of every output is bit-identical to row n of a uniform forward
+ * of this engine with pred_len = L[n]: its beams are traced back from step L[n] - 1, its
+ * logprobs are the scores after the selection at time L[n].  For t >= L[n]: greedy logits and
+ * offsets, best_beam, beam logits, grid_reg, decoded trajectories and occupancy maps are 0, ids
+ * are -1.  L[n] = 0 is a padding row: all 0 (ids -1).  Step t issues its launches on the prefix
+ * of 1 + max{n : L[n] > t} rows, so lengths sorted descending launch no finished row; any order
+ * is correct.  With all L[n] == pred_len the forward is the uniform one.  Keep the lengths set
+ * until the last forward's outputs have been decoded.  While lengths are set, mv_train_* and
+ * mv_submit_greedy fail with a message. */
+int  mv_set_pred_lengths(mv_handle h, const int32_t* lengths /* [N]; NULL clears */);
+/* sum of the row counts over every ConvLSTM problem of every grouped gate launch of the last
+ * forward (encoders and decoders): what the forward really launched, without timing anything */
+int  mv_last_forward_gate_rows(mv_handle h, int64_t* rows);
 
 /* -- training: one call == sess.run([loss, train_op, wd_loss, pred_grid_loss]) */
 int  mv_train_init(mv_handle h, const mv_train_config* tc);

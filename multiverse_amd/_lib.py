@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_grid_centers", "mv_upload_inputs_compact", "mv_upload_targets_compact",
     "mv_pipeline_create", "mv_submit_greedy", "mv_collect_greedy",
     "mv_decode_trajectories", "mv_beam_occupancy", "mv_download_beam_ids",
+    "mv_set_pred_lengths", "mv_last_forward_gate_rows",
 ]
 
 
@@ -206,6 +207,8 @@ def load():
   lib.mv_decode_trajectories.argtypes = [h, C.c_int32, C.c_int32, _dp]
   lib.mv_beam_occupancy.argtypes = [h, _fp]
   lib.mv_download_beam_ids.argtypes = [h, _ip, _fp]
+  lib.mv_set_pred_lengths.argtypes = [h, _ip]
+  lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_profiling.argtypes = [h, C.c_int32]
   lib.mv_set_graph_mode.argtypes = [h, C.c_int32]
   lib.mv_set_compute_mode.argtypes = [h, C.c_int32]
@@ -494,7 +497,28 @@ class Engine(object):
       inp.grid_obs_regress[s] = fptr(reg)
     self._keep = keep
     self._pred_len = inp.pred_len
+    self._set_pred_lengths(feed.get("pred_lengths"))
     return inp
+
+  def _set_pred_lengths(self, lengths):
+    """Per-row prediction lengths of the next forward (feed["pred_lengths"], int [N]); None
+    clears the ones a previous feed set.  Called with every feed that is uploaded."""
+    if lengths is None:
+      if getattr(self, "_lengths_set", False):
+        check(self.lib.mv_set_pred_lengths(self.handle, None), self.handle)
+        self._lengths_set = False
+      return
+    lens = i32(lengths).reshape(-1)
+    if lens.size != self.cfg.batch_size:
+      raise MvError("pred_lengths: %d values for batch_size %d" % (lens.size, self.cfg.batch_size))
+    check(self.lib.mv_set_pred_lengths(self.handle, iptr(lens)), self.handle)
+    self._lengths_set = True
+
+  def last_forward_gate_rows(self):
+    """Rows of every ConvLSTM problem of every gate launch of the last forward, summed."""
+    rows = C.c_int64()
+    check(self.lib.mv_last_forward_gate_rows(self.handle, C.byref(rows)), self.handle)
+    return int(rows.value)
 
   def _alloc_outputs(self, Tp):
     cfg = self.cfg
@@ -618,6 +642,7 @@ class Engine(object):
       keep.append(lab)
       inp.grid_obs_labels[s] = iptr(lab)
     self._pred_len = inp.pred_len
+    self._set_pred_lengths(feed.get("pred_lengths"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len

@@ -212,6 +212,9 @@ _MF_FLAGS = [
     # not in the reference: trajectories (and the occupancy map of the grid-NLL evaluation,
     # traj_id -> float32 [T, h*w]) decoded on the GPU; the beams' logits stay there
     ("--device_decode", B, None), ("--save_occupancy_file", str, None),
+    # not in the reference: samples of DIFFERENT T_pred are decoded together, one length per
+    # row (multifuture.plan_ragged_batches); the engine stops launching finished rows
+    ("--ragged_batches", B, None),
 ]
 
 

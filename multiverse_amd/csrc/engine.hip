@@ -301,6 +301,34 @@ int mv_download_beam_ids(mv_handle h, int32_t* ids, float* logprobs) {
   });
 }
 
+int mv_set_pred_lengths(mv_handle h, const int32_t* lengths) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    const size_t N = (size_t)h->cfg.batch_size;
+    // behind whatever still reads the previous lengths on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!lengths) {
+      h->lens_set = false;
+      h->ragged_now = false;
+      h->lens_host.clear();
+      return;
+    }
+    // (the bound [0, pred_len] is checked at the forward, which knows pred_len)
+    h->lens_host.assign(lengths, lengths + N);
+    HIP_CHECK(hipMemcpy(h->lens_dev.p, lengths, N * sizeof(int32_t), hipMemcpyHostToDevice));
+    h->lens_set = true;
+  });
+}
+
+int mv_last_forward_gate_rows(mv_handle h, int64_t* rows) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(rows, "mv_last_forward_gate_rows: NULL argument");
+    MV_REQUIRE(h->last_forward != 0, "mv_last_forward_gate_rows: no forward has run on this handle");
+    *rows = h->gate_rows;
+  });
+}
+
 int mv_forward_greedy(mv_handle h, const mv_inputs* in, mv_outputs* out) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -358,6 +386,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(tc, "mv_train_init: NULL config");
+    MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
+               "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(tc->optimizer >= 0 && tc->optimizer <= 3, "Optimizer not implemented: %d "
                "(0 adadelta, 1 momentum, 2 adam, 3 rmsprop; reference pred_models.py:1667-1681)",
                tc->optimizer);
@@ -400,6 +430,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
                               mv_losses* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
+               "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_forward_backward: give both inputs and targets, or neither "
                "(resident)");
@@ -431,12 +463,18 @@ int mv_upload_targets_compact(mv_handle h, const mv_targets_compact* tg) {
 
 int mv_train_apply(mv_handle h, float grad_scale) {
   if (!h) return 1;
-  return guarded(h, [&] { train_apply(h, grad_scale); });
+  return guarded(h, [&] {
+    MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
+               "training runs every row to pred_len -- clear them first", "mv_train_apply");
+    train_apply(h, grad_scale);
+  });
 }
 
 int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_losses* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
+               "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_step: give both inputs and targets, or neither (resident)");
     train_fwd_bwd(h, in, tg, out);

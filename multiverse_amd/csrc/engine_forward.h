@@ -303,6 +303,7 @@ void issue_gate_group(mv_engine* e, const GatePrep& g, const ForwardPlan& pl) {
     launch(e, "wino3_transform", 0, tr3_bytes, [&] {
       mv::launch_wino3_transforms(tr3.data(), (int)tr3.size(), e->issue);
     });
+  for (int i = 0; i < n; ++i) e->gate_rows += g.p16[i].f.rows;
   launch(e, "convlstm_step", g.flops, g.bytes, [&] {
     launch_gate_group(pl, g.p16.data(), packs, w_hwio, v3x, v3h, n, e->issue);
   }, g.dense, pl.mfma_factor);
@@ -324,6 +325,7 @@ void run_conv_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs) {
   }
   double flops = 0, bytes = 0, dense = 0;
   gate_group_cost(probs, flops, bytes, dense);
+  for (const auto& a : probs) e->gate_rows += a.rows;
   if (e->cfg.convlstm_kernel != 3) {            // --convlstm_kernel 1 / 5 / ...: plain fp32 loops
     const double kk = (double)e->cfg.convlstm_kernel * e->cfg.convlstm_kernel / 9.0;
     launch(e, "convlstm_step", flops * kk, bytes, [&] {
@@ -398,12 +400,13 @@ void run_scene(mv_engine* e) {
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
     if (!S.use) continue;
-    const size_t total = (size_t)c.batch_size * S.K * c.scene_conv_dim;
+    const int rows = e->rows_at(0);      // ragged forward: the rows that decode at all
+    const size_t total = (size_t)rows * S.K * c.scene_conv_dim;
     launch(e, "scene_mean", (double)total * c.obs_len,
            4.0 * total * (c.obs_len + 1), [&] {
       hipLaunchKernelGGL(mv::scene_mean_kernel, dim3(cdiv(total, 256)), dim3(256),
                          0, e->issue, e->scene_conv[s].p, e->obs_scene.p,
-                         S.scene_mean.p, c.batch_size, c.obs_len, S.K,
+                         S.scene_mean.p, rows, c.obs_len, S.K,
                          c.scene_conv_dim);
     });
   }
@@ -429,7 +432,9 @@ enum : int { kChainCls = 1, kChainReg = 2, kChainAll = 3 };
 void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
                            std::vector<ConvLstmArgs>& probs) {
   const mv_config& c = e->cfg;
-  const int N = c.batch_size, T = c.obs_len, D = c.scene_conv_dim;
+  // N: the rows the encoders run on (ragged forward: those that decode at all); the sparse-x
+  // tables of the encoder keep the batch's row layout
+  const int N = e->rows_at(0), Nb = c.batch_size, T = c.obs_len, D = c.scene_conv_dim;
   for (int s = 0; s < c.num_scales; ++s) {
     {
       ScaleState& S = e->sc[s];
@@ -437,7 +442,7 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
       if (chains & kChainCls) {
       const size_t total = (size_t)N * S.K * D;
       const bool sparse = sparse_x_on(e, S);
-      const size_t nc = (size_t)N * 9 * 4 * c.hidden_size;   // table of one step
+      const size_t nc = (size_t)Nb * 9 * 4 * c.hidden_size;   // table of one step
       if (e->no_scene()) {
         // x = grid_emb(one_hot(labels[:, t])): table terms of the weights alone (built with
         // the decoder's, ensure_params), or the dense embedding of this step
@@ -458,9 +463,9 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
           launch(e, "sx_encoder_corr", 2.0 * nc * D * T, 4.0 * nc * T, [&] {
             hipLaunchKernelGGL(mv::sx_encoder_corr_kernel,
                                dim3(cdiv((size_t)4 * c.hidden_size, 256), 9,
-                                    cdiv((size_t)N, mv::kSxRows) * T),
+                                    cdiv((size_t)Nb, mv::kSxRows) * T),
                                dim3(256), 0, e->issue, S.enc_cls.kernel->dev.p,
-                               e->scene_conv[s].p, e->obs_scene.p, S.labels.p, N, T, -1, S.K, D,
+                               e->scene_conv[s].p, e->obs_scene.p, S.labels.p, Nb, T, -1, S.K, D,
                                c.hidden_size, S.sx_enc_corr.p);
           });
       } else {
@@ -674,7 +679,7 @@ ConvLstmArgs reg_decoder_problem(mv_engine* e, int s, Cursors& cur, int t, int T
                                  bool embed = true) {
   const mv_config& c = e->cfg;
   ScaleState& S = e->sc[s];
-  const int N = c.batch_size, T = c.obs_len;
+  const int N = e->rows_at(t), T = c.obs_len;
   const size_t orow = (size_t)Tp * S.K * 2;
   if (t == 0)  // first_input = obs_grid_reg[:, -1]
     run_emb_dense(e, S, S.obs_reg.p + (size_t)(T - 1) * S.K * 2, (size_t)T * S.K * 2,
@@ -691,7 +696,7 @@ void reg_decoder_output(mv_engine* e, int s, const Cursors& cur, int t, int Tp) 
   ScaleState& S = e->sc[s];
   const size_t orow = (size_t)Tp * S.K * 2;
   run_hidden2grid<2>(e, S, S.reg_h[cur.reg[s]].p, S.out_reg_W->dev.p,
-                     S.out_reg.p + (size_t)t * S.K * 2, orow, e->cfg.batch_size);
+                     S.out_reg.p + (size_t)t * S.K * 2, orow, e->rows_at(t));
 }
 
 // The decoder tail of step t for all chains (decode_tail.h): hidden2grid as one
@@ -796,11 +801,14 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
 // chain pairs (enqueue_forward) instead of sharing every launch.
 void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
   const mv_config& c = e->cfg;
-  const int N = c.batch_size, T = c.obs_len;
+  const int T = c.obs_len;
   const bool v2 = tail_v2();
   MV_REQUIRE(!pairs || (v2 && !c.use_single_decoder), "internal: chain pairs need the grouped "
              "decoder tail and a regression decoder");
-  for (int t = 0; t < Tp; ++t) {
+  // ragged forward: max L steps, step t on the rows_at(t) rows of its active prefix
+  const int Tsteps = e->ragged_now ? e->ragged_steps : Tp;
+  for (int t = 0; t < Tsteps; ++t) {
+    const int N = e->rows_at(t);
     // input launches (on e->issue) and gate problems of step t for the chains in `chains`
     auto step_problems = [&](int chains, std::vector<ConvLstmArgs>& probs) {
       if ((chains & kChainCls) && c.use_gnn) {
@@ -862,6 +870,7 @@ void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
         pl.reg_h = S.reg_h[cur.reg[s]].p;
         pl.reg_out = S.out_reg.p + (size_t)t * S.K * 2; pl.reg_stride = (int64_t)Tp * S.K * 2;
         pl.reg_next = t + 1 < Tp;
+        pl.reg_rows = N;
         if (c.use_single_decoder) {    // offsets from the class decoder's state (:287-296)
           pl.reg_h = pl.cls_h;
           pl.reg_next = false;
@@ -959,6 +968,66 @@ __global__ void beam_gather_logits_kernel(const float* __restrict__ step_logits,
   out[idx] = step_logits[(((size_t)t * N + n) * B + par) * K + k];
 }
 
+// ---- finalisers of a ragged forward (per-row lengths `lens`, mv_set_pred_lengths)
+
+// row n's beams are traced back from step L[n] - 1 with parents_0 = arange(B), as a forward of
+// pred_len L[n] does; from step L[n] on the ids are -1 and the trace is -1 (nothing to gather)
+__global__ void ragged_beam_backtrace_kernel(const int32_t* __restrict__ step_ids,
+                                             const int32_t* __restrict__ step_parents,
+                                             const int32_t* __restrict__ lens,
+                                             int32_t* __restrict__ out_ids,
+                                             int32_t* __restrict__ trace, int N, int B, int T) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= N * B) return;
+  const int n = idx / B, b = idx - n * B;
+  const int L = min(max(lens[n], 0), T);
+  const size_t row = ((size_t)n * B + b) * T;
+  for (int t = T - 1; t >= L; --t) { out_ids[row + t] = -1; trace[row + t] = -1; }
+  int par = b;
+  for (int t = L - 1; t >= 0; --t) {
+    const size_t o = ((size_t)t * N + n) * B + par;
+    out_ids[row + t] = step_ids[o];
+    trace[row + t] = par;
+    par = step_parents[o];
+  }
+}
+
+// beam_gather_logits_kernel with exact zeros where the trace is -1 (steps past L[n])
+__global__ void ragged_beam_gather_kernel(const float* __restrict__ step_vals,
+                                          const int32_t* __restrict__ trace,
+                                          float* __restrict__ out, int N, int B, int T, int K) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)N * B * T * K;
+  if (idx >= total) return;
+  const int k = idx % K;
+  size_t r = idx / K;
+  const int t = r % T; r /= T;
+  const int b = r % B;
+  const int n = r / B;
+  const int par = trace[((size_t)n * B + b) * T + t];
+  out[idx] = par < 0 ? 0.f : step_vals[(((size_t)t * N + n) * B + par) * K + k];
+}
+
+// final[n, :] = lp[n, :] for the rows whose last selection was this one (L[n] == time)
+__global__ void ragged_capture_lp_kernel(const float* __restrict__ lp,
+                                         const int32_t* __restrict__ lens,
+                                         float* __restrict__ final_lp, int rows, int B, int time) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows) return;
+  if (lens[idx / B] == time) final_lp[idx] = lp[idx];
+}
+
+// out[n, t, :] = 0 for t >= L[n]: what raw_rnn emits for a finished row, through the bias-free
+// hidden2grid.  out is [N, T, row_elems]; one thread per element.
+__global__ void ragged_zero_tail_kernel(float* __restrict__ out, const int32_t* __restrict__ lens,
+                                        int N, int T, int row_elems) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)N * T * row_elems) return;
+  const size_t r = idx / row_elems;
+  const int t = r % T, n = r / T;
+  if (t >= lens[n]) out[idx] = 0.f;
+}
+
 // Beam-search class decoder (grid_decoder_beam_search,
 // code/pred_models.py:474-806) with the un-beamed regression decoder advanced
 // in lockstep (its step t shares a launch with beam time t+1).
@@ -988,6 +1057,13 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
     cur.cls[s] ^= 1;
   }
   HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  // ragged forward (per-row lengths): the cell step of time t runs on the samples that take
+  // prediction step t - 1, a prefix of rows_at(t - 1) of them; the buffers keep the batch's
+  // layout.  Row n's final scores are those after the selection at time L[n] (0 for L[n] = 0).
+  const bool ragged = e->ragged_now;
+  const int Tsteps = ragged ? e->ragged_steps : Tp;
+  if (ragged)
+    HIP_CHECK(hipMemsetAsync(e->bm_lp_final.p, 0, (size_t)R * sizeof(float), e->issue));
   int lpi = 0;
   const int32_t* src = nullptr;  // state row indirection for the next cell step
   const bool sparse = sparse_x_on(e, S);
@@ -1001,10 +1077,12 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
   const bool dedupe = dedupe_env && shared_first && c.use_gnn && K <= 64 * mv::kBeamRankJ &&
                       !(getenv("MV_BEAM_STEP") && strcmp(getenv("MV_BEAM_STEP"), "v1") == 0) &&
                       !(getenv("MV_GNN") && strcmp(getenv("MV_GNN"), "v1") == 0);
-  for (int time = 0; time <= Tp; ++time) {
+  for (int time = 0; time <= Tsteps && Tsteps > 0; ++time) {
+    // samples of this iteration's cell step / of the next one (uniform forward: N both)
+    const int n_now = e->rows_at(std::max(time - 1, 0)), n_next = e->rows_at(time);
     // rows the state holds going INTO this iteration's kernels
     const bool one_per_sample = shared_first && time <= 1;
-    const int rows_now = one_per_sample ? N : R;
+    const int rows_now = one_per_sample ? n_now : n_now * B;
     if (time > 0) {
       // cell step; h comes from the GNN buffer (identity rows) when use_gnn, c through
       // the parent indirection
@@ -1045,6 +1123,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
         pl.reg_h = S.reg_h[cur.reg[s]].p;
         pl.reg_out = S.out_reg.p + (size_t)(time - 1) * K * 2;
         pl.reg_stride = (int64_t)Tp * K * 2; pl.reg_next = time < Tp;
+        pl.reg_rows = n_now;
         }
         run_tail(e, {pl});
       } else {
@@ -1053,7 +1132,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
                            lrow, rows_now);
       }
       if (one_per_sample) {
-        const size_t total = (size_t)R * K;
+        const size_t total = (size_t)n_now * B * K;
         hipLaunchKernelGGL(tile_beam0_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
                            e->issue, logits, K, B, total);
         if (single)
@@ -1063,40 +1142,60 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
       int32_t* ids = e->bm_ids.p + (size_t)(time - 1) * R;
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
-        HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)R * sizeof(int32_t), e->issue));
-      launch(e, "beam_step", 0, 4.0 * R * K, [&] {
-        launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, N, B, K, time,
+        HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
+      launch(e, "beam_step", 0, 4.0 * n_now * B * K, [&] {
+        launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, n_now, B, K, time,
                          c.diverse_beam, logf(c.diverse_gamma), c.fix_num_timestep,
                          e->bm_lp[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
                          one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr);
       });
       lpi ^= 1;
       src = e->bm_src_row.p;
-      if (time == Tp) break;
-      if (!sparse) run_emb_onehot(e, S, ids, 1, S.xbuf_cls.p, R);
+      if (ragged)
+        hipLaunchKernelGGL(ragged_capture_lp_kernel, dim3(cdiv((size_t)n_now * B, 256)), dim3(256),
+                           0, e->issue, e->bm_lp[lpi].p, e->lens_dev.p, e->bm_lp_final.p,
+                           n_now * B, B, time);
+      if (time == Tsteps) break;
+      if (!sparse) run_emb_onehot(e, S, ids, 1, S.xbuf_cls.p, n_next * B);
     } else if (sparse) {
       // the embedded one-hot input enters the gate kernel as table terms (sparse_x.h)
     } else if (shared_first) {
       // one_hot(last observed cell) (:497-498, 531-532), one row per sample
-      run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, N, 1);
+      run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, n_next, 1);
     } else {
-      run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, R, B);
+      run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, n_next * B, B);
     }
     if (c.use_gnn) {
       // time 0 (shared): N rows in, N rows out; afterwards R rows gathered through src
       // (which, after the first selection, indexes the N-row state)
       if (dedupe) {
         // on the state rows themselves (N of them up to the first selection)
-        GnnJob job{&S, S.cls_h[cur.cls[s]].p, nullptr, S.cls_hg.p, rows_now,
-                   one_per_sample ? 1 : B};
+        GnnJob job{&S, S.cls_h[cur.cls[s]].p, nullptr, S.cls_hg.p,
+                   one_per_sample ? n_next : n_next * B, one_per_sample ? 1 : B};
         job.row_ref = time >= 2 ? e->bm_ref.p : nullptr;
         run_gnn_jobs(e, {job});
       } else {
-      const int out_rows = (shared_first && time == 0) ? N : R;
+      const int out_rows = (shared_first && time == 0) ? n_next : n_next * B;
       run_gnn(e, S, S.cls_h[cur.cls[s]].p, src, S.cls_hg.p, out_rows,
               (shared_first && time == 0) ? 1 : B);
       }
     }
+  }
+  if (ragged) {
+    // back-trace of row n from step L[n] - 1; ids -1, logits / offsets 0 from step L[n] on
+    hipLaunchKernelGGL(ragged_beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0, e->issue,
+                       e->bm_ids.p, e->bm_parents.p, e->lens_dev.p, e->bm_out_ids.p,
+                       e->bm_trace.p, N, B, Tp);
+    const size_t total = (size_t)R * Tp * K;
+    hipLaunchKernelGGL(ragged_beam_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, e->issue,
+                       e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p, N, B, Tp, K);
+    if (c.use_single_decoder)
+      hipLaunchKernelGGL(ragged_beam_gather_kernel, dim3(cdiv(total * 2, 256)), dim3(256), 0,
+                         e->issue, e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p, N, B, Tp,
+                         K * 2);
+    HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, e->bm_lp_final.p, (size_t)R * sizeof(float),
+                             hipMemcpyDeviceToDevice, e->issue));
+    return;
   }
   // back-trace (:689-806)
   hipLaunchKernelGGL(beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0,
@@ -1141,6 +1240,14 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
   const bool pairs = !beam && e->stream_b && !e->profiling && !capturing && c.beam_size == 1 &&
                      !c.use_single_decoder && tail_v2() && c.batch_size <= kChainPairMaxBatch;
   Cursors cur;
+  if (e->ragged_now && e->ragged_steps == 0) {    // every row is padding: nothing to compute
+    if (beam) {
+      int s = 0;
+      for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
+      run_decoders_beam(e, s, cur, Tp);         // (its finalisers alone)
+    }
+    return;
+  }
   if (pairs) {
     ChainFork fork(e);
     if (!e->no_scene()) { IssueOn on(e, 0); run_scene(e); }
@@ -1164,19 +1271,66 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
 // One forward = one `sess.run`.  In graph mode the ~150 (greedy) / ~120 (beam)
 // launches of a forward are captured once per (mode, T_pred, U) into a hipGraph
 // and replayed; every device pointer in it is engine-owned and stable.
+// The per-row lengths of this forward (mv_set_pred_lengths): checked against pred_len, and the
+// active-row prefix of every step.  All lengths == pred_len (or none set): the uniform forward.
+void plan_ragged(mv_engine* e) {
+  e->ragged_now = false;
+  e->ragged_steps = 0;
+  if (!e->lens_set) return;
+  const int N = e->cfg.batch_size, Tp = e->pred_len;
+  bool uniform = true;
+  for (int n = 0; n < N; ++n) {
+    MV_REQUIRE(e->lens_host[n] >= 0 && e->lens_host[n] <= Tp,
+               "pred_lengths[%d] = %d not in [0, pred_len=%d]", n, e->lens_host[n], Tp);
+    uniform = uniform && e->lens_host[n] == Tp;
+  }
+  if (uniform) return;
+  e->act_rows.assign((size_t)Tp + 1, 0);
+  for (int n = 0; n < N; ++n) {
+    for (int t = 0; t < e->lens_host[n]; ++t) e->act_rows[t] = n + 1;   // n ascending: the max
+    e->ragged_steps = std::max(e->ragged_steps, (int)e->lens_host[n]);
+  }
+  e->ragged_now = true;
+}
+
+// out_cls / out_reg of a ragged forward: exact zeros from step L[n] on (rows past a step's
+// active prefix were not written at all).  On the engine's stream, after the chain pairs met.
+void finish_ragged(mv_engine* e, bool beam) {
+  const mv_config& c = e->cfg;
+  const int N = c.batch_size, Tp = e->pred_len;
+  for (int s = 0; s < c.num_scales; ++s) {
+    ScaleState& S = e->sc[s];
+    if (!S.use) continue;
+    const size_t nc = (size_t)N * Tp * S.K;
+    if (!beam)
+      hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(cdiv(nc, 256)), dim3(256), 0, e->stream,
+                         S.out_cls.p, e->lens_dev.p, N, Tp, S.K);
+    if (!(beam && c.use_single_decoder))     // (beam, single decoder: bm_out_reg, gathered)
+      hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(cdiv(nc * 2, 256)), dim3(256), 0,
+                         e->stream, S.out_reg.p, e->lens_dev.p, N, Tp, S.K * 2);
+  }
+  HIP_CHECK(hipGetLastError());
+}
+
 void run_forward(mv_engine* e, bool beam) {
   MV_REQUIRE(e->inputs_ready, "no inputs uploaded (mv_upload_inputs)");
   ensure_params(e);
   if (beam)
     MV_REQUIRE(e->cfg.beam_size > 1, "engine was created with beam_size 1");
-  if (!e->graph_mode || e->profiling) {
+  plan_ragged(e);
+  // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
+  // is issued eagerly
+  if (!e->graph_mode || e->profiling || e->ragged_now) {
+    e->gate_rows = 0;
     enqueue_forward(e, beam);
+    if (e->ragged_now) finish_ragged(e, beam);
     e->last_forward = beam ? 2 : 1;
     return;
   }
   const auto key = std::make_tuple(beam ? 1 : 0, e->pred_len, e->num_frames);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
+    e->gate_rows = 0;
     hipGraph_t g = nullptr;
     HIP_CHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     try {
@@ -1192,7 +1346,9 @@ void run_forward(mv_engine* e, bool beam) {
     (void)hipGraphDestroy(g);
     HIP_CHECK(ie);
     it = e->graphs.emplace(key, ex).first;
+    e->graph_gate_rows[key] = e->gate_rows;
   }
+  e->gate_rows = e->graph_gate_rows[key];
   HIP_CHECK(hipGraphLaunch(it->second, e->stream));
   e->last_forward = beam ? 2 : 1;
 }

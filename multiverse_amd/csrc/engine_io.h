@@ -224,6 +224,8 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
     memcpy(pin + L.labels[s], in->grid_obs_labels[s], N * T * sizeof(int32_t));
     memcpy(pin + L.obs_reg[s], in->grid_obs_regress[s], N * T * S.K * 2 * sizeof(float));
   }
+  MV_REQUIRE(!e->lens_set, "mv_submit_greedy: per-row prediction lengths are set "
+             "(mv_set_pred_lengths); the pipelined forward is uniform -- clear them first");
   sl.num_frames = scene ? in->num_scene_frames : 0; sl.pred_len = in->pred_len;
   // copy stream: the whole input block in one transfer (it must not start before the
   // slot's previous fetch has left the same pinned / staging buffers: collect waited d2h)
@@ -355,6 +357,12 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
   const double bytes = beam ? rows * (4.0 + 16.0 + (center_only ? 16.0 : 24.0))
                             : rows * (4.0 * K + 16.0 + (center_only ? 16.0 : 24.0));
   launch(e, "decode_traj", center_only ? 0.0 : 2.0 * rows, bytes, [&] {
+    if (e->ragged_now)      // the last forward ran with per-row lengths: (0, 0) past a row's end
+      hipLaunchKernelGGL(mv::decode_traj_ragged_kernel, dim3(grid), dim3(mv::kMfBlock), 0,
+                         e->stream, beam ? e->bm_out_ids.p : nullptr, S.out_cls.p, S.out_reg.p,
+                         S.centers.p, e->mf_traj.p, (int)rows, B, Tp, K, center_only,
+                         e->lens_dev.p);
+    else
     hipLaunchKernelGGL(mv::decode_traj_kernel, dim3(grid), dim3(mv::kMfBlock), 0, e->stream,
                        beam ? e->bm_out_ids.p : nullptr, S.out_cls.p, S.out_reg.p, S.centers.p,
                        e->mf_traj.p, (int)rows, B, Tp, K, center_only);
@@ -378,6 +386,18 @@ void beam_occupancy(mv_engine* e, float* out) {
   // HBM-bound: every beam's logits row read once, the map written once
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
     const dim3 grid(N * Tp), block(mv::kMfBlock);
+    if (e->ragged_now) {    // the last forward ran with per-row lengths: 0 past a row's end
+      const int32_t* lens = e->lens_dev.p;
+      if (K <= mv::kMfBlock)
+        hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<1>, grid, block, 0, e->stream,
+                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+      else if (K <= 3 * mv::kMfBlock)
+        hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<3>, grid, block, 0, e->stream,
+                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+      else
+        hipLaunchKernelGGL(mv::beam_occupancy_anyk_ragged_kernel, grid, block, 0, e->stream,
+                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+    } else
     if (K <= mv::kMfBlock)
       hipLaunchKernelGGL(mv::beam_occupancy_kernel<1>, grid, block, 0, e->stream,
                          e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);

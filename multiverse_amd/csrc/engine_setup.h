@@ -282,6 +282,7 @@ void alloc_buffers(mv_engine* e) {
   const size_t maxU = N * T;
   const bool scene = !e->no_scene();     // no scene encoder: no scene inputs, no scene stack
   e->obs_scene.alloc(N * T);
+  e->lens_dev.alloc(N);
   if (scene) e->scene_feat.alloc(maxU * c.scene_h * c.scene_w * c.scene_class);
   int hh = c.scene_h, ww = c.scene_w;
   for (int i = 0; i < c.num_scales; ++i) {
@@ -322,6 +323,7 @@ void alloc_buffers(mv_engine* e) {
       e->bm_ids.alloc(Tp * R);
       e->bm_parents.alloc(Tp * R);
       e->bm_lp[0].alloc(R); e->bm_lp[1].alloc(R);
+      e->bm_lp_final.alloc(R);
       e->bm_cand.alloc((size_t)R * K);
       e->bm_src_row.alloc(R);
       e->bm_ref.alloc(R);

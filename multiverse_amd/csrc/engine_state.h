@@ -179,10 +179,31 @@ struct mv_engine {
   int num_frames = 0;
   int pred_len = 0;
   bool inputs_ready = false;
+  // per-row prediction lengths (mv_set_pred_lengths; sticky until cleared): L[n] in [0, pred_len],
+  // a host copy (which launches a step gets) and a device copy (the finalisers and the
+  // multi-future decode).  A forward whose lengths are not all pred_len is RAGGED: step t issues
+  // its launches on the prefix of act_rows[t] = 1 + max{n : L[n] > t} rows (rows_at), for
+  // ragged_steps = max L steps.  With no lengths, or all of them pred_len, rows_at is N and the
+  // forward is the uniform one, launch for launch.
+  std::vector<int32_t> lens_host;
+  DevBuf<int32_t> lens_dev;          // [N]
+  bool lens_set = false;
+  bool ragged_now = false;           // the forward being issued / issued last is ragged
+  std::vector<int> act_rows;         // [pred_len + 1] of that forward
+  int ragged_steps = 0;
+  int rows_at(int t) const {
+    if (!ragged_now) return cfg.batch_size;
+    return t < (int)act_rows.size() ? act_rows[t] : 0;
+  }
+  // rows of every ConvLSTM problem of every grouped gate launch of the last forward
+  // (mv_last_forward_gate_rows); a replayed graph carries the count of its capture
+  int64_t gate_rows = 0;
+  std::map<std::tuple<int, int, int>, int64_t> graph_gate_rows;
   // beam
   DevBuf<float> bm_logits;         // [T, N, B, K] per-step logits
   DevBuf<int32_t> bm_ids, bm_parents;  // [T, N, B]
   DevBuf<float> bm_lp[2];          // [N, B]
+  DevBuf<float> bm_lp_final;       // [N, B] ragged forward: row n's scores after the selection at time L[n]
   DevBuf<float> bm_cand;           // [N, B, K] candidate log-probs of one step
   DevBuf<int32_t> bm_src_row;      // [N*B]
   DevBuf<int32_t> bm_ref;          // [N*B] 1 = some surviving beam continues this state row
@@ -239,6 +260,7 @@ struct mv_engine {
   void drop_graphs() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();
+    graph_gate_rows.clear();
   }
   // pipelined greedy forward (mv_submit_greedy / mv_collect_greedy): feed of batch k+1 and
   // fetch of batch k-1 on a copy stream while batch k computes

@@ -29,19 +29,32 @@ constexpr int kOccBeamChunk = 20;             // beams of one (n, t) held in reg
 //     ties toward the lower index.  (NaN logits are not ranked; the engine produces none.)
 // reg is [N, T, K, 2]; an id outside [0, K) -- none is produced -- is clamped rather than
 // followed outside the buffers.
-__global__ __launch_bounds__(kMfBlock) void decode_traj_kernel(
+// RAGGED (per-row lengths `lens`, mv_set_pred_lengths): a row (n, b, t) with t >= lens[n] is
+// past its sample's end and decodes to (0, 0); the others exactly as without lengths.
+template <bool RAGGED>
+__device__ __forceinline__ void decode_traj_body(
     const int32_t* __restrict__ ids, const float* __restrict__ cls,
     const float* __restrict__ reg, const double* __restrict__ centers,
-    double* __restrict__ out, int rows, int B, int T, int K, int center_only) {
+    double* __restrict__ out, int rows, int B, int T, int K, int center_only,
+    const int32_t* __restrict__ lens) {
   const int lane = threadIdx.x & 63;
   int row, id;
   if (ids) {
     row = blockIdx.x * kMfBlock + threadIdx.x;
     if (row >= rows) return;
-    id = ids[row];
   } else {
     row = blockIdx.x * kMfWaves + (threadIdx.x >> 6);
     if (row >= rows) return;                       // wave-uniform
+  }
+  if constexpr (RAGGED) {
+    if (row % T >= lens[row / (T * B)]) {          // greedy: wave-uniform
+      if (ids || lane == 0) { out[2 * (size_t)row] = 0.0; out[2 * (size_t)row + 1] = 0.0; }
+      return;
+    }
+  }
+  if (ids) {
+    id = ids[row];
+  } else {
     const float* x = cls + (size_t)row * K;
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -70,6 +83,21 @@ __global__ __launch_bounds__(kMfBlock) void decode_traj_kernel(
   }
   out[2 * (size_t)row] = x;
   out[2 * (size_t)row + 1] = y;
+}
+
+__global__ __launch_bounds__(kMfBlock) void decode_traj_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ cls,
+    const float* __restrict__ reg, const double* __restrict__ centers,
+    double* __restrict__ out, int rows, int B, int T, int K, int center_only) {
+  decode_traj_body<false>(ids, cls, reg, centers, out, rows, B, T, K, center_only, nullptr);
+}
+
+__global__ __launch_bounds__(kMfBlock) void decode_traj_ragged_kernel(
+    const int32_t* __restrict__ ids, const float* __restrict__ cls,
+    const float* __restrict__ reg, const double* __restrict__ centers,
+    double* __restrict__ out, int rows, int B, int T, int K, int center_only,
+    const int32_t* __restrict__ lens) {
+  decode_traj_body<true>(ids, cls, reg, centers, out, rows, B, T, K, center_only, lens);
 }
 
 // Block-wide max / sum of `cnt` values per thread in ONE pass over LDS: butterfly within each
@@ -118,12 +146,18 @@ __device__ __forceinline__ void occ_beam_weight_norm(const float* __restrict__ l
 // every logits row is read from HBM once and the row maxima / sums of a whole chunk of beams
 // cost two barriers each.  Reductions in a fixed order, no atomics: the map is bitwise
 // reproducible, and a row's result depends on that row alone.
-template <int CPT>
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
+// RAGGED (per-row lengths): the map of a step past its sample's end (t >= lens[n]) is 0.
+template <int CPT, bool RAGGED>
+__device__ __forceinline__ void beam_occupancy_body(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
+    int B, int T, int K, const int32_t* __restrict__ lens, float* red) {
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
+  if constexpr (RAGGED) {
+    if (t >= lens[n]) {                            // block-uniform, before any barrier
+      for (int k = tid; k < K; k += kMfBlock) out[(size_t)blockIdx.x * K + k] = 0.f;
+      return;
+    }
+  }
   float wm, ws;
   occ_beam_weight_norm(lp + (size_t)n * B, B, &wm, &ws);
   float acc[CPT];
@@ -174,15 +208,37 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
   }
 }
 
+template <int CPT>
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
+    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
+    int B, int T, int K) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
+  beam_occupancy_body<CPT, false>(logits, lp, out, B, T, K, nullptr, red);
+}
+
+template <int CPT>
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_ragged_kernel(
+    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
+    int B, int T, int K, const int32_t* __restrict__ lens) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
+  beam_occupancy_body<CPT, true>(logits, lp, out, B, T, K, lens, red);
+}
+
 // Any K: the same arithmetic in the same order, one beam at a time; a thread's cells are
 // k = tid, tid + 256, ...  The row is read three times (maximum, sum, accumulation), the second
 // and third time from cache; the running map lives in the output row, which only this
 // workgroup -- and each cell only its own thread -- touches.
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
+template <bool RAGGED>
+__device__ __forceinline__ void beam_occupancy_anyk_body(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
+    int B, int T, int K, const int32_t* __restrict__ lens, float* red) {
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
+  if constexpr (RAGGED) {
+    if (t >= lens[n]) {                            // block-uniform, before any barrier
+      for (int k = tid; k < K; k += kMfBlock) out[(size_t)blockIdx.x * K + k] = 0.f;
+      return;
+    }
+  }
   float wm, ws;
   occ_beam_weight_norm(lp + (size_t)n * B, B, &wm, &ws);
   float* o = out + (size_t)blockIdx.x * K;
@@ -200,6 +256,20 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
       o[k] = b == 0 ? p : o[k] + p;
     }
   }
+}
+
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
+    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
+    int B, int T, int K) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
+  beam_occupancy_anyk_body<false>(logits, lp, out, B, T, K, nullptr, red);
+}
+
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_ragged_kernel(
+    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
+    int B, int T, int K, const int32_t* __restrict__ lens) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
+  beam_occupancy_anyk_body<true>(logits, lp, out, B, T, K, lens, red);
 }
 
 }  // namespace mv

@@ -16,11 +16,14 @@ File formats (forking_paths_dataset/code/get_prepared_data_multifuture.py:192-25
 
 The reference runs one sample at a time (batch 1, beam 20, run-time T_pred);
 `run_inference` keeps that order of results and additionally batches samples
-that share T_pred when the engine was created with batch_size > 1.
+that share T_pred when the engine was created with batch_size > 1; with
+`args.ragged_batches` it batches samples of DIFFERENT T_pred (`plan_ragged_batches`:
+one length per row, the engine stops launching the rows that have finished).
 """
 
 from __future__ import annotations
 
+import collections
 import json
 import os
 import pickle
@@ -154,19 +157,56 @@ def get_inputs(args, traj_files, gt_trajs):
   return out
 
 
-def inference_feed(inputs, args, idxs, batch_size=None):
+RaggedPlan = collections.namedtuple(
+    "RaggedPlan", ["batches", "ragged_row_steps", "grouped_row_steps"])
+
+
+def plan_ragged_batches(lengths, N):
+  """Batches of `N` rows over samples of different prediction lengths.  The samples are
+  sorted by length descending (ties by index) and cut into batches of N; the last batch is
+  padded with rows of length 0; a batch's pred_length is its maximum (its first row's).
+  -> RaggedPlan(batches, ragged_row_steps, grouped_row_steps): batches = [(idxs, row_lengths
+  [N], pred_length)] with idxs the real samples of the batch in row order, and the decoder
+  row-steps (rows x steps the decoder launches) of the two schedules: sorted rows are a tight
+  prefix at every step, so the ragged one spends sum(lengths) exactly; grouping by length and
+  padding every group's last batch spends sum over groups of ceil(g / N) * N * T_g."""
+  lengths = [int(l) for l in lengths]
+  assert N >= 1 and all(l >= 1 for l in lengths), "prediction lengths must be >= 1"
+  order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+  batches = []
+  for lo in range(0, len(order), N):
+    idxs = order[lo:lo + N]
+    row_lengths = [lengths[i] for i in idxs] + [0] * (N - len(idxs))
+    batches.append((idxs, row_lengths, row_lengths[0]))
+  groups = collections.Counter(lengths)
+  grouped = sum(-(-g // N) * N * T for T, g in groups.items())
+  return RaggedPlan(batches, sum(lengths), grouped)
+
+
+def inference_feed(inputs, args, idxs, batch_size=None, lengths=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
   PredictionModelInference.get_feed_dict (code/multifuture_inference.py:304-385):
-  the scene table is compacted to the frames the batch uses, in first-use order."""
+  the scene table is compacted to the frames the batch uses, in first-use order.
+  lengths (a batch of `plan_ragged_batches`): one prediction length per row, 0 for the
+  padding rows; the feed then carries them as "pred_lengths" and their maximum as
+  "pred_length", and the padding rows cost nothing."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
   idxs = idxs + [idxs[-1]] * (N - n_real)
   T_in = args.obs_length
-  T_pred = inputs["max_pred_lengths"][idxs[0]]
-  assert all(inputs["max_pred_lengths"][i] == T_pred for i in idxs)
+  if lengths is not None:
+    lengths = [int(l) for l in lengths]
+    assert len(lengths) == N and all(l == 0 for l in lengths[n_real:])
+    assert all(inputs["max_pred_lengths"][i] == l for i, l in zip(idxs[:n_real], lengths))
+    T_pred = max(lengths)
+  else:
+    T_pred = inputs["max_pred_lengths"][idxs[0]]
+    assert all(inputs["max_pred_lengths"][i] == T_pred for i in idxs)
   feed = {"pred_length": int(T_pred), "grid_obs_labels": [], "grid_obs_regress": []}
+  if lengths is not None:
+    feed["pred_lengths"] = np.asarray(lengths, dtype="int32")
   for j, (h, w) in enumerate(args.scene_grids):
     feed["grid_obs_labels"].append(np.stack(
         [inputs["obs_grid_class"][i][j] for i in idxs]).astype("int32"))
@@ -235,6 +275,20 @@ def model_config(args, batch_size=1, max_pred_len=None):
       use_grids=args.use_grids)
 
 
+def _inference_batches(args, inputs, n, N):
+  """[(idxs, row lengths or None)] of one run: grouped by T_pred (every group's last batch
+  padded by `inference_feed`), or -- `args.ragged_batches` -- the plan of
+  `plan_ragged_batches` over all samples."""
+  lens = [inputs["max_pred_lengths"][i] for i in range(n)]
+  if getattr(args, "ragged_batches", False):
+    return [(idxs, lengths) for idxs, lengths, _ in plan_ragged_batches(lens, N).batches]
+  by_len = {}
+  for i in range(n):
+    by_len.setdefault(lens[i], []).append(i)
+  return [(by_len[T][lo:lo + N], None) for T in sorted(by_len)
+          for lo in range(0, len(by_len[T]), N)]
+
+
 def run_inference(args, model, inputs, traj_ids):
   """The per-sample loop of code/multifuture_inference.py:458-523 ->
   (output_data {traj_id: [num_out][T][2]}, beam_prob {traj_id: (logits
@@ -243,29 +297,26 @@ def run_inference(args, model, inputs, traj_ids):
     return run_inference_device(args, model, inputs, traj_ids)
   use_grid_idx = list(args.use_grids).index(True)
   N = model.config.batch_size
-  by_len = {}
-  for i in range(len(traj_ids)):
-    by_len.setdefault(inputs["max_pred_lengths"][i], []).append(i)
   output_data, beam_prob = {}, {}
-  for T_pred in sorted(by_len):
-    group = by_len[T_pred]
-    for lo in range(0, len(group), N):
-      idxs = group[lo:lo + N]
-      feed, n_real = inference_feed(inputs, args, idxs, batch_size=N)
-      cls, reg, beam = model.run_forward(feed)
-      # --use_single_decoder with beam search: the offsets come per beam, [N*B, T, H, W, 2]
-      # (code/pred_models.py:287-296); the reference's script reshapes the B rows of its one
-      # sample as [1, T, -1, 2] (code/multifuture_inference.py:478) -- kept as it is
-      rows_per = reg[use_grid_idx].shape[0] // N
-      for r in range(n_real):
-        i = idxs[r]
-        b = None if beam is None else (beam[0][r], beam[1][r], beam[2][r])
-        reg_r = (reg[use_grid_idx][r] if rows_per == 1
-                 else reg[use_grid_idx][r * rows_per:(r + 1) * rows_per])
-        output_data[traj_ids[i]] = decode_trajectories(
-            args, cls[use_grid_idx][r], reg_r, b, T_pred, use_grid_idx)
-        if b is not None and getattr(args, "save_prob_file", None) is not None:
-          beam_prob[traj_ids[i]] = (b[0][None], b[2][None])
+  for idxs, lengths in _inference_batches(args, inputs, len(traj_ids), N):
+    feed, n_real = inference_feed(inputs, args, idxs, batch_size=N, lengths=lengths)
+    cls, reg, beam = model.run_forward(feed)
+    # --use_single_decoder with beam search: the offsets come per beam, [N*B, T, H, W, 2]
+    # (code/pred_models.py:287-296); the reference's script reshapes the B rows of its one
+    # sample as [1, T, -1, 2] (code/multifuture_inference.py:478) -- kept as it is
+    rows_per = reg[use_grid_idx].shape[0] // N
+    for r in range(n_real):
+      i = idxs[r]
+      # (ragged batch: the row's own length; its outputs past it are padding)
+      T_pred = inputs["max_pred_lengths"][i]
+      b = None if beam is None else (beam[0][r][:, :T_pred], beam[1][r][:, :T_pred],
+                                     beam[2][r])
+      reg_r = (reg[use_grid_idx][r][:T_pred] if rows_per == 1
+               else reg[use_grid_idx][r * rows_per:(r + 1) * rows_per][:, :T_pred])
+      output_data[traj_ids[i]] = decode_trajectories(
+          args, np.asarray(cls[use_grid_idx][r])[:T_pred], reg_r, b, T_pred, use_grid_idx)
+      if b is not None and getattr(args, "save_prob_file", None) is not None:
+        beam_prob[traj_ids[i]] = (b[0][None], b[2][None])
   ordered = {t: output_data[t] for t in traj_ids}
   return ordered, ({t: beam_prob[t] for t in traj_ids if t in beam_prob})
 
@@ -283,28 +334,24 @@ def run_inference_device(args, model, inputs, traj_ids):
   greedy = bool(args.greedy)
   want_occ = getattr(args, "save_occupancy_file", None) is not None and not greedy
   want_prob = getattr(args, "save_prob_file", None) is not None and not greedy
-  by_len = {}
-  for i in range(len(traj_ids)):
-    by_len.setdefault(inputs["max_pred_lengths"][i], []).append(i)
   output_data, beam_prob, occupancy = {}, {}, {}
-  for T_pred in sorted(by_len):
-    group = by_len[T_pred]
-    for lo in range(0, len(group), N):
-      idxs = group[lo:lo + N]
-      feed, n_real = inference_feed(inputs, args, idxs, batch_size=N)
-      dec = model.run_forward_decoded(feed, center_only=bool(args.center_only),
-                                      occupancy=want_occ,
-                                      grid_centers=args.scene_grid_centers,
-                                      logits=want_prob)
-      trajs = dec["trajs"]                                   # [N, B, T, 2]
-      for r in range(n_real):
-        i = idxs[r]
-        rows = [trajs[r, 0]] * args.num_out if greedy else trajs[r, :args.num_out]
-        output_data[traj_ids[i]] = [[row[t] for t in range(T_pred)] for row in rows]
-        if want_occ:
-          occupancy[traj_ids[i]] = dec["occupancy"][r]
-        if want_prob:
-          beam_prob[traj_ids[i]] = (dec["logits"][r][None], dec["logprobs"][r][None])
+  for idxs, lengths in _inference_batches(args, inputs, len(traj_ids), N):
+    feed, n_real = inference_feed(inputs, args, idxs, batch_size=N, lengths=lengths)
+    dec = model.run_forward_decoded(feed, center_only=bool(args.center_only),
+                                    occupancy=want_occ,
+                                    grid_centers=args.scene_grid_centers,
+                                    logits=want_prob)
+    trajs = dec["trajs"]                                   # [N, B, T, 2]
+    for r in range(n_real):
+      i = idxs[r]
+      T_pred = inputs["max_pred_lengths"][i]     # (ragged batch: the row's own length)
+      rows = [trajs[r, 0]] * args.num_out if greedy else trajs[r, :args.num_out]
+      output_data[traj_ids[i]] = [[row[t] for t in range(T_pred)] for row in rows]
+      if want_occ:
+        occupancy[traj_ids[i]] = dec["occupancy"][r][:T_pred]
+      if want_prob:
+        beam_prob[traj_ids[i]] = (dec["logits"][r][:, :T_pred][None],
+                                  dec["logprobs"][r][None])
   ordered = {t: output_data[t] for t in traj_ids}
   ret = (ordered, {t: beam_prob[t] for t in traj_ids if t in beam_prob})
   if getattr(args, "save_occupancy_file", None) is not None:
