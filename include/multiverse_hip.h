@@ -290,6 +290,31 @@ int  mv_set_pred_lengths(mv_handle h, const int32_t* lengths /* [N]; NULL clears
  * forward (encoders and decoders): what the forward really launched, without timing anything */
 int  mv_last_forward_gate_rows(mv_handle h, int64_t* rows);
 
+/* ---- sampled multi-future decode (not in the reference; the draw is defined here) --------------
+ * S = beam_size independent samples per row instead of beam search.  temperature > 0.
+ * Sticky until mv_set_sampling(h, 0, ..).  Applies to mv_forward_beam, mv_run_beam_resident,
+ * the beam downloads, mv_decode_trajectories, mv_beam_occupancy, mv_set_pred_lengths.
+ *
+ * Decode step t (0-based) of future s of batch row n, all in float32, K = cells of the grid:
+ *   lp[k]    = log_softmax(hidden2grid logits of the step)[k]
+ *   u[k]     = (top 24 bits of hash32(s*K + k, seed_n, t) + 0.5) * 2^-24, held below 1.0 (the
+ *              last code rounds to 1.0 in float32: it becomes the largest float32 under 1);
+ *              hash32(i, seed, stream) is the generator of the training dropout (below), and
+ *              seed_n = seed + n * 0x632BE5AB (mod 2^32): batch row n draws as row 0 of a forward
+ *              seeded seed_n does, whatever the batch around it, and future s draws the same
+ *              noise for every beam_size > s
+ *   id       = argmax_k lp[k] / temperature - log(-log(u[k])), lowest index among equal scores
+ *   next input = grid_emb(one_hot(id));  logprobs[n, s] += lp[id]  (untempered)
+ * Step 0 runs on the shared encoder state; there is no fix_num_timestep and no parent: future
+ * (n, s) continues itself.  Outputs keep the beam's shapes: logits [N,S,T,K], ids [N,S,T],
+ * logprobs [N,S] (futures in order s, unsorted), best_beam = future 0, grid_reg.
+ * mv_beam_occupancy weights the futures uniformly (1/S).  Per-row lengths hold as for the
+ * beam (the noise does not depend on them).  Graph mode: seed and temperature live in a device
+ * buffer the step kernel reads, so a replayed graph follows this call.
+ * Errors: a greedy handle, a use_single_decoder handle, temperature <= 0, a grid of more than
+ * 1024 cells (at the forward); mv_train_* while sampling is on. */
+int  mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed);
+
 /* -- training: one call == sess.run([loss, train_op, wd_loss, pred_grid_loss]) */
 int  mv_train_init(mv_handle h, const mv_train_config* tc);
 /* forward (is_train, --train_w_onehot wiring) + loss + backward + clip +

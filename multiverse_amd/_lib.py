@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_grid_centers", "mv_upload_inputs_compact", "mv_upload_targets_compact",
     "mv_pipeline_create", "mv_submit_greedy", "mv_collect_greedy",
     "mv_decode_trajectories", "mv_beam_occupancy", "mv_download_beam_ids",
-    "mv_set_pred_lengths", "mv_last_forward_gate_rows",
+    "mv_set_pred_lengths", "mv_last_forward_gate_rows", "mv_set_sampling",
 ]
 
 
@@ -209,6 +209,7 @@ def load():
   lib.mv_download_beam_ids.argtypes = [h, _ip, _fp]
   lib.mv_set_pred_lengths.argtypes = [h, _ip]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
+  lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_profiling.argtypes = [h, C.c_int32]
   lib.mv_set_graph_mode.argtypes = [h, C.c_int32]
   lib.mv_set_compute_mode.argtypes = [h, C.c_int32]
@@ -513,6 +514,16 @@ class Engine(object):
       raise MvError("pred_lengths: %d values for batch_size %d" % (lens.size, self.cfg.batch_size))
     check(self.lib.mv_set_pred_lengths(self.handle, iptr(lens)), self.handle)
     self._lengths_set = True
+
+  def set_sampling(self, temperature=1.0, seed=0):
+    """The beam_size futures of every row are SAMPLED (Gumbel-max over the step's
+    log-softmax / temperature; include/multiverse_hip.h mv_set_sampling) by forward_beam and
+    the calls around it, until clear_sampling()."""
+    check(self.lib.mv_set_sampling(self.handle, 1, float(temperature),
+                                   int(seed) & 0xFFFFFFFF), self.handle)
+
+  def clear_sampling(self):
+    check(self.lib.mv_set_sampling(self.handle, 0, 1.0, 0), self.handle)
 
   def last_forward_gate_rows(self):
     """Rows of every ConvLSTM problem of every gate launch of the last forward, summed."""

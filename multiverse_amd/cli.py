@@ -215,6 +215,9 @@ _MF_FLAGS = [
     # not in the reference: samples of DIFFERENT T_pred are decoded together, one length per
     # row (multifuture.plan_ragged_batches); the engine stops launching finished rows
     ("--ragged_batches", B, None),
+    # not in the reference: num_out futures SAMPLED from the model's step distribution
+    # (Gumbel-max, csrc/kernels_misc.h sample_step_kernel) instead of the beam search
+    ("--sample", B, None), ("--sample_temperature", float, 1.0), ("--sample_seed", int, 0),
 ]
 
 
@@ -240,6 +243,8 @@ def multifuture_inference_main(argv=None):
     args.device_decode = True
   mf.add_grid(args)
   assert sum(args.use_grids) == 1
+  if args.sample and args.greedy:
+    raise SystemExit("--sample draws num_out futures; it does not combine with --greedy")
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)

@@ -320,6 +320,25 @@ int mv_set_pred_lengths(mv_handle h, const int32_t* lengths) {
   });
 }
 
+int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    if (!enabled) { h->sampling = false; return; }
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_sampling: engine was created with beam_size 1 (a "
+               "sampled decode draws beam_size futures per row: create a beam handle)");
+    MV_REQUIRE(!h->cfg.use_single_decoder, "mv_set_sampling: use_single_decoder handles are not "
+               "supported (the sampled decode keeps the un-beamed regression decoder)");
+    MV_REQUIRE(temperature > 0.f, "mv_set_sampling: temperature %g must be > 0",
+               (double)temperature);
+    // behind whatever forward still reads the previous seed / temperature on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const uint32_t params[2] = {seed, __builtin_bit_cast(uint32_t, temperature)};
+    h->samp_params.alloc(2);
+    HIP_CHECK(hipMemcpy(h->samp_params.p, params, sizeof(params), hipMemcpyHostToDevice));
+    h->sampling = true;
+  });
+}
+
 int mv_last_forward_gate_rows(mv_handle h, int64_t* rows) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -386,6 +405,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(tc, "mv_train_init: NULL config");
+    MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
+               "clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(tc->optimizer >= 0 && tc->optimizer <= 3, "Optimizer not implemented: %d "
@@ -430,6 +451,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
                               mv_losses* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
+               "clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
@@ -464,6 +487,8 @@ int mv_upload_targets_compact(mv_handle h, const mv_targets_compact* tg) {
 int mv_train_apply(mv_handle h, float grad_scale) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
+               "clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     train_apply(h, grad_scale);
@@ -473,6 +498,8 @@ int mv_train_apply(mv_handle h, float grad_scale) {
 int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_losses* out) {
   if (!h) return 1;
   return guarded(h, [&] {
+    MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
+               "clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),

@@ -1019,13 +1019,22 @@ __global__ void ragged_capture_lp_kernel(const float* __restrict__ lp,
 
 // out[n, t, :] = 0 for t >= L[n]: what raw_rnn emits for a finished row, through the bias-free
 // hidden2grid.  out is [N, T, row_elems]; one thread per element.
+// (N rows that share a length in groups of `per_len`: the S futures of a sampled row)
 __global__ void ragged_zero_tail_kernel(float* __restrict__ out, const int32_t* __restrict__ lens,
-                                        int N, int T, int row_elems) {
+                                        int N, int T, int row_elems, int per_len = 1) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (size_t)N * T * row_elems) return;
   const size_t r = idx / row_elems;
   const int t = r % T, n = r / T;
-  if (t >= lens[n]) out[idx] = 0.f;
+  if (t >= lens[n / per_len]) out[idx] = 0.f;
+}
+
+// ids[r, t] = -1 for t >= L[r / S] (sampled forward: the ids are written in place, step by step)
+__global__ void ragged_ids_tail_kernel(int32_t* __restrict__ ids, const int32_t* __restrict__ lens,
+                                       int R, int S, int T) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= R * T) return;
+  if (idx % T >= lens[idx / T / S]) ids[idx] = -1;
 }
 
 // Beam-search class decoder (grid_decoder_beam_search,
@@ -1217,6 +1226,94 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
                              hipMemcpyDeviceToDevice, e->issue));
 }
 
+// Sampled multi-future decoder (mv_set_sampling; defined here): the class decoder
+// of run_decoders_beam with the selection replaced by one Gumbel-max draw per row.  Row (n, s)
+// always continues itself, so there is no parent indirection, no back-trace and no gather: the
+// decode tail writes step t's logits into the [R, T, K] output, sample_step_kernel draws the id
+// into the [R, T] output, and the next cell step reads it from there.  The first cell step runs
+// once per sample on the shared encoder state, like the beam's; the S rows of sample n pick that
+// state row up through bm_src_row (= n) at the second cell step, the only indexed read.
+void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
+  const mv_config& c = e->cfg;
+  ScaleState& S = e->sc[s];
+  const int N = c.batch_size, T = c.obs_len, B = c.beam_size, K = S.K;
+  const int R = N * B;
+  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampled decode: grid of %d cells (one wave holds a row "
+             "of at most %d)", K, 64 * mv::kBeamRankJ);
+  MV_REQUIRE(!c.use_single_decoder, "sampled decode: use_single_decoder is not supported");
+  MV_REQUIRE(tail_v2(), "sampled decode needs the v2 decoder tail");
+  HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  const bool ragged = e->ragged_now;
+  const int Tsteps = ragged ? e->ragged_steps : Tp;
+  const bool sparse = sparse_x_on(e, S);
+  const int64_t orow = (int64_t)Tp * K;             // one row of the [R, T, K] logits
+  for (int time = 0; time <= Tsteps && Tsteps > 0; ++time) {
+    const int n_now = e->rows_at(std::max(time - 1, 0)), n_next = e->rows_at(time);
+    const bool one_per_sample = time <= 1;          // the state going into this iteration
+    const int rows_now = one_per_sample ? n_now : n_now * B;
+    if (time > 0) {
+      const int t = time - 1;
+      const int cc = cur.cls[s];
+      const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
+      const int32_t* src = time == 2 ? e->bm_src_row.p : nullptr;
+      std::vector<ConvLstmArgs> probs;
+      probs.push_back(conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p, src, src,
+                                   S.cls_h[cc ^ 1].p, S.cls_c[cc ^ 1].p, rows_now, S.H, S.W,
+                                   false, 0, /*want_h16=*/!c.use_gnn));
+      if (sparse) {
+        if (time == 1) set_sparse_x(e, S, probs.back(), true, S.labels.p + (T - 1), T, 1);
+        else set_sparse_x(e, S, probs.back(), true, e->bm_out_ids.p + (t - 1), Tp, 1);
+      }
+      cur.cls[s] ^= 1;
+      probs.push_back(reg_decoder_problem(e, s, cur, t, Tp, false));
+      run_conv_group(e, probs);
+      float* logits = e->bm_out_logits.p + (size_t)t * K;
+      TailPlan pl{};
+      pl.s = s;
+      pl.cls_h = S.cls_h[cur.cls[s]].p; pl.cls_rows = rows_now;
+      // one row per sample: the logits land in future 0's row of each sample
+      pl.cls_out = logits; pl.cls_stride = one_per_sample ? orow * B : orow;
+      pl.cls_next = false;                          // sample_step_kernel draws
+      pl.reg_h = S.reg_h[cur.reg[s]].p;
+      pl.reg_out = S.out_reg.p + (size_t)t * K * 2;
+      pl.reg_stride = (int64_t)Tp * K * 2; pl.reg_next = time < Tp;
+      pl.reg_rows = n_now;
+      run_tail(e, {pl});
+      int32_t* ids = e->bm_out_ids.p + t;
+      const int rows = n_now * B;
+      launch(e, "sample_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
+        const dim3 grid(cdiv((size_t)rows, 4)), block(256);
+        const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
+        int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
+#define MV_SAMPLE_STEP(J)                                                                   \
+        hipLaunchKernelGGL(mv::sample_step_kernel<J>, grid, block, 0, e->issue, logits, orow, \
+                           rows, B, K, t, one_per_sample ? 1 : 0, e->samp_params.p, lens,     \
+                           e->bm_lp[0].p, ids, Tp, srow)
+        if (K <= 64 * 3) MV_SAMPLE_STEP(3);
+        else if (K <= 64 * 9) MV_SAMPLE_STEP(9);
+        else MV_SAMPLE_STEP(mv::kBeamRankJ);
+#undef MV_SAMPLE_STEP
+      });
+      if (time == Tsteps) break;
+      if (!sparse) run_emb_onehot(e, S, ids, Tp, S.xbuf_cls.p, n_next * B);
+    } else if (!sparse) {
+      // one_hot(last observed cell), one row per sample
+      run_emb_onehot(e, S, S.labels.p + (T - 1), T, S.xbuf_cls.p, n_next, 1);
+    }
+    if (c.use_gnn)     // on the state rows: one per sample until the second cell step has run
+      run_gnn(e, S, S.cls_h[cur.cls[s]].p, nullptr, S.cls_hg.p,
+              time <= 1 ? n_next : n_next * B, time <= 1 ? 1 : B);
+  }
+  if (ragged) {
+    // logits 0 and ids -1 from step L[n] on (a finished row inside a step's prefix kept decoding)
+    const size_t total = (size_t)R * Tp * K;
+    hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(cdiv(total, 256)), dim3(256), 0, e->issue,
+                       e->bm_out_logits.p, e->lens_dev.p, R, Tp, K, B);
+    hipLaunchKernelGGL(ragged_ids_tail_kernel, dim3(cdiv((size_t)R * Tp, 256)), dim3(256), 0,
+                       e->issue, e->bm_out_ids.p, e->lens_dev.p, R, B, Tp);
+  }
+}
+
 // The four chains of a greedy forward (class / regression x two scales) exchange nothing between
 // the scene stage and the end of the decode, and want different things from the chip: a gate
 // launch the matrix pipe, the attention / transform / tail kernels HBM and L2.  So the greedy
@@ -1244,7 +1341,8 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
     if (beam) {
       int s = 0;
       for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-      run_decoders_beam(e, s, cur, Tp);         // (its finalisers alone)
+      if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
+      else run_decoders_beam(e, s, cur, Tp);         // (its finalisers alone)
     }
     return;
   }
@@ -1261,7 +1359,8 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
   if (beam) {
     int s = 0;
     for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-    run_decoders_beam(e, s, cur, Tp);
+    if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
+    else run_decoders_beam(e, s, cur, Tp);
   } else {
     run_decoders_greedy(e, cur, Tp, false);
   }
@@ -1317,6 +1416,7 @@ void run_forward(mv_engine* e, bool beam) {
   ensure_params(e);
   if (beam)
     MV_REQUIRE(e->cfg.beam_size > 1, "engine was created with beam_size 1");
+  const bool sampled = beam && e->sampling;
   plan_ragged(e);
   // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
   // is issued eagerly
@@ -1325,9 +1425,11 @@ void run_forward(mv_engine* e, bool beam) {
     enqueue_forward(e, beam);
     if (e->ragged_now) finish_ragged(e, beam);
     e->last_forward = beam ? 2 : 1;
+    e->last_sampled = sampled;
     return;
   }
-  const auto key = std::make_tuple(beam ? 1 : 0, e->pred_len, e->num_frames);
+  // (a sampled forward is a graph of its own; its seed and temperature are read on the device)
+  const auto key = std::make_tuple(sampled ? 2 : beam ? 1 : 0, e->pred_len, e->num_frames);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
     e->gate_rows = 0;
@@ -1351,6 +1453,7 @@ void run_forward(mv_engine* e, bool beam) {
   e->gate_rows = e->graph_gate_rows[key];
   HIP_CHECK(hipGraphLaunch(it->second, e->stream));
   e->last_forward = beam ? 2 : 1;
+  e->last_sampled = sampled;
 }
 
 }  // namespace

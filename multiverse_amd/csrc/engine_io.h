@@ -384,29 +384,36 @@ void beam_occupancy(mv_engine* e, float* out) {
   const size_t cells = (size_t)N * Tp * K;
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
   // HBM-bound: every beam's logits row read once, the map written once
+  // a sampled forward's futures are draws, not scored hypotheses: uniform weights, which the
+  // kernels form as softmax_b of all-zero scores (exp(0) / B, exactly 1 / B)
+  const float* lp = e->bm_lp[0].p;
+  if (e->last_sampled) {
+    HIP_CHECK(hipMemsetAsync(e->bm_lp[1].p, 0, (size_t)N * B * sizeof(float), e->stream));
+    lp = e->bm_lp[1].p;
+  }
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
     const dim3 grid(N * Tp), block(mv::kMfBlock);
     if (e->ragged_now) {    // the last forward ran with per-row lengths: 0 past a row's end
       const int32_t* lens = e->lens_dev.p;
       if (K <= mv::kMfBlock)
         hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<1>, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
       else if (K <= 3 * mv::kMfBlock)
         hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<3>, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
       else
         hipLaunchKernelGGL(mv::beam_occupancy_anyk_ragged_kernel, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K, lens);
+                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
     } else
     if (K <= mv::kMfBlock)
       hipLaunchKernelGGL(mv::beam_occupancy_kernel<1>, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
     else if (K <= 3 * mv::kMfBlock)
       hipLaunchKernelGGL(mv::beam_occupancy_kernel<3>, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
     else
       hipLaunchKernelGGL(mv::beam_occupancy_anyk_kernel, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, e->bm_lp[0].p, e->mf_occ.p, B, Tp, K);
+                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
   });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, e->mf_occ.p, cells * sizeof(float), hipMemcpyDeviceToHost,

@@ -214,6 +214,12 @@ struct mv_engine {
   DevBuf<float> bm_reg_steps;      // [T, N*B, K, 2]   per step, in the step's own row order
   DevBuf<float> bm_out_reg;        // [N*B, T, K, 2]   traced back
   DevBuf<int32_t> bm_out_ids;      // [N, B, T]
+  // sampled multi-future decode (mv_set_sampling): the beam handle draws beam_size futures per
+  // row instead of searching.  {seed, temperature bits} live on the device, where the step
+  // kernel reads them: a captured forward follows a later mv_set_sampling.
+  bool sampling = false;
+  DevBuf<uint32_t> samp_params;    // [2]
+  bool last_sampled = false;       // the last beam-handle forward was a sampled one
   // multi-future decode of the last forward (multifuture_decode.h): 0 none yet, 1 greedy, 2 beam
   int last_forward = 0;
   DevBuf<double> mf_traj;          // [N, B, T, 2] pixel trajectories

@@ -1402,6 +1402,99 @@ void beam_select_kernel(const float* __restrict__ cand, int B, int K, int time,
   }
 }
 
+// ------------------------------------------------------------ sampled step
+// Counter-based generator shared by the input dropout of training (train_kernels.h
+// dropout_keep) and the sampled decode: 32 mixed bits of (element, seed, stream).
+__device__ __forceinline__ uint32_t hash32(uint32_t i, uint32_t seed, uint32_t stream) {
+  uint32_t x = i * 0x9E3779B1u + seed * 0x85EBCA77u + stream * 0xC2B2AE3Du;
+  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
+  return x;
+}
+
+// Batch row n of a sampled forward draws with seed + n * kSampleRowSeed (mod 2^32): row n is row
+// 0 of a forward seeded that way, whatever the batch around it.
+constexpr uint32_t kSampleRowSeed = 0x632BE5ABu;
+
+// u in (0, 1): (top 24 bits + 0.5) * 2^-24 in fp32.  Codes from 2^23 on need 25 significand
+// bits and round to even; the last one would round to 1.0 and is held at the largest fp32 below.
+__device__ __forceinline__ float sample_uniform(uint32_t i, uint32_t seed, uint32_t stream) {
+  const float u = ((float)(hash32(i, seed, stream) >> 8) + 0.5f) * 0x1p-24f;
+  return fminf(u, 0x1.fffffep-1f);
+}
+
+// The tail of decode step t of a SAMPLED multi-future forward (mv_set_sampling), one WAVE per
+// row r = n * S + s, the row held in registers as in beam_rank_kernel (lane l owns
+// k = l + 64 j):
+//   lp = log_softmax(logits[r]);  g[k] = -log(-log(u(s * K + k, seed_n, t)))
+//   id = argmax_k lp[k] / temperature + g[k]   (lowest index among equal scores)
+//   ids[r, t] = id;  lp_acc[r] += lp[id] unless the row is past its length
+// logits is the forward's [R, T, K] output at step t (row_stride = T * K), written by the
+// decode tail.  `shared` (step 0): the tail ran once per sample and left the logits in row
+// n * S; rows s > 0 read them there and copy them to their own row.  src_row (step 0): the
+// state row the S rows of sample n continue from.  params: {seed, temperature bits}, read
+// on the device so that a replayed graph follows mv_set_sampling.
+template <int J>
+__global__ __launch_bounds__(256)
+void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
+                        int t, int shared, const uint32_t* __restrict__ params,
+                        const int32_t* __restrict__ lens, float* __restrict__ lp_acc,
+                        int32_t* __restrict__ ids, int ids_stride,
+                        int32_t* __restrict__ src_row) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int n = r / S, s = r - n * S;
+  const float* row = logits + (size_t)(shared ? n * S : r) * row_stride;
+  float v[J];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    v[j] = k < K ? row[k] : -INFINITY;
+    mx = fmaxf(mx, v[j]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+  sum = wave_sum(sum);
+  const float lse = logf(sum);
+  const uint32_t seed = params[0] + (uint32_t)n * kSampleRowSeed;
+  const float temperature = __builtin_bit_cast(float, params[1]);
+  float best = -INFINITY, blp = 0.f;
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K) {
+      const float lp = (v[j] - mx) - lse;
+      const float u = sample_uniform((uint32_t)s * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
+      const float sc = lp / temperature + (-logf(-logf(u)));
+      if (sc > best) { best = sc; bi = k; blp = lp; }   // strict: the lane's lowest index stays
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(best, off, 64);
+    const int oi = __shfl_xor(bi, off, 64);
+    const float ol = __shfl_xor(blp, off, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; blp = ol; }
+  }
+  if (shared && s != 0) {
+    float* out = logits + (size_t)r * row_stride;
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (lane + 64 * j < K) out[lane + 64 * j] = v[j];
+  }
+  if (lane == 0) {
+    ids[(size_t)r * ids_stride] = min(bi, K - 1);   // (no score ranked: NaN logits; none is made)
+    if (!lens || t < lens[n]) lp_acc[r] += blp;
+    if (src_row) src_row[r] = n;
+  }
+}
+
 // ------------------------------------------------------------ batch assembly
 // Dense regression maps from one (x, y) per row-step: out[r, cell, :] =
 // (float)(xy[r, :] - centre[cell, :]) in double, the rounding of

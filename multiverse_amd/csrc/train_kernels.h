@@ -865,9 +865,7 @@ __global__ void masked_mean_kernel(const float* __restrict__ sum, const int32_t*
 // the generator oracle/multiverse_oracle.py dropout_keep_mask restates.
 __device__ __forceinline__ bool dropout_keep(uint32_t i, uint32_t seed, uint32_t stream,
                                              uint32_t thr) {
-  uint32_t x = i * 0x9E3779B1u + seed * 0x85EBCA77u + stream * 0xC2B2AE3Du;
-  x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;
-  return (x >> 8) < thr;
+  return (hash32(i, seed, stream) >> 8) < thr;   // (kernels_misc.h)
 }
 __global__ void dropout_kernel(float* __restrict__ x, size_t n, uint32_t seed, uint32_t stream,
                                uint32_t thr, float inv_keep) {

@@ -260,6 +260,10 @@ def model_config(args, batch_size=1, max_pred_len=None):
       beam_size=args.num_out, use_beam_search=not args.greedy,
       diverse_beam=args.diverse_beam, diverse_gamma=args.diverse_gamma,
       fix_num_timestep=args.fix_num_timestep,
+      # --sample (not in the reference): num_out sampled futures instead of the beam search
+      sample_futures=bool(getattr(args, "sample", False)),
+      sample_temperature=float(getattr(args, "sample_temperature", 1.0)),
+      sample_seed=int(getattr(args, "sample_seed", 0)),
       use_teacher_forcing=False, is_train=False,
       scene_h=args.scene_h, scene_w=args.scene_w, scene_class=args.scene_class,
       use_soft_grid_class=args.use_soft_grid_class,

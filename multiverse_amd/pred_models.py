@@ -228,6 +228,11 @@ class Model(object):
             self.compute_mode)
       self.compute_mode = "f32"
     self.engine.set_compute_mode(self.compute_mode)
+    # config.sample_futures: the beam_size futures of a row are sampled from the model's step
+    # distribution (config.sample_temperature, config.sample_seed) instead of searched
+    if getattr(config, "sample_futures", False):
+      self.engine.set_sampling(getattr(config, "sample_temperature", 1.0),
+                               getattr(config, "sample_seed", 0))
     self.global_step = 0
     # names of the fetches, kept for callers that introspect them
     self.grid_pred_decoded = ["grid_pred_decoded_%d" % i
@@ -247,6 +252,13 @@ class Model(object):
     if getattr(config, "use_beam_search", False):
       assert not getattr(config, "is_train", False)
       assert sum(config.use_grids) == 1, "only one scale test at a time"
+    if getattr(config, "sample_futures", False):
+      if not getattr(config, "use_beam_search", False):
+        raise _lib.MvError("sample_futures draws beam_size futures per row: it needs a "
+                           "multi-future (use_beam_search) model, not a greedy one")
+      if not float(getattr(config, "sample_temperature", 1.0)) > 0.0:
+        raise _lib.MvError("sample_temperature %r must be > 0"
+                           % (getattr(config, "sample_temperature", 1.0),))
 
   # -- weights (tf.train.Saver role) --------------------------------------
   def param_specs(self):
