@@ -315,6 +315,54 @@ int  mv_last_forward_gate_rows(mv_handle h, int64_t* rows);
  * 1024 cells (at the forward); mv_train_* while sampling is on. */
 int  mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed);
 
+/* ---- scoring given futures (not in the reference) ------------------------------------------
+ * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
+ * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
+ * of future (n, f), float32, K = cells of the grid, id = ids[n, f, t], for t < lengths[n, f]:
+ *   lp                     = log_softmax(hidden2grid logits of the step), the arithmetic of the
+ *                            sampled decode: scoring the ids a sampled forward drew returns its
+ *                            logprobs bit for bit
+ *   step_logprobs[n, f, t] = lp[id];  logprobs[n, f] += lp[id];  next input = grid_emb(one_hot(id))
+ *   ranks[n, f, t]         = number of cells k whose logit is greater than logit[id], or equal
+ *                            with k < id (0: the given cell is the model's argmax)
+ * and for t >= lengths[n, f]: step_logprobs 0, ranks -1.  Lengths are per future, in
+ * [0, pred_len]; 0 is a padding future, a sample whose futures are all 0 a padding sample.  The
+ * forward decodes sample n for max_f lengths[n, f] steps and does not launch finished samples
+ * (order the batch by that maximum, descending, as for mv_set_pred_lengths); it is ragged, and
+ * issued eagerly in graph mode, unless every length is pred_len.  Ids at t >= lengths[n, f] are
+ * not read.  In graph mode the uniform forward is a graph of its own whose ids live in an
+ * engine-owned buffer: a replay scores the latest upload.
+ * Afterwards mv_download_beam_outputs / mv_download_beam_ids return logits [N,F,T,K] (0 from
+ * step lengths[n, f] on), the given ids (-1 from there on), logprobs and grid_reg (0 from the
+ * sample's maximum on), mv_decode_trajectories returns centre + the model's offset along the
+ * given cells ((0, 0) past a future's length), and mv_last_forward_gate_rows counts the launch.
+ * Scoring is not sticky and neither reads nor changes mv_set_sampling: the next beam forward
+ * and mv_train_* are unaffected.
+ * Errors: a greedy handle, a use_single_decoder handle, a grid of more than 1024 cells (at the
+ * forward), an id outside [0, K) at t < length (checked on the host at upload; the message
+ * names n, f, t), a length outside [0, pred_len], mv_set_pred_lengths set at the same time,
+ * mv_run_score_resident without uploaded futures or after an mv_upload_inputs with another
+ * pred_len, mv_beam_occupancy after a scoring forward (given futures are no predictive
+ * mixture), mv_download_scores after another kind of forward. */
+typedef struct {
+  const int32_t* ids;      /* [N, F, pred_len], F = beam_size */
+  const int32_t* lengths;  /* [N, F] in [0, pred_len]; NULL = all pred_len */
+} mv_score_futures_in;
+typedef struct {           /* each may be NULL */
+  float* step_logprobs;    /* [N, F, pred_len] */
+  float* logprobs;         /* [N, F] = sum over t < length, in step order */
+  int32_t* ranks;          /* [N, F, pred_len] */
+} mv_score_outputs;
+
+/* upload + run + download */
+int  mv_score_futures(mv_handle h, const mv_inputs* in, const mv_score_futures_in* fut,
+                      mv_score_outputs* out);
+/* after mv_upload_inputs (which sets pred_len) */
+int  mv_upload_score_futures(mv_handle h, const mv_score_futures_in* fut);
+int  mv_run_score_resident(mv_handle h);
+int  mv_download_scores(mv_handle h, mv_score_outputs* out);
+int  mv_time_score_resident(mv_handle h, int32_t iters, float* ms_out);
+
 /* -- training: one call == sess.run([loss, train_op, wd_loss, pred_grid_loss]) */
 int  mv_train_init(mv_handle h, const mv_train_config* tc);
 /* forward (is_train, --train_w_onehot wiring) + loss + backward + clip +

@@ -44,6 +44,8 @@ EXPORTED_SYMBOLS = [
     "mv_pipeline_create", "mv_submit_greedy", "mv_collect_greedy",
     "mv_decode_trajectories", "mv_beam_occupancy", "mv_download_beam_ids",
     "mv_set_pred_lengths", "mv_last_forward_gate_rows", "mv_set_sampling",
+    "mv_score_futures", "mv_upload_score_futures", "mv_run_score_resident",
+    "mv_download_scores", "mv_time_score_resident",
 ]
 
 
@@ -131,6 +133,14 @@ class mv_beam_outputs(C.Structure):
   ]
 
 
+class mv_score_futures_in(C.Structure):
+  _fields_ = [("ids", _ip), ("lengths", _ip)]
+
+
+class mv_score_outputs(C.Structure):
+  _fields_ = [("step_logprobs", _fp), ("logprobs", _fp), ("ranks", _ip)]
+
+
 class mv_train_config(C.Structure):
   _fields_ = [
       ("optimizer", C.c_int32),
@@ -210,6 +220,12 @@ def load():
   lib.mv_set_pred_lengths.argtypes = [h, _ip]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
+  lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
+                                   C.POINTER(mv_score_outputs)]
+  lib.mv_upload_score_futures.argtypes = [h, C.POINTER(mv_score_futures_in)]
+  lib.mv_run_score_resident.argtypes = [h]
+  lib.mv_download_scores.argtypes = [h, C.POINTER(mv_score_outputs)]
+  lib.mv_time_score_resident.argtypes = [h, C.c_int32, _fp]
   lib.mv_set_profiling.argtypes = [h, C.c_int32]
   lib.mv_set_graph_mode.argtypes = [h, C.c_int32]
   lib.mv_set_compute_mode.argtypes = [h, C.c_int32]
@@ -524,6 +540,69 @@ class Engine(object):
 
   def clear_sampling(self):
     check(self.lib.mv_set_sampling(self.handle, 0, 1.0, 0), self.handle)
+
+  # ---- scoring given futures (include/multiverse_hip.h mv_score_futures)
+  def _score_futures_in(self, ids, lengths):
+    N, F, Tp = self.cfg.batch_size, self.cfg.beam_size, self._pred_len
+    ids = i32(ids)
+    if ids.size != N * F * Tp:
+      raise MvError("score futures: ids of shape %s, expected [N=%d, F=%d, pred_len=%d]"
+                    % (ids.shape, N, F, Tp))
+    fut = mv_score_futures_in()
+    fut.ids = iptr(ids)
+    keep = [ids]
+    if lengths is not None:
+      lens = i32(lengths).reshape(-1)
+      if lens.size != N * F:
+        raise MvError("score futures: %d lengths, expected [N=%d, F=%d]" % (lens.size, N, F))
+      fut.lengths = iptr(lens)
+      keep.append(lens)
+    return fut, keep
+
+  def _alloc_scores(self):
+    N, F, Tp = self.cfg.batch_size, self.cfg.beam_size, self._pred_len
+    arrs = {"step_logprobs": np.empty((N, F, Tp), dtype=np.float32),
+            "logprobs": np.empty((N, F), dtype=np.float32),
+            "ranks": np.empty((N, F, Tp), dtype=np.int32)}
+    out = mv_score_outputs()
+    out.step_logprobs = fptr(arrs["step_logprobs"])
+    out.logprobs = fptr(arrs["logprobs"])
+    out.ranks = iptr(arrs["ranks"])
+    return out, arrs
+
+  def score_futures(self, feed, ids, lengths=None):
+    """Teacher-forced log-likelihood of F = beam_size GIVEN futures per row: ids int
+    [N, F, pred_len] grid cells, lengths int [N, F] in [0, pred_len] (None: all pred_len) ->
+    {"step_logprobs" float32 [N, F, T], "logprobs" float32 [N, F], "ranks" int32 [N, F, T]}.
+    download_beam / beam_ids / decode_trajectories afterwards see the forward's logits, the
+    given ids and the model's offsets along them."""
+    inp = self._inputs(feed)
+    fut, keep = self._score_futures_in(ids, lengths)
+    out, arrs = self._alloc_scores()
+    check(self.lib.mv_score_futures(self.handle, C.byref(inp), C.byref(fut), C.byref(out)),
+          self.handle)
+    del keep
+    return arrs
+
+  def upload_score_futures(self, ids, lengths=None):
+    """After upload(feed): the futures the next run_score_resident scores."""
+    fut, keep = self._score_futures_in(ids, lengths)
+    check(self.lib.mv_upload_score_futures(self.handle, C.byref(fut)), self.handle)
+    del keep      # copied synchronously
+
+  def run_score_resident(self):
+    check(self.lib.mv_run_score_resident(self.handle), self.handle)
+
+  def scores(self):
+    """The outputs of the last scoring forward (see score_futures)."""
+    out, arrs = self._alloc_scores()
+    check(self.lib.mv_download_scores(self.handle, C.byref(out)), self.handle)
+    return arrs
+
+  def time_score_resident(self, iters):
+    ms = C.c_float()
+    check(self.lib.mv_time_score_resident(self.handle, int(iters), C.byref(ms)), self.handle)
+    return float(ms.value)
 
   def last_forward_gate_rows(self):
     """Rows of every ConvLSTM problem of every gate launch of the last forward, summed."""

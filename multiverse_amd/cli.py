@@ -218,6 +218,10 @@ _MF_FLAGS = [
     # not in the reference: num_out futures SAMPLED from the model's step distribution
     # (Gumbel-max, csrc/kernels_misc.h sample_step_kernel) instead of the beam search
     ("--sample", B, None), ("--sample_temperature", float, 1.0), ("--sample_seed", int, 0),
+    # not in the reference: instead of decoding, score every ground-truth future of
+    # multifuture_path under the model (teacher-forced log-likelihood per step, csrc/
+    # kernels_misc.h score_step_kernel) into this pickle and print the exact NLL table
+    ("--score_gt", str, None),
 ]
 
 
@@ -245,6 +249,9 @@ def multifuture_inference_main(argv=None):
   assert sum(args.use_grids) == 1
   if args.sample and args.greedy:
     raise SystemExit("--sample draws num_out futures; it does not combine with --greedy")
+  if args.score_gt is not None and args.greedy:
+    raise SystemExit("--score_gt scores num_out futures per row; it does not combine with "
+                     "--greedy")
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)
@@ -253,6 +260,13 @@ def multifuture_inference_main(argv=None):
                         max_pred_len=max(inputs["max_pred_lengths"] + [12]))
   model = pred_models.Model(cfg, cfg.modelname, gpuid=args.gpuid)
   model.load_params(pred_utils.load_weights(args.model_path, scope="person_pred"))
+  if args.score_gt is not None:
+    scores = mf.run_scoring(args, model, inputs, traj_ids, gt_trajs)
+    model.close()
+    with open(args.score_gt, "wb") as f:
+      pickle.dump(scores, f)
+    print_exact_nll(mf.eval_exact_nll(scores))
+    return scores
   res = mf.run_inference(args, model, inputs, traj_ids)
   output_data, beam_prob = res[0], res[1]
   model.close()
@@ -264,6 +278,17 @@ def multifuture_inference_main(argv=None):
   if args.save_prob_file is not None:
     with open(args.save_prob_file, "wb") as f:
       pickle.dump(beam_prob, f)
+
+
+def print_exact_nll(result):
+  """The table of --score_gt: (nll, counts, hits) of multifuture.eval_exact_nll."""
+  nll, counts, hits = result
+  keys = sorted(nll)
+  print([counts[k] for k in keys])
+  print("exact NLL:")
+  print(" ".join(keys))
+  print(" ".join("%s" % nll[k] for k in keys))
+  print("top-1 %s top-5 %s over %d steps" % (hits["top1"], hits["top5"], hits["steps"]))
 
 
 def multifuture_eval_trajs_main(argv=None):

@@ -339,6 +339,38 @@ int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t se
   });
 }
 
+int mv_upload_score_futures(mv_handle h, const mv_score_futures_in* fut) {
+  if (!h) return 1;
+  return guarded(h, [&] { upload_score_futures(h, fut); });
+}
+
+int mv_run_score_resident(mv_handle h) {
+  if (!h) return 1;
+  return guarded(h, [&] { run_forward_scored(h); });
+}
+
+int mv_download_scores(mv_handle h, mv_score_outputs* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(out, "mv_download_scores: NULL outputs");
+    download_scores(h, out);
+    drain_events(h);
+  });
+}
+
+int mv_score_futures(mv_handle h, const mv_inputs* in, const mv_score_futures_in* fut,
+                     mv_score_outputs* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(in && fut && out, "mv_score_futures: NULL argument");
+    upload_inputs(h, in);
+    upload_score_futures(h, fut);
+    run_forward_scored(h);
+    download_scores(h, out);
+    drain_events(h);
+  });
+}
+
 int mv_last_forward_gate_rows(mv_handle h, int64_t* rows) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -910,7 +942,8 @@ int mv_kernel_stat(mv_handle h, int32_t i, char* name_out, int32_t name_cap,
   return 0;
 }
 
-static int time_resident(mv_handle h, int32_t iters, float* ms_out, bool beam) {
+static int time_resident(mv_handle h, int32_t iters, float* ms_out, bool beam,
+                         bool scored = false) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(iters >= 1 && ms_out, "bad arguments");
@@ -918,7 +951,9 @@ static int time_resident(mv_handle h, int32_t iters, float* ms_out, bool beam) {
     HIP_CHECK(hipEventCreate(&a));
     HIP_CHECK(hipEventCreate(&b));
     HIP_CHECK(hipEventRecord(a, h->stream));
-    for (int i = 0; i < iters; ++i) run_forward(h, beam);
+    for (int i = 0; i < iters; ++i) {
+      if (scored) run_forward_scored(h); else run_forward(h, beam);
+    }
     HIP_CHECK(hipEventRecord(b, h->stream));
     HIP_CHECK(hipEventSynchronize(b));
     HIP_CHECK(hipEventElapsedTime(ms_out, a, b));
@@ -933,6 +968,9 @@ int mv_time_greedy_resident(mv_handle h, int32_t iters, float* ms_out) {
 }
 int mv_time_beam_resident(mv_handle h, int32_t iters, float* ms_out) {
   return time_resident(h, iters, ms_out, true);
+}
+int mv_time_score_resident(mv_handle h, int32_t iters, float* ms_out) {
+  return time_resident(h, iters, ms_out, true, true);
 }
 
 }  // extern "C"

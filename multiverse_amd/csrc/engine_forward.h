@@ -1233,16 +1233,30 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
 // into the [R, T] output, and the next cell step reads it from there.  The first cell step runs
 // once per sample on the shared encoder state, like the beam's; the S rows of sample n pick that
 // state row up through bm_src_row (= n) at the second cell step, the only indexed read.
-void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
+//
+// `scored` (mv_score_futures): the same loop teacher-forced.  The ids are GIVEN:
+// the forward starts by copying the uploaded futures into the [R, T] output, score_step_kernel
+// reads step t's id there instead of drawing it (log-probability and rank of the given cell),
+// and the lengths are per FUTURE (score_len [R]); the per-sample maxima drive rows_at.
+void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool scored) {
   const mv_config& c = e->cfg;
   ScaleState& S = e->sc[s];
   const int N = c.batch_size, T = c.obs_len, B = c.beam_size, K = S.K;
   const int R = N * B;
-  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampled decode: grid of %d cells (one wave holds a row "
-             "of at most %d)", K, 64 * mv::kBeamRankJ);
-  MV_REQUIRE(!c.use_single_decoder, "sampled decode: use_single_decoder is not supported");
-  MV_REQUIRE(tail_v2(), "sampled decode needs the v2 decoder tail");
+  const char* who = scored ? "scoring forward" : "sampled decode";
+  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "%s: grid of %d cells (one wave holds a row "
+             "of at most %d)", who, K, 64 * mv::kBeamRankJ);
+  MV_REQUIRE(!c.use_single_decoder, "%s: use_single_decoder is not supported", who);
+  MV_REQUIRE(tail_v2(), "%s needs the v2 decoder tail", who);
   HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  if (scored) {
+    // rows a ragged step does not launch keep step_lp 0 / rank -1 (0xFF bytes: int32 -1)
+    const size_t rt = (size_t)R * Tp;
+    HIP_CHECK(hipMemsetAsync(e->score_step_lp.p, 0, rt * sizeof(float), e->issue));
+    HIP_CHECK(hipMemsetAsync(e->score_rank.p, 0xFF, rt * sizeof(int32_t), e->issue));
+    HIP_CHECK(hipMemcpyAsync(e->bm_out_ids.p, e->score_ids.p, rt * sizeof(int32_t),
+                             hipMemcpyDeviceToDevice, e->issue));
+  }
   const bool ragged = e->ragged_now;
   const int Tsteps = ragged ? e->ragged_steps : Tp;
   const bool sparse = sparse_x_on(e, S);
@@ -1281,7 +1295,20 @@ void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
       run_tail(e, {pl});
       int32_t* ids = e->bm_out_ids.p + t;
       const int rows = n_now * B;
-      launch(e, "sample_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
+      if (scored) launch(e, "score_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
+        const dim3 grid(cdiv((size_t)rows, 4)), block(256);
+        const int32_t* lens = ragged ? e->score_len.p : nullptr;
+        int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
+#define MV_SCORE_STEP(J)                                                                    \
+        hipLaunchKernelGGL(mv::score_step_kernel<J>, grid, block, 0, e->issue, logits, orow,  \
+                           rows, B, K, t, one_per_sample ? 1 : 0, lens, e->bm_lp[0].p, ids,   \
+                           Tp, e->score_step_lp.p + t, e->score_rank.p + t, srow)
+        if (K <= 64 * 3) MV_SCORE_STEP(3);
+        else if (K <= 64 * 9) MV_SCORE_STEP(9);
+        else MV_SCORE_STEP(mv::kBeamRankJ);
+#undef MV_SCORE_STEP
+      });
+      else launch(e, "sample_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
         const dim3 grid(cdiv((size_t)rows, 4)), block(256);
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
         int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
@@ -1306,12 +1333,23 @@ void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
   }
   if (ragged) {
     // logits 0 and ids -1 from step L[n] on (a finished row inside a step's prefix kept decoding)
+    // (scored: from step len[n, f] on, one length per future)
     const size_t total = (size_t)R * Tp * K;
+    const int32_t* lens = scored ? e->score_len.p : e->lens_dev.p;
+    const int per_len = scored ? 1 : B;
     hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(cdiv(total, 256)), dim3(256), 0, e->issue,
-                       e->bm_out_logits.p, e->lens_dev.p, R, Tp, K, B);
+                       e->bm_out_logits.p, lens, R, Tp, K, per_len);
     hipLaunchKernelGGL(ragged_ids_tail_kernel, dim3(cdiv((size_t)R * Tp, 256)), dim3(256), 0,
-                       e->issue, e->bm_out_ids.p, e->lens_dev.p, R, B, Tp);
+                       e->issue, e->bm_out_ids.p, lens, R, per_len, Tp);
   }
+}
+
+void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
+  run_decoders_selfcont(e, s, cur, Tp, false);
+}
+
+void run_decoders_scored(mv_engine* e, int s, Cursors& cur, int Tp) {
+  run_decoders_selfcont(e, s, cur, Tp, true);
 }
 
 // The four chains of a greedy forward (class / regression x two scales) exchange nothing between
@@ -1341,7 +1379,8 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
     if (beam) {
       int s = 0;
       for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-      if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
+      if (e->scoring_now) run_decoders_scored(e, s, cur, Tp);
+      else if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
       else run_decoders_beam(e, s, cur, Tp);         // (its finalisers alone)
     }
     return;
@@ -1359,7 +1398,8 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
   if (beam) {
     int s = 0;
     for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-    if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
+    if (e->scoring_now) run_decoders_scored(e, s, cur, Tp);
+    else if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
     else run_decoders_beam(e, s, cur, Tp);
   } else {
     run_decoders_greedy(e, cur, Tp, false);
@@ -1392,6 +1432,34 @@ void plan_ragged(mv_engine* e) {
   e->ragged_now = true;
 }
 
+// The plan of a scoring forward: the lengths came with the futures (mv_upload_score_futures
+// checked them), one per future.  Uniform only if EVERY future runs to pred_len; otherwise the
+// per-sample maxima L[n] give the active-row prefixes and go to lens_dev, where the finalisers
+// and the trajectory decode read per-sample lengths (mv_set_pred_lengths is not set: its copy
+// there is dead until it is set again, which uploads it again).
+void plan_scored(mv_engine* e) {
+  MV_REQUIRE(!e->lens_set, "mv_run_score_resident: per-row prediction lengths are set "
+             "(mv_set_pred_lengths); the lengths of a scoring forward come with the futures -- "
+             "clear them first");
+  MV_REQUIRE(e->score_ready, "mv_run_score_resident: no futures uploaded "
+             "(mv_upload_score_futures)");
+  MV_REQUIRE(e->score_pred_len == e->pred_len, "mv_run_score_resident: the futures were uploaded "
+             "for pred_len %d, the inputs now have pred_len %d (upload the futures again after "
+             "mv_upload_inputs)", e->score_pred_len, e->pred_len);
+  e->ragged_now = false;
+  e->ragged_steps = 0;
+  if (e->score_uniform) return;
+  const int N = e->cfg.batch_size, Tp = e->pred_len;
+  e->act_rows.assign((size_t)Tp + 1, 0);
+  for (int n = 0; n < N; ++n) {
+    for (int t = 0; t < e->score_L[n]; ++t) e->act_rows[t] = n + 1;
+    e->ragged_steps = std::max(e->ragged_steps, (int)e->score_L[n]);
+  }
+  HIP_CHECK(hipMemcpyAsync(e->lens_dev.p, e->score_L.data(), N * sizeof(int32_t),
+                           hipMemcpyHostToDevice, e->stream));
+  e->ragged_now = true;
+}
+
 // out_cls / out_reg of a ragged forward: exact zeros from step L[n] on (rows past a step's
 // active prefix were not written at all).  On the engine's stream, after the chain pairs met.
 void finish_ragged(mv_engine* e, bool beam) {
@@ -1416,8 +1484,9 @@ void run_forward(mv_engine* e, bool beam) {
   ensure_params(e);
   if (beam)
     MV_REQUIRE(e->cfg.beam_size > 1, "engine was created with beam_size 1");
-  const bool sampled = beam && e->sampling;
-  plan_ragged(e);
+  const bool scored = beam && e->scoring_now;
+  const bool sampled = beam && e->sampling && !scored;
+  if (scored) plan_scored(e); else plan_ragged(e);
   // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
   // is issued eagerly
   if (!e->graph_mode || e->profiling || e->ragged_now) {
@@ -1426,10 +1495,13 @@ void run_forward(mv_engine* e, bool beam) {
     if (e->ragged_now) finish_ragged(e, beam);
     e->last_forward = beam ? 2 : 1;
     e->last_sampled = sampled;
+    e->last_scored = scored;
     return;
   }
   // (a sampled forward is a graph of its own; its seed and temperature are read on the device)
-  const auto key = std::make_tuple(sampled ? 2 : beam ? 1 : 0, e->pred_len, e->num_frames);
+  // (so is a scoring forward; its ids are read from an engine-owned buffer)
+  const auto key = std::make_tuple(scored ? 3 : sampled ? 2 : beam ? 1 : 0, e->pred_len,
+                                   e->num_frames);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
     e->gate_rows = 0;
@@ -1454,6 +1526,25 @@ void run_forward(mv_engine* e, bool beam) {
   HIP_CHECK(hipGraphLaunch(it->second, e->stream));
   e->last_forward = beam ? 2 : 1;
   e->last_sampled = sampled;
+  e->last_scored = scored;
+}
+
+// A scoring forward of the uploaded futures (mv_run_score_resident).  Not sticky: the next
+// run_forward is a beam / sampled one again.
+void run_forward_scored(mv_engine* e) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(c.beam_size > 1, "mv_score_futures: engine was created with beam_size 1 (a scoring "
+             "forward scores beam_size futures per row: create a beam handle)");
+  MV_REQUIRE(!c.use_single_decoder, "mv_score_futures: use_single_decoder handles are not "
+             "supported (the scoring forward keeps the un-beamed regression decoder)");
+  e->scoring_now = true;
+  try {
+    run_forward(e, true);
+  } catch (...) {
+    e->scoring_now = false;
+    throw;
+  }
+  e->scoring_now = false;
 }
 
 }  // namespace

@@ -379,6 +379,8 @@ void beam_occupancy(mv_engine* e, float* out) {
   MV_REQUIRE(c.beam_size > 1, "mv_beam_occupancy: engine was created with beam_size 1 (the "
              "occupancy map mixes the beams of a beam-search decode)");
   mf_require_forward(e, "mv_beam_occupancy");
+  MV_REQUIRE(!e->last_scored, "mv_beam_occupancy: the last forward scored given futures "
+             "(mv_score_futures); a set of given futures is not a predictive mixture");
   const ScaleState& S = e->sc[mf_beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;
@@ -432,6 +434,79 @@ void download_beam_ids(mv_engine* e, int32_t* ids, float* logprobs) {
   if (logprobs)
     HIP_CHECK(hipMemcpyAsync(logprobs, e->bm_lp[0].p, R * sizeof(float), hipMemcpyDeviceToHost,
                              e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
+// ---- scoring of given futures (mv_score_futures)
+
+// Checks the futures on the host and uploads them: ids with a valid cell at every step (a
+// finished future inside a live sample keeps decoding on its last valid cell, a padding future
+// on cell 0), the per-future lengths, and the per-sample maxima for the launch plan.
+void upload_score_futures(mv_engine* e, const mv_score_futures_in* in) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(in && in->ids, "mv_upload_score_futures: NULL futures");
+  MV_REQUIRE(c.beam_size > 1, "mv_upload_score_futures: engine was created with beam_size 1 (a "
+             "scoring forward scores beam_size futures per row: create a beam handle)");
+  MV_REQUIRE(!c.use_single_decoder, "mv_upload_score_futures: use_single_decoder handles are "
+             "not supported (the scoring forward keeps the un-beamed regression decoder)");
+  MV_REQUIRE(e->inputs_ready, "mv_upload_score_futures: no inputs uploaded (mv_upload_inputs "
+             "first: it sets pred_len)");
+  MV_REQUIRE(!e->lens_set, "mv_upload_score_futures: per-row prediction lengths are set "
+             "(mv_set_pred_lengths); the lengths of a scoring forward come with the futures -- "
+             "clear them first");
+  const int N = c.batch_size, F = c.beam_size, Tp = e->pred_len;
+  const int K = e->sc[mf_beam_scale(e)].K;
+  const size_t R = (size_t)N * F;
+  std::vector<int32_t> ids(R * Tp), lens(R);
+  std::vector<int32_t> L(N, 0);
+  bool uniform = true;
+  for (int n = 0; n < N; ++n)
+    for (int f = 0; f < F; ++f) {
+      const size_t r = (size_t)n * F + f;
+      const int len = in->lengths ? in->lengths[r] : Tp;
+      MV_REQUIRE(len >= 0 && len <= Tp, "mv_upload_score_futures: lengths[%d, %d] = %d not in "
+                 "[0, pred_len=%d]", n, f, len, Tp);
+      lens[r] = len;
+      L[n] = std::max(L[n], (int32_t)len);
+      uniform = uniform && len == Tp;
+      int32_t last = 0;
+      for (int t = 0; t < Tp; ++t) {
+        if (t < len) {
+          last = in->ids[r * Tp + t];
+          MV_REQUIRE(last >= 0 && last < K, "mv_upload_score_futures: ids[n=%d, f=%d, t=%d] = %d "
+                     "out of range [0, %d)", n, f, t, last, K);
+        }
+        ids[r * Tp + t] = last;
+      }
+    }
+  const size_t cap = R * (size_t)c.max_pred_len;
+  e->score_ids.alloc(cap); e->score_len.alloc(R);
+  e->score_step_lp.alloc(cap); e->score_rank.alloc(cap);
+  // behind whatever forward still reads the previous futures on the device
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  HIP_CHECK(hipMemcpy(e->score_ids.p, ids.data(), ids.size() * sizeof(int32_t),
+                      hipMemcpyHostToDevice));
+  HIP_CHECK(hipMemcpy(e->score_len.p, lens.data(), R * sizeof(int32_t), hipMemcpyHostToDevice));
+  e->score_L = L;
+  e->score_uniform = uniform;
+  e->score_pred_len = Tp;
+  e->score_ready = true;
+}
+
+void download_scores(mv_engine* e, mv_score_outputs* out) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(e->last_forward == 2 && e->last_scored, "mv_download_scores: the last forward of "
+             "this handle was not a scoring one (mv_run_score_resident)");
+  const size_t R = (size_t)c.batch_size * c.beam_size, Tp = e->pred_len;
+  if (out->step_logprobs)
+    HIP_CHECK(hipMemcpyAsync(out->step_logprobs, e->score_step_lp.p, R * Tp * sizeof(float),
+                             hipMemcpyDeviceToHost, e->stream));
+  if (out->logprobs)
+    HIP_CHECK(hipMemcpyAsync(out->logprobs, e->bm_lp[0].p, R * sizeof(float),
+                             hipMemcpyDeviceToHost, e->stream));
+  if (out->ranks)
+    HIP_CHECK(hipMemcpyAsync(out->ranks, e->score_rank.p, R * Tp * sizeof(int32_t),
+                             hipMemcpyDeviceToHost, e->stream));
   HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 

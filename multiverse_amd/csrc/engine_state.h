@@ -220,6 +220,21 @@ struct mv_engine {
   bool sampling = false;
   DevBuf<uint32_t> samp_params;    // [2]
   bool last_sampled = false;       // the last beam-handle forward was a sampled one
+  // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
+  // sampled driver.  Not sticky: scoring_now is up only while run_forward_scored issues it.
+  // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps
+  // decoding); every forward copies them into bm_out_ids, which the cell steps read and the
+  // finalisers mark -1 past a future's length, so a replayed graph scores the latest upload.
+  bool scoring_now = false;
+  bool last_scored = false;        // the last beam-handle forward was a scoring one
+  bool score_ready = false;        // futures uploaded (mv_upload_score_futures) ...
+  int score_pred_len = 0;          // ... for inputs of this pred_len
+  bool score_uniform = true;       // every future's length is pred_len
+  std::vector<int32_t> score_L;    // [N] per-sample length = max over its futures
+  DevBuf<int32_t> score_ids;       // [N, F, T] as uploaded, filled past the length
+  DevBuf<int32_t> score_len;       // [N, F] per-future lengths
+  DevBuf<float> score_step_lp;     // [N, F, T]
+  DevBuf<int32_t> score_rank;      // [N, F, T]
   // multi-future decode of the last forward (multifuture_decode.h): 0 none yet, 1 greedy, 2 beam
   int last_forward = 0;
   DevBuf<double> mf_traj;          // [N, B, T, 2] pixel trajectories

@@ -1495,6 +1495,75 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   }
 }
 
+// The tail of decode step t of a SCORING forward (mv_score_futures): sample_step_kernel with
+// the id GIVEN instead of drawn, one wave per row r = n * F + f, the row in registers.
+//   lp = log_softmax(logits[r]), the arithmetic of sample_step_kernel operation for operation
+//        (scoring the ids a sampled forward drew reproduces its logprobs bit for bit)
+//   id = ids[r, t];  live = t < lens[r] (lens: one length per FUTURE; NULL = every step live)
+//   live:  step_lp[r, t] = lp[id];  lp_acc[r] += lp[id]
+//          rank[r, t] = #{k : logit[k] > logit[id], or logit[k] == logit[id] and k < id}
+//   else:  step_lp[r, t] = 0;  rank[r, t] = -1
+// `shared` and src_row as in sample_step_kernel.  ids is only read: the upload holds a valid
+// cell at every step (the clamp below keeps a foreign buffer from indexing outside the row).
+template <int J>
+__global__ __launch_bounds__(256)
+void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
+                       int t, int shared, const int32_t* __restrict__ lens,
+                       float* __restrict__ lp_acc, const int32_t* __restrict__ ids,
+                       int ids_stride, float* __restrict__ step_lp, int32_t* __restrict__ rank,
+                       int32_t* __restrict__ src_row) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int n = r / S, s = r - n * S;
+  const float* row = logits + (size_t)(shared ? n * S : r) * row_stride;
+  float v[J];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    v[j] = k < K ? row[k] : -INFINITY;
+    mx = fmaxf(mx, v[j]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+  sum = wave_sum(sum);
+  const float lse = logf(sum);
+  const int id = min(max(ids[(size_t)r * ids_stride], 0), K - 1);
+  // the given cell's logit: lane id % 64 holds it in slot id / 64 (static indexing: no scratch)
+  float mine = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (j == (id >> 6)) mine = v[j];
+  const float vid = __shfl(mine, id & 63, 64);
+  int cnt = 0;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K && (v[j] > vid || (v[j] == vid && k < id))) cnt += 1;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+  if (shared && s != 0) {
+    float* out = logits + (size_t)r * row_stride;
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (lane + 64 * j < K) out[lane + 64 * j] = v[j];
+  }
+  if (lane == 0) {
+    const bool live = !lens || t < lens[r];
+    const float lp = (vid - mx) - lse;
+    step_lp[(size_t)r * ids_stride] = live ? lp : 0.f;
+    rank[(size_t)r * ids_stride] = live ? cnt : -1;
+    if (live) lp_acc[r] += lp;
+    if (src_row) src_row[r] = n;
+  }
+}
+
 // ------------------------------------------------------------ batch assembly
 // Dense regression maps from one (x, y) per row-step: out[r, cell, :] =
 // (float)(xy[r, :] - centre[cell, :]) in double, the rounding of

@@ -54,6 +54,10 @@ __device__ __forceinline__ void decode_traj_body(
   }
   if (ids) {
     id = ids[row];
+    if constexpr (RAGGED) {
+      // a scoring forward's lengths are per future: -1 marks a step past this future's own end
+      if (id < 0) { out[2 * (size_t)row] = 0.0; out[2 * (size_t)row + 1] = 0.0; return; }
+    }
   } else {
     const float* x = cls + (size_t)row * K;
     float best = -INFINITY;

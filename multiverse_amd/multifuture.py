@@ -183,14 +183,16 @@ def plan_ragged_batches(lengths, N):
   return RaggedPlan(batches, sum(lengths), grouped)
 
 
-def inference_feed(inputs, args, idxs, batch_size=None, lengths=None):
+def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_length=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
   PredictionModelInference.get_feed_dict (code/multifuture_inference.py:304-385):
   the scene table is compacted to the frames the batch uses, in first-use order.
   lengths (a batch of `plan_ragged_batches`): one prediction length per row, 0 for the
   padding rows; the feed then carries them as "pred_lengths" and their maximum as
-  "pred_length", and the padding rows cost nothing."""
+  "pred_length", and the padding rows cost nothing.
+  pred_length (a batch of `plan_score_batches`): the feed's "pred_length" as given, whatever
+  the samples' own; the lengths then travel with the futures, not with the feed."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
@@ -201,6 +203,8 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None):
     assert len(lengths) == N and all(l == 0 for l in lengths[n_real:])
     assert all(inputs["max_pred_lengths"][i] == l for i, l in zip(idxs[:n_real], lengths))
     T_pred = max(lengths)
+  elif pred_length is not None:
+    T_pred = int(pred_length)
   else:
     T_pred = inputs["max_pred_lengths"][idxs[0]]
     assert all(inputs["max_pred_lengths"][i] == T_pred for i in idxs)
@@ -361,6 +365,109 @@ def run_inference_device(args, model, inputs, traj_ids):
   if getattr(args, "save_occupancy_file", None) is not None:
     ret += ({t: occupancy[t] for t in traj_ids if t in occupancy},)
   return ret
+
+
+# ------------------------------------------------- scoring given futures (not in the reference)
+
+def futures_to_grid_ids(args, gt_by_traj, traj_id, use_grid_idx):
+  """The ground-truth futures of one sample as grid cells of scale `use_grid_idx`, in the
+  order of the sample's future ids -> (ids int32 [n_fut, T_max], lengths int32 [n_fut]);
+  every (x, y) goes through `xy_to_grid_class`, steps past a future's length hold 0."""
+  h, w = args.scene_grids[use_grid_idx]
+  gt = gt_by_traj[traj_id]
+  lengths = np.asarray([len(gt[fid]["x_agent_traj"]) for fid in gt], dtype="int32")
+  ids = np.zeros((len(lengths), int(lengths.max()) if len(lengths) else 0), dtype="int32")
+  for j, fid in enumerate(gt):
+    xy = np.asarray([one[2:] for one in gt[fid]["x_agent_traj"]], dtype="float64")
+    if len(xy):
+      ids[j, :len(xy)] = xy_to_grid_class(xy, h, w, args.video_h, args.video_w)
+  return ids, lengths
+
+
+ScoreRow = collections.namedtuple("ScoreRow", ["sample", "futures", "lengths"])
+
+
+def plan_score_batches(n_futures_per_sample, lengths, N, F):
+  """Batches of N rows x F futures over samples with any number of futures of any length.
+  lengths[i][j] >= 1: the length of future j of sample i (n_futures_per_sample[i] of them).
+  A sample's futures fill a row in order; a sample with more than F futures takes several
+  rows (the engine then runs the same inputs once per row); a row's last futures and a
+  batch's last rows are padding of length 0.  Rows are sorted by their longest future,
+  descending (ties by sample, then by position), as `plan_ragged_batches` sorts samples: the
+  live rows of every step are a prefix.
+  -> [(rows, pred_length)], rows = N x ScoreRow(sample or None for a padding row, futures
+  [indices into the sample's futures], lengths [F]), pred_length = the first row's longest."""
+  assert N >= 1 and F >= 1
+  rows = []
+  for i, n_fut in enumerate(n_futures_per_sample):
+    lens = [int(l) for l in lengths[i]]
+    assert len(lens) == int(n_fut) and all(l >= 1 for l in lens), \
+        "future lengths must be >= 1"
+    for lo in range(0, len(lens), F):
+      futs = list(range(lo, min(lo + F, len(lens))))
+      rows.append(ScoreRow(i, futs, [lens[j] for j in futs] + [0] * (F - len(futs))))
+  order = sorted(range(len(rows)), key=lambda r: (-max(rows[r].lengths), r))
+  batches = []
+  for lo in range(0, len(order), N):
+    batch = [rows[r] for r in order[lo:lo + N]]
+    batch += [ScoreRow(None, [], [0] * F)] * (N - len(batch))
+    batches.append((batch, max(batch[0].lengths)))
+  return batches
+
+
+def run_scoring(args, model, inputs, traj_ids, gt):
+  """Exact teacher-forced log-likelihood of every ground-truth future under the model
+  (`model.run_score`: one scoring forward per batch of `plan_score_batches`) ->
+  {traj_id: {future_id: {"logprob": float32, "step_logprobs": float32 [T], "ranks": int32
+  [T]}}}, T the future's own length."""
+  use_grid_idx = list(args.use_grids).index(True)
+  N, F = model.config.batch_size, model.config.beam_size
+  cells = [futures_to_grid_ids(args, gt, t, use_grid_idx) for t in traj_ids]
+  plan = plan_score_batches([len(c[1]) for c in cells], [c[1] for c in cells], N, F)
+  scores = {t: {} for t in traj_ids}
+  for rows, T_pred in plan:
+    real = [row.sample for row in rows if row.sample is not None]
+    feed, _ = inference_feed(inputs, args, real, batch_size=N, pred_length=T_pred)
+    ids = np.zeros((N, F, T_pred), dtype="int32")
+    lens = np.asarray([row.lengths for row in rows], dtype="int32")
+    for n, row in enumerate(rows):
+      for f, j in enumerate(row.futures):
+        ids[n, f, :lens[n, f]] = cells[row.sample][0][j, :lens[n, f]]
+    out = model.run_score(feed, ids, lens)
+    for n, row in enumerate(rows):
+      if row.sample is None:
+        continue
+      fids = list(gt[traj_ids[row.sample]])
+      for f, j in enumerate(row.futures):
+        L = int(lens[n, f])
+        scores[traj_ids[row.sample]][fids[j]] = {
+            "logprob": out["logprobs"][n, f],
+            "step_logprobs": out["step_logprobs"][n, f, :L].copy(),
+            "ranks": out["ranks"][n, f, :L].copy()}
+  return {t: {fid: scores[t][fid] for fid in gt[t]} for t in traj_ids}
+
+
+def eval_exact_nll(scores, time_list=(0, 1, 2, 3, 4)):
+  """Exact per-step negative log-likelihood of the scored futures (`run_scoring`) at
+  T=1..5: the mean of -step_logprob[t] over the futures that reach step t.
+  -> (nll, counts) in the form of `eval_grid_nll`, and the hit rates of the model's step
+  distribution over every scored step, {"top1": share of ranks == 0, "top5": of ranks < 5,
+  "steps": their number}."""
+  nlls = {"T=%d" % (t + 1): [] for t in time_list}
+  ranks = []
+  for traj_id in scores:
+    for fid in scores[traj_id]:
+      one = scores[traj_id][fid]
+      ranks.append(np.asarray(one["ranks"]).reshape(-1))
+      for t in time_list:
+        if len(one["step_logprobs"]) > t:
+          nlls["T=%d" % (t + 1)].append(-float(one["step_logprobs"][t]))
+  ranks = np.concatenate(ranks) if ranks else np.zeros(0, dtype="int32")
+  hits = {"top1": float(np.mean(ranks == 0)) if ranks.size else float("nan"),
+          "top5": float(np.mean(ranks < 5)) if ranks.size else float("nan"),
+          "steps": int(ranks.size)}
+  return {k: (float(np.mean(v)) if v else float("nan")) for k, v in nlls.items()}, \
+      {k: len(v) for k, v in nlls.items()}, hits
 
 
 # ------------------------------------------------------------------ metrics

@@ -317,6 +317,15 @@ class Model(object):
                 else self.engine.forward_greedy(feed))
     return cls, reg, None
 
+  def run_score(self, feed, ids, lengths=None):
+    """Teacher-forced log-likelihood of beam_size GIVEN futures per row (Engine.score_futures):
+    ids int [N, F, pred_length] grid cells of the used scale, lengths int [N, F] or None ->
+    {"step_logprobs" [N, F, T], "logprobs" [N, F], "ranks" [N, F, T]}."""
+    if not getattr(self.config, "use_beam_search", False):
+      raise _lib.MvError("run_score scores beam_size futures per row: it needs a multi-future "
+                         "(use_beam_search) model, not a greedy one")
+    return self.engine.score_futures(feed, ids, lengths)
+
 
   def run_forward_decoded(self, feed, center_only=False, occupancy=False, grid_centers=None,
                           logits=False):
