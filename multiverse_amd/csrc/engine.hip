@@ -20,6 +20,7 @@
 #include <set>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "convlstm_mfma.h"
@@ -68,6 +69,11 @@ struct OpCtx {
   }
 };
 
+// what mv_run_beam_resident / mv_forward_beam run: a beam search, or (mv_set_sampling) draws
+ForwardKind beam_kind(const mv_engine* e) {
+  return e->sampling ? ForwardKind::Sampled : ForwardKind::Beam;
+}
+
 }  // namespace
 
 // ===================================================================== C ABI
@@ -104,9 +110,7 @@ int mv_create(const mv_config* cfg, int device, mv_handle* out) {
     build_param_table(e);
     alloc_buffers(e);
     if (cfg->beam_size > 1) {
-      size_t K = 0;
-      for (int s = 0; s < cfg->num_scales; ++s)
-        if (e->sc[s].use) K = e->sc[s].K;
+      const size_t K = e->sc[beam_scale(e)].K;
       ensure_beam_step_lds(device, ((size_t)2 * cfg->beam_size * K + 512) * sizeof(float));
     }
   });
@@ -244,13 +248,13 @@ int mv_run_greedy_resident(mv_handle h) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(h->cfg.beam_size == 1, "engine was created for beam search");
-    run_forward(h, false);
+    run_forward(h, ForwardKind::Greedy);
   });
 }
 
 int mv_run_beam_resident(mv_handle h) {
   if (!h) return 1;
-  return guarded(h, [&] { run_forward(h, true); });
+  return guarded(h, [&] { run_forward(h, beam_kind(h)); });
 }
 
 int mv_synchronize(mv_handle h) {
@@ -309,7 +313,7 @@ int mv_set_pred_lengths(mv_handle h, const int32_t* lengths) {
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!lengths) {
       h->lens_set = false;
-      h->ragged_now = false;
+      h->len.reset();
       h->lens_host.clear();
       return;
     }
@@ -346,7 +350,7 @@ int mv_upload_score_futures(mv_handle h, const mv_score_futures_in* fut) {
 
 int mv_run_score_resident(mv_handle h) {
   if (!h) return 1;
-  return guarded(h, [&] { run_forward_scored(h); });
+  return guarded(h, [&] { run_forward(h, ForwardKind::Scored); });
 }
 
 int mv_download_scores(mv_handle h, mv_score_outputs* out) {
@@ -365,7 +369,7 @@ int mv_score_futures(mv_handle h, const mv_inputs* in, const mv_score_futures_in
     MV_REQUIRE(in && fut && out, "mv_score_futures: NULL argument");
     upload_inputs(h, in);
     upload_score_futures(h, fut);
-    run_forward_scored(h);
+    run_forward(h, ForwardKind::Scored);
     download_scores(h, out);
     drain_events(h);
   });
@@ -375,7 +379,7 @@ int mv_last_forward_gate_rows(mv_handle h, int64_t* rows) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(rows, "mv_last_forward_gate_rows: NULL argument");
-    MV_REQUIRE(h->last_forward != 0, "mv_last_forward_gate_rows: no forward has run on this handle");
+    MV_REQUIRE(h->last != ForwardKind::None, "mv_last_forward_gate_rows: no forward has run on this handle");
     *rows = h->gate_rows;
   });
 }
@@ -386,7 +390,7 @@ int mv_forward_greedy(mv_handle h, const mv_inputs* in, mv_outputs* out) {
     MV_REQUIRE(in && out, "mv_forward_greedy: NULL argument");
     MV_REQUIRE(h->cfg.beam_size == 1, "engine was created for beam search");
     upload_inputs(h, in);
-    run_forward(h, false);
+    run_forward(h, ForwardKind::Greedy);
     download_outputs(h, out);
     drain_events(h);
   });
@@ -421,7 +425,7 @@ int mv_forward_beam(mv_handle h, const mv_inputs* in, mv_beam_outputs* out) {
   return guarded(h, [&] {
     MV_REQUIRE(in && out, "mv_forward_beam: NULL argument");
     upload_inputs(h, in);
-    run_forward(h, true);
+    run_forward(h, beam_kind(h));
     download_beam(h, out);
     drain_events(h);
   });
@@ -942,35 +946,32 @@ int mv_kernel_stat(mv_handle h, int32_t i, char* name_out, int32_t name_cap,
   return 0;
 }
 
-static int time_resident(mv_handle h, int32_t iters, float* ms_out, bool beam,
-                         bool scored = false) {
-  if (!h) return 1;
+static int time_resident(mv_handle h, int32_t iters, float* ms_out, ForwardKind kind) {
   return guarded(h, [&] {
     MV_REQUIRE(iters >= 1 && ms_out, "bad arguments");
-    hipEvent_t a, b;
-    HIP_CHECK(hipEventCreate(&a));
-    HIP_CHECK(hipEventCreate(&b));
-    HIP_CHECK(hipEventRecord(a, h->stream));
-    for (int i = 0; i < iters; ++i) {
-      if (scored) run_forward_scored(h); else run_forward(h, beam);
-    }
-    HIP_CHECK(hipEventRecord(b, h->stream));
-    HIP_CHECK(hipEventSynchronize(b));
-    HIP_CHECK(hipEventElapsedTime(ms_out, a, b));
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
+    struct Event {              // released on every way out (a forward may throw)
+      hipEvent_t ev = nullptr;
+      ~Event() { if (ev) (void)hipEventDestroy(ev); }
+    } a, b;
+    HIP_CHECK(hipEventCreate(&a.ev));
+    HIP_CHECK(hipEventCreate(&b.ev));
+    HIP_CHECK(hipEventRecord(a.ev, h->stream));
+    for (int i = 0; i < iters; ++i) run_forward(h, kind);
+    HIP_CHECK(hipEventRecord(b.ev, h->stream));
+    HIP_CHECK(hipEventSynchronize(b.ev));
+    HIP_CHECK(hipEventElapsedTime(ms_out, a.ev, b.ev));
     drain_events(h);
   });
 }
 
 int mv_time_greedy_resident(mv_handle h, int32_t iters, float* ms_out) {
-  return time_resident(h, iters, ms_out, false);
+  return h ? time_resident(h, iters, ms_out, ForwardKind::Greedy) : 1;
 }
 int mv_time_beam_resident(mv_handle h, int32_t iters, float* ms_out) {
-  return time_resident(h, iters, ms_out, true);
+  return h ? time_resident(h, iters, ms_out, beam_kind(h)) : 1;
 }
 int mv_time_score_resident(mv_handle h, int32_t iters, float* ms_out) {
-  return time_resident(h, iters, ms_out, true, true);
+  return h ? time_resident(h, iters, ms_out, ForwardKind::Scored) : 1;
 }
 
 }  // extern "C"

@@ -795,6 +795,39 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
   });
 }
 
+// The un-beamed regression chain's part of step t's tail: offsets into out_reg step t, and the
+// embedding of step t + 1.
+void tail_reg_chain(const ScaleState& S, const Cursors& cur, int s, int t, int Tp, int rows,
+                    TailPlan& pl) {
+  pl.reg_h = S.reg_h[cur.reg[s]].p;
+  pl.reg_out = S.out_reg.p + (size_t)t * S.K * 2; pl.reg_stride = (int64_t)Tp * S.K * 2;
+  pl.reg_next = t + 1 < Tp;
+  pl.reg_rows = rows;
+}
+
+// The class decoder's gate problem of cell step `time` >= 1 of a beam-handle forward (beam search,
+// sampled, scored) and the cursor flip: h from the attention buffer when use_gnn, the state rows
+// through src_h / src_c.  Sparse x: the one-hot input enters as table terms -- at the first step
+// the last observed cell (first_div rows share a sample's label), afterwards the previous step's
+// ids, row r's at prev_ids[r * prev_stride].
+ConvLstmArgs beam_cls_problem(mv_engine* e, int s, Cursors& cur, int time, int rows,
+                              const int32_t* src_h, const int32_t* src_c, int first_div,
+                              const int32_t* prev_ids, int prev_stride) {
+  const mv_config& c = e->cfg;
+  ScaleState& S = e->sc[s];
+  const int cc = cur.cls[s], T = c.obs_len;
+  const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
+  ConvLstmArgs a = conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p, src_h, src_c,
+                                S.cls_h[cc ^ 1].p, S.cls_c[cc ^ 1].p, rows, S.H, S.W, false, 0,
+                                /*want_h16=*/!c.use_gnn);
+  if (sparse_x_on(e, S)) {
+    if (time == 1) set_sparse_x(e, S, a, true, S.labels.p + (T - 1), T, first_div);
+    else set_sparse_x(e, S, a, true, prev_ids, prev_stride, 1);
+  }
+  cur.cls[s] ^= 1;
+  return a;
+}
+
 // Greedy decoders of every enabled scale in lockstep: class decoder
 // (grid_decoder with input_onehot, use_gnn; code/pred_models.py:311-471) and
 // regression decoder.  `pairs`: the class chains and the regression chains are issued as two
@@ -806,7 +839,7 @@ void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
   MV_REQUIRE(!pairs || (v2 && !c.use_single_decoder), "internal: chain pairs need the grouped "
              "decoder tail and a regression decoder");
   // ragged forward: max L steps, step t on the rows_at(t) rows of its active prefix
-  const int Tsteps = e->ragged_now ? e->ragged_steps : Tp;
+  const int Tsteps = e->len.ragged ? e->len.steps : Tp;
   for (int t = 0; t < Tsteps; ++t) {
     const int N = e->rows_at(t);
     // input launches (on e->issue) and gate problems of step t for the chains in `chains`
@@ -867,10 +900,7 @@ void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
         pl.cls_h = S.cls_h[cur.cls[s]].p; pl.cls_rows = N;
         pl.cls_out = S.out_cls.p + (size_t)t * S.K; pl.cls_stride = (int64_t)Tp * S.K;
         pl.cls_next = t + 1 < Tp && !c.class_feedback_dense;
-        pl.reg_h = S.reg_h[cur.reg[s]].p;
-        pl.reg_out = S.out_reg.p + (size_t)t * S.K * 2; pl.reg_stride = (int64_t)Tp * S.K * 2;
-        pl.reg_next = t + 1 < Tp;
-        pl.reg_rows = N;
+        tail_reg_chain(S, cur, s, t, Tp, N, pl);
         if (c.use_single_decoder) {    // offsets from the class decoder's state (:287-296)
           pl.reg_h = pl.cls_h;
           pl.reg_next = false;
@@ -935,52 +965,18 @@ __global__ void tile_beam0_kernel(float* __restrict__ logits, int K, int B, size
   if (r % B) logits[idx] = logits[(r - r % B) * K + (idx - r * K)];
 }
 
+// Back-trace (:689-806) of row n's beams from step L[n] - 1 with parents_0 = arange(B)
+// (code/pred_models.py:714-716), as a forward of pred_len L[n] does; from step L[n] on the ids and
+// the trace are -1 (nothing to gather).  lens == NULL (no per-row lengths): L[n] = T.
 __global__ void beam_backtrace_kernel(const int32_t* __restrict__ step_ids,
                                       const int32_t* __restrict__ step_parents,
+                                      const int32_t* __restrict__ lens,
                                       int32_t* __restrict__ out_ids,
-                                      int32_t* __restrict__ trace, int N, int B,
-                                      int T) {
+                                      int32_t* __restrict__ trace, int N, int B, int T) {
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= N * B) return;
   const int n = idx / B, b = idx - n * B;
-  int par = b;  // parents_0 = arange(B), code/pred_models.py:714-716
-  for (int t = T - 1; t >= 0; --t) {
-    const size_t o = ((size_t)t * N + n) * B + par;
-    out_ids[((size_t)n * B + b) * T + t] = step_ids[o];
-    trace[((size_t)n * B + b) * T + t] = par;
-    par = step_parents[o];
-  }
-}
-
-__global__ void beam_gather_logits_kernel(const float* __restrict__ step_logits,
-                                          const int32_t* __restrict__ trace,
-                                          float* __restrict__ out, int N, int B,
-                                          int T, int K) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t total = (size_t)N * B * T * K;
-  if (idx >= total) return;
-  const int k = idx % K;
-  size_t r = idx / K;
-  const int t = r % T; r /= T;
-  const int b = r % B;
-  const int n = r / B;
-  const int par = trace[((size_t)n * B + b) * T + t];
-  out[idx] = step_logits[(((size_t)t * N + n) * B + par) * K + k];
-}
-
-// ---- finalisers of a ragged forward (per-row lengths `lens`, mv_set_pred_lengths)
-
-// row n's beams are traced back from step L[n] - 1 with parents_0 = arange(B), as a forward of
-// pred_len L[n] does; from step L[n] on the ids are -1 and the trace is -1 (nothing to gather)
-__global__ void ragged_beam_backtrace_kernel(const int32_t* __restrict__ step_ids,
-                                             const int32_t* __restrict__ step_parents,
-                                             const int32_t* __restrict__ lens,
-                                             int32_t* __restrict__ out_ids,
-                                             int32_t* __restrict__ trace, int N, int B, int T) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= N * B) return;
-  const int n = idx / B, b = idx - n * B;
-  const int L = min(max(lens[n], 0), T);
+  const int L = lens ? min(max(lens[n], 0), T) : T;
   const size_t row = ((size_t)n * B + b) * T;
   for (int t = T - 1; t >= L; --t) { out_ids[row + t] = -1; trace[row + t] = -1; }
   int par = b;
@@ -992,10 +988,11 @@ __global__ void ragged_beam_backtrace_kernel(const int32_t* __restrict__ step_id
   }
 }
 
-// beam_gather_logits_kernel with exact zeros where the trace is -1 (steps past L[n])
-__global__ void ragged_beam_gather_kernel(const float* __restrict__ step_vals,
-                                          const int32_t* __restrict__ trace,
-                                          float* __restrict__ out, int N, int B, int T, int K) {
+// out[n, b, t, :] = step_vals[t, n, trace[n, b, t], :], exact zeros where the trace is -1 (steps
+// past L[n]; a back-trace without lengths leaves none)
+__global__ void beam_gather_kernel(const float* __restrict__ step_vals,
+                                   const int32_t* __restrict__ trace,
+                                   float* __restrict__ out, int N, int B, int T, int K) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t total = (size_t)N * B * T * K;
   if (idx >= total) return;
@@ -1007,6 +1004,8 @@ __global__ void ragged_beam_gather_kernel(const float* __restrict__ step_vals,
   const int par = trace[((size_t)n * B + b) * T + t];
   out[idx] = par < 0 ? 0.f : step_vals[(((size_t)t * N + n) * B + par) * K + k];
 }
+
+// ---- finalisers of a ragged forward (per-row lengths `lens`, mv_set_pred_lengths)
 
 // final[n, :] = lp[n, :] for the rows whose last selection was this one (L[n] == time)
 __global__ void ragged_capture_lp_kernel(const float* __restrict__ lp,
@@ -1069,8 +1068,8 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
   // ragged forward (per-row lengths): the cell step of time t runs on the samples that take
   // prediction step t - 1, a prefix of rows_at(t - 1) of them; the buffers keep the batch's
   // layout.  Row n's final scores are those after the selection at time L[n] (0 for L[n] = 0).
-  const bool ragged = e->ragged_now;
-  const int Tsteps = ragged ? e->ragged_steps : Tp;
+  const bool ragged = e->len.ragged;
+  const int Tsteps = ragged ? e->len.steps : Tp;
   if (ragged)
     HIP_CHECK(hipMemsetAsync(e->bm_lp_final.p, 0, (size_t)R * sizeof(float), e->issue));
   int lpi = 0;
@@ -1095,20 +1094,11 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
     if (time > 0) {
       // cell step; h comes from the GNN buffer (identity rows) when use_gnn, c through
       // the parent indirection
-      const int cc = cur.cls[s];
-      const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
       std::vector<ConvLstmArgs> probs;
-      probs.push_back(conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p,
-                                   (c.use_gnn && !dedupe) ? nullptr : src, src,
-                                   S.cls_h[cc ^ 1].p, S.cls_c[cc ^ 1].p, rows_now, S.H, S.W,
-                                   false, 0, /*want_h16=*/!c.use_gnn));
-      if (sparse) {
-        if (time == 1)
-          set_sparse_x(e, S, probs.back(), true, S.labels.p + (T - 1), T, one_per_sample ? 1 : B);
-        else
-          set_sparse_x(e, S, probs.back(), true, e->bm_ids.p + (size_t)(time - 2) * R, 1, 1);
-      }
-      cur.cls[s] ^= 1;
+      probs.push_back(beam_cls_problem(e, s, cur, time, rows_now,
+                                       (c.use_gnn && !dedupe) ? nullptr : src, src,
+                                       one_per_sample ? 1 : B,
+                                       e->bm_ids.p + (size_t)std::max(time - 2, 0) * R, 1));
       const bool v2 = tail_v2();
       const bool single = c.use_single_decoder != 0;
       MV_REQUIRE(!single || v2, "use_single_decoder with beam search needs the v2 decoder tail");
@@ -1129,10 +1119,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
           pl.reg_h = pl.cls_h; pl.reg_rows = rows_now;
           pl.reg_out = regstep; pl.reg_stride = (int64_t)lrow * 2; pl.reg_next = false;
         } else {
-        pl.reg_h = S.reg_h[cur.reg[s]].p;
-        pl.reg_out = S.out_reg.p + (size_t)(time - 1) * K * 2;
-        pl.reg_stride = (int64_t)Tp * K * 2; pl.reg_next = time < Tp;
-        pl.reg_rows = n_now;
+          tail_reg_chain(S, cur, s, time - 1, Tp, n_now, pl);
         }
         run_tail(e, {pl});
       } else {
@@ -1190,39 +1177,21 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
       }
     }
   }
-  if (ragged) {
-    // back-trace of row n from step L[n] - 1; ids -1, logits / offsets 0 from step L[n] on
-    hipLaunchKernelGGL(ragged_beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0, e->issue,
-                       e->bm_ids.p, e->bm_parents.p, e->lens_dev.p, e->bm_out_ids.p,
-                       e->bm_trace.p, N, B, Tp);
-    const size_t total = (size_t)R * Tp * K;
-    hipLaunchKernelGGL(ragged_beam_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, e->issue,
-                       e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p, N, B, Tp, K);
-    if (c.use_single_decoder)
-      hipLaunchKernelGGL(ragged_beam_gather_kernel, dim3(cdiv(total * 2, 256)), dim3(256), 0,
-                         e->issue, e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p, N, B, Tp,
-                         K * 2);
-    HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, e->bm_lp_final.p, (size_t)R * sizeof(float),
-                             hipMemcpyDeviceToDevice, e->issue));
-    return;
-  }
-  // back-trace (:689-806)
-  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0,
-                     e->issue, e->bm_ids.p, e->bm_parents.p, e->bm_out_ids.p,
-                     e->bm_trace.p, N, B, Tp);
+  // back-trace of row n from step L[n] - 1 (uniform: pred_len - 1); ids -1, logits / offsets 0
+  // from step L[n] on
+  hipLaunchKernelGGL(beam_backtrace_kernel, dim3(cdiv(R, 256)), dim3(256), 0, e->issue,
+                     e->bm_ids.p, e->bm_parents.p, ragged ? e->lens_dev.p : nullptr,
+                     e->bm_out_ids.p, e->bm_trace.p, N, B, Tp);
   const size_t total = (size_t)R * Tp * K;
-  hipLaunchKernelGGL(beam_gather_logits_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
-                     e->issue, e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p,
-                     N, B, Tp, K);
-  if (c.use_single_decoder) {       // offsets along every beam: the same gather, 2K per row
-    const size_t tot2 = (size_t)R * Tp * K * 2;
-    hipLaunchKernelGGL(beam_gather_logits_kernel, dim3(cdiv(tot2, 256)), dim3(256), 0,
-                       e->issue, e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p,
-                       N, B, Tp, K * 2);
-  }
-  // final logprobs are in bm_lp[lpi]
-  if (lpi != 0)
-    HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, e->bm_lp[1].p, (size_t)R * sizeof(float),
+  hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(total, 256)), dim3(256), 0, e->issue,
+                     e->bm_logits.p, e->bm_trace.p, e->bm_out_logits.p, N, B, Tp, K);
+  if (c.use_single_decoder)         // offsets along every beam: the same gather, 2K per row
+    hipLaunchKernelGGL(beam_gather_kernel, dim3(cdiv(total * 2, 256)), dim3(256), 0, e->issue,
+                       e->bm_reg_steps.p, e->bm_trace.p, e->bm_out_reg.p, N, B, Tp, K * 2);
+  // the final logprobs go to bm_lp[0]
+  const float* lp_final = ragged ? e->bm_lp_final.p : e->bm_lp[lpi].p;
+  if (lp_final != e->bm_lp[0].p)
+    HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, lp_final, (size_t)R * sizeof(float),
                              hipMemcpyDeviceToDevice, e->issue));
 }
 
@@ -1257,8 +1226,8 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
     HIP_CHECK(hipMemcpyAsync(e->bm_out_ids.p, e->score_ids.p, rt * sizeof(int32_t),
                              hipMemcpyDeviceToDevice, e->issue));
   }
-  const bool ragged = e->ragged_now;
-  const int Tsteps = ragged ? e->ragged_steps : Tp;
+  const bool ragged = e->len.ragged;
+  const int Tsteps = ragged ? e->len.steps : Tp;
   const bool sparse = sparse_x_on(e, S);
   const int64_t orow = (int64_t)Tp * K;             // one row of the [R, T, K] logits
   for (int time = 0; time <= Tsteps && Tsteps > 0; ++time) {
@@ -1267,18 +1236,10 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
     const int rows_now = one_per_sample ? n_now : n_now * B;
     if (time > 0) {
       const int t = time - 1;
-      const int cc = cur.cls[s];
-      const float* hin = c.use_gnn ? S.cls_hg.p : S.cls_h[cc].p;
       const int32_t* src = time == 2 ? e->bm_src_row.p : nullptr;
       std::vector<ConvLstmArgs> probs;
-      probs.push_back(conv_problem(e, S.dec_cls, S.xbuf_cls.p, hin, S.cls_c[cc].p, src, src,
-                                   S.cls_h[cc ^ 1].p, S.cls_c[cc ^ 1].p, rows_now, S.H, S.W,
-                                   false, 0, /*want_h16=*/!c.use_gnn));
-      if (sparse) {
-        if (time == 1) set_sparse_x(e, S, probs.back(), true, S.labels.p + (T - 1), T, 1);
-        else set_sparse_x(e, S, probs.back(), true, e->bm_out_ids.p + (t - 1), Tp, 1);
-      }
-      cur.cls[s] ^= 1;
+      probs.push_back(beam_cls_problem(e, s, cur, time, rows_now, src, src, 1,
+                                       e->bm_out_ids.p + std::max(t - 1, 0), Tp));
       probs.push_back(reg_decoder_problem(e, s, cur, t, Tp, false));
       run_conv_group(e, probs);
       float* logits = e->bm_out_logits.p + (size_t)t * K;
@@ -1288,38 +1249,29 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
       // one row per sample: the logits land in future 0's row of each sample
       pl.cls_out = logits; pl.cls_stride = one_per_sample ? orow * B : orow;
       pl.cls_next = false;                          // sample_step_kernel draws
-      pl.reg_h = S.reg_h[cur.reg[s]].p;
-      pl.reg_out = S.out_reg.p + (size_t)t * K * 2;
-      pl.reg_stride = (int64_t)Tp * K * 2; pl.reg_next = time < Tp;
-      pl.reg_rows = n_now;
+      tail_reg_chain(S, cur, s, t, Tp, n_now, pl);
       run_tail(e, {pl});
       int32_t* ids = e->bm_out_ids.p + t;
       const int rows = n_now * B;
-      if (scored) launch(e, "score_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
-        const dim3 grid(cdiv((size_t)rows, 4)), block(256);
+      const double step_bytes = 4.0 * rows * K * (one_per_sample ? 2 : 1);
+      const dim3 grid(cdiv((size_t)rows, 4)), block(256);
+      const int shared = one_per_sample ? 1 : 0;
+      int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
+      if (scored) launch(e, "score_step", 0, step_bytes, [&] {
         const int32_t* lens = ragged ? e->score_len.p : nullptr;
-        int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
-#define MV_SCORE_STEP(J)                                                                    \
-        hipLaunchKernelGGL(mv::score_step_kernel<J>, grid, block, 0, e->issue, logits, orow,  \
-                           rows, B, K, t, one_per_sample ? 1 : 0, lens, e->bm_lp[0].p, ids,   \
-                           Tp, e->score_step_lp.p + t, e->score_rank.p + t, srow)
-        if (K <= 64 * 3) MV_SCORE_STEP(3);
-        else if (K <= 64 * 9) MV_SCORE_STEP(9);
-        else MV_SCORE_STEP(mv::kBeamRankJ);
-#undef MV_SCORE_STEP
+        with_rank_j(K, [&](auto j) {
+          hipLaunchKernelGGL(mv::score_step_kernel<decltype(j)::value>, grid, block, 0, e->issue,
+                             logits, orow, rows, B, K, t, shared, lens, e->bm_lp[0].p, ids, Tp,
+                             e->score_step_lp.p + t, e->score_rank.p + t, srow);
+        });
       });
-      else launch(e, "sample_step", 0, 4.0 * rows * K * (one_per_sample ? 2 : 1), [&] {
-        const dim3 grid(cdiv((size_t)rows, 4)), block(256);
+      else launch(e, "sample_step", 0, step_bytes, [&] {
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
-        int32_t* srow = time == 1 ? e->bm_src_row.p : nullptr;
-#define MV_SAMPLE_STEP(J)                                                                   \
-        hipLaunchKernelGGL(mv::sample_step_kernel<J>, grid, block, 0, e->issue, logits, orow, \
-                           rows, B, K, t, one_per_sample ? 1 : 0, e->samp_params.p, lens,     \
-                           e->bm_lp[0].p, ids, Tp, srow)
-        if (K <= 64 * 3) MV_SAMPLE_STEP(3);
-        else if (K <= 64 * 9) MV_SAMPLE_STEP(9);
-        else MV_SAMPLE_STEP(mv::kBeamRankJ);
-#undef MV_SAMPLE_STEP
+        with_rank_j(K, [&](auto j) {
+          hipLaunchKernelGGL(mv::sample_step_kernel<decltype(j)::value>, grid, block, 0, e->issue,
+                             logits, orow, rows, B, K, t, shared, e->samp_params.p, lens,
+                             e->bm_lp[0].p, ids, Tp, srow);
+        });
       });
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, Tp, S.xbuf_cls.p, n_next * B);
@@ -1344,14 +1296,6 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
   }
 }
 
-void run_decoders_sampled(mv_engine* e, int s, Cursors& cur, int Tp) {
-  run_decoders_selfcont(e, s, cur, Tp, false);
-}
-
-void run_decoders_scored(mv_engine* e, int s, Cursors& cur, int Tp) {
-  run_decoders_selfcont(e, s, cur, Tp, true);
-}
-
 // The four chains of a greedy forward (class / regression x two scales) exchange nothing between
 // the scene stage and the end of the decode, and want different things from the chip: a gate
 // launch the matrix pipe, the attention / transform / tail kernels HBM and L2.  So the greedy
@@ -1369,20 +1313,26 @@ void run_decoders_scored(mv_engine* e, int s, Cursors& cur, int Tp) {
 // hide); sizes in between are unmeasured and stay on one stream.
 constexpr int kChainPairMaxBatch = 64;
 
-void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
+// "The last enabled scale": the one a beam handle decodes on.
+int beam_scale(const mv_engine* e) {
+  int s = 0;
+  for (int i = 0; i < e->cfg.num_scales; ++i) if (e->sc[i].use) s = i;
+  return s;
+}
+
+void enqueue_forward(mv_engine* e, ForwardKind kind, bool capturing = false) {
   const mv_config& c = e->cfg;
   const int Tp = e->pred_len;
+  const bool beam = kind != ForwardKind::Greedy;
   const bool pairs = !beam && e->stream_b && !e->profiling && !capturing && c.beam_size == 1 &&
                      !c.use_single_decoder && tail_v2() && c.batch_size <= kChainPairMaxBatch;
   Cursors cur;
-  if (e->ragged_now && e->ragged_steps == 0) {    // every row is padding: nothing to compute
-    if (beam) {
-      int s = 0;
-      for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-      if (e->scoring_now) run_decoders_scored(e, s, cur, Tp);
-      else if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
-      else run_decoders_beam(e, s, cur, Tp);         // (its finalisers alone)
-    }
+  auto decode_on_beams = [&] {
+    if (kind == ForwardKind::Beam) run_decoders_beam(e, beam_scale(e), cur, Tp);
+    else run_decoders_selfcont(e, beam_scale(e), cur, Tp, kind == ForwardKind::Scored);
+  };
+  if (e->len.ragged && e->len.steps == 0) {       // every row is padding: nothing to compute
+    if (beam) decode_on_beams();                  // (its finalisers alone)
     return;
   }
   if (pairs) {
@@ -1395,26 +1345,15 @@ void enqueue_forward(mv_engine* e, bool beam, bool capturing = false) {
   }
   if (!e->no_scene()) run_scene(e);
   run_encoders(e, cur, false);
-  if (beam) {
-    int s = 0;
-    for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-    if (e->scoring_now) run_decoders_scored(e, s, cur, Tp);
-    else if (e->sampling) run_decoders_sampled(e, s, cur, Tp);
-    else run_decoders_beam(e, s, cur, Tp);
-  } else {
-    run_decoders_greedy(e, cur, Tp, false);
-  }
+  if (beam) decode_on_beams();
+  else run_decoders_greedy(e, cur, Tp, false);
   HIP_CHECK(hipGetLastError());
 }
 
-// One forward = one `sess.run`.  In graph mode the ~150 (greedy) / ~120 (beam)
-// launches of a forward are captured once per (mode, T_pred, U) into a hipGraph
-// and replayed; every device pointer in it is engine-owned and stable.
 // The per-row lengths of this forward (mv_set_pred_lengths): checked against pred_len, and the
 // active-row prefix of every step.  All lengths == pred_len (or none set): the uniform forward.
 void plan_ragged(mv_engine* e) {
-  e->ragged_now = false;
-  e->ragged_steps = 0;
+  e->len.reset();
   if (!e->lens_set) return;
   const int N = e->cfg.batch_size, Tp = e->pred_len;
   bool uniform = true;
@@ -1423,13 +1362,7 @@ void plan_ragged(mv_engine* e) {
                "pred_lengths[%d] = %d not in [0, pred_len=%d]", n, e->lens_host[n], Tp);
     uniform = uniform && e->lens_host[n] == Tp;
   }
-  if (uniform) return;
-  e->act_rows.assign((size_t)Tp + 1, 0);
-  for (int n = 0; n < N; ++n) {
-    for (int t = 0; t < e->lens_host[n]; ++t) e->act_rows[t] = n + 1;   // n ascending: the max
-    e->ragged_steps = std::max(e->ragged_steps, (int)e->lens_host[n]);
-  }
-  e->ragged_now = true;
+  if (!uniform) e->len.build(e->lens_host, Tp);
 }
 
 // The plan of a scoring forward: the lengths came with the futures (mv_upload_score_futures
@@ -1446,18 +1379,11 @@ void plan_scored(mv_engine* e) {
   MV_REQUIRE(e->score_pred_len == e->pred_len, "mv_run_score_resident: the futures were uploaded "
              "for pred_len %d, the inputs now have pred_len %d (upload the futures again after "
              "mv_upload_inputs)", e->score_pred_len, e->pred_len);
-  e->ragged_now = false;
-  e->ragged_steps = 0;
+  e->len.reset();
   if (e->score_uniform) return;
-  const int N = e->cfg.batch_size, Tp = e->pred_len;
-  e->act_rows.assign((size_t)Tp + 1, 0);
-  for (int n = 0; n < N; ++n) {
-    for (int t = 0; t < e->score_L[n]; ++t) e->act_rows[t] = n + 1;
-    e->ragged_steps = std::max(e->ragged_steps, (int)e->score_L[n]);
-  }
-  HIP_CHECK(hipMemcpyAsync(e->lens_dev.p, e->score_L.data(), N * sizeof(int32_t),
+  e->len.build(e->score_L, e->pred_len);
+  HIP_CHECK(hipMemcpyAsync(e->lens_dev.p, e->score_L.data(), e->score_L.size() * sizeof(int32_t),
                            hipMemcpyHostToDevice, e->stream));
-  e->ragged_now = true;
 }
 
 // out_cls / out_reg of a ragged forward: exact zeros from step L[n] on (rows past a step's
@@ -1479,36 +1405,42 @@ void finish_ragged(mv_engine* e, bool beam) {
   HIP_CHECK(hipGetLastError());
 }
 
-void run_forward(mv_engine* e, bool beam) {
+// One forward = one `sess.run`.  In graph mode the ~150 (greedy) / ~120 (beam)
+// launches of a forward are captured once per (kind, T_pred, U) into a hipGraph
+// and replayed; every device pointer in it is engine-owned and stable.  (A sampled forward reads
+// its seed and temperature on the device, a scoring forward its ids from an engine-owned buffer:
+// their graphs follow a later mv_set_sampling / mv_upload_score_futures.)
+void run_forward(mv_engine* e, ForwardKind kind) {
+  const mv_config& c = e->cfg;
+  const bool beam = kind != ForwardKind::Greedy;
+  if (kind == ForwardKind::Scored) {
+    MV_REQUIRE(c.beam_size > 1, "mv_score_futures: engine was created with beam_size 1 (a scoring "
+               "forward scores beam_size futures per row: create a beam handle)");
+    MV_REQUIRE(!c.use_single_decoder, "mv_score_futures: use_single_decoder handles are not "
+               "supported (the scoring forward keeps the un-beamed regression decoder)");
+  }
   MV_REQUIRE(e->inputs_ready, "no inputs uploaded (mv_upload_inputs)");
   ensure_params(e);
   if (beam)
-    MV_REQUIRE(e->cfg.beam_size > 1, "engine was created with beam_size 1");
-  const bool scored = beam && e->scoring_now;
-  const bool sampled = beam && e->sampling && !scored;
-  if (scored) plan_scored(e); else plan_ragged(e);
+    MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
+  if (kind == ForwardKind::Scored) plan_scored(e); else plan_ragged(e);
   // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
   // is issued eagerly
-  if (!e->graph_mode || e->profiling || e->ragged_now) {
+  if (!e->graph_mode || e->profiling || e->len.ragged) {
     e->gate_rows = 0;
-    enqueue_forward(e, beam);
-    if (e->ragged_now) finish_ragged(e, beam);
-    e->last_forward = beam ? 2 : 1;
-    e->last_sampled = sampled;
-    e->last_scored = scored;
+    enqueue_forward(e, kind);
+    if (e->len.ragged) finish_ragged(e, beam);
+    e->last = kind;
     return;
   }
-  // (a sampled forward is a graph of its own; its seed and temperature are read on the device)
-  // (so is a scoring forward; its ids are read from an engine-owned buffer)
-  const auto key = std::make_tuple(scored ? 3 : sampled ? 2 : beam ? 1 : 0, e->pred_len,
-                                   e->num_frames);
+  const auto key = std::make_tuple(kind, e->pred_len, e->num_frames);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
     e->gate_rows = 0;
     hipGraph_t g = nullptr;
     HIP_CHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
     try {
-      enqueue_forward(e, beam, /*capturing=*/true);
+      enqueue_forward(e, kind, /*capturing=*/true);
     } catch (...) {
       (void)hipStreamEndCapture(e->stream, &g);
       if (g) (void)hipGraphDestroy(g);
@@ -1524,27 +1456,7 @@ void run_forward(mv_engine* e, bool beam) {
   }
   e->gate_rows = e->graph_gate_rows[key];
   HIP_CHECK(hipGraphLaunch(it->second, e->stream));
-  e->last_forward = beam ? 2 : 1;
-  e->last_sampled = sampled;
-  e->last_scored = scored;
-}
-
-// A scoring forward of the uploaded futures (mv_run_score_resident).  Not sticky: the next
-// run_forward is a beam / sampled one again.
-void run_forward_scored(mv_engine* e) {
-  const mv_config& c = e->cfg;
-  MV_REQUIRE(c.beam_size > 1, "mv_score_futures: engine was created with beam_size 1 (a scoring "
-             "forward scores beam_size futures per row: create a beam handle)");
-  MV_REQUIRE(!c.use_single_decoder, "mv_score_futures: use_single_decoder handles are not "
-             "supported (the scoring forward keeps the un-beamed regression decoder)");
-  e->scoring_now = true;
-  try {
-    run_forward(e, true);
-  } catch (...) {
-    e->scoring_now = false;
-    throw;
-  }
-  e->scoring_now = false;
+  e->last = kind;
 }
 
 }  // namespace

@@ -4,19 +4,39 @@
 
 namespace {
 
+// The checks every input upload makes (dense, compact, pipelined) after its own NULL checks: the
+// scene frame count, pred_len, the compact form's row count, the scene indices.
+void check_inputs(const mv_engine* e, int num_scene_frames, int pred_len,
+                  const int32_t* obs_scene, int num_rows = 0) {
+  const mv_config& c = e->cfg;
+  const size_t N = c.batch_size, T = c.obs_len;
+  const bool scene = !e->no_scene();
+  MV_REQUIRE(!scene || (num_scene_frames >= 1 && (size_t)num_scene_frames <= N * T),
+             "num_scene_frames %d not in [1, N*T_o=%zu]", num_scene_frames, N * T);
+  MV_REQUIRE(pred_len >= 1 && pred_len <= c.max_pred_len,
+             "pred_len %d not in [1, max_pred_len=%d]", pred_len, c.max_pred_len);
+  MV_REQUIRE(num_rows >= 0 && (size_t)num_rows <= N, "num_rows %d not in [0, N=%zu]",
+             num_rows, N);
+  for (size_t i = 0; scene && i < N * T; ++i)
+    MV_REQUIRE(obs_scene[i] >= 0 && obs_scene[i] < num_scene_frames,
+               "obs_scene[%zu] = %d out of range [0,%d)", i, obs_scene[i], num_scene_frames);
+}
+
+// ... and per enabled scale: every observed label is a cell of the grid
+void check_labels(const mv_engine* e, int s, const int32_t* labels) {
+  const size_t NT = (size_t)e->cfg.batch_size * e->cfg.obs_len;
+  const int K = e->sc[s].K;
+  for (size_t i = 0; i < NT; ++i)
+    MV_REQUIRE(labels[i] >= 0 && labels[i] < K,
+               "grid_obs_labels[%d][%zu] = %d out of range [0,%d)", s, i, labels[i], K);
+}
+
 void upload_inputs(mv_engine* e, const mv_inputs* in) {
   const mv_config& c = e->cfg;
   const size_t N = c.batch_size, T = c.obs_len;
   const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
   MV_REQUIRE(!scene || (in->obs_scene && in->scene_feat), "obs_scene / scene_feat is NULL");
-  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
-             "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
-  MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
-             "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
-  for (size_t i = 0; scene && i < N * T; ++i)
-    MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
-               "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
-               in->num_scene_frames);
+  check_inputs(e, in->num_scene_frames, in->pred_len, in->obs_scene);
   e->num_frames = scene ? in->num_scene_frames : 0;
   e->pred_len = in->pred_len;
   if (scene) {
@@ -32,10 +52,7 @@ void upload_inputs(mv_engine* e, const mv_inputs* in) {
     if (!S.use) continue;
     MV_REQUIRE(in->grid_obs_labels[s] && in->grid_obs_regress[s],
                "grid_obs_labels/grid_obs_regress[%d] is NULL for an enabled scale", s);
-    for (size_t i = 0; i < N * T; ++i)
-      MV_REQUIRE(in->grid_obs_labels[s][i] >= 0 && in->grid_obs_labels[s][i] < S.K,
-                 "grid_obs_labels[%d][%zu] = %d out of range [0,%d)", s, i,
-                 in->grid_obs_labels[s][i], S.K);
+    check_labels(e, s, in->grid_obs_labels[s]);
     HIP_CHECK(hipMemcpyAsync(S.labels.p, in->grid_obs_labels[s],
                              N * T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     HIP_CHECK(hipMemcpyAsync(S.obs_reg.p, in->grid_obs_regress[s],
@@ -53,16 +70,7 @@ void upload_inputs_compact(mv_engine* e, const mv_inputs_compact* in) {
   const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
   MV_REQUIRE(in->obs_xy && (!scene || (in->obs_scene && in->scene_feat_u8)),
              "obs_scene / scene_feat_u8 / obs_xy is NULL");
-  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
-             "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
-  MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
-             "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
-  MV_REQUIRE(in->num_rows >= 0 && (size_t)in->num_rows <= N, "num_rows %d not in [0, N=%zu]",
-             in->num_rows, N);
-  for (size_t i = 0; scene && i < N * T; ++i)
-    MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
-               "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
-               in->num_scene_frames);
+  check_inputs(e, in->num_scene_frames, in->pred_len, in->obs_scene, in->num_rows);
   e->num_frames = scene ? in->num_scene_frames : 0;
   e->pred_len = in->pred_len;
   if (scene) {
@@ -83,10 +91,7 @@ void upload_inputs_compact(mv_engine* e, const mv_inputs_compact* in) {
     if (!S.use) continue;
     MV_REQUIRE(in->grid_obs_labels[s], "grid_obs_labels[%d] is NULL for an enabled scale", s);
     MV_REQUIRE(S.centers.p, "mv_set_grid_centers(%d) has not been called", s);
-    for (size_t i = 0; i < N * T; ++i)
-      MV_REQUIRE(in->grid_obs_labels[s][i] >= 0 && in->grid_obs_labels[s][i] < S.K,
-                 "grid_obs_labels[%d][%zu] = %d out of range [0,%d)", s, i,
-                 in->grid_obs_labels[s][i], S.K);
+    check_labels(e, s, in->grid_obs_labels[s]);
     HIP_CHECK(hipMemcpyAsync(S.labels.p, in->grid_obs_labels[s],
                              N * T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(mv::regress_from_xy_kernel, dim3(cdiv(N * T * S.K, 256)), dim3(256), 0,
@@ -196,14 +201,7 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
              e->pipe.size());
   const bool scene = !e->no_scene();   // no scene encoder: the scene arrays may be NULL
   MV_REQUIRE(!scene || (in->obs_scene && in->scene_feat), "obs_scene / scene_feat is NULL");
-  MV_REQUIRE(!scene || (in->num_scene_frames >= 1 && (size_t)in->num_scene_frames <= N * T),
-             "num_scene_frames %d not in [1, N*T_o=%zu]", in->num_scene_frames, N * T);
-  MV_REQUIRE(in->pred_len >= 1 && in->pred_len <= c.max_pred_len,
-             "pred_len %d not in [1, max_pred_len=%d]", in->pred_len, c.max_pred_len);
-  for (size_t i = 0; scene && i < N * T; ++i)
-    MV_REQUIRE(in->obs_scene[i] >= 0 && in->obs_scene[i] < in->num_scene_frames,
-               "obs_scene[%zu] = %d out of range [0,%d)", i, in->obs_scene[i],
-               in->num_scene_frames);
+  check_inputs(e, in->num_scene_frames, in->pred_len, in->obs_scene);
   const PipeLayout L = pipe_layout(e);
   char* pin = static_cast<char*>(sl.pin);
   const size_t sf_bytes = scene ? (size_t)in->num_scene_frames * c.scene_h * c.scene_w *
@@ -217,10 +215,7 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
     if (!S.use) continue;
     MV_REQUIRE(in->grid_obs_labels[s] && in->grid_obs_regress[s],
                "grid_obs_labels/grid_obs_regress[%d] is NULL for an enabled scale", s);
-    for (size_t i = 0; i < N * T; ++i)
-      MV_REQUIRE(in->grid_obs_labels[s][i] >= 0 && in->grid_obs_labels[s][i] < S.K,
-                 "grid_obs_labels[%d][%zu] = %d out of range [0,%d)", s, i,
-                 in->grid_obs_labels[s][i], S.K);
+    check_labels(e, s, in->grid_obs_labels[s]);
     memcpy(pin + L.labels[s], in->grid_obs_labels[s], N * T * sizeof(int32_t));
     memcpy(pin + L.obs_reg[s], in->grid_obs_regress[s], N * T * S.K * 2 * sizeof(float));
   }
@@ -249,7 +244,7 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
   e->num_frames = sl.num_frames;
   e->pred_len = sl.pred_len;
   e->inputs_ready = true;
-  run_forward(e, false);
+  run_forward(e, ForwardKind::Greedy);
   const size_t Tp = sl.pred_len;
   for (int s = 0; s < c.num_scales; ++s) {
     ScaleState& S = e->sc[s];
@@ -291,9 +286,7 @@ void pipeline_collect(mv_engine* e, mv_outputs* out) {
 void download_beam(mv_engine* e, mv_beam_outputs* out) {
   const mv_config& c = e->cfg;
   const size_t N = c.batch_size, Tp = e->pred_len, B = c.beam_size;
-  int s = 0;
-  for (int i = 0; i < c.num_scales; ++i) if (e->sc[i].use) s = i;
-  ScaleState& S = e->sc[s];
+  ScaleState& S = e->sc[beam_scale(e)];
   const size_t K = S.K;
   if (out->logits)
     HIP_CHECK(hipMemcpyAsync(out->logits, e->bm_out_logits.p, N * B * Tp * K * sizeof(float),
@@ -324,19 +317,13 @@ void download_beam(mv_engine* e, mv_beam_outputs* out) {
 // ---- multi-future decode of the last forward, on the device (multifuture_decode.h).  Both
 // run on the handle's stream behind whatever forward was queued, copy their small result to
 // the caller's buffer and synchronise.
-static int mf_beam_scale(const mv_engine* e) {
-  int s = 0;
-  for (int i = 0; i < e->cfg.num_scales; ++i) if (e->sc[i].use) s = i;
-  return s;
-}
-
 static void mf_require_forward(const mv_engine* e, const char* who) {
   const mv_config& c = e->cfg;
   MV_REQUIRE(!(c.beam_size > 1 && c.use_single_decoder),
              "%s: use_single_decoder with beam search decodes on the host (the offsets come "
              "per beam, and the reference's own reshape of them mixes beams)", who);
-  MV_REQUIRE(e->last_forward != 0, "%s: no forward has run on this handle", who);
-  MV_REQUIRE(e->last_forward == (c.beam_size > 1 ? 2 : 1),
+  MV_REQUIRE(e->last != ForwardKind::None, "%s: no forward has run on this handle", who);
+  MV_REQUIRE(e->last_on_beams() == (c.beam_size > 1),
              "%s: the last forward of this beam handle was a greedy one", who);
 }
 
@@ -345,7 +332,7 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
   MV_REQUIRE(out, "mv_decode_trajectories: NULL out");
   mf_require_forward(e, "mv_decode_trajectories");
   const bool beam = c.beam_size > 1;
-  if (beam) scale = mf_beam_scale(e);
+  if (beam) scale = beam_scale(e);
   MV_REQUIRE(scale >= 0 && scale < c.num_scales && e->sc[scale].use,
              "mv_decode_trajectories: scale %d is not an enabled scale", scale);
   ScaleState& S = e->sc[scale];
@@ -357,20 +344,30 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
   const double bytes = beam ? rows * (4.0 + 16.0 + (center_only ? 16.0 : 24.0))
                             : rows * (4.0 * K + 16.0 + (center_only ? 16.0 : 24.0));
   launch(e, "decode_traj", center_only ? 0.0 : 2.0 * rows, bytes, [&] {
-    if (e->ragged_now)      // the last forward ran with per-row lengths: (0, 0) past a row's end
-      hipLaunchKernelGGL(mv::decode_traj_ragged_kernel, dim3(grid), dim3(mv::kMfBlock), 0,
-                         e->stream, beam ? e->bm_out_ids.p : nullptr, S.out_cls.p, S.out_reg.p,
-                         S.centers.p, e->mf_traj.p, (int)rows, B, Tp, K, center_only,
-                         e->lens_dev.p);
-    else
-    hipLaunchKernelGGL(mv::decode_traj_kernel, dim3(grid), dim3(mv::kMfBlock), 0, e->stream,
+    // the last forward ran with per-row lengths: (0, 0) past a row's end
+    const bool ragged = e->len.ragged;
+    hipLaunchKernelGGL(ragged ? mv::decode_traj_kernel<true> : mv::decode_traj_kernel<false>,
+                       dim3(grid), dim3(mv::kMfBlock), 0, e->stream,
                        beam ? e->bm_out_ids.p : nullptr, S.out_cls.p, S.out_reg.p, S.centers.p,
-                       e->mf_traj.p, (int)rows, B, Tp, K, center_only);
+                       e->mf_traj.p, (int)rows, B, Tp, K, center_only,
+                       ragged ? e->lens_dev.p : nullptr);
   });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, e->mf_traj.p, rows * 2 * sizeof(double), hipMemcpyDeviceToHost,
                            e->stream));
   HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
+// K <= CPT * 256 cells: a thread's cells in registers (CPT 1 or 3); any K beyond
+template <bool RAGGED>
+void launch_beam_occupancy(mv_engine* e, const float* lp, int N, int B, int Tp, int K) {
+  auto go = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(N * Tp), dim3(mv::kMfBlock), 0, e->stream, e->bm_out_logits.p,
+                       lp, e->mf_occ.p, B, Tp, K, RAGGED ? e->lens_dev.p : nullptr);
+  };
+  if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED>);
+  else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED>);
+  else go(mv::beam_occupancy_anyk_kernel<RAGGED>);
 }
 
 void beam_occupancy(mv_engine* e, float* out) {
@@ -379,9 +376,9 @@ void beam_occupancy(mv_engine* e, float* out) {
   MV_REQUIRE(c.beam_size > 1, "mv_beam_occupancy: engine was created with beam_size 1 (the "
              "occupancy map mixes the beams of a beam-search decode)");
   mf_require_forward(e, "mv_beam_occupancy");
-  MV_REQUIRE(!e->last_scored, "mv_beam_occupancy: the last forward scored given futures "
-             "(mv_score_futures); a set of given futures is not a predictive mixture");
-  const ScaleState& S = e->sc[mf_beam_scale(e)];
+  MV_REQUIRE(e->last != ForwardKind::Scored, "mv_beam_occupancy: the last forward scored given "
+             "futures (mv_score_futures); a set of given futures is not a predictive mixture");
+  const ScaleState& S = e->sc[beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
@@ -389,33 +386,14 @@ void beam_occupancy(mv_engine* e, float* out) {
   // a sampled forward's futures are draws, not scored hypotheses: uniform weights, which the
   // kernels form as softmax_b of all-zero scores (exp(0) / B, exactly 1 / B)
   const float* lp = e->bm_lp[0].p;
-  if (e->last_sampled) {
+  if (e->last == ForwardKind::Sampled) {
     HIP_CHECK(hipMemsetAsync(e->bm_lp[1].p, 0, (size_t)N * B * sizeof(float), e->stream));
     lp = e->bm_lp[1].p;
   }
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
-    const dim3 grid(N * Tp), block(mv::kMfBlock);
-    if (e->ragged_now) {    // the last forward ran with per-row lengths: 0 past a row's end
-      const int32_t* lens = e->lens_dev.p;
-      if (K <= mv::kMfBlock)
-        hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<1>, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
-      else if (K <= 3 * mv::kMfBlock)
-        hipLaunchKernelGGL(mv::beam_occupancy_ragged_kernel<3>, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
-      else
-        hipLaunchKernelGGL(mv::beam_occupancy_anyk_ragged_kernel, grid, block, 0, e->stream,
-                           e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K, lens);
-    } else
-    if (K <= mv::kMfBlock)
-      hipLaunchKernelGGL(mv::beam_occupancy_kernel<1>, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
-    else if (K <= 3 * mv::kMfBlock)
-      hipLaunchKernelGGL(mv::beam_occupancy_kernel<3>, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
-    else
-      hipLaunchKernelGGL(mv::beam_occupancy_anyk_kernel, grid, block, 0, e->stream,
-                         e->bm_out_logits.p, lp, e->mf_occ.p, B, Tp, K);
+    // the last forward ran with per-row lengths: 0 past a row's end
+    if (e->len.ragged) launch_beam_occupancy<true>(e, lp, N, B, Tp, K);
+    else launch_beam_occupancy<false>(e, lp, N, B, Tp, K);
   });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, e->mf_occ.p, cells * sizeof(float), hipMemcpyDeviceToHost,
@@ -426,7 +404,7 @@ void beam_occupancy(mv_engine* e, float* out) {
 void download_beam_ids(mv_engine* e, int32_t* ids, float* logprobs) {
   const mv_config& c = e->cfg;
   MV_REQUIRE(c.beam_size > 1, "mv_download_beam_ids: engine was created with beam_size 1");
-  MV_REQUIRE(e->last_forward == 2, "mv_download_beam_ids: no beam forward has run on this handle");
+  MV_REQUIRE(e->last_on_beams(), "mv_download_beam_ids: no beam forward has run on this handle");
   const size_t R = (size_t)c.batch_size * c.beam_size;
   if (ids)
     HIP_CHECK(hipMemcpyAsync(ids, e->bm_out_ids.p, R * e->pred_len * sizeof(int32_t),
@@ -455,7 +433,7 @@ void upload_score_futures(mv_engine* e, const mv_score_futures_in* in) {
              "(mv_set_pred_lengths); the lengths of a scoring forward come with the futures -- "
              "clear them first");
   const int N = c.batch_size, F = c.beam_size, Tp = e->pred_len;
-  const int K = e->sc[mf_beam_scale(e)].K;
+  const int K = e->sc[beam_scale(e)].K;
   const size_t R = (size_t)N * F;
   std::vector<int32_t> ids(R * Tp), lens(R);
   std::vector<int32_t> L(N, 0);
@@ -495,7 +473,7 @@ void upload_score_futures(mv_engine* e, const mv_score_futures_in* in) {
 
 void download_scores(mv_engine* e, mv_score_outputs* out) {
   const mv_config& c = e->cfg;
-  MV_REQUIRE(e->last_forward == 2 && e->last_scored, "mv_download_scores: the last forward of "
+  MV_REQUIRE(e->last == ForwardKind::Scored, "mv_download_scores: the last forward of "
              "this handle was not a scoring one (mv_run_score_resident)");
   const size_t R = (size_t)c.batch_size * c.beam_size, Tp = e->pred_len;
   if (out->step_logprobs)

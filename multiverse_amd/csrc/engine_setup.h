@@ -24,6 +24,16 @@ void ensure_beam_step_lds(int device, size_t lds) {
   }
 }
 
+// The kernels that hold a K-cell row in one wave's registers (lane l owns k = l + 64 j, j < J)
+// are instantiated for J = 3, 9 and kBeamRankJ: fn(std::integral_constant<int, J>) for the
+// smallest of them that holds K <= 64 * kBeamRankJ cells.
+template <typename F>
+void with_rank_j(int K, F&& fn) {
+  if (K <= 64 * 3) fn(std::integral_constant<int, 3>{});
+  else if (K <= 64 * 9) fn(std::integral_constant<int, 9>{});
+  else fn(std::integral_constant<int, mv::kBeamRankJ>{});
+}
+
 // One beam step (log-softmax + diversity penalty + top-B).  K <= 1024: the rank count on
 // one wave per (n, b) row over the whole chip, then the per-sample selection; larger K
 // (or MV_BEAM_STEP=v1): the single-launch kernel.  `cand` = [N*B, K] scratch.
@@ -43,15 +53,10 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   }
   const int R = N * B;
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
-  if (K <= 64 * 3)
-    hipLaunchKernelGGL(mv::beam_rank_kernel<3>, grid, block, 0, stream, logits, prev_lp, R, B,
-                       K, time, diverse, log_gamma, cand);
-  else if (K <= 64 * 9)
-    hipLaunchKernelGGL(mv::beam_rank_kernel<9>, grid, block, 0, stream, logits, prev_lp, R, B,
-                       K, time, diverse, log_gamma, cand);
-  else
-    hipLaunchKernelGGL(mv::beam_rank_kernel<mv::kBeamRankJ>, grid, block, 0, stream, logits,
+  with_rank_j(K, [&](auto j) {
+    hipLaunchKernelGGL(mv::beam_rank_kernel<decltype(j)::value>, grid, block, 0, stream, logits,
                        prev_lp, R, B, K, time, diverse, log_gamma, cand);
+  });
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
                      fix_num_timestep, new_lp, ids, parents, src_row, rows_per_sample, row_ref);

@@ -113,6 +113,34 @@ struct PendingEvent {
   hipEvent_t a, b;
 };
 
+// What a forward decodes with.  Beam, Sampled and Scored run on a beam handle (beam_size > 1) and
+// leave their results in the bm_* buffers; Greedy leaves out_cls / out_reg.
+enum class ForwardKind { None, Greedy, Beam, Sampled, Scored };
+
+// Per-sample prediction lengths L[n] in [0, pred_len] as a launch plan.  A forward whose lengths
+// are not all pred_len is RAGGED: step t issues its launches on the prefix of
+// act_rows[t] = 1 + max{n : L[n] > t} rows, for steps = max L steps.  Otherwise every step runs
+// on the whole batch and the forward is the uniform one, launch for launch.
+struct LengthPlan {
+  bool ragged = false;               // the forward being issued / issued last is ragged
+  int steps = 0;
+  std::vector<int> act_rows;         // [pred_len + 1] of that forward
+  void reset() { ragged = false; steps = 0; }
+  void build(const std::vector<int32_t>& L, int pred_len) {
+    act_rows.assign((size_t)pred_len + 1, 0);
+    steps = 0;
+    for (int n = 0; n < (int)L.size(); ++n) {
+      for (int t = 0; t < L[n]; ++t) act_rows[t] = n + 1;   // n ascending: the max
+      steps = std::max(steps, (int)L[n]);
+    }
+    ragged = true;
+  }
+  int rows_at(int t, int batch) const {
+    if (!ragged) return batch;
+    return t < (int)act_rows.size() ? act_rows[t] : 0;
+  }
+};
+
 struct ScaleState {
   int H = 0, W = 0, K = 0;
   bool use = false;
@@ -181,24 +209,16 @@ struct mv_engine {
   bool inputs_ready = false;
   // per-row prediction lengths (mv_set_pred_lengths; sticky until cleared): L[n] in [0, pred_len],
   // a host copy (which launches a step gets) and a device copy (the finalisers and the
-  // multi-future decode).  A forward whose lengths are not all pred_len is RAGGED: step t issues
-  // its launches on the prefix of act_rows[t] = 1 + max{n : L[n] > t} rows (rows_at), for
-  // ragged_steps = max L steps.  With no lengths, or all of them pred_len, rows_at is N and the
-  // forward is the uniform one, launch for launch.
+  // multi-future decode); `len` is the plan of the forward being issued / issued last.
   std::vector<int32_t> lens_host;
   DevBuf<int32_t> lens_dev;          // [N]
   bool lens_set = false;
-  bool ragged_now = false;           // the forward being issued / issued last is ragged
-  std::vector<int> act_rows;         // [pred_len + 1] of that forward
-  int ragged_steps = 0;
-  int rows_at(int t) const {
-    if (!ragged_now) return cfg.batch_size;
-    return t < (int)act_rows.size() ? act_rows[t] : 0;
-  }
+  LengthPlan len;
+  int rows_at(int t) const { return len.rows_at(t, cfg.batch_size); }
   // rows of every ConvLSTM problem of every grouped gate launch of the last forward
   // (mv_last_forward_gate_rows); a replayed graph carries the count of its capture
   int64_t gate_rows = 0;
-  std::map<std::tuple<int, int, int>, int64_t> graph_gate_rows;
+  std::map<std::tuple<ForwardKind, int, int>, int64_t> graph_gate_rows;
   // beam
   DevBuf<float> bm_logits;         // [T, N, B, K] per-step logits
   DevBuf<int32_t> bm_ids, bm_parents;  // [T, N, B]
@@ -219,14 +239,11 @@ struct mv_engine {
   // kernel reads them: a captured forward follows a later mv_set_sampling.
   bool sampling = false;
   DevBuf<uint32_t> samp_params;    // [2]
-  bool last_sampled = false;       // the last beam-handle forward was a sampled one
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
-  // sampled driver.  Not sticky: scoring_now is up only while run_forward_scored issues it.
+  // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps
   // decoding); every forward copies them into bm_out_ids, which the cell steps read and the
   // finalisers mark -1 past a future's length, so a replayed graph scores the latest upload.
-  bool scoring_now = false;
-  bool last_scored = false;        // the last beam-handle forward was a scoring one
   bool score_ready = false;        // futures uploaded (mv_upload_score_futures) ...
   int score_pred_len = 0;          // ... for inputs of this pred_len
   bool score_uniform = true;       // every future's length is pred_len
@@ -235,8 +252,10 @@ struct mv_engine {
   DevBuf<int32_t> score_len;       // [N, F] per-future lengths
   DevBuf<float> score_step_lp;     // [N, F, T]
   DevBuf<int32_t> score_rank;      // [N, F, T]
-  // multi-future decode of the last forward (multifuture_decode.h): 0 none yet, 1 greedy, 2 beam
-  int last_forward = 0;
+  // the kind of the last forward: which downloads and which multi-future decode
+  // (multifuture_decode.h) its results allow
+  ForwardKind last = ForwardKind::None;
+  bool last_on_beams() const { return last != ForwardKind::None && last != ForwardKind::Greedy; }
   DevBuf<double> mf_traj;          // [N, B, T, 2] pixel trajectories
   DevBuf<float> mf_occ;            // [N, T, K] occupancy map of the beams
   // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = f16x3 split on the fp16 matrix pipe,
@@ -275,9 +294,9 @@ struct mv_engine {
     auto it = planes.find(dst);
     if (it != planes.end()) it->second.valid = false;
   }
-  // hipGraph replay of the forward (one graph per (mode, T_pred, U))
+  // hipGraph replay of the forward (one graph per (kind, T_pred, U))
   bool graph_mode = false;
-  std::map<std::tuple<int, int, int>, hipGraphExec_t> graphs;
+  std::map<std::tuple<ForwardKind, int, int>, hipGraphExec_t> graphs;
   void drop_graphs() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();

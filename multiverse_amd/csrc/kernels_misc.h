@@ -1422,6 +1422,40 @@ __device__ __forceinline__ float sample_uniform(uint32_t i, uint32_t seed, uint3
   return fminf(u, 0x1.fffffep-1f);
 }
 
+// What the step kernels of the sampled and the scoring forward share, so that scoring the ids a
+// sampled forward drew reproduces its log-probabilities bit for bit: one WAVE per row, the row
+// held in registers as in beam_rank_kernel (lane l owns k = l + 64 j).
+// The row's logits (-inf past K) and the terms of lp[k] = (v[k] - mx) - lse.
+template <int J>
+__device__ __forceinline__ void step_row_log_softmax(const float* __restrict__ row, int K,
+                                                     int lane, float (&v)[J], float& mx,
+                                                     float& lse) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    v[j] = k < K ? row[k] : -INFINITY;
+    mx = fmaxf(mx, v[j]);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+  sum = wave_sum(sum);
+  lse = logf(sum);
+}
+
+// `shared` step: the logits the tail left in the sample's first row, copied to row r's own
+template <int J>
+__device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K, int lane,
+                                                  const float (&v)[J]) {
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) out[lane + 64 * j] = v[j];
+}
+
 // The tail of decode step t of a SAMPLED multi-future forward (mv_set_sampling), one WAVE per
 // row r = n * S + s, the row held in registers as in beam_rank_kernel (lane l owns
 // k = l + 64 j):
@@ -1445,22 +1479,8 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   if (r >= R) return;
   const int n = r / S, s = r - n * S;
   const float* row = logits + (size_t)(shared ? n * S : r) * row_stride;
-  float v[J];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int k = lane + 64 * j;
-    v[j] = k < K ? row[k] : -INFINITY;
-    mx = fmaxf(mx, v[j]);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j)
-    if (lane + 64 * j < K) sum += expf(v[j] - mx);
-  sum = wave_sum(sum);
-  const float lse = logf(sum);
+  float v[J], mx, lse;
+  step_row_log_softmax<J>(row, K, lane, v, mx, lse);
   const uint32_t seed = params[0] + (uint32_t)n * kSampleRowSeed;
   const float temperature = __builtin_bit_cast(float, params[1]);
   float best = -INFINITY, blp = 0.f;
@@ -1482,12 +1502,7 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
     const float ol = __shfl_xor(blp, off, 64);
     if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; blp = ol; }
   }
-  if (shared && s != 0) {
-    float* out = logits + (size_t)r * row_stride;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-      if (lane + 64 * j < K) out[lane + 64 * j] = v[j];
-  }
+  if (shared && s != 0) step_row_copy_out<J>(logits + (size_t)r * row_stride, K, lane, v);
   if (lane == 0) {
     ids[(size_t)r * ids_stride] = min(bi, K - 1);   // (no score ranked: NaN logits; none is made)
     if (!lens || t < lens[n]) lp_acc[r] += blp;
@@ -1497,8 +1512,7 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
 
 // The tail of decode step t of a SCORING forward (mv_score_futures): sample_step_kernel with
 // the id GIVEN instead of drawn, one wave per row r = n * F + f, the row in registers.
-//   lp = log_softmax(logits[r]), the arithmetic of sample_step_kernel operation for operation
-//        (scoring the ids a sampled forward drew reproduces its logprobs bit for bit)
+//   lp = log_softmax(logits[r]) through step_row_log_softmax, as sample_step_kernel
 //   id = ids[r, t];  live = t < lens[r] (lens: one length per FUTURE; NULL = every step live)
 //   live:  step_lp[r, t] = lp[id];  lp_acc[r] += lp[id]
 //          rank[r, t] = #{k : logit[k] > logit[id], or logit[k] == logit[id] and k < id}
@@ -1517,22 +1531,8 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
   if (r >= R) return;
   const int n = r / S, s = r - n * S;
   const float* row = logits + (size_t)(shared ? n * S : r) * row_stride;
-  float v[J];
-  float mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int k = lane + 64 * j;
-    v[j] = k < K ? row[k] : -INFINITY;
-    mx = fmaxf(mx, v[j]);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j)
-    if (lane + 64 * j < K) sum += expf(v[j] - mx);
-  sum = wave_sum(sum);
-  const float lse = logf(sum);
+  float v[J], mx, lse;
+  step_row_log_softmax<J>(row, K, lane, v, mx, lse);
   const int id = min(max(ids[(size_t)r * ids_stride], 0), K - 1);
   // the given cell's logit: lane id % 64 holds it in slot id / 64 (static indexing: no scratch)
   float mine = 0.f;
@@ -1548,12 +1548,7 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
   }
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
-  if (shared && s != 0) {
-    float* out = logits + (size_t)r * row_stride;
-#pragma unroll
-    for (int j = 0; j < J; ++j)
-      if (lane + 64 * j < K) out[lane + 64 * j] = v[j];
-  }
+  if (shared && s != 0) step_row_copy_out<J>(logits + (size_t)r * row_stride, K, lane, v);
   if (lane == 0) {
     const bool live = !lens || t < lens[r];
     const float lp = (vid - mx) - lse;

@@ -30,9 +30,10 @@ constexpr int kOccBeamChunk = 20;             // beams of one (n, t) held in reg
 // reg is [N, T, K, 2]; an id outside [0, K) -- none is produced -- is clamped rather than
 // followed outside the buffers.
 // RAGGED (per-row lengths `lens`, mv_set_pred_lengths): a row (n, b, t) with t >= lens[n] is
-// past its sample's end and decodes to (0, 0); the others exactly as without lengths.
+// past its sample's end and decodes to (0, 0); the others exactly as without lengths.  (Here and
+// below, a kernel instantiated without RAGGED does not read `lens` at all.)
 template <bool RAGGED>
-__device__ __forceinline__ void decode_traj_body(
+__global__ __launch_bounds__(kMfBlock) void decode_traj_kernel(
     const int32_t* __restrict__ ids, const float* __restrict__ cls,
     const float* __restrict__ reg, const double* __restrict__ centers,
     double* __restrict__ out, int rows, int B, int T, int K, int center_only,
@@ -89,21 +90,6 @@ __device__ __forceinline__ void decode_traj_body(
   out[2 * (size_t)row + 1] = y;
 }
 
-__global__ __launch_bounds__(kMfBlock) void decode_traj_kernel(
-    const int32_t* __restrict__ ids, const float* __restrict__ cls,
-    const float* __restrict__ reg, const double* __restrict__ centers,
-    double* __restrict__ out, int rows, int B, int T, int K, int center_only) {
-  decode_traj_body<false>(ids, cls, reg, centers, out, rows, B, T, K, center_only, nullptr);
-}
-
-__global__ __launch_bounds__(kMfBlock) void decode_traj_ragged_kernel(
-    const int32_t* __restrict__ ids, const float* __restrict__ cls,
-    const float* __restrict__ reg, const double* __restrict__ centers,
-    double* __restrict__ out, int rows, int B, int T, int K, int center_only,
-    const int32_t* __restrict__ lens) {
-  decode_traj_body<true>(ids, cls, reg, centers, out, rows, B, T, K, center_only, lens);
-}
-
 // Block-wide max / sum of `cnt` values per thread in ONE pass over LDS: butterfly within each
 // wave (every lane ends with the wave's result), the kMfWaves partials through `red`, combined
 // by every thread in wave order -- a fixed order, so the result is bitwise reproducible.
@@ -152,9 +138,10 @@ __device__ __forceinline__ void occ_beam_weight_norm(const float* __restrict__ l
 // reproducible, and a row's result depends on that row alone.
 // RAGGED (per-row lengths): the map of a step past its sample's end (t >= lens[n]) is 0.
 template <int CPT, bool RAGGED>
-__device__ __forceinline__ void beam_occupancy_body(
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens, float* red) {
+    int B, int T, int K, const int32_t* __restrict__ lens) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
   if constexpr (RAGGED) {
     if (t >= lens[n]) {                            // block-uniform, before any barrier
@@ -212,30 +199,15 @@ __device__ __forceinline__ void beam_occupancy_body(
   }
 }
 
-template <int CPT>
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
-    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
-  beam_occupancy_body<CPT, false>(logits, lp, out, B, T, K, nullptr, red);
-}
-
-template <int CPT>
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_ragged_kernel(
-    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
-  beam_occupancy_body<CPT, true>(logits, lp, out, B, T, K, lens, red);
-}
-
 // Any K: the same arithmetic in the same order, one beam at a time; a thread's cells are
 // k = tid, tid + 256, ...  The row is read three times (maximum, sum, accumulation), the second
 // and third time from cache; the running map lives in the output row, which only this
 // workgroup -- and each cell only its own thread -- touches.
 template <bool RAGGED>
-__device__ __forceinline__ void beam_occupancy_anyk_body(
+__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens, float* red) {
+    int B, int T, int K, const int32_t* __restrict__ lens) {
+  __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
   if constexpr (RAGGED) {
     if (t >= lens[n]) {                            // block-uniform, before any barrier
@@ -260,20 +232,6 @@ __device__ __forceinline__ void beam_occupancy_anyk_body(
       o[k] = b == 0 ? p : o[k] + p;
     }
   }
-}
-
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
-    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
-  beam_occupancy_anyk_body<false>(logits, lp, out, B, T, K, nullptr, red);
-}
-
-__global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_ragged_kernel(
-    const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens) {
-  __shared__ float red[kOccBeamChunk * kMfWaves];
-  beam_occupancy_anyk_body<true>(logits, lp, out, B, T, K, lens, red);
 }
 
 }  // namespace mv
