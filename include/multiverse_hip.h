@@ -315,6 +315,47 @@ int  mv_last_forward_gate_rows(mv_handle h, int64_t* rows);
  * 1024 cells (at the forward); mv_train_* while sampling is on. */
 int  mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed);
 
+/* ---- sampling WITHOUT replacement (not in the reference; defined here) -----------------------
+ * Stochastic beam search (Kool, van Hoof, Welling, ICML 2019): the B = beam_size futures of a row
+ * are DISTINCT and still a sample of the model -- a Gumbel-top-B over whole sequences, computed
+ * top-down -- each with its exact log-probability.  mode 0 = independent draws (the default, the
+ * sampler above), 1 = without replacement.  Sticky; stored while sampling is off, in effect while
+ * sampling is on (mv_set_sampling(h, 1, temperature, seed)).  Everything is float32, K = cells.
+ *
+ * Slot b of batch row n carries phi (the tempered log-probability that drives the search), LP (the
+ * untempered log-probability that is reported) and G (the slot's perturbed score).  Before the
+ * first step there is one root per row with phi = LP = G = 0.  Decode step t (0-based), parent
+ * slot b of row n, logits l:
+ *   lp      = log_softmax(l), the arithmetic of the sampler and the scorer
+ *   q       = lp when temperature == 1 (same bits), else log_softmax(l / temperature) formed the
+ *             same way on the divided logits
+ *   u[k]    = the sampler's uniform of (b*K + k, seed_n, t), b the PARENT's slot,
+ *             seed_n = seed + n * 0x632BE5AB (mod 2^32);  gum[k] = -logf(-logf(u[k]))
+ *   g[k]    = (phi_b + q[k]) + gum[k];  Z = max_k g[k];  d = g[k] - Z
+ *   v       = (G_b - g[k]) + logf(-expm1f(d)) for d < 0, v = -inf for d == 0
+ *   Gt[k]   = (G_b - fmaxf(v, 0)) - log1pf(expf(-fabsf(v)))
+ * (the expm1 form, not log1p(-exp(d)): the best child of a parent gets Gt == G_b bit for bit).
+ * The new slots are the B largest Gt over all (parent, k) of the row, in descending order, ties
+ * to the lower flat index b*K + k.  At step 0 the candidates are the root's K children (the step
+ * runs once per sample, as the beam's shared first step).  New slot j from (b, k) carries
+ * phi = phi_b + q[k], LP = LP_b + lp[k], G = Gt[k], parent b, id k.  diverse_beam, diverse_gamma
+ * and fix_num_timestep are not read.
+ * Consequences: the B futures of a row are pairwise different id sequences; gumbels[n, :] is
+ * non-increasing and <= 0 with gumbels[n, 0] == 0.0 exactly; slot 0 is an exact sample of the
+ * (tempered) model; logprobs are exact untempered model log-probabilities; row n does not depend
+ * on its batch; the futures of a width-B handle are the first B futures of any wider handle.
+ * Outputs as the beam's: mv_download_beam_outputs / mv_download_beam_ids return the back-traced
+ * ids and logits, logprobs = LP, best_beam = slot 0; mv_decode_trajectories works unchanged;
+ * mv_beam_occupancy takes the BEAM's weighting softmax_b(logprobs) (the model's distribution
+ * renormalised over the drawn distinct set), not the sampler's 1/B; per-row lengths hold as for
+ * the beam (row n's LP and G are those after the selection at time L[n]); a replayed graph
+ * follows mv_set_sampling.  mv_download_beam_gumbels: G [N, B] of the last forward of this kind.
+ * Errors: a greedy handle, a mode outside {0, 1}; at the forward: use_single_decoder, a grid of
+ * more than 1024 cells, beam_size > K; mv_download_beam_gumbels after a forward of another kind
+ * (the message names it); mv_train_* while sampling is on. */
+int  mv_set_sampling_mode(mv_handle h, int32_t mode);
+int  mv_download_beam_gumbels(mv_handle h, float* out /* [N, B] */);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -527,6 +568,15 @@ int  mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
                      int32_t N, int32_t B, int32_t K, int32_t time,
                      int32_t diverse, float gamma, int32_t fix_num_timestep,
                      float* new_logprob, int32_t* ids, int32_t* parents);
+
+/* One step of the sampling without replacement (mv_set_sampling_mode above): logits [N,B,K],
+ * prev_phi, prev_logprob, prev_gumbel [N,B] -> new_phi, new_logprob, new_gumbel, ids, parents
+ * [N,B].  t = 0-based decode step; with t == 0 only row n*B of the logits and of the prev_* (the
+ * root's values) are read.  K <= 1024, B <= K, temperature > 0. */
+int  mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
+                    const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
+                    int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
+                    float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
 
 /* Backward of one ConvLSTMCell step (tf.gradients through the cell): inputs as
  * mv_op_convlstm_step (c == h == NULL: zero state) plus d h', d c' [M,H,W,C];

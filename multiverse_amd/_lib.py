@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_pred_lengths", "mv_last_forward_gate_rows", "mv_set_sampling",
     "mv_score_futures", "mv_upload_score_futures", "mv_run_score_resident",
     "mv_download_scores", "mv_time_score_resident",
+    "mv_set_sampling_mode", "mv_download_beam_gumbels", "mv_op_sbs_step",
 ]
 
 
@@ -220,6 +221,10 @@ def load():
   lib.mv_set_pred_lengths.argtypes = [h, _ip]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
+  lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
+  lib.mv_download_beam_gumbels.argtypes = [h, _fp]
+  lib.mv_op_sbs_step.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
+                                 C.c_int32, C.c_float, C.c_uint32, _fp, _fp, _fp, _ip, _ip]
   lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
                                    C.POINTER(mv_score_outputs)]
   lib.mv_upload_score_futures.argtypes = [h, C.POINTER(mv_score_futures_in)]
@@ -531,15 +536,36 @@ class Engine(object):
     check(self.lib.mv_set_pred_lengths(self.handle, iptr(lens)), self.handle)
     self._lengths_set = True
 
-  def set_sampling(self, temperature=1.0, seed=0):
+  def set_sampling(self, temperature=1.0, seed=0, without_replacement=False):
     """The beam_size futures of every row are SAMPLED (Gumbel-max over the step's
     log-softmax / temperature; include/multiverse_hip.h mv_set_sampling) by forward_beam and
-    the calls around it, until clear_sampling()."""
+    the calls around it, until clear_sampling().  without_replacement: the futures of a row are
+    DISTINCT, a sample without replacement (stochastic beam search; mv_set_sampling_mode),
+    and forward_beam / forward_beam_decoded add their perturbed scores as "gumbels"."""
+    mode = 1 if without_replacement else 0
+    if mode != getattr(self, "_sampling_mode", 0):
+      check(self.lib.mv_set_sampling_mode(self.handle, mode), self.handle)
+      self._sampling_mode = mode
     check(self.lib.mv_set_sampling(self.handle, 1, float(temperature),
                                    int(seed) & 0xFFFFFFFF), self.handle)
+    self._sampling_on = True
 
   def clear_sampling(self):
     check(self.lib.mv_set_sampling(self.handle, 0, 1.0, 0), self.handle)
+    self._sampling_on = False
+
+  def _without_replacement(self):
+    """Does the next / did the last beam forward sample without replacement?"""
+    return getattr(self, "_sampling_on", False) and getattr(self, "_sampling_mode", 0) == 1
+
+  def beam_gumbels(self):
+    """float32 [N, B]: the perturbed scores G of the last forward that sampled without
+    replacement -- non-increasing along B, gumbels[:, 0] == 0 (multifuture.
+    wor_importance_weights turns them and the logprobs into importance weights)."""
+    c = self.c_cfg
+    g = np.empty((c.batch_size, c.beam_size), dtype=np.float32)
+    check(self.lib.mv_download_beam_gumbels(self.handle, fptr(g)), self.handle)
+    return g
 
   # ---- scoring given futures (include/multiverse_hip.h mv_score_futures)
   def _score_futures_in(self, ids, lengths):
@@ -662,6 +688,8 @@ class Engine(object):
     out, arrs, s = self._alloc_beam(inp.pred_len)
     check(self.lib.mv_forward_beam(self.handle, C.byref(inp), C.byref(out)),
           self.handle)
+    if self._without_replacement():
+      arrs["gumbels"] = self.beam_gumbels()
     return arrs, s
 
   # ---- resident-input path (bench)
@@ -880,6 +908,8 @@ class Engine(object):
     Tp = self._last_pred_len()
     arrs = {"trajs": self.decode_trajectories(center_only=center_only)}
     arrs["ids"], arrs["logprobs"] = self.beam_ids()
+    if self._without_replacement():
+      arrs["gumbels"] = self.beam_gumbels()
     if occupancy:
       arrs["occupancy"] = self.beam_occupancy()
     if logits:
@@ -1185,6 +1215,21 @@ def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device
                             1 if diverse else 0, float(gamma), int(fix_num_timestep),
                             fptr(new_lp), iptr(ids), iptr(parents)))
   return new_lp, ids, parents
+
+
+def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0):
+  """One step of the sampling without replacement (mv_op_sbs_step): logits [N, B, K], prev_*
+  [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B]."""
+  lib = load()
+  logits, prev_phi, prev_lp, prev_g = f32(logits), f32(prev_phi), f32(prev_lp), f32(prev_g)
+  N, B, K = logits.shape
+  phi, lp, g = (np.empty((N, B), dtype=np.float32) for _ in range(3))
+  ids = np.empty((N, B), dtype=np.int32)
+  parents = np.empty((N, B), dtype=np.int32)
+  check(lib.mv_op_sbs_step(device, fptr(logits), fptr(prev_phi), fptr(prev_lp), fptr(prev_g),
+                           N, B, K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
+                           fptr(phi), fptr(lp), fptr(g), iptr(ids), iptr(parents)))
+  return phi, lp, g, ids, parents
 
 
 def op_convlstm_bwd(x, c, h, kernel, biases, dh_new, dc_new, device=0):

@@ -218,6 +218,10 @@ _MF_FLAGS = [
     # not in the reference: num_out futures SAMPLED from the model's step distribution
     # (Gumbel-max, csrc/kernels_misc.h sample_step_kernel) instead of the beam search
     ("--sample", B, None), ("--sample_temperature", float, 1.0), ("--sample_seed", int, 0),
+    # not in the reference: with --sample, the num_out futures are DISTINCT, a sample WITHOUT
+    # replacement (stochastic beam search, csrc/kernels_misc.h sbs_perturb_kernel); the output
+    # has the beam's layout
+    ("--sample_without_replacement", B, None),
     # not in the reference: instead of decoding, score every ground-truth future of
     # multifuture_path under the model (teacher-forced log-likelihood per step, csrc/
     # kernels_misc.h score_step_kernel) into this pickle and print the exact NLL table
@@ -249,6 +253,8 @@ def multifuture_inference_main(argv=None):
   assert sum(args.use_grids) == 1
   if args.sample and args.greedy:
     raise SystemExit("--sample draws num_out futures; it does not combine with --greedy")
+  if args.sample_without_replacement and not args.sample:
+    raise SystemExit("--sample_without_replacement is a mode of --sample; give --sample as well")
   if args.score_gt is not None and args.greedy:
     raise SystemExit("--score_gt scores num_out futures per row; it does not combine with "
                      "--greedy")

@@ -69,9 +69,11 @@ struct OpCtx {
   }
 };
 
-// what mv_run_beam_resident / mv_forward_beam run: a beam search, or (mv_set_sampling) draws
+// what mv_run_beam_resident / mv_forward_beam run: a beam search, or (mv_set_sampling) draws,
+// independent or (mv_set_sampling_mode 1) without replacement
 ForwardKind beam_kind(const mv_engine* e) {
-  return e->sampling ? ForwardKind::Sampled : ForwardKind::Beam;
+  if (!e->sampling) return ForwardKind::Beam;
+  return e->sampling_mode == 1 ? ForwardKind::SampledWor : ForwardKind::Sampled;
 }
 
 }  // namespace
@@ -340,6 +342,25 @@ int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t se
     h->samp_params.alloc(2);
     HIP_CHECK(hipMemcpy(h->samp_params.p, params, sizeof(params), hipMemcpyHostToDevice));
     h->sampling = true;
+  });
+}
+
+int mv_set_sampling_mode(mv_handle h, int32_t mode) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_sampling_mode: engine was created with beam_size 1 "
+               "(a sampled decode draws beam_size futures per row: create a beam handle)");
+    MV_REQUIRE(mode == 0 || mode == 1, "mv_set_sampling_mode: mode %d not in {0 (independent "
+               "draws), 1 (without replacement)}", (int)mode);
+    h->sampling_mode = mode;
+  });
+}
+
+int mv_download_beam_gumbels(mv_handle h, float* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    download_beam_gumbels(h, out);
+    drain_events(h);
   });
 }
 

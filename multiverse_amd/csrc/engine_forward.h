@@ -1039,7 +1039,12 @@ __global__ void ragged_ids_tail_kernel(int32_t* __restrict__ ids, const int32_t*
 // Beam-search class decoder (grid_decoder_beam_search,
 // code/pred_models.py:474-806) with the un-beamed regression decoder advanced
 // in lockstep (its step t shares a launch with beam time t+1).
-void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
+//
+// `wor` (mv_set_sampling_mode 1): the same loop with the selection replaced by the
+// stochastic-beam-search step (launch_sbs_step): bm_lp carries the untempered LP, bm_phi / bm_g
+// the tempered log-probability and the perturbed score.  Shared first step, bm_ref dedupe, parent
+// indirection, back-trace and gather are the beam's.
+void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
   const mv_config& c = e->cfg;
   ScaleState& S = e->sc[s];
   const int N = c.batch_size, T = c.obs_len, B = c.beam_size, K = S.K,
@@ -1065,6 +1070,16 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
     cur.cls[s] ^= 1;
   }
   HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  if (wor) {
+    MV_REQUIRE(!c.use_single_decoder, "sampling without replacement: use_single_decoder is not "
+               "supported");
+    MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampling without replacement: grid of %d cells (one "
+               "wave holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
+    MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first "
+               "step has only K distinct candidates)", B, K);
+    HIP_CHECK(hipMemsetAsync(e->bm_phi[0].p, 0, (size_t)R * sizeof(float), e->issue));
+    HIP_CHECK(hipMemsetAsync(e->bm_g[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  }
   // ragged forward (per-row lengths): the cell step of time t runs on the samples that take
   // prediction step t - 1, a prefix of rows_at(t - 1) of them; the buffers keep the batch's
   // layout.  Row n's final scores are those after the selection at time L[n] (0 for L[n] = 0).
@@ -1072,6 +1087,8 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
   const int Tsteps = ragged ? e->len.steps : Tp;
   if (ragged)
     HIP_CHECK(hipMemsetAsync(e->bm_lp_final.p, 0, (size_t)R * sizeof(float), e->issue));
+  if (ragged && wor)
+    HIP_CHECK(hipMemsetAsync(e->bm_g_final.p, 0, (size_t)R * sizeof(float), e->issue));
   int lpi = 0;
   const int32_t* src = nullptr;  // state row indirection for the next cell step
   const bool sparse = sparse_x_on(e, S);
@@ -1139,7 +1156,14 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
         HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
-      launch(e, "beam_step", 0, 4.0 * n_now * B * K, [&] {
+      if (wor) launch(e, "sbs_step", 0, 16.0 * n_now * B * K, [&] {
+        launch_sbs_step(e->issue, logits, e->bm_phi[lpi].p, e->bm_lp[lpi].p, e->bm_g[lpi].p,
+                        e->bm_cand.p, e->bm_sbs_lp.p, e->bm_sbs_q.p, e->samp_params.p, n_now, B,
+                        K, time - 1, e->bm_phi[lpi ^ 1].p, e->bm_lp[lpi ^ 1].p,
+                        e->bm_g[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
+                        one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr);
+      });
+      else launch(e, "beam_step", 0, 4.0 * n_now * B * K, [&] {
         launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, n_now, B, K, time,
                          c.diverse_beam, logf(c.diverse_gamma), c.fix_num_timestep,
                          e->bm_lp[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
@@ -1150,6 +1174,10 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
       if (ragged)
         hipLaunchKernelGGL(ragged_capture_lp_kernel, dim3(cdiv((size_t)n_now * B, 256)), dim3(256),
                            0, e->issue, e->bm_lp[lpi].p, e->lens_dev.p, e->bm_lp_final.p,
+                           n_now * B, B, time);
+      if (ragged && wor)
+        hipLaunchKernelGGL(ragged_capture_lp_kernel, dim3(cdiv((size_t)n_now * B, 256)), dim3(256),
+                           0, e->issue, e->bm_g[lpi].p, e->lens_dev.p, e->bm_g_final.p,
                            n_now * B, B, time);
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, 1, S.xbuf_cls.p, n_next * B);
@@ -1193,6 +1221,12 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp) {
   if (lp_final != e->bm_lp[0].p)
     HIP_CHECK(hipMemcpyAsync(e->bm_lp[0].p, lp_final, (size_t)R * sizeof(float),
                              hipMemcpyDeviceToDevice, e->issue));
+  if (wor) {                        // and the final perturbed scores to bm_g[0]
+    const float* g_final = ragged ? e->bm_g_final.p : e->bm_g[lpi].p;
+    if (g_final != e->bm_g[0].p)
+      HIP_CHECK(hipMemcpyAsync(e->bm_g[0].p, g_final, (size_t)R * sizeof(float),
+                               hipMemcpyDeviceToDevice, e->issue));
+  }
 }
 
 // Sampled multi-future decoder (mv_set_sampling; defined here): the class decoder
@@ -1328,7 +1362,8 @@ void enqueue_forward(mv_engine* e, ForwardKind kind, bool capturing = false) {
                      !c.use_single_decoder && tail_v2() && c.batch_size <= kChainPairMaxBatch;
   Cursors cur;
   auto decode_on_beams = [&] {
-    if (kind == ForwardKind::Beam) run_decoders_beam(e, beam_scale(e), cur, Tp);
+    if (kind == ForwardKind::Beam || kind == ForwardKind::SampledWor)
+      run_decoders_beam(e, beam_scale(e), cur, Tp, kind == ForwardKind::SampledWor);
     else run_decoders_selfcont(e, beam_scale(e), cur, Tp, kind == ForwardKind::Scored);
   };
   if (e->len.ragged && e->len.steps == 0) {       // every row is padding: nothing to compute

@@ -383,8 +383,10 @@ void beam_occupancy(mv_engine* e, float* out) {
   const size_t cells = (size_t)N * Tp * K;
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
   // HBM-bound: every beam's logits row read once, the map written once
-  // a sampled forward's futures are draws, not scored hypotheses: uniform weights, which the
-  // kernels form as softmax_b of all-zero scores (exp(0) / B, exactly 1 / B)
+  // independently sampled futures are draws, not scored hypotheses: uniform weights, which the
+  // kernels form as softmax_b of all-zero scores (exp(0) / B, exactly 1 / B).  (Futures drawn
+  // WITHOUT replacement are distinct: the model's own distribution renormalised over the drawn
+  // set, softmax_b(logprobs), the beam's weighting.)
   const float* lp = e->bm_lp[0].p;
   if (e->last == ForwardKind::Sampled) {
     HIP_CHECK(hipMemsetAsync(e->bm_lp[1].p, 0, (size_t)N * B * sizeof(float), e->stream));
@@ -412,6 +414,31 @@ void download_beam_ids(mv_engine* e, int32_t* ids, float* logprobs) {
   if (logprobs)
     HIP_CHECK(hipMemcpyAsync(logprobs, e->bm_lp[0].p, R * sizeof(float), hipMemcpyDeviceToHost,
                              e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
+const char* forward_kind_name(ForwardKind k) {
+  switch (k) {
+    case ForwardKind::None: return "none";
+    case ForwardKind::Greedy: return "greedy";
+    case ForwardKind::Beam: return "beam search";
+    case ForwardKind::Sampled: return "independent samples";
+    case ForwardKind::Scored: return "scoring";
+    case ForwardKind::SampledWor: return "sampling without replacement";
+  }
+  return "?";
+}
+
+// the perturbed scores G [N, B] of a forward that sampled without replacement
+void download_beam_gumbels(mv_engine* e, float* out) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(out, "mv_download_beam_gumbels: NULL out");
+  MV_REQUIRE(e->last == ForwardKind::SampledWor, "mv_download_beam_gumbels: the last forward of "
+             "this handle was not one that sampled without replacement (mv_set_sampling + "
+             "mv_set_sampling_mode 1); last forward: %s", forward_kind_name(e->last));
+  const size_t R = (size_t)c.batch_size * c.beam_size;
+  HIP_CHECK(hipMemcpyAsync(out, e->bm_g[0].p, R * sizeof(float), hipMemcpyDeviceToHost,
+                           e->stream));
   HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 

@@ -278,6 +278,33 @@ int mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
   });
 }
 
+int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
+                   const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
+                   int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
+                   float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
+    MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
+               (double)temperature);
+    OpCtx ctx(device);
+    ensure_beam_step_lds(device, ((size_t)2 * B * K + 512) * sizeof(float));
+    const size_t R = (size_t)N * B;
+    DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
+    DevBuf<int32_t> di, dpa;
+    DevBuf<uint32_t> dprm;
+    const uint32_t params[2] = {seed, __builtin_bit_cast(uint32_t, temperature)};
+    ctx.up(dl, logits, R * K);
+    ctx.up(dphi, prev_phi, R); ctx.up(dlp, prev_logprob, R); ctx.up(dg, prev_gumbel, R);
+    ctx.up(dprm, params, (size_t)2);
+    nphi.alloc(R); nlp.alloc(R); ng.alloc(R); di.alloc(R); dpa.alloc(R);
+    cand.alloc(R * K); lpp.alloc(R * K); qp.alloc(R * K);
+    launch_sbs_step(ctx.stream, dl.p, dphi.p, dlp.p, dg.p, cand.p, lpp.p, qp.p, dprm.p, N, B, K,
+                    t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B);
+    ctx.down(new_phi, nphi, R); ctx.down(new_logprob, nlp, R); ctx.down(new_gumbel, ng, R);
+    ctx.down(ids, di, R); ctx.down(parents, dpa, R);
+  });
+}
+
 int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* h,
                        const float* kernel, const float* biases, const float* dh_new,
                        const float* dc_new, int32_t M, int32_t H, int32_t W, int32_t Cx,

@@ -20,6 +20,8 @@ void ensure_beam_step_lds(int device, size_t lds) {
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(mv::beam_select_kernel),
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(mv::sbs_select_kernel),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     cur = lds;
   }
 }
@@ -60,6 +62,32 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
                      fix_num_timestep, new_lp, ids, parents, src_row, rows_per_sample, row_ref);
+  HIP_CHECK(hipGetLastError());
+}
+
+// One step of the sampling without replacement (stochastic beam search, kernels_misc.h): the
+// perturbed candidates on one wave per parent row, then the per-sample top-B that carries phi,
+// LP and G.  t = 0-based decode step; K <= 1024, B <= K.  `cand`, `lp_plane`, `q_plane` =
+// [N*B, K] scratch; params = {seed, temperature bits} on the device.
+void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_phi,
+                     const float* prev_lp, const float* prev_g, float* cand, float* lp_plane,
+                     float* q_plane, const uint32_t* params, int N, int B, int K, int t,
+                     float* new_phi, float* new_lp, float* new_g, int32_t* ids, int32_t* parents,
+                     int32_t* src_row, int rows_per_sample, int32_t* row_ref = nullptr) {
+  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampling without replacement: grid of %d cells (one wave "
+             "holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
+  MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first step "
+             "has only K distinct candidates)", B, K);
+  const int R = N * B;
+  const dim3 grid(cdiv((size_t)R, 4)), block(256);
+  with_rank_j(K, [&](auto j) {
+    hipLaunchKernelGGL(mv::sbs_perturb_kernel<decltype(j)::value>, grid, block, 0, stream, logits,
+                       prev_phi, prev_g, R, B, K, t, params, cand, lp_plane, q_plane);
+  });
+  hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
+                     ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
+                     prev_phi, prev_lp, B, K, t, new_phi, new_lp, new_g, ids, parents, src_row,
+                     rows_per_sample, row_ref);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -330,6 +358,9 @@ void alloc_buffers(mv_engine* e) {
       e->bm_lp[0].alloc(R); e->bm_lp[1].alloc(R);
       e->bm_lp_final.alloc(R);
       e->bm_cand.alloc((size_t)R * K);
+      for (int i = 0; i < 2; ++i) { e->bm_phi[i].alloc(R); e->bm_g[i].alloc(R); }
+      e->bm_g_final.alloc(R);
+      e->bm_sbs_lp.alloc((size_t)R * K); e->bm_sbs_q.alloc((size_t)R * K);
       e->bm_src_row.alloc(R);
       e->bm_ref.alloc(R);
       e->bm_trace.alloc(R * Tp);

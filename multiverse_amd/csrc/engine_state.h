@@ -113,9 +113,10 @@ struct PendingEvent {
   hipEvent_t a, b;
 };
 
-// What a forward decodes with.  Beam, Sampled and Scored run on a beam handle (beam_size > 1) and
-// leave their results in the bm_* buffers; Greedy leaves out_cls / out_reg.
-enum class ForwardKind { None, Greedy, Beam, Sampled, Scored };
+// What a forward decodes with.  Beam, Sampled, SampledWor and Scored run on a beam handle
+// (beam_size > 1) and leave their results in the bm_* buffers; Greedy leaves out_cls / out_reg.
+// SampledWor: the beam driver with the stochastic-beam-search step (mv_set_sampling_mode 1).
+enum class ForwardKind { None, Greedy, Beam, Sampled, Scored, SampledWor };
 
 // Per-sample prediction lengths L[n] in [0, pred_len] as a launch plan.  A forward whose lengths
 // are not all pred_len is RAGGED: step t issues its launches on the prefix of
@@ -225,6 +226,12 @@ struct mv_engine {
   DevBuf<float> bm_lp[2];          // [N, B]
   DevBuf<float> bm_lp_final;       // [N, B] ragged forward: row n's scores after the selection at time L[n]
   DevBuf<float> bm_cand;           // [N, B, K] candidate log-probs of one step
+  // sampling without replacement (ForwardKind::SampledWor): bm_lp carries LP; phi (the tempered
+  // log-probability that drives the search) and G (the perturbed score) ping-pong beside it, and
+  // the perturb kernel leaves the step's lp / q planes for the selection
+  DevBuf<float> bm_phi[2], bm_g[2];    // [N, B]; the final G goes to bm_g[0]
+  DevBuf<float> bm_g_final;            // [N, B] ragged forward: row n's G after the selection at time L[n]
+  DevBuf<float> bm_sbs_lp, bm_sbs_q;   // [N, B, K]
   DevBuf<int32_t> bm_src_row;      // [N*B]
   DevBuf<int32_t> bm_ref;          // [N*B] 1 = some surviving beam continues this state row
   DevBuf<int32_t> bm_trace;        // [N, B, T]
@@ -238,6 +245,7 @@ struct mv_engine {
   // row instead of searching.  {seed, temperature bits} live on the device, where the step
   // kernel reads them: a captured forward follows a later mv_set_sampling.
   bool sampling = false;
+  int sampling_mode = 0;           // mv_set_sampling_mode: 0 independent draws, 1 without replacement
   DevBuf<uint32_t> samp_params;    // [2]
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.

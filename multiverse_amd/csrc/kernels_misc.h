@@ -1559,6 +1559,166 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
   }
 }
 
+// ------------------------------------------------------------ sampling without replacement
+// Stochastic beam search (Kool, van Hoof, Welling, ICML 2019; defined in
+// include/multiverse_hip.h mv_set_sampling_mode): one step in two launches, split as the beam's.
+//   sbs_perturb_kernel  one WAVE per parent row r = n * B + b, the row in registers (lane l owns
+//                       k = l + 64 j; no LDS, no scratch):
+//                         lp = log_softmax(l) through step_row_log_softmax;  q = lp at
+//                         temperature 1, else log_softmax(l / temperature) formed the same way
+//                         g[k] = (phi_b + q[k]) - log(-log(u(b * K + k, seed_n, t)))
+//                         Z = max_k g[k] (butterfly);  d = g[k] - Z
+//                         v = (G_b - g[k]) + log(-expm1(d)), -inf at d == 0
+//                         cand[r, k] = (G_b - max(v, 0)) - log1p(exp(-|v|))
+//                       and the planes lp [R, K] and (temperature != 1) q [R, K] the selection
+//                       forms a winner's LP and phi from.  t == 0: only slot 0 of a sample is a
+//                       candidate row (the root; its phi and G are read at n * B).
+//   sbs_select_kernel   beam_select_kernel's algorithm over cand; winner j from (b, k) carries
+//                       G = cand, phi = phi_b + q[k], LP = LP_b + lp[k], parent b, id k.
+// params: {seed, temperature bits} of the sampler, read on the device.
+
+// log_softmax terms of a row already in registers (-inf past K): step_row_log_softmax's
+// arithmetic in its order
+template <int J>
+__device__ __forceinline__ void step_regs_log_softmax(const float (&v)[J], int K, int lane,
+                                                      float& mx, float& lse) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) mx = fmaxf(mx, v[j]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+  sum = wave_sum(sum);
+  lse = logf(sum);
+}
+
+template <int J>
+__global__ __launch_bounds__(256)
+void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
+                        const float* __restrict__ prev_g, int R, int B, int K, int t,
+                        const uint32_t* __restrict__ params, float* __restrict__ cand,
+                        float* __restrict__ lp_plane, float* __restrict__ q_plane) {
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= R) return;
+  const int n = r / B, b = r - n * B;
+  if (t == 0 && b != 0) return;              // the root's K children are the candidates
+  float v[J], mx, lse;
+  step_row_log_softmax<J>(logits + (size_t)r * K, K, lane, v, mx, lse);
+  const uint32_t seed = params[0] + (uint32_t)n * kSampleRowSeed;
+  const float temperature = __builtin_bit_cast(float, params[1]);
+  const bool tempered = temperature != 1.f;  // uniform
+  float mxq = mx, lseq = lse;
+  float w[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
+  if (tempered) step_regs_log_softmax<J>(w, K, lane, mxq, lseq);
+  const float phi = prev_phi[r], G = prev_g[r];
+  float* lp_out = lp_plane + (size_t)r * K;
+  float* q_out = q_plane + (size_t)r * K;
+  float Z = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K) {
+      const float lp = (v[j] - mx) - lse;
+      const float q = (w[j] - mxq) - lseq;   // == lp bit for bit at temperature 1
+      lp_out[k] = lp;
+      if (tempered) q_out[k] = q;
+      const float u = sample_uniform((uint32_t)b * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
+      w[j] = (phi + q) + (-logf(-logf(u)));
+      Z = fmaxf(Z, w[j]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) Z = fmaxf(Z, __shfl_xor(Z, off, 64));
+  float* out = cand + (size_t)r * K;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K) {
+      const float g = w[j], d = g - Z;
+      const float vv = d < 0.f ? (G - g) + logf(-expm1f(d)) : -INFINITY;
+      out[k] = (G - fmaxf(vv, 0.f)) - log1pf(expf(-fabsf(vv)));
+    }
+  }
+}
+
+// Dynamic LDS as beam_select_kernel: cand [B*K] + 2 x 16 (value, index) reduction entries.
+__global__ __launch_bounds__(1024)
+void sbs_select_kernel(const float* __restrict__ cand, const float* __restrict__ lp_plane,
+                       const float* __restrict__ q_plane, const uint32_t* __restrict__ params,
+                       const float* __restrict__ prev_phi, const float* __restrict__ prev_lp,
+                       int B, int K, int t, float* __restrict__ new_phi,
+                       float* __restrict__ new_lp, float* __restrict__ new_g,
+                       int32_t* __restrict__ ids, int32_t* __restrict__ parents,
+                       int32_t* __restrict__ state_src_row, int state_rows_per_sample,
+                       int32_t* __restrict__ row_ref) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ncand = (t > 0) ? B * K : K;
+  float* lp = sm;
+  float* redv = sm + B * K;                              // [2][16]
+  int* redi = reinterpret_cast<int*>(redv + 32);         // [2][16]
+  const float* src = cand + (size_t)n * B * K;
+  float best = -INFINITY;
+  int bi = 0x7fffffff;
+  for (int v = tid; v < ncand; v += 1024) {
+    const float x = src[v];
+    lp[v] = x;
+    if (beam_better(x, v, best, bi)) { best = x; bi = v; }
+  }
+  for (int sel = 0; sel < B; ++sel) {
+    float wv = best;
+    int wi = bi;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const float ov = __shfl_xor(wv, off, 64);
+      const int oi = __shfl_xor(wi, off, 64);
+      if (beam_better(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+    }
+    const int pp = (sel & 1) * 16;
+    if (lane == 0) { redv[pp + wave] = wv; redi[pp + wave] = wi; }
+    __syncthreads();
+    wv = redv[pp];
+    wi = redi[pp];
+#pragma unroll
+    for (int w = 1; w < 16; ++w) {
+      const float ov = redv[pp + w];
+      const int oi = redi[pp + w];
+      if (beam_better(ov, oi, wv, wi)) { wv = ov; wi = oi; }
+    }
+    if (tid == 0) {
+      // (no candidate ranked: NaN logits; none is made -- the clamp keeps the reads in the row)
+      const int flat = min(max(wi, 0), ncand - 1);
+      const int par = flat / K;
+      const size_t o = (size_t)n * B + sel, pr = (size_t)n * B + par;
+      const size_t cell = (size_t)n * B * K + flat;
+      const bool tempered = __builtin_bit_cast(float, params[1]) != 1.f;
+      const float lpk = lp_plane[cell];
+      new_g[o] = wv;
+      new_phi[o] = prev_phi[pr] + (tempered ? q_plane[cell] : lpk);
+      new_lp[o] = prev_lp[pr] + lpk;
+      ids[o] = flat - par * K;
+      parents[o] = par;
+      if (state_src_row) state_src_row[o] = n * state_rows_per_sample + par;
+      if (row_ref) row_ref[n * state_rows_per_sample + par] = 1;   // a state row some beam continues
+    }
+    if (wi < ncand && (wi & 1023) == tid) {   // the owner removes the winner and rescans its own
+      lp[wi] = -INFINITY;
+      best = -INFINITY;
+      bi = 0x7fffffff;
+      for (int v = tid; v < ncand; v += 1024) {
+        const float x = lp[v];
+        if (beam_better(x, v, best, bi)) { best = x; bi = v; }
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------ batch assembly
 // Dense regression maps from one (x, y) per row-step: out[r, cell, :] =
 // (float)(xy[r, :] - centre[cell, :]) in double, the rounding of

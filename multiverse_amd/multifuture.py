@@ -268,6 +268,7 @@ def model_config(args, batch_size=1, max_pred_len=None):
       sample_futures=bool(getattr(args, "sample", False)),
       sample_temperature=float(getattr(args, "sample_temperature", 1.0)),
       sample_seed=int(getattr(args, "sample_seed", 0)),
+      sample_without_replacement=bool(getattr(args, "sample_without_replacement", False)),
       use_teacher_forcing=False, is_train=False,
       scene_h=args.scene_h, scene_w=args.scene_w, scene_class=args.scene_class,
       use_soft_grid_class=args.use_soft_grid_class,
@@ -365,6 +366,42 @@ def run_inference_device(args, model, inputs, traj_ids):
   if getattr(args, "save_occupancy_file", None) is not None:
     ret += ({t: occupancy[t] for t in traj_ids if t in occupancy},)
   return ret
+
+
+def wor_importance_weights(logprobs, gumbels):
+  """Importance weights of futures sampled WITHOUT replacement (stochastic beam search; after
+  Kool, van Hoof, Welling, ICML 2019, eq. 19-20).  logprobs, gumbels [..., B] of one forward
+  (Engine.forward_beam in that mode: exact log-probabilities and perturbed scores, the latter
+  non-increasing along B, gumbels[..., 0] == 0), B >= 3.  kappa = the last slot's perturbed
+  score is the threshold the first B - 1 futures exceeded; with p = exp(logprob)
+      w_0 = p_0
+      w_j = p_j / (1 - exp(-(exp(logprob_j - kappa) - p_j)))      0 < j < B - 1
+  makes  sum_j w_j f(future_j)  an unbiased estimate of  E_model[f].
+
+  The paper's weight, p / (1 - exp(-exp(logprob - kappa))), is unbiased for perturbed scores
+  whose maximum is itself Gumbel(0)-distributed.  The engine's are CONDITIONED on that maximum
+  being 0 (the root starts at G = 0; the drawn set does not depend on the maximum), and under
+  that condition the paper's weight is biased (tests/test_sbs_host.py measures it).  In arrival
+  times exp(-G): future i arrives at an Exp(p_i) time, the first arrival is at time 1, and by
+  memorylessness every other future arrives at 1 + Exp(p_i): slot 0 is certain and weighs p_0,
+  and a later one was included with probability 1 - exp(-p_j (exp(-kappa) - 1)), which is the
+  denominator above.  (B = 2 leaves no future between slot 0 and the threshold: refused.)
+  -> (raw [..., B - 1] float64, normalised [..., B - 1] float64 summing to 1: the lower-variance,
+  biased estimator).  Valid for temperature 1 -- at another temperature the futures are a sample
+  of the TEMPERED model, whose log-probabilities the engine does not report."""
+  lp = np.asarray(logprobs, dtype=np.float64)
+  g = np.asarray(gumbels, dtype=np.float64)
+  if lp.shape != g.shape or lp.shape[-1] < 3:
+    raise ValueError("wor_importance_weights: logprobs %s and gumbels %s must agree, B >= 3"
+                     % (lp.shape, g.shape))
+  kappa = g[..., -1:]
+  lp = lp[..., :-1]
+  p = np.exp(lp)
+  with np.errstate(divide="ignore", invalid="ignore"):
+    # 1 - exp(-x) = -expm1(-x)
+    raw = p / -np.expm1(-(np.exp(lp - kappa) - p))
+  raw[..., 0] = p[..., 0]
+  return raw, raw / raw.sum(axis=-1, keepdims=True)
 
 
 # ------------------------------------------------- scoring given futures (not in the reference)

@@ -230,9 +230,11 @@ class Model(object):
     self.engine.set_compute_mode(self.compute_mode)
     # config.sample_futures: the beam_size futures of a row are sampled from the model's step
     # distribution (config.sample_temperature, config.sample_seed) instead of searched
+    # (config.sample_without_replacement: distinct futures, stochastic beam search)
     if getattr(config, "sample_futures", False):
       self.engine.set_sampling(getattr(config, "sample_temperature", 1.0),
-                               getattr(config, "sample_seed", 0))
+                               getattr(config, "sample_seed", 0),
+                               bool(getattr(config, "sample_without_replacement", False)))
     self.global_step = 0
     # names of the fetches, kept for callers that introspect them
     self.grid_pred_decoded = ["grid_pred_decoded_%d" % i
@@ -252,6 +254,10 @@ class Model(object):
     if getattr(config, "use_beam_search", False):
       assert not getattr(config, "is_train", False)
       assert sum(config.use_grids) == 1, "only one scale test at a time"
+    if getattr(config, "sample_without_replacement", False) and \
+        not getattr(config, "sample_futures", False):
+      raise _lib.MvError("sample_without_replacement is a mode of the sampled decode: it needs "
+                         "sample_futures")
     if getattr(config, "sample_futures", False):
       if not getattr(config, "use_beam_search", False):
         raise _lib.MvError("sample_futures draws beam_size futures per row: it needs a "
@@ -312,7 +318,10 @@ class Model(object):
       reg = [[] for _ in cfg.scene_grids]
       cls[s] = arrs["best_beam"]
       reg[s] = arrs["grid_reg"]
-      return cls, reg, [arrs["logits"], arrs["ids"], arrs["logprobs"]]
+      beam = [arrs["logits"], arrs["ids"], arrs["logprobs"]]
+      if "gumbels" in arrs:      # sampled without replacement: the perturbed scores [N, B]
+        beam.append(arrs["gumbels"])
+      return cls, reg, beam
     cls, reg = (self.engine.forward_greedy_compact(feed) if compact
                 else self.engine.forward_greedy(feed))
     return cls, reg, None
@@ -331,8 +340,8 @@ class Model(object):
                           logits=False):
     """One decode whose fetch is what a multi-future caller uses, decoded on the device:
     {"trajs": float64 [N, B, T, 2]} (B = 1 for a greedy model) and, for a beam-search model,
-    "ids" [N, B, T], "logprobs" [N, B] and -- with occupancy -- "occupancy" float32
-    [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
+    "ids" [N, B, T], "logprobs" [N, B], "gumbels" [N, B] when the model samples without
+    replacement, and -- with occupancy -- "occupancy" float32 [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
     [N, B, T, K] is fetched as well, for a caller that stores them).  grid_centers: list over
     scales of [H, W, 2] cell centres (default: the feed's, else those already resident)."""
     cfg = self.config
