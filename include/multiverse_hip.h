@@ -356,6 +356,47 @@ int  mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t s
 int  mv_set_sampling_mode(mv_handle h, int32_t mode);
 int  mv_download_beam_gumbels(mv_handle h, float* out /* [N, B] */);
 
+/* ---- truncated sampling: top-k and nucleus limits (not in the reference; defined here) -------
+ * Cuts the tail of the step distribution both samplers draw from and keeps the temperature.  In
+ * effect while sampling is on, in both sampling modes.  Everything is float32, K = cells, l = the
+ * step's hidden2grid logits, tau = the temperature; top_k is an int32 >= 0 (0 = off), top_p a
+ * float in (0, 1] (1 = off).  Per row, at decode step t:
+ *   w[k]    = l[k] / tau (the division of the sampling without replacement);  mxq = max w
+ *   e[k]    = expf(w[k] - mxq);  sum_e = their sum in the order of the log-softmax (per lane over
+ *             j, lane owning k = lane + 64 j, then the wave butterfly); at tau = 1 the terms of lp
+ *   c(k)    = #{j : l[j] > l[k]}  (strictly better, an integer)
+ *   m(k)    = sum of e[j] over {j : l[j] > l[k]}, in that same order over the masked terms
+ *   keep(k) = c(k) < floor, or both of
+ *               top_k == 0 or c(k) < top_k
+ *               top_p >= 1 or m(k) < top_p * sum_e
+ * A top_p >= 1 is never evaluated: off means off (m(k) < sum_e is not guaranteed in float32).
+ * floor is 1 everywhere except step 0 of a forward that samples without replacement, where it is
+ * beam_size: the root needs B children.  With the floor no slot can lack a finite candidate.
+ * Cells with exactly equal logits are kept or dropped together, so the kept set may exceed top_k
+ * by a tie group; keep is an upper set of the logit order, described by one threshold.
+ * The proposal is  q~[k] = (w[k] - mxq) - logf(sum of e over the kept cells)  on kept cells (that
+ * sum in the same order) and -inf elsewhere.  Both limits off: q~ == lp bit for bit at tau = 1,
+ * and q~ == the q of the sampling without replacement bit for bit at any other tau.
+ * Independent mode: id = argmax over the KEPT k of lp[k] / tau + gum[k]; noise, tie rule and all
+ * else as above.  logprobs[n, s] += lp[id] stays the model's exact, untruncated, untempered
+ * log-probability (scoring the drawn ids reproduces it bit for bit); a second accumulator takes
+ * qlogprobs[n, s] += q~[id] and stops at the row's length as logprobs does.
+ * Without replacement: q~ replaces q in g, in the winner's phi and in the plane the selection
+ * reads (written whenever tau != 1 or a limit is on).  A dropped cell is the candidate -inf and
+ * is never selected.  LP, G and every consequence listed above hold: distinct futures,
+ * gumbels[n, 0] == 0.0, exact LP.  qlogprobs is the final phi; a ragged forward captures it at
+ * L[n] as it does LP and G.  One exception: "a width-B handle draws the first B futures of a
+ * wider one" holds only while the step-0 floor does not widen either handle's kept set.
+ * With both limits off every output of every call is bit-identical to a handle that never had
+ * them.  Sticky; stored while sampling is off (as mv_set_sampling_mode); the limits live in the
+ * sampler's device buffer {seed, tau bits, top_k, top_p bits}, so a replayed graph follows this
+ * call without re-capture.
+ * mv_download_beam_proposal_logprobs: qlogprobs [N, B] of the last forward, which must have been
+ * a sampled one of either mode (the message names the kind otherwise).
+ * Errors: a greedy handle; top_k < 0; top_p outside (0, 1] or NaN. */
+int  mv_set_sampling_truncation(mv_handle h, int32_t top_k, float top_p);
+int  mv_download_beam_proposal_logprobs(mv_handle h, float* out /* [N, B] */);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -577,6 +618,15 @@ int  mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
                     const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
                     int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                     float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
+
+/* One step of the independent sampler with the limits of mv_set_sampling_truncation: logits
+ * [R, K], R = samples x S rows (row r is future r % S of sample r / S) -> ids [R], lp [R] (the
+ * model's log-probability of the drawn cell), qlp [R] (the proposal's), keep [R, K] (1 = the cell
+ * is in the kept set).  t = 0-based decode step; floor >= 1 as in the definition; K <= 1024. */
+int  mv_op_sample_step(int device, const float* logits /* [R, K] */, int32_t R, int32_t S,
+                       int32_t K, int32_t t, float temperature, uint32_t seed, int32_t top_k,
+                       float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
+                       uint8_t* keep /* [R, K] */);
 
 /* Backward of one ConvLSTMCell step (tf.gradients through the cell): inputs as
  * mv_op_convlstm_step (c == h == NULL: zero state) plus d h', d c' [M,H,W,C];

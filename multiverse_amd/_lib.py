@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = [
     "mv_score_futures", "mv_upload_score_futures", "mv_run_score_resident",
     "mv_download_scores", "mv_time_score_resident",
     "mv_set_sampling_mode", "mv_download_beam_gumbels", "mv_op_sbs_step",
+    "mv_set_sampling_truncation", "mv_download_beam_proposal_logprobs", "mv_op_sample_step",
 ]
 
 
@@ -223,6 +224,11 @@ def load():
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
   lib.mv_download_beam_gumbels.argtypes = [h, _fp]
+  lib.mv_set_sampling_truncation.argtypes = [h, C.c_int32, C.c_float]
+  lib.mv_download_beam_proposal_logprobs.argtypes = [h, _fp]
+  lib.mv_op_sample_step.argtypes = [C.c_int, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_float, C.c_uint32, C.c_int32, C.c_float, C.c_int32,
+                                    _ip, _fp, _fp, _u8p]
   lib.mv_op_sbs_step.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, C.c_uint32, _fp, _fp, _fp, _ip, _ip]
   lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
@@ -536,12 +542,19 @@ class Engine(object):
     check(self.lib.mv_set_pred_lengths(self.handle, iptr(lens)), self.handle)
     self._lengths_set = True
 
-  def set_sampling(self, temperature=1.0, seed=0, without_replacement=False):
+  def set_sampling(self, temperature=1.0, seed=0, without_replacement=False, top_k=0,
+                   top_p=1.0):
     """The beam_size futures of every row are SAMPLED (Gumbel-max over the step's
     log-softmax / temperature; include/multiverse_hip.h mv_set_sampling) by forward_beam and
     the calls around it, until clear_sampling().  without_replacement: the futures of a row are
     DISTINCT, a sample without replacement (stochastic beam search; mv_set_sampling_mode),
-    and forward_beam / forward_beam_decoded add their perturbed scores as "gumbels"."""
+    and forward_beam / forward_beam_decoded add their perturbed scores as "gumbels".
+    top_k (0 = off) / top_p (1 = off): the step distribution is cut to its top_k best cells /
+    its smallest head of mass top_p and renormalised (mv_set_sampling_truncation); while a
+    limit is on, the forwards add the futures' log-probability under that proposal as
+    "proposal_logprobs" (logprobs stays the model's own)."""
+    if (int(top_k), float(top_p)) != getattr(self, "_sampling_limits", (0, 1.0)):
+      self.set_sampling_truncation(top_k, top_p)
     mode = 1 if without_replacement else 0
     if mode != getattr(self, "_sampling_mode", 0):
       check(self.lib.mv_set_sampling_mode(self.handle, mode), self.handle)
@@ -553,6 +566,27 @@ class Engine(object):
   def clear_sampling(self):
     check(self.lib.mv_set_sampling(self.handle, 0, 1.0, 0), self.handle)
     self._sampling_on = False
+
+  def set_sampling_truncation(self, top_k=0, top_p=1.0):
+    """The top-k / nucleus limits of the sampled decode (mv_set_sampling_truncation): sticky,
+    stored while sampling is off, followed by a replayed graph.  (0, 1.0) = off."""
+    check(self.lib.mv_set_sampling_truncation(self.handle, int(top_k), float(top_p)),
+          self.handle)
+    self._sampling_limits = (int(top_k), float(top_p))
+
+  def _truncated(self):
+    """Does the next / did the last beam forward sample under a top-k / nucleus limit?"""
+    top_k, top_p = getattr(self, "_sampling_limits", (0, 1.0))
+    return getattr(self, "_sampling_on", False) and (top_k > 0 or top_p < 1.0)
+
+  def beam_proposal_logprobs(self):
+    """float32 [N, B]: the log-probability of each future of the last SAMPLED forward under the
+    proposal it was drawn from -- the tempered, truncated step distribution -- where logprobs
+    is the model's own (multifuture.proposal_importance_weights turns the two into weights)."""
+    c = self.c_cfg
+    q = np.empty((c.batch_size, c.beam_size), dtype=np.float32)
+    check(self.lib.mv_download_beam_proposal_logprobs(self.handle, fptr(q)), self.handle)
+    return q
 
   def _without_replacement(self):
     """Does the next / did the last beam forward sample without replacement?"""
@@ -690,6 +724,8 @@ class Engine(object):
           self.handle)
     if self._without_replacement():
       arrs["gumbels"] = self.beam_gumbels()
+    if self._truncated():
+      arrs["proposal_logprobs"] = self.beam_proposal_logprobs()
     return arrs, s
 
   # ---- resident-input path (bench)
@@ -910,6 +946,8 @@ class Engine(object):
     arrs["ids"], arrs["logprobs"] = self.beam_ids()
     if self._without_replacement():
       arrs["gumbels"] = self.beam_gumbels()
+    if self._truncated():
+      arrs["proposal_logprobs"] = self.beam_proposal_logprobs()
     if occupancy:
       arrs["occupancy"] = self.beam_occupancy()
     if logits:
@@ -1230,6 +1268,22 @@ def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, d
                            N, B, K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
                            fptr(phi), fptr(lp), fptr(g), iptr(ids), iptr(parents)))
   return phi, lp, g, ids, parents
+
+
+def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0):
+  """One step of the independent sampler under top-k / nucleus limits (mv_op_sample_step):
+  logits [R, K], row r = future r % S of sample r // S -> (ids int32 [R], lp [R] the model's
+  log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set)."""
+  lib = load()
+  logits = f32(logits)
+  R, K = logits.shape
+  ids = np.empty(R, dtype=np.int32)
+  lp, qlp = (np.empty(R, dtype=np.float32) for _ in range(2))
+  keep = np.empty((R, K), dtype=np.uint8)
+  check(lib.mv_op_sample_step(device, fptr(logits), R, int(S), K, int(t), float(temperature),
+                              int(seed) & 0xFFFFFFFF, int(top_k), float(top_p), int(floor),
+                              iptr(ids), fptr(lp), fptr(qlp), keep.ctypes.data_as(_u8p)))
+  return ids, lp, qlp, keep.astype(bool)
 
 
 def op_convlstm_bwd(x, c, h, kernel, biases, dh_new, dc_new, device=0):

@@ -222,6 +222,10 @@ _MF_FLAGS = [
     # replacement (stochastic beam search, csrc/kernels_misc.h sbs_perturb_kernel); the output
     # has the beam's layout
     ("--sample_without_replacement", B, None),
+    # not in the reference: with --sample, every step draws from its N best cells / from its
+    # smallest head of probability mass P only (csrc/kernels_misc.h step_row_keep_threshold);
+    # 0 and 1.0 = off
+    ("--sample_top_k", int, 0), ("--sample_top_p", float, 1.0),
     # not in the reference: instead of decoding, score every ground-truth future of
     # multifuture_path under the model (teacher-forced log-likelihood per step, csrc/
     # kernels_misc.h score_step_kernel) into this pickle and print the exact NLL table
@@ -255,6 +259,9 @@ def multifuture_inference_main(argv=None):
     raise SystemExit("--sample draws num_out futures; it does not combine with --greedy")
   if args.sample_without_replacement and not args.sample:
     raise SystemExit("--sample_without_replacement is a mode of --sample; give --sample as well")
+  if (args.sample_top_k != 0 or args.sample_top_p != 1.0) and not args.sample:
+    raise SystemExit("--sample_top_k / --sample_top_p limit the draws of --sample; give --sample "
+                     "as well")
   if args.score_gt is not None and args.greedy:
     raise SystemExit("--score_gt scores num_out futures per row; it does not combine with "
                      "--greedy")

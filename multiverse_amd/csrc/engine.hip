@@ -338,10 +338,40 @@ int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t se
                (double)temperature);
     // behind whatever forward still reads the previous seed / temperature on the device
     HIP_CHECK(hipStreamSynchronize(h->stream));
-    const uint32_t params[2] = {seed, __builtin_bit_cast(uint32_t, temperature)};
-    h->samp_params.alloc(2);
+    const uint32_t params[4] = {seed, __builtin_bit_cast(uint32_t, temperature),
+                                (uint32_t)h->samp_top_k,
+                                __builtin_bit_cast(uint32_t, h->samp_top_p)};
+    h->samp_params.alloc(4);
     HIP_CHECK(hipMemcpy(h->samp_params.p, params, sizeof(params), hipMemcpyHostToDevice));
     h->sampling = true;
+  });
+}
+
+int mv_set_sampling_truncation(mv_handle h, int32_t top_k, float top_p) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_sampling_truncation: engine was created with "
+               "beam_size 1 (a sampled decode draws beam_size futures per row: create a beam "
+               "handle)");
+    MV_REQUIRE(top_k >= 0, "mv_set_sampling_truncation: top_k %d must be >= 0 (0 = off)",
+               (int)top_k);
+    MV_REQUIRE(top_p > 0.f && top_p <= 1.f, "mv_set_sampling_truncation: top_p %g not in (0, 1] "
+               "(1 = off)", (double)top_p);          // (a NaN fails both comparisons)
+    h->samp_top_k = top_k;
+    h->samp_top_p = top_p;
+    if (!h->samp_params.p) return;                   // mv_set_sampling writes all four words
+    // behind whatever forward still reads the previous limits on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    const uint32_t lim[2] = {(uint32_t)top_k, __builtin_bit_cast(uint32_t, top_p)};
+    HIP_CHECK(hipMemcpy(h->samp_params.p + 2, lim, sizeof(lim), hipMemcpyHostToDevice));
+  });
+}
+
+int mv_download_beam_proposal_logprobs(mv_handle h, float* out) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    download_beam_proposal_logprobs(h, out);
+    drain_events(h);
   });
 }
 

@@ -1087,8 +1087,10 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
   const int Tsteps = ragged ? e->len.steps : Tp;
   if (ragged)
     HIP_CHECK(hipMemsetAsync(e->bm_lp_final.p, 0, (size_t)R * sizeof(float), e->issue));
-  if (ragged && wor)
+  if (ragged && wor) {
     HIP_CHECK(hipMemsetAsync(e->bm_g_final.p, 0, (size_t)R * sizeof(float), e->issue));
+    HIP_CHECK(hipMemsetAsync(e->bm_phi_final.p, 0, (size_t)R * sizeof(float), e->issue));
+  }
   int lpi = 0;
   const int32_t* src = nullptr;  // state row indirection for the next cell step
   const bool sparse = sparse_x_on(e, S);
@@ -1179,6 +1181,10 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
         hipLaunchKernelGGL(ragged_capture_lp_kernel, dim3(cdiv((size_t)n_now * B, 256)), dim3(256),
                            0, e->issue, e->bm_g[lpi].p, e->lens_dev.p, e->bm_g_final.p,
                            n_now * B, B, time);
+      if (ragged && wor)
+        hipLaunchKernelGGL(ragged_capture_lp_kernel, dim3(cdiv((size_t)n_now * B, 256)), dim3(256),
+                           0, e->issue, e->bm_phi[lpi].p, e->lens_dev.p, e->bm_phi_final.p,
+                           n_now * B, B, time);
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, 1, S.xbuf_cls.p, n_next * B);
     } else if (sparse) {
@@ -1226,6 +1232,9 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
     if (g_final != e->bm_g[0].p)
       HIP_CHECK(hipMemcpyAsync(e->bm_g[0].p, g_final, (size_t)R * sizeof(float),
                                hipMemcpyDeviceToDevice, e->issue));
+    // the final phi is the futures' log-probability under the proposal
+    HIP_CHECK(hipMemcpyAsync(e->lq_acc.p, ragged ? e->bm_phi_final.p : e->bm_phi[lpi].p,
+                             (size_t)R * sizeof(float), hipMemcpyDeviceToDevice, e->issue));
   }
 }
 
@@ -1252,6 +1261,7 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
   MV_REQUIRE(!c.use_single_decoder, "%s: use_single_decoder is not supported", who);
   MV_REQUIRE(tail_v2(), "%s needs the v2 decoder tail", who);
   HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
+  if (!scored) HIP_CHECK(hipMemsetAsync(e->lq_acc.p, 0, (size_t)R * sizeof(float), e->issue));
   if (scored) {
     // rows a ragged step does not launch keep step_lp 0 / rank -1 (0xFF bytes: int32 -1)
     const size_t rt = (size_t)R * Tp;
@@ -1303,8 +1313,8 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
         with_rank_j(K, [&](auto j) {
           hipLaunchKernelGGL(mv::sample_step_kernel<decltype(j)::value>, grid, block, 0, e->issue,
-                             logits, orow, rows, B, K, t, shared, e->samp_params.p, lens,
-                             e->bm_lp[0].p, ids, Tp, srow);
+                             logits, orow, rows, B, K, t, shared, e->samp_params.p, 1, lens,
+                             e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr);
         });
       });
       if (time == Tsteps) break;

@@ -442,6 +442,20 @@ void download_beam_gumbels(mv_engine* e, float* out) {
   HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 
+// the futures' log-probability under the PROPOSAL [N, B] of a sampled forward:
+// tempered and truncated, where logprobs is the model's own
+void download_beam_proposal_logprobs(mv_engine* e, float* out) {
+  const mv_config& c = e->cfg;
+  MV_REQUIRE(out, "mv_download_beam_proposal_logprobs: NULL out");
+  MV_REQUIRE(e->last == ForwardKind::Sampled || e->last == ForwardKind::SampledWor,
+             "mv_download_beam_proposal_logprobs: the last forward of this handle was not a "
+             "sampled one (mv_set_sampling); last forward: %s", forward_kind_name(e->last));
+  const size_t R = (size_t)c.batch_size * c.beam_size;
+  HIP_CHECK(hipMemcpyAsync(out, e->lq_acc.p, R * sizeof(float), hipMemcpyDeviceToHost,
+                           e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+}
+
 // ---- scoring of given futures (mv_score_futures)
 
 // Checks the futures on the host and uploads them: ids with a valid cell at every step (a

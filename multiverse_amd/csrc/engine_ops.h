@@ -292,16 +292,56 @@ int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
     DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
     DevBuf<int32_t> di, dpa;
     DevBuf<uint32_t> dprm;
-    const uint32_t params[2] = {seed, __builtin_bit_cast(uint32_t, temperature)};
+    const uint32_t params[4] = {seed, __builtin_bit_cast(uint32_t, temperature), 0u,
+                                __builtin_bit_cast(uint32_t, 1.f)};       // limits off
     ctx.up(dl, logits, R * K);
     ctx.up(dphi, prev_phi, R); ctx.up(dlp, prev_logprob, R); ctx.up(dg, prev_gumbel, R);
-    ctx.up(dprm, params, (size_t)2);
+    ctx.up(dprm, params, (size_t)4);
     nphi.alloc(R); nlp.alloc(R); ng.alloc(R); di.alloc(R); dpa.alloc(R);
     cand.alloc(R * K); lpp.alloc(R * K); qp.alloc(R * K);
     launch_sbs_step(ctx.stream, dl.p, dphi.p, dlp.p, dg.p, cand.p, lpp.p, qp.p, dprm.p, N, B, K,
                     t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B);
     ctx.down(new_phi, nphi, R); ctx.down(new_logprob, nlp, R); ctx.down(new_gumbel, ng, R);
     ctx.down(ids, di, R); ctx.down(parents, dpa, R);
+  });
+}
+
+int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K, int32_t t,
+                      float temperature, uint32_t seed, int32_t top_k, float top_p, int32_t floor,
+                      int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
+    MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
+               (int)R, (int)S);
+    MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "mv_op_sample_step: K = %d cells (one wave holds a row "
+               "of at most %d)", (int)K, 64 * mv::kBeamRankJ);
+    MV_REQUIRE(temperature > 0.f, "mv_op_sample_step: temperature %g must be > 0",
+               (double)temperature);
+    MV_REQUIRE(top_k >= 0, "mv_op_sample_step: top_k %d must be >= 0 (0 = off)", (int)top_k);
+    MV_REQUIRE(top_p > 0.f && top_p <= 1.f, "mv_op_sample_step: top_p %g not in (0, 1] (1 = off)",
+               (double)top_p);
+    MV_REQUIRE(floor >= 1, "mv_op_sample_step: floor %d must be >= 1", (int)floor);
+    OpCtx ctx(device);
+    DevBuf<float> dl, dlp, dq;
+    DevBuf<int32_t> di;
+    DevBuf<uint8_t> dk;
+    DevBuf<uint32_t> dprm;
+    const uint32_t params[4] = {seed, __builtin_bit_cast(uint32_t, temperature), (uint32_t)top_k,
+                                __builtin_bit_cast(uint32_t, top_p)};
+    ctx.up(dl, logits, (size_t)R * K);
+    ctx.up(dprm, params, (size_t)4);
+    dlp.alloc(R); dq.alloc(R); di.alloc(R); dk.alloc((size_t)R * K);
+    HIP_CHECK(hipMemsetAsync(dlp.p, 0, (size_t)R * sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(dq.p, 0, (size_t)R * sizeof(float), ctx.stream));
+    const dim3 grid(cdiv((size_t)R, 4)), block(256);
+    with_rank_j(K, [&](auto j) {
+      hipLaunchKernelGGL(mv::sample_step_kernel<decltype(j)::value>, grid, block, 0, ctx.stream,
+                         dl.p, (int64_t)K, R, S, K, t, 0, dprm.p, floor, (const int32_t*)nullptr,
+                         dlp.p, dq.p, di.p, 1, (int32_t*)nullptr, dk.p);
+    });
+    HIP_CHECK(hipGetLastError());
+    ctx.down(ids, di, R); ctx.down(lp, dlp, R); ctx.down(qlp, dq, R);
+    ctx.down(keep, dk, (size_t)R * K);
   });
 }
 

@@ -68,7 +68,8 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
 // One step of the sampling without replacement (stochastic beam search, kernels_misc.h): the
 // perturbed candidates on one wave per parent row, then the per-sample top-B that carries phi,
 // LP and G.  t = 0-based decode step; K <= 1024, B <= K.  `cand`, `lp_plane`, `q_plane` =
-// [N*B, K] scratch; params = {seed, temperature bits} on the device.
+// [N*B, K] scratch; params = {seed, temperature bits, top_k, top_p bits} on the device.  The
+// truncation's floor is B at the first step (the root needs B children), 1 after it.
 void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_phi,
                      const float* prev_lp, const float* prev_g, float* cand, float* lp_plane,
                      float* q_plane, const uint32_t* params, int N, int B, int K, int t,
@@ -82,7 +83,8 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     hipLaunchKernelGGL(mv::sbs_perturb_kernel<decltype(j)::value>, grid, block, 0, stream, logits,
-                       prev_phi, prev_g, R, B, K, t, params, cand, lp_plane, q_plane);
+                       prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
+                       q_plane);
   });
   hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
@@ -359,7 +361,8 @@ void alloc_buffers(mv_engine* e) {
       e->bm_lp_final.alloc(R);
       e->bm_cand.alloc((size_t)R * K);
       for (int i = 0; i < 2; ++i) { e->bm_phi[i].alloc(R); e->bm_g[i].alloc(R); }
-      e->bm_g_final.alloc(R);
+      e->bm_g_final.alloc(R); e->bm_phi_final.alloc(R);
+      e->lq_acc.alloc(R);
       e->bm_sbs_lp.alloc((size_t)R * K); e->bm_sbs_q.alloc((size_t)R * K);
       e->bm_src_row.alloc(R);
       e->bm_ref.alloc(R);

@@ -231,6 +231,7 @@ struct mv_engine {
   // the perturb kernel leaves the step's lp / q planes for the selection
   DevBuf<float> bm_phi[2], bm_g[2];    // [N, B]; the final G goes to bm_g[0]
   DevBuf<float> bm_g_final;            // [N, B] ragged forward: row n's G after the selection at time L[n]
+  DevBuf<float> bm_phi_final;          // [N, B] the same for phi (the proposal's log-probability)
   DevBuf<float> bm_sbs_lp, bm_sbs_q;   // [N, B, K]
   DevBuf<int32_t> bm_src_row;      // [N*B]
   DevBuf<int32_t> bm_ref;          // [N*B] 1 = some surviving beam continues this state row
@@ -242,11 +243,17 @@ struct mv_engine {
   DevBuf<float> bm_out_reg;        // [N*B, T, K, 2]   traced back
   DevBuf<int32_t> bm_out_ids;      // [N, B, T]
   // sampled multi-future decode (mv_set_sampling): the beam handle draws beam_size futures per
-  // row instead of searching.  {seed, temperature bits} live on the device, where the step
-  // kernel reads them: a captured forward follows a later mv_set_sampling.
+  // row instead of searching.  {seed, temperature bits, top_k, top_p bits} live on the device,
+  // where the step kernels read them: a captured forward follows a later mv_set_sampling or
+  // mv_set_sampling_truncation.
   bool sampling = false;
   int sampling_mode = 0;           // mv_set_sampling_mode: 0 independent draws, 1 without replacement
-  DevBuf<uint32_t> samp_params;    // [2]
+  int32_t samp_top_k = 0;          // mv_set_sampling_truncation: 0 = off
+  float samp_top_p = 1.f;          //                             1 = off
+  DevBuf<uint32_t> samp_params;    // [4]
+  // [N, B] log-probability of each future under the PROPOSAL (tempered, truncated):
+  // the independent sampler accumulates it beside bm_lp[0]; without replacement it is the final phi
+  DevBuf<float> lq_acc;
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps

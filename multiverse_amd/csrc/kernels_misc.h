@@ -1447,6 +1447,90 @@ __device__ __forceinline__ void step_row_log_softmax(const float* __restrict__ r
   lse = logf(sum);
 }
 
+// log_softmax terms of a row already in registers (-inf past K): step_row_log_softmax's
+// arithmetic in its order
+template <int J>
+__device__ __forceinline__ void step_regs_log_softmax(const float (&v)[J], int K, int lane,
+                                                      float& mx, float& lse) {
+  mx = -INFINITY;
+#pragma unroll
+  for (int j = 0; j < J; ++j) mx = fmaxf(mx, v[j]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+  sum = wave_sum(sum);
+  lse = logf(sum);
+}
+
+// ------------------------------------------------------------ truncated sampling
+// Top-k / nucleus limits of the two samplers (include/multiverse_hip.h
+// mv_set_sampling_truncation).  With w = l / temperature, e[k] = exp(w[k] - max w),
+//   c(k) = #{j : l[j] > l[k]},  m(k) = sum of e[j] over {j : l[j] > l[k]},
+//   keep(k) = c(k) < floor || ((top_k == 0 || c(k) < top_k) && (top_p >= 1 || m(k) < top_p * sum_e))
+// keep is an upper set of the logit order: one threshold on an order-preserving integer key of
+// the logit describes it.  The sums run in step_row_log_softmax's order (per lane over j, then
+// wave_sum), so that a fixed-order sum of non-negative terms is monotone in its term set and the
+// predicate is monotone in the threshold.
+
+// Order-preserving key of a float (no NaN): a > b <=> key(a) > key(b); -0 and +0 share a key.
+__device__ __forceinline__ uint32_t float_order_key(float x) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, x + 0.f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// The row in registers (v = logits, -inf past K; w = v / temperature; mxq = max w): bisection over
+// the 32 key bits for the smallest key whose cells are kept, 32 probes of one masked per-lane
+// count and sum over j and two butterflies.  No LDS, no scratch, no indexed register arrays.
+// -> the threshold (keep(k) <=> float_order_key(v[k]) >= threshold); lse_kept = logf of the kept
+// cells' sum of e, taken in the same order.
+template <int J>
+__device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
+                                                            const float (&w)[J], float mxq, int K,
+                                                            int lane, int top_k, float top_p,
+                                                            int floor, float& lse_kept) {
+  uint32_t key[J];
+  float e[J];
+  float sum_e = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const bool in = lane + 64 * j < K;
+    key[j] = in ? float_order_key(v[j]) : 0u;     // (a pad never counts: masked by e and `in`)
+    e[j] = in ? expf(w[j] - mxq) : 0.f;
+    if (in) sum_e += e[j];
+  }
+  sum_e = wave_sum(sum_e);
+  const bool use_p = top_p < 1.f;                 // off means off: never evaluated at top_p >= 1
+  const float mass = top_p * sum_e;
+  uint32_t thr = 0u;                              // the smallest kept key lies in [thr, thr + 2^(bit+1))
+#pragma unroll 1
+  for (int bit = 31; bit >= 0; --bit) {
+    const uint32_t cand = thr | (1u << bit);
+    const uint32_t probe = cand - 1u;             // are the cells of key `probe` kept?
+    int cnt = 0;
+    float m = 0.f;
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const bool above = lane + 64 * j < K && key[j] > probe;
+      cnt += above ? 1 : 0;
+      if (above) m += e[j];
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off, 64);
+    m = wave_sum(m);
+    const bool kept = cnt < floor || ((top_k == 0 || cnt < top_k) && (!use_p || m < mass));
+    if (!kept) thr = cand;                        // uniform: cnt and m are the wave's
+  }
+  float sum_kept = 0.f;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K && key[j] >= thr) sum_kept += e[j];
+  lse_kept = logf(wave_sum(sum_kept));
+  return thr;
+}
+
 // `shared` step: the logits the tail left in the sample's first row, copied to row r's own
 template <int J>
 __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K, int lane,
@@ -1460,20 +1544,24 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // row r = n * S + s, the row held in registers as in beam_rank_kernel (lane l owns
 // k = l + 64 j):
 //   lp = log_softmax(logits[r]);  g[k] = -log(-log(u(s * K + k, seed_n, t)))
-//   id = argmax_k lp[k] / temperature + g[k]   (lowest index among equal scores)
-//   ids[r, t] = id;  lp_acc[r] += lp[id] unless the row is past its length
+//   id = argmax over the KEPT k of lp[k] / temperature + g[k]   (lowest index among equal scores)
+//   ids[r, t] = id;  lp_acc[r] += lp[id], lq_acc[r] += q~[id] unless the row is past its length
+// q~ is the proposal's log-probability: log_softmax(l / temperature) renormalised over the kept
+// cells (step_row_keep_threshold; with both limits off every cell is kept, and at temperature 1
+// q~ is lp bit for bit).
 // logits is the forward's [R, T, K] output at step t (row_stride = T * K), written by the
 // decode tail.  `shared` (step 0): the tail ran once per sample and left the logits in row
 // n * S; rows s > 0 read them there and copy them to their own row.  src_row (step 0): the
-// state row the S rows of sample n continue from.  params: {seed, temperature bits}, read
-// on the device so that a replayed graph follows mv_set_sampling.
+// state row the S rows of sample n continue from.  params: {seed, temperature bits, top_k,
+// top_p bits}, read on the device so that a replayed graph follows mv_set_sampling and
+// mv_set_sampling_truncation.  keep_out (mv_op_sample_step only): the kept set [R, K].
 template <int J>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
-                        int t, int shared, const uint32_t* __restrict__ params,
+                        int t, int shared, const uint32_t* __restrict__ params, int floor,
                         const int32_t* __restrict__ lens, float* __restrict__ lp_acc,
-                        int32_t* __restrict__ ids, int ids_stride,
-                        int32_t* __restrict__ src_row) {
+                        float* __restrict__ lq_acc, int32_t* __restrict__ ids, int ids_stride,
+                        int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1483,16 +1571,32 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   step_row_log_softmax<J>(row, K, lane, v, mx, lse);
   const uint32_t seed = params[0] + (uint32_t)n * kSampleRowSeed;
   const float temperature = __builtin_bit_cast(float, params[1]);
-  float best = -INFINITY, blp = 0.f;
+  const int top_k = (int)params[2];
+  const float top_p = __builtin_bit_cast(float, params[3]);
+  const bool tempered = temperature != 1.f;            // uniform, as is `limited`
+  const bool limited = top_k > 0 || top_p < 1.f;
+  float mxq = mx, lseq = lse;
+  uint32_t thr = 0u;
+  float w[J];
+#pragma unroll
+  for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
+  if (tempered) step_regs_log_softmax<J>(w, K, lane, mxq, lseq);
+  if (limited) thr = step_row_keep_threshold<J>(v, w, mxq, K, lane, top_k, top_p, floor, lseq);
+  float best = -INFINITY, blp = 0.f, blq = 0.f;
   int bi = 0x7fffffff;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
     const int k = lane + 64 * j;
     if (k < K) {
-      const float lp = (v[j] - mx) - lse;
-      const float u = sample_uniform((uint32_t)s * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
-      const float sc = lp / temperature + (-logf(-logf(u)));
-      if (sc > best) { best = sc; bi = k; blp = lp; }   // strict: the lane's lowest index stays
+      const bool kept = !limited || float_order_key(v[j]) >= thr;
+      if (keep_out) keep_out[(size_t)r * K + k] = kept ? 1 : 0;
+      if (kept) {
+        const float lp = (v[j] - mx) - lse;
+        const float u = sample_uniform((uint32_t)s * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
+        const float sc = lp / temperature + (-logf(-logf(u)));
+        // strict: the lane's lowest index stays
+        if (sc > best) { best = sc; bi = k; blp = lp; blq = (w[j] - mxq) - lseq; }
+      }
     }
   }
 #pragma unroll
@@ -1500,12 +1604,13 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
     const float ov = __shfl_xor(best, off, 64);
     const int oi = __shfl_xor(bi, off, 64);
     const float ol = __shfl_xor(blp, off, 64);
-    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; blp = ol; }
+    const float oq = __shfl_xor(blq, off, 64);
+    if (ov > best || (ov == best && oi < bi)) { best = ov; bi = oi; blp = ol; blq = oq; }
   }
   if (shared && s != 0) step_row_copy_out<J>(logits + (size_t)r * row_stride, K, lane, v);
   if (lane == 0) {
     ids[(size_t)r * ids_stride] = min(bi, K - 1);   // (no score ranked: NaN logits; none is made)
-    if (!lens || t < lens[n]) lp_acc[r] += blp;
+    if (!lens || t < lens[n]) { lp_acc[r] += blp; lq_acc[r] += blq; }
     if (src_row) src_row[r] = n;
   }
 }
@@ -1575,32 +1680,17 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 //                       candidate row (the root; its phi and G are read at n * B).
 //   sbs_select_kernel   beam_select_kernel's algorithm over cand; winner j from (b, k) carries
 //                       G = cand, phi = phi_b + q[k], LP = LP_b + lp[k], parent b, id k.
-// params: {seed, temperature bits} of the sampler, read on the device.
-
-// log_softmax terms of a row already in registers (-inf past K): step_row_log_softmax's
-// arithmetic in its order
-template <int J>
-__device__ __forceinline__ void step_regs_log_softmax(const float (&v)[J], int K, int lane,
-                                                      float& mx, float& lse) {
-  mx = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < J; ++j) mx = fmaxf(mx, v[j]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
-  float sum = 0.f;
-#pragma unroll
-  for (int j = 0; j < J; ++j)
-    if (lane + 64 * j < K) sum += expf(v[j] - mx);
-  sum = wave_sum(sum);
-  lse = logf(sum);
-}
+// params: {seed, temperature bits, top_k, top_p bits} of the sampler, read on the device.
+// With a top-k / nucleus limit on (step_row_keep_threshold; floor = B at t == 0, else 1), q is
+// renormalised over the kept cells and a dropped cell is the candidate -inf, never selected.
 
 template <int J>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
-                        const uint32_t* __restrict__ params, float* __restrict__ cand,
-                        float* __restrict__ lp_plane, float* __restrict__ q_plane) {
+                        const uint32_t* __restrict__ params, int floor,
+                        float* __restrict__ cand, float* __restrict__ lp_plane,
+                        float* __restrict__ q_plane) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1616,6 +1706,13 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   if (tempered) step_regs_log_softmax<J>(w, K, lane, mxq, lseq);
+  // top-k / nucleus limits (mv_set_sampling_truncation): q renormalised over the kept cells; a
+  // dropped cell is no candidate (q = cand = -inf, written as such, not computed)
+  const int top_k = (int)params[2];
+  const float top_p = __builtin_bit_cast(float, params[3]);
+  const bool limited = top_k > 0 || top_p < 1.f;   // uniform
+  uint32_t thr = 0u;
+  if (limited) thr = step_row_keep_threshold<J>(v, w, mxq, K, lane, top_k, top_p, floor, lseq);
   const float phi = prev_phi[r], G = prev_g[r];
   float* lp_out = lp_plane + (size_t)r * K;
   float* q_out = q_plane + (size_t)r * K;
@@ -1625,11 +1722,13 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
     const int k = lane + 64 * j;
     if (k < K) {
       const float lp = (v[j] - mx) - lse;
-      const float q = (w[j] - mxq) - lseq;   // == lp bit for bit at temperature 1
+      const bool kept = !limited || float_order_key(v[j]) >= thr;
+      // == lp bit for bit at temperature 1 with the limits off
+      const float q = kept ? (w[j] - mxq) - lseq : -INFINITY;
       lp_out[k] = lp;
-      if (tempered) q_out[k] = q;
+      if (tempered || limited) q_out[k] = q;
       const float u = sample_uniform((uint32_t)b * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
-      w[j] = (phi + q) + (-logf(-logf(u)));
+      w[j] = kept ? (phi + q) + (-logf(-logf(u))) : -INFINITY;
       Z = fmaxf(Z, w[j]);
     }
   }
@@ -1642,7 +1741,7 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
     if (k < K) {
       const float g = w[j], d = g - Z;
       const float vv = d < 0.f ? (G - g) + logf(-expm1f(d)) : -INFINITY;
-      out[k] = (G - fmaxf(vv, 0.f)) - log1pf(expf(-fabsf(vv)));
+      out[k] = g == -INFINITY ? -INFINITY : (G - fmaxf(vv, 0.f)) - log1pf(expf(-fabsf(vv)));
     }
   }
 }
@@ -1697,10 +1796,12 @@ void sbs_select_kernel(const float* __restrict__ cand, const float* __restrict__
       const int par = flat / K;
       const size_t o = (size_t)n * B + sel, pr = (size_t)n * B + par;
       const size_t cell = (size_t)n * B * K + flat;
-      const bool tempered = __builtin_bit_cast(float, params[1]) != 1.f;
+      // the q plane exists when the proposal differs from the model: tempered or truncated
+      const bool has_q = __builtin_bit_cast(float, params[1]) != 1.f || (int)params[2] > 0 ||
+                         __builtin_bit_cast(float, params[3]) < 1.f;
       const float lpk = lp_plane[cell];
       new_g[o] = wv;
-      new_phi[o] = prev_phi[pr] + (tempered ? q_plane[cell] : lpk);
+      new_phi[o] = prev_phi[pr] + (has_q ? q_plane[cell] : lpk);
       new_lp[o] = prev_lp[pr] + lpk;
       ids[o] = flat - par * K;
       parents[o] = par;

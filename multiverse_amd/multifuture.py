@@ -269,6 +269,8 @@ def model_config(args, batch_size=1, max_pred_len=None):
       sample_temperature=float(getattr(args, "sample_temperature", 1.0)),
       sample_seed=int(getattr(args, "sample_seed", 0)),
       sample_without_replacement=bool(getattr(args, "sample_without_replacement", False)),
+      sample_top_k=int(getattr(args, "sample_top_k", 0)),
+      sample_top_p=float(getattr(args, "sample_top_p", 1.0)),
       use_teacher_forcing=False, is_train=False,
       scene_h=args.scene_h, scene_w=args.scene_w, scene_class=args.scene_class,
       use_soft_grid_class=args.use_soft_grid_class,
@@ -402,6 +404,28 @@ def wor_importance_weights(logprobs, gumbels):
     raw = p / -np.expm1(-(np.exp(lp - kappa) - p))
   raw[..., 0] = p[..., 0]
   return raw, raw / raw.sum(axis=-1, keepdims=True)
+
+
+def proposal_importance_weights(logprobs, proposal_logprobs):
+  """Self-normalised importance weights of INDEPENDENTLY sampled futures whose proposal differs
+  from the model (a temperature != 1, a top-k / nucleus limit): logprobs, proposal_logprobs
+  [..., S] of one forward (Engine.forward_beam: the model's exact log-probabilities and
+  "proposal_logprobs", those of the distribution the futures were drawn from) ->
+  softmax_s(logprobs - proposal_logprobs), float64 [..., S] summing to 1.
+  sum_s w_s f(future_s) estimates E[f] under the model RESTRICTED TO THE PROPOSAL'S SUPPORT (and
+  renormalised there): a future with a dropped cell has proposal probability 0, is never drawn,
+  and no weight can bring it back -- with a temperature alone the support is everything and the
+  estimate is of the model itself.  Consistent, biased of order 1 / S as every self-normalised
+  estimator.  Futures sampled WITHOUT replacement are not independent draws: use
+  wor_importance_weights on their logprobs and gumbels instead."""
+  lp = np.asarray(logprobs, dtype=np.float64)
+  lq = np.asarray(proposal_logprobs, dtype=np.float64)
+  if lp.shape != lq.shape:
+    raise ValueError("proposal_importance_weights: logprobs %s and proposal_logprobs %s must "
+                     "agree" % (lp.shape, lq.shape))
+  d = lp - lq
+  w = np.exp(d - d.max(axis=-1, keepdims=True))
+  return w / w.sum(axis=-1, keepdims=True)
 
 
 # ------------------------------------------------- scoring given futures (not in the reference)

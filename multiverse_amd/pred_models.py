@@ -230,11 +230,14 @@ class Model(object):
     self.engine.set_compute_mode(self.compute_mode)
     # config.sample_futures: the beam_size futures of a row are sampled from the model's step
     # distribution (config.sample_temperature, config.sample_seed) instead of searched
-    # (config.sample_without_replacement: distinct futures, stochastic beam search)
+    # (config.sample_without_replacement: distinct futures, stochastic beam search;
+    # config.sample_top_k / sample_top_p: the step distribution cut to its head)
     if getattr(config, "sample_futures", False):
       self.engine.set_sampling(getattr(config, "sample_temperature", 1.0),
                                getattr(config, "sample_seed", 0),
-                               bool(getattr(config, "sample_without_replacement", False)))
+                               bool(getattr(config, "sample_without_replacement", False)),
+                               top_k=int(getattr(config, "sample_top_k", 0)),
+                               top_p=float(getattr(config, "sample_top_p", 1.0)))
     self.global_step = 0
     # names of the fetches, kept for callers that introspect them
     self.grid_pred_decoded = ["grid_pred_decoded_%d" % i
@@ -258,7 +261,15 @@ class Model(object):
         not getattr(config, "sample_futures", False):
       raise _lib.MvError("sample_without_replacement is a mode of the sampled decode: it needs "
                          "sample_futures")
+    top_k, top_p = getattr(config, "sample_top_k", 0), getattr(config, "sample_top_p", 1.0)
+    if (int(top_k) != 0 or float(top_p) != 1.0) and not getattr(config, "sample_futures", False):
+      raise _lib.MvError("sample_top_k / sample_top_p limit the sampled decode: they need "
+                         "sample_futures")
     if getattr(config, "sample_futures", False):
+      if int(top_k) < 0:
+        raise _lib.MvError("sample_top_k %r must be >= 0 (0 = off)" % (top_k,))
+      if not 0.0 < float(top_p) <= 1.0:
+        raise _lib.MvError("sample_top_p %r not in (0, 1] (1 = off)" % (top_p,))
       if not getattr(config, "use_beam_search", False):
         raise _lib.MvError("sample_futures draws beam_size futures per row: it needs a "
                            "multi-future (use_beam_search) model, not a greedy one")
@@ -321,6 +332,8 @@ class Model(object):
       beam = [arrs["logits"], arrs["ids"], arrs["logprobs"]]
       if "gumbels" in arrs:      # sampled without replacement: the perturbed scores [N, B]
         beam.append(arrs["gumbels"])
+      # (truncated sampling: the log-probability under the proposal is a key of
+      # run_forward_decoded's dict; this positional list keeps its members)
       return cls, reg, beam
     cls, reg = (self.engine.forward_greedy_compact(feed) if compact
                 else self.engine.forward_greedy(feed))
@@ -341,7 +354,8 @@ class Model(object):
     """One decode whose fetch is what a multi-future caller uses, decoded on the device:
     {"trajs": float64 [N, B, T, 2]} (B = 1 for a greedy model) and, for a beam-search model,
     "ids" [N, B, T], "logprobs" [N, B], "gumbels" [N, B] when the model samples without
-    replacement, and -- with occupancy -- "occupancy" float32 [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
+    replacement, "proposal_logprobs" [N, B] when it samples under a top-k / nucleus limit
+    (config.sample_top_k / sample_top_p), and -- with occupancy -- "occupancy" float32 [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
     [N, B, T, K] is fetched as well, for a caller that stores them).  grid_centers: list over
     scales of [H, W, 2] cell centres (default: the feed's, else those already resident)."""
     cfg = self.config
