@@ -628,6 +628,18 @@ int  mv_op_sample_step(int device, const float* logits /* [R, K] */, int32_t R, 
                        float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
                        uint8_t* keep /* [R, K] */);
 
+/* Light cone of the class encoder (MV_ENC_CONE): the wave tiles of the F(3,3) gate
+ * kernel each encoder step computes, as every upload builds them from the labels.  Host only: no
+ * device is touched.  labels [N, T] cell indices of an H x W grid; r0: reach of a step's own input
+ * (1 with the scene encoder, 2 without).  A tile is 32 consecutive triple-cells
+ * q = (row * ceil(H / 3) + y / 3) * W + x of the N + 1 rows (row N: the input-free background row),
+ * ntile = ceil((N + 1) * ceil(H / 3) * W / 32).  lists [T, 4 + 2 * ntile]: count | 3 zeros | the
+ * active tile indices, ascending, zero-filled | per tile 1 = computed at this step; cells [T]: the
+ * cells the step computes.  Returns ntile (lists / cells may be NULL to ask for it), -1 on bad
+ * arguments. */
+int  mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,
+                       int32_t r0, int32_t* lists, int64_t* cells);
+
 /* Backward of one ConvLSTMCell step (tf.gradients through the cell): inputs as
  * mv_op_convlstm_step (c == h == NULL: zero state) plus d h', d c' [M,H,W,C];
  * outputs d x [M,H,W,Cx], d h, d c [M,H,W,C], d kernel [3,3,Cx+C,4C], d biases [4C]. */

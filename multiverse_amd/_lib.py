@@ -48,6 +48,7 @@ EXPORTED_SYMBOLS = [
     "mv_download_scores", "mv_time_score_resident",
     "mv_set_sampling_mode", "mv_download_beam_gumbels", "mv_op_sbs_step",
     "mv_set_sampling_truncation", "mv_download_beam_proposal_logprobs", "mv_op_sample_step",
+    "mv_enc_cone_build",
 ]
 
 
@@ -229,6 +230,8 @@ def load():
   lib.mv_op_sample_step.argtypes = [C.c_int, _fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                     C.c_float, C.c_uint32, C.c_int32, C.c_float, C.c_int32,
                                     _ip, _fp, _fp, _u8p]
+  if hasattr(lib, "mv_enc_cone_build"):     # (an A/B build through MV_LIB_PATH may predate it)
+    lib.mv_enc_cone_build.argtypes = [_ip] + [C.c_int32] * 5 + [_ip, C.POINTER(C.c_int64)]
   lib.mv_op_sbs_step.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, C.c_uint32, _fp, _fp, _fp, _ip, _ip]
   lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
@@ -1268,6 +1271,25 @@ def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, d
                            N, B, K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
                            fptr(phi), fptr(lp), fptr(g), iptr(ids), iptr(parents)))
   return phi, lp, g, ids, parents
+
+
+def enc_cone_build(labels, H, W, r0=1):
+  """Tile lists of the class encoder's light cone as every upload builds them
+  (mv_enc_cone_build; host only).  labels [N, T] -> (lists [T, 4 + 2 * ntile] int32,
+  cells [T] int64, ntile)."""
+  lib = load()
+  labels = np.ascontiguousarray(labels, dtype=np.int32)
+  N, T = labels.shape
+  ip = lambda a: a.ctypes.data_as(_ip)
+  ntile = lib.mv_enc_cone_build(None, N, T, int(H), int(W), int(r0), None, None)
+  if ntile < 0:
+    raise MvError("mv_enc_cone_build: bad arguments")
+  lists = np.zeros((T, 4 + 2 * ntile), np.int32)
+  cells = np.zeros((T,), np.int64)
+  if lib.mv_enc_cone_build(ip(labels), N, T, int(H), int(W), int(r0), ip(lists),
+                           cells.ctypes.data_as(C.POINTER(C.c_int64))) < 0:
+    raise MvError("mv_enc_cone_build: a label is not a cell of the %d x %d grid" % (H, W))
+  return lists, cells, int(ntile)
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0):

@@ -99,6 +99,17 @@ struct ConvLstmArgs {
   const int32_t* sx_hot;       // hot cell of row r: sx_hot[(r / sx_hot_div) * sx_hot_stride]
   const uint32_t* sx_cellyx;   // [H*W]: y << 16 | x
   int32_t sx_hot_stride, sx_hot_div, sx_rad, sx_by_class;
+  // --- light cone of the class encoder (sparse x, F(3,3) row-triple kernel in its exact tiling;
+  // gate_plan.h enc_cone_planned, engine_io.h build_enc_cone).  The encoder's state starts at
+  // zero and its x is one hot cell per row and step, so outside the cone of the observed cells a
+  // row's state IS the state of an input-free row: the BACKGROUND row, row rows - 1 of the
+  // problem, computed once.  cone_list: [count | 3 pad | wave-tile indices] of this step (null:
+  // every tile); cone_prev: per wave tile, 1 = computed at the previous step (null: all were) --
+  // a tile that was not reads the background row's state instead of its own.
+  const int32_t* cone_list;
+  const int32_t* cone_prev;
+  int32_t cone_on;             // 1: row rows - 1 is the background row (no hot cell)
+  int32_t cone_cells;          // host-side: cells this launch executes (0: rows * H * W)
 };
 
 struct ConvLstmGroup {

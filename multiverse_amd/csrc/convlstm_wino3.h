@@ -159,6 +159,11 @@ struct Wn3TransformItem {
   _Float16* out;
   const int32_t* src_row;    // optional [rows]
   int32_t rows, H, W, Cc;    // Cc: channels, a multiple of 16
+  // light cone of the class encoder (ConvLstmArgs::cone_*): the tiles to transform (null: all),
+  // which (row, triple) tiles the previous step computed (null: all), rows - 1 = background row
+  const int32_t* cone_list;
+  const int32_t* cone_prev;
+  int32_t cone_cells;        // host-side: cells transformed (0: rows * H * W)
 };
 constexpr int kW3TrGroup = 8;
 struct Wn3TransformGroup {
@@ -189,7 +194,12 @@ void wino3_transform_kernel(const Wn3TransformGroup g) {
   const int ntile = (Q_total + 31) >> 5;
   const int wid = block * 4 + wave;
   if (wid >= ntile * KG) return;
-  const int tile = wid / KG, cg = wid - tile * KG;
+  int tile = wid / KG;
+  const int cg = wid - tile * KG;
+  if (it.cone_list) {        // the grid is the dense one: waves past the count have nothing to do
+    if (tile >= it.cone_list[0]) return;
+    tile = it.cone_list[4 + tile];
+  }
   const int col = lane & 31, half = lane >> 5;
   const int q = tile * 32 + col;
   const bool valid = q < Q_total;
@@ -202,12 +212,22 @@ void wino3_transform_kernel(const Wn3TransformGroup g) {
     xpos = pc - t * W;
   }
   const int sr = (valid && it.src_row) ? it.src_row[r] : r;
+  // light cone: rows d1 .. d3 are the lane's own triple, d0 / d4 the neighbour triples'; a
+  // (row, triple) tile the previous step did not compute holds the background row's values
+  int sr_up = sr, sr_mid = sr, sr_dn = sr;
+  if (it.cone_prev && valid) {
+    const int bg = it.rows - 1;
+    const int* prev = it.cone_prev;
+    sr_mid = prev[q >> 5] ? sr : bg;
+    sr_up = (y0 > 0 && !prev[(q - W) >> 5]) ? bg : sr;
+    sr_dn = (y0 + 3 < H && !prev[(q + W) >> 5]) ? bg : sr;
+  }
   f16x8 dh[5], dl[5];
 #pragma unroll
   for (int i = 0; i < 5; ++i) {
     const int rho = y0 - 1 + i;
     const bool ok = valid & (rho >= 0) & (rho < H);
-    const long long m = (long long)sr * HW + rho * W + xpos;
+    const long long m = (long long)(i == 0 ? sr_up : (i == 4 ? sr_dn : sr_mid)) * HW + rho * W + xpos;
     const size_t o = ((size_t)(m >> 5) * KG + cg) * 512 + (size_t)(half * 256 + (int)(m & 31) * 8);
     const f16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     dh[i] = ok ? *reinterpret_cast<const f16x8*>(it.p0 + o) : z;
@@ -283,7 +303,19 @@ __device__ __forceinline__ void convlstm_wino3_body(const ConvLstmWinoArgs& p, i
   const int H = a.H, W = a.W, HW = H * W, C = a.C, Cx = a.Cx;
   const int Ht = (H + 2) / 3, Kt = Ht * W;
   const int Q_total = a.rows * Kt;
-  const int q_own = mt * kTriples + wave * kOwn;       // first triple-cell the wave owns
+  int q_own = mt * kTriples + wave * kOwn;             // first triple-cell the wave owns
+  // light cone of the class encoder (exact tiling only): wave w of row tile mt takes entry
+  // 4 mt + w of the step's tile list; the grid is the dense one (a captured graph must not hold
+  // one batch's count), so a workgroup past the count leaves here, before its first barrier
+  constexpr bool kCone = !HALO && !BF16D;
+  bool cone_bg_src = false;                            // the wave's tile reads the background row's c
+  if (kCone && a.cone_list) {
+    const int cnt = a.cone_list[0];
+    if (mt * WAVES >= cnt) return;
+    const int li = mt * WAVES + wave;
+    q_own = li < cnt ? 32 * a.cone_list[4 + li] : Q_total;
+  }
+  if (kCone && a.cone_prev && q_own < Q_total) cone_bg_src = a.cone_prev[q_own >> 5] == 0;
   const int q_wave = HALO ? q_own - 1 : q_own;         // ... and lane 0's
   const bool wave_live = q_own < Q_total;        // dead waves still copy and hit barriers
   const int col = lane & 31, half = lane >> 5;
@@ -351,7 +383,7 @@ __device__ __forceinline__ void convlstm_wino3_body(const ConvLstmWinoArgs& p, i
     cell[e] = (y0 + e) * W + xpos;
   }
   if (wave_live) {
-    const int src_c0 = (valid && a.src_row_c) ? a.src_row_c[r] : r;
+    const int src_c0 = cone_bg_src ? a.rows - 1 : ((valid && a.src_row_c) ? a.src_row_c[r] : r);
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
       otab[e * 32 + col] = okc[e] ? (uint32_t)(src_c0 * HW + cell[e]) * rowb : kNone;
@@ -680,8 +712,10 @@ __device__ __forceinline__ void convlstm_wino3_body(const ConvLstmWinoArgs& p, i
   }
   // sparse x: hot cell of the lane's image
   int hot_y = 0, hot_x = 0;
+  // (light cone: the background row has no hot cell -- row 0's stands in, its terms are dropped)
+  const bool bg_row = kCone && a.cone_on && r == a.rows - 1;
   if (a.sx_corr) {
-    const int hr = a.sx_hot_div > 1 ? r / a.sx_hot_div : r;
+    const int hr = bg_row ? 0 : (a.sx_hot_div > 1 ? r / a.sx_hot_div : r);
     const uint32_t hyx = a.sx_cellyx[a.sx_hot[(size_t)hr * a.sx_hot_stride]];
     hot_y = (int)(hyx >> 16); hot_x = (int)(hyx & 0xffffu);
   }
@@ -712,14 +746,14 @@ __device__ __forceinline__ void convlstm_wino3_body(const ConvLstmWinoArgs& p, i
           // row and row block behind the bias row's): a cell outside the radius reads the
           // clamped table row and drops it
           const int dy = y - hot_y, dxh = xpos - hot_x, rad = a.sx_rad;
-          const bool inr = okc[e] && dy >= -rad && dy <= rad && dxh >= -rad && dxh <= rad;
+          const bool inr = okc[e] && !bg_row && dy >= -rad && dy <= rad && dxh >= -rad && dxh <= rad;
           const int dyc = dy < -rad ? -rad : (dy > rad ? rad : dy);
           const int dxc = dxh < -rad ? -rad : (dxh > rad ? rad : dxh);
           const int side = 2 * rad + 1;
           const int idx = a.sx_by_class
                               ? 3 * (hot_y == 0 ? 0 : (hot_y == H - 1 ? 2 : 1)) +
                                     (hot_x == 0 ? 0 : (hot_x == W - 1 ? 2 : 1))
-                              : (valid ? r : 0);
+                              : ((valid && !bg_row) ? r : 0);
           const float* ct = a.sx_corr +
               ((size_t)idx * side * side + (dyc + rad) * side + (dxc + rad)) * 4 * C + ch;
           const float keep = inr ? 1.0f : 0.0f;

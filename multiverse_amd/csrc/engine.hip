@@ -907,7 +907,7 @@ int mv_set_compute_mode(mv_handle h, int32_t mode) {
         const size_t rows = (size_t)c.batch_size * ((i % 2 == 0) ? c.beam_size : 1);
         // [pad | plane 0 | pad | plane 1], pads zero (out-of-image taps read them)
         h->px16[i].alloc(2 * (rows * K * xc + mv::kPlaneSlack + mv::kPlanePad));
-        h->ph16[i].alloc(2 * (rows * K * c.hidden_size + mv::kPlaneSlack + mv::kPlanePad));
+        h->ph16[i].alloc(2 * ((rows + 1) * K * c.hidden_size + mv::kPlaneSlack + mv::kPlanePad));
         HIP_CHECK(hipMemset(h->px16[i].p, 0, h->px16[i].n * sizeof(_Float16)));
         if (c.activation != 0) h->xexp[i].alloc(65);    // never inside a graph capture
         if (wino3_possible(mode, c.activation)) {    // F(3,3): the pre-transformed operands
@@ -915,7 +915,8 @@ int mv_set_compute_mode(mv_handle h, int32_t mode) {
           for (int s = 0; s < c.num_scales; ++s) {
             if (!h->sc[s].use) continue;
             vx = std::max(vx, wino3_scratch_elems((int)rows, h->sc[s].H, h->sc[s].W, (int)xc));
-            vh = std::max(vh, wino3_scratch_elems((int)rows, h->sc[s].H, h->sc[s].W, c.hidden_size));
+            // (one more row: the class encoder's background row, enc_cone_on)
+            vh = std::max(vh, wino3_scratch_elems((int)rows + 1, h->sc[s].H, h->sc[s].W, c.hidden_size));
           }
           if (vx) h->pv3x[i].alloc(vx);
           if (vh) h->pv3h[i].alloc(vh);

@@ -191,7 +191,9 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
 // instead of in every one of the C / 16 column-block workgroups of the gate kernel.
 double queue_wino3_transform(std::vector<mv::Wn3TransformItem>& tr, const mv::Wn3TransformItem& it) {
   tr.push_back(it);
-  return (double)it.rows * it.H * it.W * it.Cc * 4.0 * (1.0 + 5.0 / 3.0);     // bytes moved
+  // (light cone: the tiles the step transforms, not the whole operand)
+  const double cells = it.cone_cells ? (double)it.cone_cells : (double)it.rows * it.H * it.W;
+  return cells * it.Cc * 4.0 * (1.0 + 5.0 / 3.0);     // bytes moved
 }
 
 // The grouped gate launch in the planned form.  p16: the prepared problems; packs: per problem
@@ -233,8 +235,11 @@ void gate_group_cost(const std::vector<ConvLstmArgs>& probs, double& flops, doub
                      double& dense) {
   flops = bytes = dense = 0;
   for (const auto& a : probs) {
-    const double M = (double)a.rows * a.H * a.W;
-    dense += 2.0 * M * 9.0 * (a.Cx + a.C) * 4.0 * a.C;
+    // light cone of the class encoder: the reference computes the batch's rows, the launch the
+    // cone's tiles (and the background row)
+    const double Md = (double)(a.rows - (a.cone_on ? 1 : 0)) * a.H * a.W;
+    const double M = a.cone_cells ? (double)a.cone_cells : (double)a.rows * a.H * a.W;
+    dense += 2.0 * Md * 9.0 * (a.Cx + a.C) * 4.0 * a.C;
     // sparse x: the x k-steps are not executed (table terms in the epilogue)
     const double cx = a.sx_corr ? 0.0 : (double)a.Cx;
     flops += 2.0 * M * 9.0 * (cx + (a.zero_state ? 0 : a.C)) * 4.0 * a.C;
@@ -268,7 +273,9 @@ ForwardPlan plan_gate_groups(mv_engine* e, const GatePrep* const* groups, int ng
       const int sl = groups[g]->slot0 + i;
       fp[n++] = ForwardProblem{&groups[g]->p16[i], groups[g]->cells[i], e->pv3x[sl].n, e->pv3h[sl].n};
     }
-  return plan_forward_group(e->compute_mode, fp, n);
+  const ForwardPlan pl = plan_forward_group(e->compute_mode, fp, n);
+  check_cone_plan(pl, fp, n);
+  return pl;
 }
 
 // Input transforms (F(3,3)) and the grouped gate launch of a prepared group, on e->issue.
@@ -291,7 +298,8 @@ void issue_gate_group(mv_engine* e, const GatePrep& g, const ForwardPlan& pl) {
     if (!a.zero_state) {
       v3h[i] = e->pv3h[sl].p;
       tr3_bytes += queue_wino3_transform(tr3, {q.h16, q.h_plane_stride, v3h[i], a.src_row_h,
-                                               a.rows, a.H, a.W, a.C});
+                                               a.rows, a.H, a.W, a.C, a.cone_list, a.cone_prev,
+                                               a.cone_cells});
     }
     if (has_dense_x(a)) {
       v3x[i] = e->pv3x[sl].p;
@@ -303,7 +311,8 @@ void issue_gate_group(mv_engine* e, const GatePrep& g, const ForwardPlan& pl) {
     launch(e, "wino3_transform", 0, tr3_bytes, [&] {
       mv::launch_wino3_transforms(tr3.data(), (int)tr3.size(), e->issue);
     });
-  for (int i = 0; i < n; ++i) e->gate_rows += g.p16[i].f.rows;
+  for (int i = 0; i < n; ++i)      // (the batch's rows: not the encoder's background row)
+    e->gate_rows += g.p16[i].f.rows - (g.p16[i].f.cone_on ? 1 : 0);
   launch(e, "convlstm_step", g.flops, g.bytes, [&] {
     launch_gate_group(pl, g.p16.data(), packs, w_hwio, v3x, v3h, n, e->issue);
   }, g.dense, pl.mfma_factor);
@@ -479,10 +488,26 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
       });
       }
       const int cc = cur.cls[s];
+      // light cone (gate_plan.h enc_cone_planned): one more row, the input-free background row
+      const bool cone = sparse && enc_cone_on(e, S);
       probs.push_back(conv_problem(e, S.enc_cls, S.xbuf_cls.p, S.cls_h[cc].p,
                                    S.cls_c[cc].p, nullptr, nullptr, S.cls_h[cc ^ 1].p,
-                                   S.cls_c[cc ^ 1].p, N, S.H, S.W, t == 0, 0,
+                                   S.cls_c[cc ^ 1].p, N + (cone ? 1 : 0), S.H, S.W, t == 0, 0,
                                    /*want_h16=*/t + 1 < T || !c.use_gnn));
+      if (cone) {
+        // the first and the last step run every tile; a step reads the flags of the one before
+        // it unless that one ran every tile
+        ConvLstmArgs& a = probs.back();
+        const size_t stride = enc_cone_step_elems(Nb + 1, S.H, S.W);
+        const int ntile = enc_cone_tiles(Nb + 1, S.H, S.W);
+        a.cone_on = 1;
+        a.cone_list = (t > 0 && t + 1 < T) ? S.cone.p + (size_t)t * stride : nullptr;
+        a.cone_prev = t > 1 ? S.cone.p + (size_t)(t - 1) * stride + 4 + ntile : nullptr;
+        // (fits: conv_problem bounds rows * H * W * C by 2^31)
+        MV_REQUIRE(S.cone_cells[t] > 0 && S.cone_cells[t] <= (int64_t)(N + 1) * S.H * S.W,
+                   "internal: cone cell count %lld", (long long)S.cone_cells[t]);
+        a.cone_cells = (int32_t)S.cone_cells[t];
+      }
       // the class encoder's h' is read as fp32 only by the graph attention in front of the
       // first decoder step (and by the tiled-first-step A/B path of the beam decoder); the
       // regression encoder's never

@@ -31,6 +31,97 @@ void check_labels(const mv_engine* e, int s, const int32_t* labels) {
                "grid_obs_labels[%d][%zu] = %d out of range [0,%d)", s, i, labels[i], K);
 }
 
+// ---- light cone of the class encoder (gate_plan.h enc_cone_planned): which wave tiles of the
+// gate kernel -- 32 consecutive triple-cells q = (row * ceil(H / 3) + triple) * W + x -- each
+// encoder step has to compute.  The encoder starts from the zero state and its x is one hot cell
+// per row and step, so a row's state equals the input-free (background) row's except at DIRTY
+// cells.  A cell is dirty after step t if the step's own x reaches it (within Chebyshev distance
+// r0 of the observed cell: 1 for scene_conv * one_hot, 2 for grid_emb(one_hot), the kernels'
+// sx_rad) or if the h operand of its gate convolution held a dirty cell.  That operand is NOT the
+// 3 x 3 neighbourhood: the F(3,3) form computes the three rows of a triple from the FIVE input
+// rows 3k - 1 .. 3k + 3, and the rows a 3 x 3 stencil would not read cancel only in exact
+// arithmetic -- they reach the result's last bits.  So dirt spreads one column per step along x
+// (the direct taps) and from any of those five rows to the whole triple along y, and the result
+// stays bit-identical to the dense encoder's.  A tile is active at step t if it holds a dirty
+// cell or any cell of the background row (row N).  The first step (zero state: no main loop) and
+// the last (the decoders want a dense state) run every tile.  Host loop over the labels, no
+// device; W <= 32 (a grid row is one 32-bit column mask).
+//   out [T][enc_cone_step_elems(N + 1, H, W)]: count | 3 pad | active tile indices, ascending |
+//       per tile 1 = computed at this step;  cells [T]: cells the step executes
+void build_enc_cone(const int32_t* labels, int N, int T, int H, int W, int r0, int32_t* out,
+                    int64_t* cells) {
+  const int Ht = (H + 2) / 3, Kt = Ht * W, Q = (N + 1) * Kt;
+  const int ntile = enc_cone_tiles(N + 1, H, W);
+  const size_t stride = enc_cone_step_elems(N + 1, H, W);
+  const uint32_t wmask = W >= 32 ? 0xffffffffu : ((1u << W) - 1u);
+  std::vector<uint32_t> dirty((size_t)N * H, 0u), tmp(H);
+  for (int t = 0; t < T; ++t) {
+    int32_t* blk = out + (size_t)t * stride;
+    int32_t* list = blk + 4;
+    int32_t* flag = blk + 4 + ntile;
+    const bool all = t == 0 || t == T - 1;
+    for (int g = 0; g < ntile; ++g) flag[g] = all ? 1 : 0;
+    if (!all)
+      for (int q = N * Kt; q < Q; ++q) flag[q >> 5] = 1;          // the background row
+    for (int n = 0; n < N; ++n) {
+      uint32_t* d = &dirty[(size_t)n * H];
+      for (int k = 0; k < Ht; ++k) {          // the h operand: rows 3k - 1 .. 3k + 3, columns +- 1
+        uint32_t m = 0;
+        for (int y = std::max(3 * k - 1, 0); y <= std::min(3 * k + 3, H - 1); ++y) m |= d[y];
+        m = (m | (m << 1) | (m >> 1)) & wmask;
+        for (int y = 3 * k; y < std::min(3 * k + 3, H); ++y) tmp[y] = m;
+      }
+      const int cell = labels[(size_t)n * T + t], ys = cell / W, xs = cell % W;
+      uint32_t xm = 0;                        // the step's own x
+      for (int x = std::max(xs - r0, 0); x <= std::min(xs + r0, W - 1); ++x) xm |= 1u << x;
+      for (int y = 0; y < H; ++y) d[y] = tmp[y] | ((y >= ys - r0 && y <= ys + r0) ? xm : 0u);
+      if (all) continue;
+      for (int k = 0; k < Ht; ++k) {
+        uint32_t m = 0;
+        for (int y = 3 * k; y < std::min(3 * k + 3, H); ++y) m |= d[y];
+        for (int x = 0; m; ++x, m >>= 1)
+          if (m & 1u) flag[(n * Kt + k * W + x) >> 5] = 1;
+      }
+    }
+    int cnt = 0;
+    int64_t nc = 0;
+    for (int g = 0; g < ntile; ++g) {
+      if (!flag[g]) continue;
+      list[cnt++] = g;
+      for (int q = 32 * g; q < std::min(32 * g + 32, Q); ++q)
+        nc += std::min(3, H - 3 * ((q % Kt) / W));
+    }
+    for (int g = cnt; g < ntile; ++g) list[g] = 0;
+    blk[0] = cnt; blk[1] = blk[2] = blk[3] = 0;
+    if (cells) cells[t] = nc;
+  }
+}
+
+// do the uploads of this scale build the lists?  Geometry and the switch only: the compute mode
+// may still change before the forward, which asks enc_cone_on (engine_setup.h)
+bool enc_cone_wanted(const mv_engine* e, const ScaleState& S) {
+  return S.use && enc_cone_geometry(e->cfg.obs_len, S.H, S.W, e->cfg.batch_size);
+}
+size_t enc_cone_elems(const mv_engine* e, const ScaleState& S) {
+  return (size_t)e->cfg.obs_len * enc_cone_step_elems(e->cfg.batch_size + 1, S.H, S.W);
+}
+// the lists of `labels` into `dst` (host; pinned slot or the scale's own staging vector) and the
+// per-step cell counts into the scale: once per upload, on every path that brings labels
+void build_scale_cone(mv_engine* e, ScaleState& S, const int32_t* labels, int32_t* dst) {
+  S.cone_cells.assign(e->cfg.obs_len, 0);
+  build_enc_cone(labels, e->cfg.batch_size, e->cfg.obs_len, S.H, S.W, e->no_scene() ? 2 : 1, dst,
+                 S.cone_cells.data());
+  S.cone_ready = true;
+}
+void upload_scale_cone(mv_engine* e, ScaleState& S, const int32_t* labels) {
+  if (!enc_cone_wanted(e, S)) return;
+  S.cone_host.resize(enc_cone_elems(e, S));
+  S.cone.alloc(S.cone_host.size());
+  build_scale_cone(e, S, labels, S.cone_host.data());
+  HIP_CHECK(hipMemcpyAsync(S.cone.p, S.cone_host.data(), S.cone_host.size() * sizeof(int32_t),
+                           hipMemcpyHostToDevice, e->stream));
+}
+
 void upload_inputs(mv_engine* e, const mv_inputs* in) {
   const mv_config& c = e->cfg;
   const size_t N = c.batch_size, T = c.obs_len;
@@ -55,6 +146,7 @@ void upload_inputs(mv_engine* e, const mv_inputs* in) {
     check_labels(e, s, in->grid_obs_labels[s]);
     HIP_CHECK(hipMemcpyAsync(S.labels.p, in->grid_obs_labels[s],
                              N * T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    upload_scale_cone(e, S, in->grid_obs_labels[s]);
     HIP_CHECK(hipMemcpyAsync(S.obs_reg.p, in->grid_obs_regress[s],
                              N * T * S.K * 2 * sizeof(float), hipMemcpyHostToDevice,
                              e->stream));
@@ -94,6 +186,7 @@ void upload_inputs_compact(mv_engine* e, const mv_inputs_compact* in) {
     check_labels(e, s, in->grid_obs_labels[s]);
     HIP_CHECK(hipMemcpyAsync(S.labels.p, in->grid_obs_labels[s],
                              N * T * sizeof(int32_t), hipMemcpyHostToDevice, e->stream));
+    upload_scale_cone(e, S, in->grid_obs_labels[s]);
     hipLaunchKernelGGL(mv::regress_from_xy_kernel, dim3(cdiv(N * T * S.K, 256)), dim3(256), 0,
                        e->stream, e->xy_dev.p, S.centers.p, S.obs_reg.p, (int)(N * T), (int)T,
                        S.K, in->num_rows);
@@ -128,10 +221,10 @@ void download_outputs(mv_engine* e, mv_outputs* out) {
 // returns; mv_collect_greedy waits for the OLDEST submission and hands its outputs over.
 // With two slots the PCIe traffic of batches k+1 and k-1 runs under the kernels of batch k.
 // Layout of a slot: obs_scene | scene_feat (N*T frames max) | per used scale labels,
-// obs_regress || per used scale out_cls, out_reg (max_pred_len).
+// obs_regress, class-encoder tile lists || per used scale out_cls, out_reg (max_pred_len).
 struct PipeLayout {
   size_t obs_scene = 0, scene_feat = 0, labels[MV_MAX_SCALES] = {0, 0},
-         obs_reg[MV_MAX_SCALES] = {0, 0}, in_bytes = 0;
+         obs_reg[MV_MAX_SCALES] = {0, 0}, cone[MV_MAX_SCALES] = {0, 0}, in_bytes = 0;
   size_t out_cls[MV_MAX_SCALES] = {0, 0}, out_reg[MV_MAX_SCALES] = {0, 0}, out_bytes = 0;
 };
 static PipeLayout pipe_layout(const mv_engine* e) {
@@ -148,6 +241,9 @@ static PipeLayout pipe_layout(const mv_engine* e) {
     const size_t K = e->sc[s].K;
     L.labels[s] = o; o = al(o + N * T * sizeof(int32_t));
     L.obs_reg[s] = o; o = al(o + N * T * K * 2 * sizeof(float));
+    // the class encoder's tile lists travel with the labels they were built from
+    L.cone[s] = o;
+    if (enc_cone_wanted(e, e->sc[s])) o = al(o + enc_cone_elems(e, e->sc[s]) * sizeof(int32_t));
   }
   L.in_bytes = o;
   for (int s = 0; s < c.num_scales; ++s) {
@@ -218,6 +314,8 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
     check_labels(e, s, in->grid_obs_labels[s]);
     memcpy(pin + L.labels[s], in->grid_obs_labels[s], N * T * sizeof(int32_t));
     memcpy(pin + L.obs_reg[s], in->grid_obs_regress[s], N * T * S.K * 2 * sizeof(float));
+    if (enc_cone_wanted(e, S))
+      build_scale_cone(e, S, in->grid_obs_labels[s], reinterpret_cast<int32_t*>(pin + L.cone[s]));
   }
   MV_REQUIRE(!e->lens_set, "mv_submit_greedy: per-row prediction lengths are set "
              "(mv_set_pred_lengths); the pipelined forward is uniform -- clear them first");
@@ -240,6 +338,10 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
     if (!S.use) continue;
     d2d(S.labels.p, sl.dev + L.labels[s], N * T * sizeof(int32_t));
     d2d(S.obs_reg.p, sl.dev + L.obs_reg[s], N * T * S.K * 2 * sizeof(float));
+    if (enc_cone_wanted(e, S)) {
+      S.cone.alloc(enc_cone_elems(e, S));
+      d2d(S.cone.p, sl.dev + L.cone[s], enc_cone_elems(e, S) * sizeof(int32_t));
+    }
   }
   e->num_frames = sl.num_frames;
   e->pred_len = sl.pred_len;

@@ -345,6 +345,18 @@ int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int
   });
 }
 
+int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,
+                      int32_t r0, int32_t* lists, int64_t* cells) {
+  if (N <= 0 || T <= 0 || H <= 0 || W <= 0 || W > 32 || r0 < 0) return -1;
+  if (lists) {
+    if (!labels) return -1;
+    for (size_t i = 0; i < (size_t)N * T; ++i)
+      if (labels[i] < 0 || labels[i] >= H * W) return -1;
+    build_enc_cone(labels, N, T, H, W, r0, lists, cells);
+  }
+  return enc_cone_tiles(N + 1, H, W);
+}
+
 int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* h,
                        const float* kernel, const float* biases, const float* dh_new,
                        const float* dc_new, int32_t M, int32_t H, int32_t W, int32_t Cx,

@@ -337,7 +337,8 @@ void alloc_buffers(mv_engine* e) {
     S.labels.alloc(N * T);
     S.obs_reg.alloc(N * T * K * 2);
     for (int i = 0; i < 2; ++i) {
-      S.cls_c[i].alloc(R * K * C); S.cls_h[i].alloc(R * K * C);
+      // (one more row: the class encoder's background row, enc_cone_on)
+      S.cls_c[i].alloc((R + 1) * K * C); S.cls_h[i].alloc((R + 1) * K * C);
       S.reg_c[i].alloc(N * K * C); S.reg_h[i].alloc(N * K * C);
     }
     if (c.use_gnn) S.cls_hg.alloc(R * K * C);
@@ -571,6 +572,25 @@ bool sparse_x_on(const mv_engine* e, const ScaleState& S) {
   return !off && e->compute_mode != 0 && !e->train && S.use && S.H >= 3 && S.W >= 3 &&
          S.dec_cls.Cx == c.emb_size && c.emb_size % 16 == 0 && c.scene_conv_dim % 16 == 0 &&
          c.scene_conv_dim <= 64;
+}
+
+// Does the class encoder of this scale run on its light cone in the forward being issued
+// (gate_plan.h enc_cone_planned decides; this gathers what it asks)?  Asked after ensure_params:
+// the packs say which form the encoder cells take.  A ragged forward whose encoders run on a
+// prefix of the batch keeps the dense encoder (the lists are built for the whole batch).
+bool enc_cone_on(mv_engine* e, ScaleState& S) {
+  const mv_config& c = e->cfg;
+  bool step_exact = true;
+  for (int s = 0; s < c.num_scales; ++s) {
+    ScaleState& O = e->sc[s];
+    if (!O.use) continue;
+    step_exact = step_exact &&
+                 cone_step_member_ok(O.H, O.W, O.enc_cls.wpw3.p &&
+                                                   (c.use_single_decoder || O.enc_reg.wpw3.p));
+  }
+  return S.cone_ready && S.cone.p && e->rows_at(0) == c.batch_size &&
+         enc_cone_planned(e->compute_mode, c.activation, sparse_x_on(e, S), step_exact, c.obs_len,
+                          S.H, S.W, c.hidden_size, c.batch_size);
 }
 
 void ensure_params(mv_engine* e) {

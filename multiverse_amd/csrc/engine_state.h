@@ -170,6 +170,12 @@ struct ScaleState {
   // decoder's -- by-class tables of the encoder kernel and the shared person_pred/grid_emb
   DevBuf<float> sx_enc_bias, sx_enc_tab;    // [9][4C], [9][25][4C]
   bool sx_valid = false;
+  // light cone of the class encoder (engine_io.h build_enc_cone): the tile lists of every encoder
+  // step, built from the labels at upload; cone_cells [T_o]: cells each step executes
+  DevBuf<int32_t> cone;
+  std::vector<int32_t> cone_host;
+  std::vector<int64_t> cone_cells;
+  bool cone_ready = false;
 };
 
 }  // namespace

@@ -32,6 +32,8 @@ struct GateKnobs {
   bool wgrad_wide_x;    // MV_WGRAD_WIDE_X=1: the x rows on the wide tile too
   bool wgrad_wino, wgrad_wino_bf16;   // MV_WGRAD_WINO, MV_WGRAD_WINO_BF16 (=0: off)
   int wgrad_x_splits;   // MV_WGRAD_X_SPLITS (12)
+  int enc_cone;         // MV_ENC_CONE: 0 the class encoder computes every tile of every row; 1 (default)
+                        // light cone from kEncConeMinBatch rows on; 2 at any batch size
 };
 
 inline const GateKnobs& gate_knobs() {
@@ -62,6 +64,7 @@ inline const GateKnobs& gate_knobs() {
     g.wgrad_wide_x = num("MV_WGRAD_WIDE_X", 0) == 1;
     g.wgrad_wino = on("MV_WGRAD_WINO"); g.wgrad_wino_bf16 = on("MV_WGRAD_WINO_BF16");
     g.wgrad_x_splits = num("MV_WGRAD_X_SPLITS", 12);
+    g.enc_cone = num("MV_ENC_CONE", 1);
     return g;
   }();
   return k;
@@ -114,6 +117,48 @@ inline size_t wino3_scratch_elems(int rows, int H, int W, int Cc) {
 // may an engine in this mode ever launch the F(3,3) form?  (activation 0: no per-tensor x exponent)
 inline bool wino3_possible(int mode, int activation) {
   return mode == 1 && gate_knobs().wino && gate_knobs().wino3 && activation == 0;
+}
+
+// ------------------------------------------------------------------ light cone of the class encoder
+// The class encoder starts from the zero state and its x is one hot cell per row and step (sparse
+// x), so outside the cone of the observed cells a row's state equals that of an input-free row.
+// Where this answers yes, the encoder problem carries one more row -- that background row -- and
+// its h-steps between the first and the last run only the wave tiles the cone touches
+// (ConvLstmArgs::cone_*; lists: engine_io.h build_enc_cone).  The lists exist for the F(3,3)
+// row-triple kernel in its exact tiling only, so the rule restates what leads there: the f16x3
+// mode with the form possible, a grid of whole row triples, whole channel blocks -- and a width
+// of exactly 32, where a wave tile IS one (row, triple): narrower grids, whose tiles hold two
+// triples or straddle two images, stay dense.  `sparse`: sparse_x_on of the scale; `step_exact`:
+// every member of the step's launches passes cone_step_member_ok (one tiling and one form per
+// step).  obs_len <= 2 has no step between the first and the last.  In the F(3,3) form the
+// cone widens by a whole row TRIPLE per step (build_enc_cone): an observed cell's x reaches up to
+// two triples and the step after it up to four, so a grid of fewer than five triples (9 x 16:
+// three) would pay for the background row and skip next to nothing: it stays dense.
+// The background row adds 1 / batch to every step of a coned encoder, and on the benchmark's feed
+// the cone skips 17 % of the h-steps' tiles: from 16 rows on the row costs at most a third of
+// that; below, down to batch 1 where it doubles the encoder, the dense encoder stays
+// (MV_ENC_CONE=2 cones any batch: the small shapes of the tests).
+constexpr int kEncConeMinBatch = 16;
+inline bool enc_cone_geometry(int obs_len, int H, int W, int batch) {
+  const int k = gate_knobs().enc_cone;
+  return k != 0 && (k == 2 || batch >= kEncConeMinBatch) && obs_len >= 3 && H % 3 == 0 &&
+         H / 3 >= 5 && W == 32;
+}
+// a scale whose encoders share the step's launches: exact tiling (no HALO), and the encoder cells
+// carry the F(3,3) pack (has_packs: enc_cls and, where it runs, enc_reg)
+inline bool cone_step_member_ok(int H, int W, bool has_packs) {
+  return H >= 3 && W > 0 && 32 % W == 0 && has_packs;
+}
+inline bool enc_cone_planned(int mode, int activation, bool sparse, bool step_exact, int obs_len,
+                             int H, int W, int C, int batch) {
+  return enc_cone_geometry(obs_len, H, W, batch) && sparse && step_exact &&
+         wino3_possible(mode, activation) && C % mv::kWnCh == 0;
+}
+// wave tiles (32 triple-cells) of a coned problem of `rows` rows, the background row included
+inline int enc_cone_tiles(int rows, int H, int W) { return (rows * ((H + 2) / 3) * W + 31) / 32; }
+// int32 elements of one step's lists: [count | 3 pad | tile list | computed-at-this-step flags]
+inline size_t enc_cone_step_elems(int rows, int H, int W) {
+  return 4 + 2 * (size_t)enc_cone_tiles(rows, H, W);
 }
 
 enum class GateForm { Direct16, Wino2, Wino3, Bf16, Bf16T };
@@ -183,6 +228,12 @@ inline ForwardPlan plan_forward_group(int mode, const ForwardProblem* p, int n) 
   }
   pl.mfma_factor = den > 0 ? num / den : (wino3 ? 5.0 / 3.0 : 2.0);
   return pl;
+}
+// a coned problem runs in the exact F(3,3) tiling or not at all (enc_cone_planned promised it)
+inline void check_cone_plan(const ForwardPlan& pl, const ForwardProblem* p, int n) {
+  for (int i = 0; i < n; ++i)
+    MV_REQUIRE(!p[i].q->f.cone_on || (pl.form == GateForm::Wino3 && !pl.halo),
+               "internal: a coned class-encoder step was planned outside the exact F(3,3) tiling");
 }
 
 // ------------------------------------------------------------------ dgrad
