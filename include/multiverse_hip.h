@@ -286,6 +286,30 @@ int  mv_download_beam_ids(mv_handle h, int32_t* ids, float* logprobs);
  * until the last forward's outputs have been decoded.  While lengths are set, mv_train_* and
  * mv_submit_greedy fail with a message. */
 int  mv_set_pred_lengths(mv_handle h, const int32_t* lengths /* [N]; NULL clears */);
+/* Per-row observation lengths: one forward encodes tracks of different history lengths.
+ * lengths[n] = Lo[n] in [1, obs_len] (checked at the forward); NULL clears.  Sticky until
+ * cleared; applies to every forward kind (greedy, beam, sampled, sampled without replacement,
+ * scored).  Row n's observations are RIGHT-ALIGNED: columns obs_len - Lo[n] .. obs_len - 1 of
+ * obs_scene, grid_obs_labels[s], grid_obs_regress[s] (and obs_xy of the compact upload) hold
+ * them, so the decoders' first inputs stay labels[:, -1] and obs_grid_reg[:, -1].  The columns
+ * before them are ignored: they must hold in-range labels / frame indices and finite floats (the
+ * upload checks read them), and no output depends on them.
+ * Meaning: row n of every output is, bit for bit, row n of a uniform forward of an engine
+ * created with obs_len = Lo[n], the same weights, fed the row's last Lo[n] columns.  The encoders
+ * start from the zero state at the row's first observation, and scene_mean is the mean over the
+ * row's own Lo[n] frames, summed in ascending time order and divided by (float)Lo[n].  This is
+ * the reference's model at another obs_len, NOT dynamic_rnn's left-aligned copy-through of a
+ * sequence_length (the reference's obs_length placeholder, which its feed code always fills with
+ * obs_len): that would take the decoders' first inputs from padding.
+ * Encoder step t (0-based) issues each chain on the prefix of p_t = 1 + max{n < rows that decode
+ * at all : Lo[n] >= obs_len - t} rows, and a step with no such row is not launched: lengths
+ * sorted descending launch no unstarted row (sum_t p_t = sum_n Lo[n]); any order is correct.
+ * Combines with mv_set_pred_lengths (row n equals the obs_len = Lo[n] engine's forward at
+ * pred_len = L[n]).  With all Lo[n] == obs_len the forward is the uniform one, launch for launch;
+ * otherwise it is issued eagerly in graph mode and the class encoder's light cone stays off, and
+ * mv_train_*, mv_attack_begin / mv_attack_step and mv_submit_greedy fail with a message that
+ * names the call. */
+int  mv_set_obs_lengths(mv_handle h, const int32_t* lengths /* [N]; NULL clears */);
 /* sum of the row counts over every ConvLSTM problem of every grouped gate launch of the last
  * forward (encoders and decoders): what the forward really launched, without timing anything */
 int  mv_last_forward_gate_rows(mv_handle h, int64_t* rows);

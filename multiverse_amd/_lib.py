@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_sampling_mode", "mv_download_beam_gumbels", "mv_op_sbs_step",
     "mv_set_sampling_truncation", "mv_download_beam_proposal_logprobs", "mv_op_sample_step",
     "mv_enc_cone_build",
+    "mv_set_obs_lengths",
 ]
 
 
@@ -221,6 +222,8 @@ def load():
   lib.mv_beam_occupancy.argtypes = [h, _fp]
   lib.mv_download_beam_ids.argtypes = [h, _ip, _fp]
   lib.mv_set_pred_lengths.argtypes = [h, _ip]
+  if hasattr(lib, "mv_set_obs_lengths"):    # (an A/B build through MV_LIB_PATH may predate it)
+    lib.mv_set_obs_lengths.argtypes = [h, _ip]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
@@ -529,6 +532,7 @@ class Engine(object):
     self._keep = keep
     self._pred_len = inp.pred_len
     self._set_pred_lengths(feed.get("pred_lengths"))
+    self._set_obs_lengths(feed.get("obs_lengths"))
     return inp
 
   def _set_pred_lengths(self, lengths):
@@ -544,6 +548,21 @@ class Engine(object):
       raise MvError("pred_lengths: %d values for batch_size %d" % (lens.size, self.cfg.batch_size))
     check(self.lib.mv_set_pred_lengths(self.handle, iptr(lens)), self.handle)
     self._lengths_set = True
+
+  def _set_obs_lengths(self, lengths):
+    """Per-row observation lengths of the next forward (feed["obs_lengths"], int [N], the
+    observations right-aligned; include/multiverse_hip.h mv_set_obs_lengths); None clears the
+    ones a previous feed set.  Called with every feed that is uploaded."""
+    if lengths is None:
+      if getattr(self, "_obs_lengths_set", False):
+        check(self.lib.mv_set_obs_lengths(self.handle, None), self.handle)
+        self._obs_lengths_set = False
+      return
+    lens = i32(lengths).reshape(-1)
+    if lens.size != self.cfg.batch_size:
+      raise MvError("obs_lengths: %d values for batch_size %d" % (lens.size, self.cfg.batch_size))
+    check(self.lib.mv_set_obs_lengths(self.handle, iptr(lens)), self.handle)
+    self._obs_lengths_set = True
 
   def set_sampling(self, temperature=1.0, seed=0, without_replacement=False, top_k=0,
                    top_p=1.0):
@@ -800,6 +819,7 @@ class Engine(object):
       inp.grid_obs_labels[s] = iptr(lab)
     self._pred_len = inp.pred_len
     self._set_pred_lengths(feed.get("pred_lengths"))
+    self._set_obs_lengths(feed.get("obs_lengths"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len

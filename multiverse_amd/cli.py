@@ -230,6 +230,10 @@ _MF_FLAGS = [
     # multifuture_path under the model (teacher-forced log-likelihood per step, csrc/
     # kernels_misc.h score_step_kernel) into this pickle and print the exact NLL table
     ("--score_gt", str, None),
+    # not in the reference: a track may have 1 .. obs_length observed frames; a short one is
+    # encoded over its own frames, as a model of that obs_length would (multifuture.inference_feed
+    # right-aligns it, the engine takes one observation length per row: mv_set_obs_lengths)
+    ("--allow_short_obs", B, None),
 ]
 
 

@@ -326,6 +326,38 @@ int mv_set_pred_lengths(mv_handle h, const int32_t* lengths) {
   });
 }
 
+int mv_set_obs_lengths(mv_handle h, const int32_t* lengths) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    const int N = h->cfg.batch_size, T = h->cfg.obs_len;
+    // behind whatever still reads the previous lengths / join list on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->obs.reset();
+    if (!lengths) {
+      h->obs_lens_set = false;
+      h->obs_lens_host.clear();
+      return;
+    }
+    // (the bound [1, obs_len] is checked at the forward, as the prediction lengths' is)
+    h->obs_lens_host.assign(lengths, lengths + N);
+    // the rows in the order they join the encoders: step obs_len - Lo[n], ascending
+    std::vector<int32_t> join;
+    h->obs_join_at.assign((size_t)T + 1, 0);
+    for (int t = 0; t < T; ++t) {
+      h->obs_join_at[t] = (int)join.size();
+      for (int n = 0; n < N; ++n)
+        if (lengths[n] == T - t) join.push_back(n);
+    }
+    h->obs_join_at[T] = (int)join.size();
+    join.resize((size_t)N, 0);            // (rows with a length out of range: the forward fails)
+    HIP_CHECK(hipMemcpy(h->obs_lens_dev.p, lengths, (size_t)N * sizeof(int32_t),
+                        hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(h->obs_join_rows.p, join.data(), (size_t)N * sizeof(int32_t),
+                        hipMemcpyHostToDevice));
+    h->obs_lens_set = true;
+  });
+}
+
 int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -496,6 +528,9 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
                "clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); training encodes every row over obs_len frames -- clear "
+               "them first", "mv_train_init");
     MV_REQUIRE(tc->optimizer >= 0 && tc->optimizer <= 3, "Optimizer not implemented: %d "
                "(0 adadelta, 1 momentum, 2 adam, 3 rmsprop; reference pred_models.py:1667-1681)",
                tc->optimizer);
@@ -542,6 +577,9 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
                "clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); training encodes every row over obs_len frames -- clear "
+               "them first", "mv_train_forward_backward");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_forward_backward: give both inputs and targets, or neither "
                "(resident)");
@@ -578,6 +616,9 @@ int mv_train_apply(mv_handle h, float grad_scale) {
                "clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); training encodes every row over obs_len frames -- clear "
+               "them first", "mv_train_apply");
     train_apply(h, grad_scale);
   });
 }
@@ -589,6 +630,9 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
                "clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); training encodes every row over obs_len frames -- clear "
+               "them first", "mv_train_step");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_step: give both inputs and targets, or neither (resident)");
     train_fwd_bwd(h, in, tg, out);
@@ -691,6 +735,9 @@ int mv_attack_begin(mv_handle h) {
                "there are no scene features");
     MV_REQUIRE(h->train, "mv_train_init has not been called");
     MV_REQUIRE(h->inputs_ready, "no inputs uploaded");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); the attack runs the training forward, which encodes every "
+               "row over obs_len frames -- clear them first", "mv_attack_begin");
     TrainState& t = TS(h);
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
     t.scene_clean.alloc((size_t)h->cfg.batch_size * h->cfg.obs_len * h->cfg.scene_h *
@@ -749,6 +796,9 @@ int mv_attack_step(mv_handle h, float epsilon, float step) {
   return guarded(h, [&] {
     MV_REQUIRE(!h->no_scene(), "mv_attack_step: the model has no scene encoder (scene_conv_dim 0): "
                "there are no scene features");
+    MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
+               "(mv_set_obs_lengths); the attack runs the training forward, which encodes every "
+               "row over obs_len frames -- clear them first", "mv_attack_step");
     MV_REQUIRE(h->train && TS(h).have_dscene && TS(h).scene_clean.p,
                "mv_attack_step: mv_attack_begin + mv_train_forward_backward first");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;

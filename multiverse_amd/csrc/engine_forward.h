@@ -416,7 +416,8 @@ void run_scene(mv_engine* e) {
       hipLaunchKernelGGL(mv::scene_mean_kernel, dim3(cdiv(total, 256)), dim3(256),
                          0, e->issue, e->scene_conv[s].p, e->obs_scene.p,
                          S.scene_mean.p, rows, c.obs_len, S.K,
-                         c.scene_conv_dim);
+                         c.scene_conv_dim,
+                         e->obs.ragged ? e->obs_lens_dev.p : (const int32_t*)nullptr);
     });
   }
 }
@@ -441,9 +442,27 @@ enum : int { kChainCls = 1, kChainReg = 2, kChainAll = 3 };
 void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
                            std::vector<ConvLstmArgs>& probs) {
   const mv_config& c = e->cfg;
-  // N: the rows the encoders run on (ragged forward: those that decode at all); the sparse-x
-  // tables of the encoder keep the batch's row layout
-  const int N = e->rows_at(0), Nb = c.batch_size, T = c.obs_len, D = c.scene_conv_dim;
+  // N: the rows the step runs on (ragged forward: those that decode at all; obs-ragged forward:
+  // the prefix that has started by step t); the sparse-x tables of the encoder keep the batch's
+  // row layout
+  const int N = e->enc_rows_at(t), Nb = c.batch_size, T = c.obs_len, D = c.scene_conv_dim;
+  // obs-ragged forward: the first step that has rows takes the zero-state form; later steps
+  // clear the state rows of the rows that join (one launch for the chains of this call)
+  const int t0 = e->obs.ragged ? e->obs.first : 0;
+  const int njoin = (e->obs.ragged && t > t0) ? e->obs_join_at[t + 1] - e->obs_join_at[t] : 0;
+  mv::ZeroRowsArgs zr{};
+  int nzr = 0, zrK = 0;
+  auto join_rows = [&](float* cbuf, float* hbuf, int K) {
+    if (!njoin) return;
+    mv::ZeroRowsJob& j = zr.job[nzr++];
+    j.c = cbuf; j.h = hbuf; j.K = K;
+    zrK = std::max(zrK, K);
+    auto it = e->planes.find(hbuf);
+    if (e->compute_mode != 0 && it != e->planes.end()) {
+      j.p0 = it->second.p;
+      j.p1 = e->compute_mode == 2 ? nullptr : it->second.p + it->second.n;
+    }
+  };
   for (int s = 0; s < c.num_scales; ++s) {
     {
       ScaleState& S = e->sc[s];
@@ -468,7 +487,7 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
           });
         }
       } else if (sparse) {
-        if (t == 0)      // the tables of all T_o steps in one launch
+        if (t == t0)     // the tables of all T_o steps in one launch
           launch(e, "sx_encoder_corr", 2.0 * nc * D * T, 4.0 * nc * T, [&] {
             hipLaunchKernelGGL(mv::sx_encoder_corr_kernel,
                                dim3(cdiv((size_t)4 * c.hidden_size, 256), 9,
@@ -492,8 +511,9 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
       const bool cone = sparse && enc_cone_on(e, S);
       probs.push_back(conv_problem(e, S.enc_cls, S.xbuf_cls.p, S.cls_h[cc].p,
                                    S.cls_c[cc].p, nullptr, nullptr, S.cls_h[cc ^ 1].p,
-                                   S.cls_c[cc ^ 1].p, N + (cone ? 1 : 0), S.H, S.W, t == 0, 0,
+                                   S.cls_c[cc ^ 1].p, N + (cone ? 1 : 0), S.H, S.W, t == t0, 0,
                                    /*want_h16=*/t + 1 < T || !c.use_gnn));
+      join_rows(S.cls_c[cc].p, S.cls_h[cc].p, S.K);
       if (cone) {
         // the first and the last step run every tile; a step reads the flags of the one before
         // it unless that one ran every tile
@@ -527,19 +547,32 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
       // x = grid_obs_regress[:, t] is read in place through the row stride
       const size_t row = (size_t)S.K * 2;
       const int cr = cur.reg[s];
-      if (!c.use_single_decoder)     // single decoder: the regression encoder feeds nothing
+      if (!c.use_single_decoder) {   // single decoder: the regression encoder feeds nothing
         probs.push_back(conv_problem(e, S.enc_reg, S.obs_reg.p + (size_t)t * row,
                                      S.reg_h[cr].p, S.reg_c[cr].p, nullptr, nullptr,
                                      S.reg_h[cr ^ 1].p, S.reg_c[cr ^ 1].p, N, S.H, S.W,
-                                     t == 0, (size_t)T * row));
+                                     t == t0, (size_t)T * row));
+        join_rows(S.reg_c[cr].p, S.reg_h[cr].p, S.K);
+      }
       if (!c.use_single_decoder) probs.back().skip_h32 = 1;
       cur.reg[s] ^= 1;
     }
   }
+  if (nzr) {
+    zr.rows = e->obs_join_rows.p + e->obs_join_at[t];
+    zr.nrows = njoin; zr.C = c.hidden_size;
+    const size_t total = (size_t)njoin * zrK * (c.hidden_size / 8);    // 8 channels per thread
+    launch(e, "enc_join_zero", 0, (double)nzr * total * 8 * 12.0, [&] {
+      hipLaunchKernelGGL(mv::zero_state_rows_kernel, dim3(cdiv(total, 256), nzr), dim3(256), 0,
+                         e->issue, zr);
+    });
+  }
 }
 
 void run_encoders(mv_engine* e, Cursors& cur, bool pairs) {
-  for (int t = 0; t < e->cfg.obs_len; ++t) {
+  // (obs-ragged forward: a step no row has reached is not launched and moves no cursor; every
+  // row ends in the buffer the last step writes, which the decoders find through `cur`)
+  for (int t = e->obs.ragged ? e->obs.first : 0; t < e->cfg.obs_len; ++t) {
     if (!pairs) {
       std::vector<ConvLstmArgs> probs;
       encoder_step_problems(e, cur, t, kChainAll, probs);
@@ -1435,6 +1468,22 @@ void plan_ragged(mv_engine* e) {
   if (!uniform) e->len.build(e->lens_host, Tp);
 }
 
+// The per-row observation lengths of this forward (mv_set_obs_lengths): checked against
+// obs_len, and the started-row prefix of every encoder step over the rows that decode at all
+// (after plan_ragged / plan_scored).  All lengths == obs_len (or none set): the uniform forward.
+void plan_obs(mv_engine* e) {
+  e->obs.reset();
+  if (!e->obs_lens_set) return;
+  const int N = e->cfg.batch_size, T = e->cfg.obs_len;
+  bool uniform = true;
+  for (int n = 0; n < N; ++n) {
+    MV_REQUIRE(e->obs_lens_host[n] >= 1 && e->obs_lens_host[n] <= T,
+               "obs_lengths[%d] = %d not in [1, obs_len=%d]", n, e->obs_lens_host[n], T);
+    uniform = uniform && e->obs_lens_host[n] == T;
+  }
+  if (!uniform) e->obs.build(e->obs_lens_host, T, e->rows_at(0));
+}
+
 // The plan of a scoring forward: the lengths came with the futures (mv_upload_score_futures
 // checked them), one per future.  Uniform only if EVERY future runs to pred_len; otherwise the
 // per-sample maxima L[n] give the active-row prefixes and go to lens_dev, where the finalisers
@@ -1494,9 +1543,10 @@ void run_forward(mv_engine* e, ForwardKind kind) {
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
   if (kind == ForwardKind::Scored) plan_scored(e); else plan_ragged(e);
+  plan_obs(e);
   // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
-  // is issued eagerly
-  if (!e->graph_mode || e->profiling || e->len.ragged) {
+  // is issued eagerly; so is an obs-ragged one
+  if (!e->graph_mode || e->profiling || e->len.ragged || e->obs.ragged) {
     e->gate_rows = 0;
     enqueue_forward(e, kind);
     if (e->len.ragged) finish_ragged(e, beam);

@@ -319,6 +319,8 @@ void pipeline_submit(mv_engine* e, const mv_inputs* in) {
   }
   MV_REQUIRE(!e->lens_set, "mv_submit_greedy: per-row prediction lengths are set "
              "(mv_set_pred_lengths); the pipelined forward is uniform -- clear them first");
+  MV_REQUIRE(!e->obs_lens_short(), "mv_submit_greedy: per-row observation lengths are set "
+             "(mv_set_obs_lengths); the pipelined forward is uniform -- clear them first");
   sl.num_frames = scene ? in->num_scene_frames : 0; sl.pred_len = in->pred_len;
   // copy stream: the whole input block in one transfer (it must not start before the
   // slot's previous fetch has left the same pinned / staging buffers: collect waited d2h)

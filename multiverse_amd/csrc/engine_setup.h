@@ -318,6 +318,8 @@ void alloc_buffers(mv_engine* e) {
   const bool scene = !e->no_scene();     // no scene encoder: no scene inputs, no scene stack
   e->obs_scene.alloc(N * T);
   e->lens_dev.alloc(N);
+  e->obs_lens_dev.alloc(N);
+  e->obs_join_rows.alloc(N);
   if (scene) e->scene_feat.alloc(maxU * c.scene_h * c.scene_w * c.scene_class);
   int hh = c.scene_h, ww = c.scene_w;
   for (int i = 0; i < c.num_scales; ++i) {
@@ -577,7 +579,9 @@ bool sparse_x_on(const mv_engine* e, const ScaleState& S) {
 // Does the class encoder of this scale run on its light cone in the forward being issued
 // (gate_plan.h enc_cone_planned decides; this gathers what it asks)?  Asked after ensure_params:
 // the packs say which form the encoder cells take.  A ragged forward whose encoders run on a
-// prefix of the batch keeps the dense encoder (the lists are built for the whole batch).
+// prefix of the batch keeps the dense encoder (the lists are built for the whole batch), and so
+// does an obs-ragged one (mv_set_obs_lengths: the lists and the one background row are built for
+// a common start).
 bool enc_cone_on(mv_engine* e, ScaleState& S) {
   const mv_config& c = e->cfg;
   bool step_exact = true;
@@ -588,7 +592,7 @@ bool enc_cone_on(mv_engine* e, ScaleState& S) {
                  cone_step_member_ok(O.H, O.W, O.enc_cls.wpw3.p &&
                                                    (c.use_single_decoder || O.enc_reg.wpw3.p));
   }
-  return S.cone_ready && S.cone.p && e->rows_at(0) == c.batch_size &&
+  return S.cone_ready && S.cone.p && e->rows_at(0) == c.batch_size && !e->obs.ragged &&
          enc_cone_planned(e->compute_mode, c.activation, sparse_x_on(e, S), step_exact, c.obs_len,
                           S.H, S.W, c.hidden_size, c.batch_size);
 }

@@ -142,6 +142,29 @@ struct LengthPlan {
   }
 };
 
+// Per-sample observation lengths Lo[n] in [1, obs_len] as a launch plan (mv_set_obs_lengths;
+// DESIGN.md 8.9).  The observations are right-aligned: row n JOINS the encoders at step
+// obs_len - Lo[n], from the zero state.  A forward whose lengths are not all obs_len is
+// OBS-RAGGED: encoder step t issues its launches on the prefix of
+// rows[t] = 1 + max{n < rows_at(0) : Lo[n] >= obs_len - t} rows, and the first step that has
+// rows (`first`) runs the zero-state form.  At a later step the rows that join have their
+// state rows (c, h and the operand planes of h) cleared in front of the gate launch, so the
+// ordinary form reads the zero state for them (mv_engine::obs_join_rows lists them by step).
+struct ObsPlan {
+  bool ragged = false;               // the forward being issued / issued last is obs-ragged
+  int first = 0;
+  std::vector<int> rows;             // [obs_len] of that forward
+  void reset() { ragged = false; first = 0; }
+  void build(const std::vector<int32_t>& Lo, int obs_len, int live_rows) {
+    rows.assign((size_t)obs_len, 0);
+    for (int n = 0; n < live_rows; ++n)
+      for (int t = obs_len - Lo[n]; t < obs_len; ++t) rows[t] = n + 1;   // n ascending: the max
+    first = 0;
+    while (first < obs_len && rows[first] == 0) ++first;
+    ragged = true;
+  }
+};
+
 struct ScaleState {
   int H = 0, W = 0, K = 0;
   bool use = false;
@@ -222,6 +245,24 @@ struct mv_engine {
   bool lens_set = false;
   LengthPlan len;
   int rows_at(int t) const { return len.rows_at(t, cfg.batch_size); }
+  // per-row observation lengths (mv_set_obs_lengths; sticky until cleared): Lo[n] in [1, obs_len],
+  // a host copy, a device copy (the scene mean's window) and the rows in the order they join
+  // the encoders (obs_join_rows [N], ascending join step; obs_join_at [obs_len + 1] its offsets);
+  // `obs` is the plan of the forward being issued / issued last.
+  std::vector<int32_t> obs_lens_host;
+  DevBuf<int32_t> obs_lens_dev;      // [N]
+  DevBuf<int32_t> obs_join_rows;     // [N]
+  std::vector<int> obs_join_at;
+  bool obs_lens_set = false;
+  ObsPlan obs;
+  // set and not all obs_len: what training, the attack calls and the pipelined forward refuse
+  bool obs_lens_short() const {
+    if (!obs_lens_set) return false;
+    for (int32_t l : obs_lens_host) if (l != cfg.obs_len) return true;
+    return false;
+  }
+  // rows encoder step t runs on
+  int enc_rows_at(int t) const { return obs.ragged ? obs.rows[(size_t)t] : rows_at(0); }
   // rows of every ConvLSTM problem of every grouped gate launch of the last forward
   // (mv_last_forward_gate_rows); a replayed graph carries the count of its capture
   int64_t gate_rows = 0;

@@ -138,18 +138,59 @@ void scene_proj1x1_mfma_kernel(const float* __restrict__ in, const float* __rest
 // mean over the T_o observed frames of the per-sample scene feature
 // (tf.reduce_mean(scene_features, axis=1), code/pred_models.py:826-828).
 // conv [U, K, D] (K = H*W), obs_scene [N, T], out [N, K, D].
+// obs_lens (mv_set_obs_lengths; NULL: every row has T frames): row n's mean is taken over its
+// own last obs_lens[n] columns, in ascending time order, as an engine of that obs_len takes it.
 __global__ void scene_mean_kernel(const float* __restrict__ conv,
                                   const int32_t* __restrict__ obs_scene,
                                   float* __restrict__ out, int N, int T, int K,
-                                  int D) {
+                                  int D, const int32_t* __restrict__ obs_lens) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const size_t per = (size_t)K * D;
   if (idx >= (size_t)N * per) return;
   const int n = idx / per;
   const size_t off = idx - (size_t)n * per;
   float s = 0.f;
-  for (int t = 0; t < T; ++t) s += conv[(size_t)obs_scene[n * T + t] * per + off];
-  out[idx] = s / (float)T;
+  if (!obs_lens) {
+    for (int t = 0; t < T; ++t) s += conv[(size_t)obs_scene[n * T + t] * per + off];
+    out[idx] = s / (float)T;
+    return;
+  }
+  const int L = min(max(obs_lens[n], 1), T);      // (host-checked: in [1, T])
+  for (int t = T - L; t < T; ++t) s += conv[(size_t)obs_scene[n * T + t] * per + off];
+  out[idx] = s / (float)L;
+}
+
+// Rows that join the encoders at this step (mv_set_obs_lengths): their state rows are cleared
+// in front of the gate launch, which then reads the zero state for them -- fp32 c and h [M][C]
+// and the operand planes of h (plane_layout.h; p1 NULL: one plane, p0 NULL: none).
+struct ZeroRowsJob { float* c; float* h; _Float16* p0; _Float16* p1; int K; };
+struct ZeroRowsArgs {
+  ZeroRowsJob job[4];
+  const int32_t* rows;         // [nrows] the joining rows
+  int nrows, C;
+};
+// One thread clears 8 channels of a cell (C % 32 == 0): two 16-byte stores per fp32 tensor, one
+// per plane -- 8 channels of a cell are contiguous in the tiled plane layout.
+__global__ void zero_state_rows_kernel(ZeroRowsArgs a) {
+  const ZeroRowsJob j = a.job[blockIdx.y];
+  const int C8 = a.C >> 3;
+  const size_t per = (size_t)j.K * C8;
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (size_t)a.nrows * per) return;
+  const int i = (int)(idx / per);
+  const size_t e = idx - (size_t)i * per;
+  const size_t cell = e / C8;
+  const int ch = (int)(e - cell * C8) * 8;
+  const long long m = (long long)a.rows[i] * j.K + (long long)cell;
+  const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4* c4 = reinterpret_cast<float4*>(j.c + (size_t)m * a.C + ch);
+  float4* h4 = reinterpret_cast<float4*>(j.h + (size_t)m * a.C + ch);
+  c4[0] = z4; c4[1] = z4;
+  h4[0] = z4; h4[1] = z4;
+  const size_t o = plane_index(m, ch, a.C);
+  const uint4 z8 = make_uint4(0u, 0u, 0u, 0u);
+  if (j.p0) *reinterpret_cast<uint4*>(j.p0 + o) = z8;
+  if (j.p1) *reinterpret_cast<uint4*>(j.p1 + o) = z8;
 }
 
 // Class-encoder input: scene feature masked to the occupied cell

@@ -19,6 +19,10 @@ The reference runs one sample at a time (batch 1, beam 20, run-time T_pred);
 that share T_pred when the engine was created with batch_size > 1; with
 `args.ragged_batches` it batches samples of DIFFERENT T_pred (`plan_ragged_batches`:
 one length per row, the engine stops launching the rows that have finished).
+With `args.allow_short_obs` (not in the reference) a track may have FEWER than obs_length
+observed frames: `get_inputs` keeps its own length, `inference_feed` right-aligns it and the
+feed carries "obs_lengths" (the engine then encodes the row over its own frames only, as an
+engine of that obs_len would; include/multiverse_hip.h mv_set_obs_lengths).
 """
 
 from __future__ import annotations
@@ -121,10 +125,15 @@ def scene_to_masks(scene_feat, old2new, total_class):
 
 
 def get_inputs(args, traj_files, gt_trajs):
-  """code/multifuture_inference.py:158-272."""
+  """code/multifuture_inference.py:158-272.  `args.allow_short_obs`: a track of 1 ..
+  obs_length observed frames is accepted, its arrays keep its own length, and the result
+  carries "obs_lengths" (one per sample); without it every track has obs_length frames."""
   old2new, total_class = load_scene_id_map(args.scene_id2name)
+  allow_short = bool(getattr(args, "allow_short_obs", False))
   out = {"obs_traj": [], "obs_traj_rel": [], "obs_grid_class": [], "obs_grid_target": [],
          "obs_scene": [], "max_pred_lengths": []}
+  if allow_short:
+    out["obs_lengths"] = []
   scene_feats = []
   for traj_file in traj_files:
     traj_id = os.path.splitext(os.path.basename(traj_file))[0]
@@ -133,11 +142,16 @@ def get_inputs(args, traj_files, gt_trajs):
     data = load_traj(traj_file)
     frame_idxs = np.unique(data[:, 0]).tolist()
     obs = data[x_agent_pid == data[:, 1], 2:]
-    assert len(obs) == args.obs_length, (traj_id, obs.shape)
+    if allow_short:
+      assert 1 <= len(obs) <= args.obs_length, (traj_id, obs.shape)
+      assert len(frame_idxs) == len(obs), (traj_id, len(frame_idxs), obs.shape)
+      out["obs_lengths"].append(len(obs))
+    else:
+      assert len(obs) == args.obs_length, (traj_id, obs.shape)
     rel = np.zeros_like(obs)
     rel[1:] = obs[1:] - obs[:-1]
     grid_class, grid_target = get_grid_input(args, obs)
-    featidx = np.zeros([args.obs_length, 1], dtype="int32")
+    featidx = np.zeros([len(obs), 1], dtype="int32")
     for i, frame_idx in enumerate(frame_idxs):
       featidx[i, 0] = len(scene_feats)
       scene_feats.append(np.load(os.path.join(
@@ -161,9 +175,30 @@ RaggedPlan = collections.namedtuple(
     "RaggedPlan", ["batches", "ragged_row_steps", "grouped_row_steps"])
 
 
-def plan_ragged_batches(lengths, N):
+def sum_enc_prefix_rows(obs_lengths, obs_len, live_rows=None):
+  """Rows the encoders of an obs-ragged forward launch per chain: sum over the steps t of
+  p_t = 1 + max{n < live_rows : Lo[n] >= obs_len - t} (0 for a step no row has reached;
+  include/multiverse_hip.h mv_set_obs_lengths).  Row n is inside the prefix of step t iff some
+  row n' >= n has started by then, which holds for m_n = max(Lo[n:]) steps: the sum is
+  sum_n m_n -- sum(Lo) when the lengths are sorted descending.  live_rows: the rows that decode
+  at all (a batch with prediction lengths: 1 + the last row whose length is not 0)."""
+  lo = [int(l) for l in obs_lengths]
+  if live_rows is not None:
+    lo = lo[:int(live_rows)]
+  assert all(1 <= l <= obs_len for l in lo), "observation lengths must be in [1, obs_len]"
+  total, m = 0, 0
+  for l in reversed(lo):
+    m = max(m, l)
+    total += m
+  return total
+
+
+def plan_ragged_batches(lengths, N, obs_lengths=None):
   """Batches of `N` rows over samples of different prediction lengths.  The samples are
-  sorted by length descending (ties by index) and cut into batches of N; the last batch is
+  sorted by length descending (ties by index; with `obs_lengths`, one observation length per
+  sample, ties by observation length descending first: the rows that join the encoders late
+  then sit at the end of their run, and the encoders launch fewer unstarted rows) and cut into
+  batches of N; the last batch is
   padded with rows of length 0; a batch's pred_length is its maximum (its first row's).
   -> RaggedPlan(batches, ragged_row_steps, grouped_row_steps): batches = [(idxs, row_lengths
   [N], pred_length)] with idxs the real samples of the batch in row order, and the decoder
@@ -172,7 +207,12 @@ def plan_ragged_batches(lengths, N):
   padding every group's last batch spends sum over groups of ceil(g / N) * N * T_g."""
   lengths = [int(l) for l in lengths]
   assert N >= 1 and all(l >= 1 for l in lengths), "prediction lengths must be >= 1"
-  order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+  if obs_lengths is None:
+    order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], i))
+  else:
+    obs_lengths = [int(l) for l in obs_lengths]
+    assert len(obs_lengths) == len(lengths)
+    order = sorted(range(len(lengths)), key=lambda i: (-lengths[i], -obs_lengths[i], i))
   batches = []
   for lo in range(0, len(order), N):
     idxs = order[lo:lo + N]
@@ -192,12 +232,27 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   padding rows; the feed then carries them as "pred_lengths" and their maximum as
   "pred_length", and the padding rows cost nothing.
   pred_length (a batch of `plan_score_batches`): the feed's "pred_length" as given, whatever
-  the samples' own; the lengths then travel with the futures, not with the feed."""
+  the samples' own; the lengths then travel with the futures, not with the feed.
+  Short tracks (`get_inputs` with args.allow_short_obs): a sample with fewer than obs_length
+  frames is RIGHT-ALIGNED, the columns in front of it repeat its first observation (label,
+  frame index, regress map: in range and finite, and ignored by the engine), and the feed
+  carries "obs_lengths" [N] -- only when some row of the batch is short."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
   idxs = idxs + [idxs[-1]] * (N - n_real)
   T_in = args.obs_length
+  obs_lens = [int(inputs["obs_lengths"][i]) if "obs_lengths" in inputs else T_in for i in idxs]
+
+  def right_aligned(a, L, axis):
+    """[.., L, ..] -> [.., T_in, ..]: the first observation repeated in front"""
+    a = np.asarray(a)
+    assert a.shape[axis] == L, (a.shape, L, axis)
+    if L == T_in:
+      return a
+    first = np.take(a, [0], axis=axis)
+    return np.concatenate([np.repeat(first, T_in - L, axis=axis), a], axis=axis)
+
   if lengths is not None:
     lengths = [int(l) for l in lengths]
     assert len(lengths) == N and all(l == 0 for l in lengths[n_real:])
@@ -211,19 +266,24 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   feed = {"pred_length": int(T_pred), "grid_obs_labels": [], "grid_obs_regress": []}
   if lengths is not None:
     feed["pred_lengths"] = np.asarray(lengths, dtype="int32")
+  if any(L != T_in for L in obs_lens):
+    feed["obs_lengths"] = np.asarray(obs_lens, dtype="int32")
   for j, (h, w) in enumerate(args.scene_grids):
     feed["grid_obs_labels"].append(np.stack(
-        [inputs["obs_grid_class"][i][j] for i in idxs]).astype("int32"))
+        [right_aligned(inputs["obs_grid_class"][i][j], L, 0)
+         for i, L in zip(idxs, obs_lens)]).astype("int32"))
     if not args.use_grids[j]:
       feed["grid_obs_regress"].append(None)
       continue
     feed["grid_obs_regress"].append(np.stack(
-        [inputs["obs_grid_target"][i][j] for i in idxs]).astype("float32"))
+        [right_aligned(inputs["obs_grid_target"][i][j], L, 0)
+         for i, L in zip(idxs, obs_lens)]).astype("float32"))
   old2new = {}
   obs_scene = np.zeros((N, T_in), dtype="int32")
-  for r, i in enumerate(idxs):
+  for r, (i, L) in enumerate(zip(idxs, obs_lens)):
+    frames = right_aligned(inputs["obs_scene"][i], L, 0)
     for t in range(T_in):
-      old = int(inputs["obs_scene"][i][t][0])
+      old = int(frames[t][0])
       if old not in old2new:
         old2new[old] = len(old2new)
       obs_scene[r, t] = old2new[old]
@@ -291,11 +351,16 @@ def _inference_batches(args, inputs, n, N):
   padded by `inference_feed`), or -- `args.ragged_batches` -- the plan of
   `plan_ragged_batches` over all samples."""
   lens = [inputs["max_pred_lengths"][i] for i in range(n)]
+  obs = [inputs["obs_lengths"][i] for i in range(n)] if "obs_lengths" in inputs else None
   if getattr(args, "ragged_batches", False):
-    return [(idxs, lengths) for idxs, lengths, _ in plan_ragged_batches(lens, N).batches]
+    return [(idxs, lengths)
+            for idxs, lengths, _ in plan_ragged_batches(lens, N, obs_lengths=obs).batches]
   by_len = {}
   for i in range(n):
     by_len.setdefault(lens[i], []).append(i)
+  if obs is not None:      # short tracks: a group's rows by observation length, descending
+    for T in by_len:
+      by_len[T].sort(key=lambda i: (-obs[i], i))
   return [(by_len[T][lo:lo + N], None) for T in sorted(by_len)
           for lo in range(0, len(by_len[T]), N)]
 
@@ -448,14 +513,15 @@ def futures_to_grid_ids(args, gt_by_traj, traj_id, use_grid_idx):
 ScoreRow = collections.namedtuple("ScoreRow", ["sample", "futures", "lengths"])
 
 
-def plan_score_batches(n_futures_per_sample, lengths, N, F):
+def plan_score_batches(n_futures_per_sample, lengths, N, F, obs_lengths=None):
   """Batches of N rows x F futures over samples with any number of futures of any length.
   lengths[i][j] >= 1: the length of future j of sample i (n_futures_per_sample[i] of them).
   A sample's futures fill a row in order; a sample with more than F futures takes several
   rows (the engine then runs the same inputs once per row); a row's last futures and a
   batch's last rows are padding of length 0.  Rows are sorted by their longest future,
   descending (ties by sample, then by position), as `plan_ragged_batches` sorts samples: the
-  live rows of every step are a prefix.
+  live rows of every step are a prefix.  obs_lengths (one observation length per sample, short
+  tracks): ties of the longest future are ordered by observation length descending first.
   -> [(rows, pred_length)], rows = N x ScoreRow(sample or None for a padding row, futures
   [indices into the sample's futures], lengths [F]), pred_length = the first row's longest."""
   assert N >= 1 and F >= 1
@@ -467,7 +533,12 @@ def plan_score_batches(n_futures_per_sample, lengths, N, F):
     for lo in range(0, len(lens), F):
       futs = list(range(lo, min(lo + F, len(lens))))
       rows.append(ScoreRow(i, futs, [lens[j] for j in futs] + [0] * (F - len(futs))))
-  order = sorted(range(len(rows)), key=lambda r: (-max(rows[r].lengths), r))
+  if obs_lengths is None:
+    order = sorted(range(len(rows)), key=lambda r: (-max(rows[r].lengths), r))
+  else:
+    assert len(obs_lengths) == len(n_futures_per_sample)
+    order = sorted(range(len(rows)), key=lambda r: (-max(rows[r].lengths),
+                                                    -int(obs_lengths[rows[r].sample]), r))
   batches = []
   for lo in range(0, len(order), N):
     batch = [rows[r] for r in order[lo:lo + N]]
@@ -484,7 +555,8 @@ def run_scoring(args, model, inputs, traj_ids, gt):
   use_grid_idx = list(args.use_grids).index(True)
   N, F = model.config.batch_size, model.config.beam_size
   cells = [futures_to_grid_ids(args, gt, t, use_grid_idx) for t in traj_ids]
-  plan = plan_score_batches([len(c[1]) for c in cells], [c[1] for c in cells], N, F)
+  plan = plan_score_batches([len(c[1]) for c in cells], [c[1] for c in cells], N, F,
+                            obs_lengths=inputs.get("obs_lengths"))
   scores = {t: {} for t in traj_ids}
   for rows, T_pred in plan:
     real = [row.sample for row in rows if row.sample is not None]
