@@ -421,6 +421,57 @@ int  mv_download_beam_gumbels(mv_handle h, float* out /* [N, B] */);
 int  mv_set_sampling_truncation(mv_handle h, int32_t top_k, float top_p);
 int  mv_download_beam_proposal_logprobs(mv_handle h, float* out /* [N, B] */);
 
+/* ---- constrained decode: per-row allowed cells (not in the reference; defined here) ---------
+ * allowed [N, Tm, K] bytes, K = the cells of the handle's one used grid; allowed[n, tm, k] != 0
+ * means row n may choose cell k.  Tm == 1: one mask for every decode step; otherwise step t reads
+ * plane t, and Tm must be at least the forward's pred_len (checked at the forward).  NULL clears.
+ * Sticky until cleared.  It applies to every forward of a beam handle that CHOOSES cells -- the
+ * beam search, the independent sampler, the sampling without replacement -- and to
+ * mv_beam_occupancy after them.  mv_score_futures neither reads nor changes it: the likelihood of
+ * a given future is the model's.  Everything is float32; A = A(n, t) is the allowed set of the row
+ * at the step, l the step's hidden2grid logits, tau the temperature.
+ *   lp = log_softmax(l) over ALL K cells, unchanged: logprobs of both samplers stay the model's
+ *        exact log-probabilities (scoring the returned ids with mv_score_futures reproduces them
+ *        bit for bit), and the logits outputs are the model's, unmasked.
+ * Beam search: after lp + prev_lp and BEFORE the diversity ranks a cell outside A becomes the
+ * candidate -inf.  The rank and penalty arithmetic then runs as it is -- a -inf candidate precedes
+ * nothing, so an allowed cell's rank counts allowed cells only -- and the selection is unchanged.
+ * With a mask the step always takes the two-launch rank + select form, whatever MV_BEAM_STEP says.
+ * Independent sampler and sampling without replacement: a cell outside A is treated exactly as a
+ * cell past K, i.e. absent from the proposal.  In the terms of mv_set_sampling_truncation:
+ *   w[k]    = l[k] / tau;  mxq = max of w over A  (deliberately over A: with the row maximum
+ *             outside A every allowed e could underflow and q~ would not be finite)
+ *   e, sum_e, c(k), m(k) and the step-0 floor run over A
+ *   keep(k) = k in A and the predicate of mv_set_sampling_truncation
+ *   q~[k]   = (w[k] - mxq) - logf(sum of e over the kept cells) on kept cells, that sum in the
+ *             order of the log-softmax; -inf elsewhere
+ * A mask makes the proposal differ from the model: qlogprobs accumulates q~[id], and the
+ * without-replacement q plane is written and read, whenever a mask is set -- even at tau == 1 with
+ * no limit.  mv_download_beam_proposal_logprobs returns it as under a limit.
+ * mv_beam_occupancy: each future's step map is the softmax over A (maximum and sum over A, a cell
+ * outside exactly 0.0f); the mixture weights are unchanged.  It reads the mask that is set when
+ * it is called.
+ * Identity, in eager and in graph mode: with allowed all non-zero every output of every call is
+ * bit-identical to a handle that never had a mask; with no mask set no launch differs.
+ * Validity: the allowed cells per (n, tm) are counted on the host when the mask is set and checked
+ * at the forward, for rows that decode at all and steps below the row's length:
+ *   |A(n, t)| >= 1 at every such step;  |A(n, 0)| >= beam_size for the beam search and for the
+ *   sampling without replacement (only the root's K children are candidates at the first step).
+ * The message names n, t and the count.  With these no slot ever lacks a finite candidate: a dead
+ * beam cannot occur and is not defined.
+ * The mask lives in an engine-owned device buffer; this call synchronises the stream and rewrites
+ * it, so a replayed graph follows a new mask without re-capture (the graph key carries whether a
+ * mask is set and whether Tm > 1).  It combines with mv_set_pred_lengths and mv_set_obs_lengths
+ * with no new rule: row n equals its own uniform forward under the same mask row.
+ * Errors: a greedy handle (the constrained argmax decode is the beam search of width 1 without
+ * diversity, which a greedy handle does not run: its forward reads no mask); Tm < 1;
+ * 1 < Tm < pred_len (at the forward); a grid of more than 1024 cells (at the forward); mv_train_*
+ * and mv_submit_greedy while a mask is set (the message names the call). */
+int  mv_set_cell_mask(mv_handle h, const uint8_t* allowed /* [N, Tm, K]; NULL clears */,
+                      int32_t Tm);
+/* forwards captured into a hipGraph on this handle so far (a replay does not count) */
+int  mv_graph_captures(mv_handle h, int64_t* captures);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -651,6 +702,24 @@ int  mv_op_sample_step(int device, const float* logits /* [R, K] */, int32_t R, 
                        int32_t K, int32_t t, float temperature, uint32_t seed, int32_t top_k,
                        float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
                        uint8_t* keep /* [R, K] */);
+
+/* The masked forms of the three step ops (mv_set_cell_mask above): allowed [samples, K] bytes,
+ * one plane per SAMPLE (N for the beam and the sampling without replacement, R / S for the
+ * sampler), non-zero = the cell may be chosen; all else as the unmasked op.  K <= 1024. */
+int  mv_op_beam_step_masked(int device, const float* logits, const float* prev_logprob,
+                            const uint8_t* allowed /* [N, K] */, int32_t N, int32_t B, int32_t K,
+                            int32_t time, int32_t diverse, float gamma, int32_t fix_num_timestep,
+                            float* new_logprob, int32_t* ids, int32_t* parents);
+int  mv_op_sbs_step_masked(int device, const float* logits, const float* prev_phi,
+                           const float* prev_logprob, const float* prev_gumbel,
+                           const uint8_t* allowed /* [N, K] */, int32_t N, int32_t B, int32_t K,
+                           int32_t t, float temperature, uint32_t seed, float* new_phi,
+                           float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
+int  mv_op_sample_step_masked(int device, const float* logits /* [R, K] */,
+                              const uint8_t* allowed /* [R / S, K] */, int32_t R, int32_t S,
+                              int32_t K, int32_t t, float temperature, uint32_t seed,
+                              int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
+                              float* qlp, uint8_t* keep /* [R, K] */);
 
 /* Light cone of the class encoder (MV_ENC_CONE): the wave tiles of the F(3,3) gate
  * kernel each encoder step computes, as every upload builds them from the labels.  Host only: no

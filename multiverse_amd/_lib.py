@@ -50,6 +50,8 @@ EXPORTED_SYMBOLS = [
     "mv_set_sampling_truncation", "mv_download_beam_proposal_logprobs", "mv_op_sample_step",
     "mv_enc_cone_build",
     "mv_set_obs_lengths",
+    "mv_set_cell_mask", "mv_graph_captures", "mv_op_beam_step_masked", "mv_op_sbs_step_masked",
+    "mv_op_sample_step_masked",
 ]
 
 
@@ -224,6 +226,18 @@ def load():
   lib.mv_set_pred_lengths.argtypes = [h, _ip]
   if hasattr(lib, "mv_set_obs_lengths"):    # (an A/B build through MV_LIB_PATH may predate it)
     lib.mv_set_obs_lengths.argtypes = [h, _ip]
+  if hasattr(lib, "mv_set_cell_mask"):      # (as above)
+    lib.mv_set_cell_mask.argtypes = [h, _u8p, C.c_int32]
+    lib.mv_graph_captures.argtypes = [h, C.POINTER(C.c_int64)]
+    lib.mv_op_beam_step_masked.argtypes = [C.c_int, _fp, _fp, _u8p, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                           C.c_int32, _fp, _ip, _ip]
+    lib.mv_op_sbs_step_masked.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _u8p, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                          _fp, _fp, _fp, _ip, _ip]
+    lib.mv_op_sample_step_masked.argtypes = [C.c_int, _fp, _u8p, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_float, C.c_uint32, C.c_int32,
+                                             C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
@@ -533,6 +547,7 @@ class Engine(object):
     self._pred_len = inp.pred_len
     self._set_pred_lengths(feed.get("pred_lengths"))
     self._set_obs_lengths(feed.get("obs_lengths"))
+    self._set_feed_cell_mask(feed.get("cell_mask"))
     return inp
 
   def _set_pred_lengths(self, lengths):
@@ -563,6 +578,52 @@ class Engine(object):
       raise MvError("obs_lengths: %d values for batch_size %d" % (lens.size, self.cfg.batch_size))
     check(self.lib.mv_set_obs_lengths(self.handle, iptr(lens)), self.handle)
     self._obs_lengths_set = True
+
+  def set_cell_mask(self, mask):
+    """The cells the futures of each row may choose (include/multiverse_hip.h mv_set_cell_mask):
+    [N, K] (one mask for every decode step) or [N, Tm, K] (plane t for step t, Tm >= pred_len),
+    non-zero = allowed; a grid-shaped [N, (Tm,) h, w] is taken as well.  None clears.  Sticky:
+    a mask set here stays through every later feed that has no "cell_mask" key, until it is
+    cleared here or a feed brings its own (which then follows the feeds' rule: the next feed
+    without the key clears it).  The beam search, both samplers and beam_occupancy read it,
+    score_futures does not.  While sampling is on under a mask, the forwards add
+    "proposal_logprobs"."""
+    self._cell_mask_from_feed = False
+    if mask is None:
+      check(self.lib.mv_set_cell_mask(self.handle, None, 0), self.handle)
+      self._cell_mask_set = False
+      return
+    N = self.cfg.batch_size
+    h, w = self.cfg.scene_grids[self._beam_scale()]
+    m = np.asarray(mask)
+    if m.ndim >= 2 and m.shape[-2:] == (h, w) and m.shape[-1] != h * w:
+      m = m.reshape(m.shape[:-2] + (h * w,))
+    if m.ndim == 2:
+      m = m[:, None, :]
+    if m.ndim != 3 or m.shape[0] != N or m.shape[2] != h * w:
+      raise MvError("cell_mask: shape %s is neither [N=%d, K=%d] nor [N, Tm, K]"
+                    % (tuple(np.asarray(mask).shape), N, h * w))
+    m = np.ascontiguousarray(m != 0, dtype=np.uint8)
+    check(self.lib.mv_set_cell_mask(self.handle, m.ctypes.data_as(_u8p), int(m.shape[1])),
+          self.handle)
+    self._cell_mask_set = True
+
+  def _set_feed_cell_mask(self, mask):
+    """feed["cell_mask"], handled as feed["obs_lengths"] is: set when present; a feed without
+    the key clears the mask a previous FEED set, and leaves one set through set_cell_mask alone.
+    Called with every feed that is uploaded."""
+    if mask is None:
+      if getattr(self, "_cell_mask_from_feed", False):
+        self.set_cell_mask(None)
+      return
+    self.set_cell_mask(mask)
+    self._cell_mask_from_feed = True
+
+  def graph_captures(self):
+    """Forwards captured into a hipGraph on this handle so far (a replay does not count)."""
+    n = C.c_int64()
+    check(self.lib.mv_graph_captures(self.handle, C.byref(n)), self.handle)
+    return int(n.value)
 
   def set_sampling(self, temperature=1.0, seed=0, without_replacement=False, top_k=0,
                    top_p=1.0):
@@ -597,9 +658,11 @@ class Engine(object):
     self._sampling_limits = (int(top_k), float(top_p))
 
   def _truncated(self):
-    """Does the next / did the last beam forward sample under a top-k / nucleus limit?"""
+    """Does the next / did the last beam forward sample under a top-k / nucleus limit or a cell
+    mask, i.e. from a proposal that is not the (tempered) model?"""
     top_k, top_p = getattr(self, "_sampling_limits", (0, 1.0))
-    return getattr(self, "_sampling_on", False) and (top_k > 0 or top_p < 1.0)
+    return getattr(self, "_sampling_on", False) and \
+        (top_k > 0 or top_p < 1.0 or getattr(self, "_cell_mask_set", False))
 
   def beam_proposal_logprobs(self):
     """float32 [N, B]: the log-probability of each future of the last SAMPLED forward under the
@@ -820,6 +883,7 @@ class Engine(object):
     self._pred_len = inp.pred_len
     self._set_pred_lengths(feed.get("pred_lengths"))
     self._set_obs_lengths(feed.get("obs_lengths"))
+    self._set_feed_cell_mask(feed.get("cell_mask"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len
@@ -1265,28 +1329,50 @@ def op_hidden2grid(h, w, device=0):
   return out
 
 
-def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device=0):
+def _allowed_plane(allowed, samples, K):
+  a = np.ascontiguousarray(np.asarray(allowed).reshape(samples, K) != 0, dtype=np.uint8)
+  return a, a.ctypes.data_as(_u8p)
+
+
+def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device=0,
+                 allowed=None):
+  """allowed [N, K] (non-zero = the cell may be chosen): the masked step, mv_op_beam_step_masked."""
   lib = load()
   logits, prev_lp = f32(logits), f32(prev_lp)
   N, B, K = logits.shape
   new_lp = np.empty((N, B), dtype=np.float32)
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if allowed is not None:
+    a, ap = _allowed_plane(allowed, N, K)
+    check(lib.mv_op_beam_step_masked(device, fptr(logits), fptr(prev_lp), ap, N, B, K, int(time),
+                                     1 if diverse else 0, float(gamma), int(fix_num_timestep),
+                                     fptr(new_lp), iptr(ids), iptr(parents)))
+    return new_lp, ids, parents
   check(lib.mv_op_beam_step(device, fptr(logits), fptr(prev_lp), N, B, K, int(time),
                             1 if diverse else 0, float(gamma), int(fix_num_timestep),
                             fptr(new_lp), iptr(ids), iptr(parents)))
   return new_lp, ids, parents
 
 
-def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0):
+def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0,
+                allowed=None):
   """One step of the sampling without replacement (mv_op_sbs_step): logits [N, B, K], prev_*
-  [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B]."""
+  [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B].  allowed [N, K]: the
+  masked step (mv_op_sbs_step_masked)."""
   lib = load()
   logits, prev_phi, prev_lp, prev_g = f32(logits), f32(prev_phi), f32(prev_lp), f32(prev_g)
   N, B, K = logits.shape
   phi, lp, g = (np.empty((N, B), dtype=np.float32) for _ in range(3))
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if allowed is not None:
+    a, ap = _allowed_plane(allowed, N, K)
+    check(lib.mv_op_sbs_step_masked(device, fptr(logits), fptr(prev_phi), fptr(prev_lp),
+                                    fptr(prev_g), ap, N, B, K, int(t), float(temperature),
+                                    int(seed) & 0xFFFFFFFF, fptr(phi), fptr(lp), fptr(g),
+                                    iptr(ids), iptr(parents)))
+    return phi, lp, g, ids, parents
   check(lib.mv_op_sbs_step(device, fptr(logits), fptr(prev_phi), fptr(prev_lp), fptr(prev_g),
                            N, B, K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
                            fptr(phi), fptr(lp), fptr(g), iptr(ids), iptr(parents)))
@@ -1312,16 +1398,25 @@ def enc_cone_build(labels, H, W, r0=1):
   return lists, cells, int(ntile)
 
 
-def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0):
+def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,
+                   allowed=None):
   """One step of the independent sampler under top-k / nucleus limits (mv_op_sample_step):
   logits [R, K], row r = future r % S of sample r // S -> (ids int32 [R], lp [R] the model's
-  log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set)."""
+  log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set).
+  allowed [R // S, K], one plane per sample: the masked step (mv_op_sample_step_masked)."""
   lib = load()
   logits = f32(logits)
   R, K = logits.shape
   ids = np.empty(R, dtype=np.int32)
   lp, qlp = (np.empty(R, dtype=np.float32) for _ in range(2))
   keep = np.empty((R, K), dtype=np.uint8)
+  if allowed is not None:
+    a, ap = _allowed_plane(allowed, R // int(S), K)
+    check(lib.mv_op_sample_step_masked(device, fptr(logits), ap, R, int(S), K, int(t),
+                                       float(temperature), int(seed) & 0xFFFFFFFF, int(top_k),
+                                       float(top_p), int(floor), iptr(ids), fptr(lp), fptr(qlp),
+                                       keep.ctypes.data_as(_u8p)))
+    return ids, lp, qlp, keep.astype(bool)
   check(lib.mv_op_sample_step(device, fptr(logits), R, int(S), K, int(t), float(temperature),
                               int(seed) & 0xFFFFFFFF, int(top_k), float(top_p), int(floor),
                               iptr(ids), fptr(lp), fptr(qlp), keep.ctypes.data_as(_u8p)))

@@ -234,6 +234,12 @@ _MF_FLAGS = [
     # encoded over its own frames, as a model of that obs_length would (multifuture.inference_feed
     # right-aligns it, the engine takes one observation length per row: mv_set_obs_lengths)
     ("--allow_short_obs", B, None),
+    # not in the reference: constrained decode.  --allowed_classes 1,4,7 (new ids of the
+    # scene_id2name map): a future may only enter grid cells of which at least the share
+    # --allowed_min_share (and at least one pixel) of the row's LAST observed frame belongs to
+    # these classes (multifuture.cell_mask_from_scene; the engine takes the mask per row:
+    # mv_set_cell_mask).  A row with fewer than num_out such cells is decoded unconstrained.
+    ("--allowed_classes", str, None), ("--allowed_min_share", float, 0.0),
 ]
 
 
@@ -269,6 +275,7 @@ def multifuture_inference_main(argv=None):
   if args.score_gt is not None and args.greedy:
     raise SystemExit("--score_gt scores num_out futures per row; it does not combine with "
                      "--greedy")
+  parse_allowed_classes(args)
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)
@@ -287,6 +294,10 @@ def multifuture_inference_main(argv=None):
   res = mf.run_inference(args, model, inputs, traj_ids)
   output_data, beam_prob = res[0], res[1]
   model.close()
+  if args.allowed_classes:
+    print("unconstrained: %d of %d (fewer than num_out = %d allowed cells)%s"
+          % (len(args.unconstrained), len(traj_ids), args.num_out,
+             "".join(" " + t for t in args.unconstrained)))
   if args.save_occupancy_file is not None:
     with open(args.save_occupancy_file, "wb") as f:
       pickle.dump(res[2], f)
@@ -295,6 +306,35 @@ def multifuture_inference_main(argv=None):
   if args.save_prob_file is not None:
     with open(args.save_prob_file, "wb") as f:
       pickle.dump(beam_prob, f)
+
+
+def parse_allowed_classes(args):
+  """--allowed_classes "1,4,7" -> args.allowed_classes [1, 4, 7] (None when not given) and
+  args.unconstrained, the list `multifuture.run_inference` fills; refused with --greedy (the
+  greedy decode chooses by argmax and reads no mask) and with --score_gt (a given future's
+  likelihood is the model's)."""
+  if args.allowed_classes is None:
+    if args.allowed_min_share != 0.0:
+      raise SystemExit("--allowed_min_share is the share of --allowed_classes; give "
+                       "--allowed_classes as well")
+    return
+  if args.greedy:
+    raise SystemExit("--allowed_classes constrains the beam search and the samplers; it does "
+                     "not combine with --greedy")
+  if args.score_gt is not None:
+    raise SystemExit("--allowed_classes constrains a decode; --score_gt decodes nothing")
+  try:
+    classes = [int(c) for c in str(args.allowed_classes).split(",") if c.strip() != ""]
+  except ValueError:
+    raise SystemExit("--allowed_classes: a comma-separated list of class ids, not %r"
+                     % args.allowed_classes)
+  if not classes or any(c < 0 or c >= args.scene_class for c in classes):
+    raise SystemExit("--allowed_classes %r: ids in [0, scene_class = %d)"
+                     % (args.allowed_classes, args.scene_class))
+  if not 0.0 <= args.allowed_min_share <= 1.0:
+    raise SystemExit("--allowed_min_share %s not in [0, 1]" % args.allowed_min_share)
+  args.allowed_classes = classes
+  args.unconstrained = []
 
 
 def print_exact_nll(result):

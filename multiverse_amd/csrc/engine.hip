@@ -358,6 +358,49 @@ int mv_set_obs_lengths(mv_handle h, const int32_t* lengths) {
   });
 }
 
+int mv_set_cell_mask(mv_handle h, const uint8_t* allowed, int32_t Tm) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_cell_mask: engine was created with beam_size 1 (the "
+               "greedy forward chooses by argmax and reads no mask: create a beam handle)");
+    // behind whatever forward or occupancy map still reads the previous mask on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!allowed) {
+      h->cmask_tm = 0;
+      h->cmask_count.clear();
+      return;
+    }
+    MV_REQUIRE(Tm >= 1, "mv_set_cell_mask: Tm = %d must be >= 1 (1 = one mask for every step)",
+               (int)Tm);
+    const size_t N = (size_t)h->cfg.batch_size, K = (size_t)h->sc[beam_scale(h)].K;
+    const size_t Tcap = (size_t)h->cfg.max_pred_len;
+    h->cmask_count.assign(N * Tm, 0);
+    for (size_t p = 0; p < N * Tm; ++p) {
+      int32_t cnt = 0;
+      for (size_t k = 0; k < K; ++k) cnt += allowed[p * K + k] != 0;
+      h->cmask_count[p] = cnt;
+    }
+    // one allocation for both layouts: the address a captured forward holds never changes
+    h->cmask_dev.alloc(N * Tcap * K);
+    if (Tm == 1) {
+      HIP_CHECK(hipMemcpy(h->cmask_dev.p, allowed, N * K, hipMemcpyHostToDevice));
+    } else {
+      const size_t planes = std::min((size_t)Tm, Tcap);   // a forward reads planes < pred_len
+      HIP_CHECK(hipMemcpy2D(h->cmask_dev.p, Tcap * K, allowed, (size_t)Tm * K, planes * K, N,
+                            hipMemcpyHostToDevice));
+    }
+    h->cmask_tm = Tm;
+  });
+}
+
+int mv_graph_captures(mv_handle h, int64_t* captures) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(captures, "mv_graph_captures: NULL argument");
+    *captures = h->graph_captures;
+  });
+}
+
 int mv_set_sampling(mv_handle h, int32_t enabled, float temperature, uint32_t seed) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -488,6 +531,8 @@ int mv_submit_greedy(mv_handle h, const mv_inputs* in) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(in, "mv_submit_greedy: NULL argument");
+    MV_REQUIRE(!h->cmask_set(), "mv_submit_greedy: a cell mask is set (mv_set_cell_mask); the "
+               "greedy forward chooses by argmax and reads no mask -- clear it first");
     pipeline_submit(h, in);
   });
 }
@@ -526,6 +571,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
     MV_REQUIRE(tc, "mv_train_init: NULL config");
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_init");
+    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -575,6 +622,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_forward_backward");
+    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -614,6 +663,8 @@ int mv_train_apply(mv_handle h, float grad_scale) {
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_apply");
+    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -628,6 +679,8 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_step");
+    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "

@@ -1094,6 +1094,16 @@ __global__ void ragged_ids_tail_kernel(int32_t* __restrict__ ids, const int32_t*
   if (idx % T >= lens[idx / T / S]) ids[idx] = -1;
 }
 
+// The allowed cells of decode step t (mv_set_cell_mask): plane t of every row, or the one plane.
+// No mask set: the empty StepMask, and the step launches exactly what it launched before.
+StepMask step_mask(const mv_engine* e, int K, int t) {
+  StepMask m;
+  if (!e->cmask_set()) return m;
+  m.p = e->cmask_dev.p + (size_t)t * e->cmask_step(K);
+  m.stride = e->cmask_stride(K);
+  return m;
+}
+
 // Beam-search class decoder (grid_decoder_beam_search,
 // code/pred_models.py:474-806) with the un-beamed regression decoder advanced
 // in lockstep (its step t shares a launch with beam time t+1).
@@ -1216,18 +1226,19 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
         HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
+      const StepMask mask = step_mask(e, K, time - 1);
       if (wor) launch(e, "sbs_step", 0, 16.0 * n_now * B * K, [&] {
         launch_sbs_step(e->issue, logits, e->bm_phi[lpi].p, e->bm_lp[lpi].p, e->bm_g[lpi].p,
                         e->bm_cand.p, e->bm_sbs_lp.p, e->bm_sbs_q.p, e->samp_params.p, n_now, B,
                         K, time - 1, e->bm_phi[lpi ^ 1].p, e->bm_lp[lpi ^ 1].p,
                         e->bm_g[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
-                        one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr);
+                        one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, mask);
       });
       else launch(e, "beam_step", 0, 4.0 * n_now * B * K, [&] {
         launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, n_now, B, K, time,
                          c.diverse_beam, logf(c.diverse_gamma), c.fix_num_timestep,
                          e->bm_lp[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
-                         one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr);
+                         one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, mask);
       });
       lpi ^= 1;
       src = e->bm_src_row.p;
@@ -1369,11 +1380,9 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
       });
       else launch(e, "sample_step", 0, step_bytes, [&] {
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
-        with_rank_j(K, [&](auto j) {
-          hipLaunchKernelGGL(mv::sample_step_kernel<decltype(j)::value>, grid, block, 0, e->issue,
-                             logits, orow, rows, B, K, t, shared, e->samp_params.p, 1, lens,
-                             e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr);
-        });
+        launch_sample_step(e->issue, logits, orow, rows, B, K, t, shared, e->samp_params.p, 1,
+                           lens, e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr,
+                           step_mask(e, K, t));
       });
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, Tp, S.xbuf_cls.p, n_next * B);
@@ -1505,6 +1514,30 @@ void plan_scored(mv_engine* e) {
                            hipMemcpyHostToDevice, e->stream));
 }
 
+// The cell mask of this forward (mv_set_cell_mask), checked for the forwards that CHOOSE cells
+// (after plan_ragged): every row that decodes needs an allowed cell at every step below its
+// length, and beam_size of them at step 0 where only the root's K children are candidates.
+void plan_cell_mask(mv_engine* e, ForwardKind kind) {
+  if (!e->cmask_set() || kind == ForwardKind::Scored || kind == ForwardKind::Greedy) return;
+  const mv_config& c = e->cfg;
+  const int N = c.batch_size, Tp = e->pred_len, Tm = e->cmask_tm, B = c.beam_size;
+  MV_REQUIRE(Tm == 1 || Tm >= Tp, "mv_set_cell_mask: the mask has Tm = %d planes, the forward "
+             "pred_len = %d steps (Tm must be 1 or at least pred_len)", Tm, Tp);
+  const bool top_b = kind == ForwardKind::Beam || kind == ForwardKind::SampledWor;
+  for (int n = 0; n < N; ++n) {
+    const int L = e->len.ragged ? e->lens_host[n] : Tp;
+    for (int t = 0; t < L; ++t) {
+      const int cnt = e->cmask_count[(size_t)n * Tm + (Tm > 1 ? t : 0)];
+      MV_REQUIRE(cnt >= 1, "mv_set_cell_mask: row n = %d has %d allowed cells at step t = %d "
+                 "(every step below the row's length needs at least one)", n, cnt, t);
+      if (t == 0 && top_b)
+        MV_REQUIRE(cnt >= B, "mv_set_cell_mask: row n = %d has %d allowed cells at step t = 0, "
+                   "fewer than beam_size = %d (only the root's children are candidates at the "
+                   "first step)", n, cnt, B);
+    }
+  }
+}
+
 // out_cls / out_reg of a ragged forward: exact zeros from step L[n] on (rows past a step's
 // active prefix were not written at all).  On the engine's stream, after the chain pairs met.
 void finish_ragged(mv_engine* e, bool beam) {
@@ -1539,11 +1572,17 @@ void run_forward(mv_engine* e, ForwardKind kind) {
                "supported (the scoring forward keeps the un-beamed regression decoder)");
   }
   MV_REQUIRE(e->inputs_ready, "no inputs uploaded (mv_upload_inputs)");
+  // a masked step holds a row in one wave: refused before anything is launched
+  if (beam && kind != ForwardKind::Scored && e->cmask_set())
+    MV_REQUIRE(e->sc[beam_scale(e)].K <= 64 * mv::kBeamRankJ, "mv_set_cell_mask: grid of %d "
+               "cells (under a mask one wave holds a row of at most %d)",
+               e->sc[beam_scale(e)].K, 64 * mv::kBeamRankJ);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
   if (kind == ForwardKind::Scored) plan_scored(e); else plan_ragged(e);
   plan_obs(e);
+  plan_cell_mask(e, kind);
   // a ragged forward's launches depend on the lengths, which the graph key does not carry: it
   // is issued eagerly; so is an obs-ragged one
   if (!e->graph_mode || e->profiling || e->len.ragged || e->obs.ragged) {
@@ -1553,7 +1592,10 @@ void run_forward(mv_engine* e, ForwardKind kind) {
     e->last = kind;
     return;
   }
-  const auto key = std::make_tuple(kind, e->pred_len, e->num_frames);
+  // (a scoring forward reads no mask: one graph whatever is set)
+  const int mask_key = (kind == ForwardKind::Scored || kind == ForwardKind::Greedy ||
+                        !e->cmask_set()) ? 0 : (e->cmask_tm > 1 ? 2 : 1);
+  const auto key = std::make_tuple(kind, e->pred_len, e->num_frames, mask_key);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {
     e->gate_rows = 0;
@@ -1572,6 +1614,7 @@ void run_forward(mv_engine* e, ForwardKind kind) {
     (void)hipGraphDestroy(g);
     HIP_CHECK(ie);
     it = e->graphs.emplace(key, ex).first;
+    ++e->graph_captures;
     e->graph_gate_rows[key] = e->gate_rows;
   }
   e->gate_rows = e->graph_gate_rows[key];

@@ -463,15 +463,19 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
 }
 
 // K <= CPT * 256 cells: a thread's cells in registers (CPT 1 or 3); any K beyond
-template <bool RAGGED>
+// MASKED (mv_set_cell_mask): each future's step map is the softmax over the allowed cells
+template <bool RAGGED, bool MASKED>
 void launch_beam_occupancy(mv_engine* e, const float* lp, int N, int B, int Tp, int K) {
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(N * Tp), dim3(mv::kMfBlock), 0, e->stream, e->bm_out_logits.p,
-                       lp, e->mf_occ.p, B, Tp, K, RAGGED ? e->lens_dev.p : nullptr);
+                       lp, e->mf_occ.p, B, Tp, K, RAGGED ? e->lens_dev.p : nullptr,
+                       MASKED ? e->cmask_dev.p : (const uint8_t*)nullptr,
+                       MASKED ? e->cmask_stride(K) : (int64_t)0,
+                       MASKED ? e->cmask_step(K) : (int64_t)0);
   };
-  if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED>);
-  else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED>);
-  else go(mv::beam_occupancy_anyk_kernel<RAGGED>);
+  if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED, MASKED>);
+  else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED, MASKED>);
+  else go(mv::beam_occupancy_anyk_kernel<RAGGED, MASKED>);
 }
 
 void beam_occupancy(mv_engine* e, float* out) {
@@ -485,6 +489,21 @@ void beam_occupancy(mv_engine* e, float* out) {
   const ScaleState& S = e->sc[beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;
+  // the mask the forward chose its cells under, if it is still set (the forward checked it)
+  const bool masked = e->cmask_set();
+  if (masked) {
+    MV_REQUIRE(e->cmask_tm == 1 || e->cmask_tm >= Tp, "mv_beam_occupancy: the cell mask has "
+               "Tm = %d planes, the last forward pred_len = %d steps", e->cmask_tm, Tp);
+    // the mask may have been set after the forward, which checked ITS mask: a step map over an
+    // empty set would be 0 / 0
+    const bool rag = e->len.ragged && e->lens_host.size() == (size_t)N;
+    for (int n = 0; n < N; ++n)
+      for (int t = 0; t < (rag ? e->lens_host[n] : Tp); ++t) {
+        const int cnt = e->cmask_count[(size_t)n * e->cmask_tm + (e->cmask_tm > 1 ? t : 0)];
+        MV_REQUIRE(cnt >= 1, "mv_beam_occupancy: row n = %d has %d allowed cells at step t = %d "
+                   "under the cell mask that is set now (mv_set_cell_mask)", n, cnt, t);
+      }
+  }
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
   // HBM-bound: every beam's logits row read once, the map written once
   // independently sampled futures are draws, not scored hypotheses: uniform weights, which the
@@ -498,8 +517,10 @@ void beam_occupancy(mv_engine* e, float* out) {
   }
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
     // the last forward ran with per-row lengths: 0 past a row's end
-    if (e->len.ragged) launch_beam_occupancy<true>(e, lp, N, B, Tp, K);
-    else launch_beam_occupancy<false>(e, lp, N, B, Tp, K);
+    if (masked && e->len.ragged) launch_beam_occupancy<true, true>(e, lp, N, B, Tp, K);
+    else if (masked) launch_beam_occupancy<false, true>(e, lp, N, B, Tp, K);
+    else if (e->len.ragged) launch_beam_occupancy<true, false>(e, lp, N, B, Tp, K);
+    else launch_beam_occupancy<false, false>(e, lp, N, B, Tp, K);
   });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, e->mf_occ.p, cells * sizeof(float), hipMemcpyDeviceToHost,

@@ -255,12 +255,28 @@ int mv_op_hidden2grid(int device, const float* h, const float* w, int32_t M,
   });
 }
 
-int mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
-                    int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
-                    float gamma, int32_t fix_num_timestep, float* new_logprob,
-                    int32_t* ids, int32_t* parents) {
+// the masked forms of the three step ops: `allowed` [samples, K] goes up beside the logits
+static StepMask op_mask_up(OpCtx& ctx, DevBuf<uint8_t>& dm, const uint8_t* allowed, size_t samples,
+                           int K, const char* who) {
+  MV_REQUIRE(allowed, "%s: NULL allowed", who);
+  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "%s: K = %d cells (under a mask one wave holds a row of at "
+             "most %d)", who, K, 64 * mv::kBeamRankJ);
+  ctx.up(dm, allowed, samples * K);
+  StepMask m;
+  m.p = dm.p;
+  m.stride = K;
+  return m;
+}
+
+static int op_beam_step(int device, const float* logits, const float* prev_logprob,
+                        int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
+                        float gamma, int32_t fix_num_timestep, float* new_logprob,
+                        int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked) {
   return guarded(nullptr, [&] {
     OpCtx ctx(device);
+    DevBuf<uint8_t> dm;
+    StepMask mask;
+    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
     const size_t lds = ((size_t)2 * B * K + 512) * sizeof(float);
     ensure_beam_step_lds(device, lds);
     DevBuf<float> dl, dp, dn;
@@ -271,22 +287,42 @@ int mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
     DevBuf<float> dc;
     dc.alloc((size_t)N * B * K);
     launch_beam_step(ctx.stream, dl.p, dp.p, dc.p, N, B, K, time, diverse, logf(gamma),
-                     fix_num_timestep, dn.p, di.p, dpa.p, (int32_t*)nullptr, B);
+                     fix_num_timestep, dn.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, mask);
     ctx.down(new_logprob, dn, (size_t)N * B);
     ctx.down(ids, di, (size_t)N * B);
     ctx.down(parents, dpa, (size_t)N * B);
   });
 }
 
-int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
-                   const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
-                   int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
-                   float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
+int mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
+                    int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
+                    float gamma, int32_t fix_num_timestep, float* new_logprob,
+                    int32_t* ids, int32_t* parents) {
+  return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
+                      fix_num_timestep, new_logprob, ids, parents, nullptr, false);
+}
+
+int mv_op_beam_step_masked(int device, const float* logits, const float* prev_logprob,
+                           const uint8_t* allowed, int32_t N, int32_t B, int32_t K, int32_t time,
+                           int32_t diverse, float gamma, int32_t fix_num_timestep,
+                           float* new_logprob, int32_t* ids, int32_t* parents) {
+  return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
+                      fix_num_timestep, new_logprob, ids, parents, allowed, true);
+}
+
+static int op_sbs_step(int device, const float* logits, const float* prev_phi,
+                       const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
+                       int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
+                       float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents,
+                       const uint8_t* allowed, bool masked) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
     MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
                (double)temperature);
     OpCtx ctx(device);
+    DevBuf<uint8_t> dm;
+    StepMask mask;
+    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
     ensure_beam_step_lds(device, ((size_t)2 * B * K + 512) * sizeof(float));
     const size_t R = (size_t)N * B;
     DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
@@ -300,15 +336,33 @@ int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
     nphi.alloc(R); nlp.alloc(R); ng.alloc(R); di.alloc(R); dpa.alloc(R);
     cand.alloc(R * K); lpp.alloc(R * K); qp.alloc(R * K);
     launch_sbs_step(ctx.stream, dl.p, dphi.p, dlp.p, dg.p, cand.p, lpp.p, qp.p, dprm.p, N, B, K,
-                    t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B);
+                    t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, mask);
     ctx.down(new_phi, nphi, R); ctx.down(new_logprob, nlp, R); ctx.down(new_gumbel, ng, R);
     ctx.down(ids, di, R); ctx.down(parents, dpa, R);
   });
 }
 
-int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K, int32_t t,
-                      float temperature, uint32_t seed, int32_t top_k, float top_p, int32_t floor,
-                      int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
+int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
+                   const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
+                   int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
+                   float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
+  return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents, nullptr, false);
+}
+
+int mv_op_sbs_step_masked(int device, const float* logits, const float* prev_phi,
+                          const float* prev_logprob, const float* prev_gumbel,
+                          const uint8_t* allowed, int32_t N, int32_t B, int32_t K, int32_t t,
+                          float temperature, uint32_t seed, float* new_phi, float* new_logprob,
+                          float* new_gumbel, int32_t* ids, int32_t* parents) {
+  return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed, true);
+}
+
+static int op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K,
+                          int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
+                          int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep,
+                          const uint8_t* allowed, bool masked) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
@@ -322,6 +376,9 @@ int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int
                (double)top_p);
     MV_REQUIRE(floor >= 1, "mv_op_sample_step: floor %d must be >= 1", (int)floor);
     OpCtx ctx(device);
+    DevBuf<uint8_t> dm;
+    StepMask mask;
+    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)(R / S), K, "mv_op_sample_step_masked");
     DevBuf<float> dl, dlp, dq;
     DevBuf<int32_t> di;
     DevBuf<uint8_t> dk;
@@ -333,16 +390,27 @@ int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int
     dlp.alloc(R); dq.alloc(R); di.alloc(R); dk.alloc((size_t)R * K);
     HIP_CHECK(hipMemsetAsync(dlp.p, 0, (size_t)R * sizeof(float), ctx.stream));
     HIP_CHECK(hipMemsetAsync(dq.p, 0, (size_t)R * sizeof(float), ctx.stream));
-    const dim3 grid(cdiv((size_t)R, 4)), block(256);
-    with_rank_j(K, [&](auto j) {
-      hipLaunchKernelGGL(mv::sample_step_kernel<decltype(j)::value>, grid, block, 0, ctx.stream,
-                         dl.p, (int64_t)K, R, S, K, t, 0, dprm.p, floor, (const int32_t*)nullptr,
-                         dlp.p, dq.p, di.p, 1, (int32_t*)nullptr, dk.p);
-    });
+    launch_sample_step(ctx.stream, dl.p, (int64_t)K, R, S, K, t, 0, dprm.p, floor,
+                       (const int32_t*)nullptr, dlp.p, dq.p, di.p, 1, (int32_t*)nullptr, dk.p, mask);
     HIP_CHECK(hipGetLastError());
     ctx.down(ids, di, R); ctx.down(lp, dlp, R); ctx.down(qlp, dq, R);
     ctx.down(keep, dk, (size_t)R * K);
   });
+}
+
+int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K, int32_t t,
+                      float temperature, uint32_t seed, int32_t top_k, float top_p, int32_t floor,
+                      int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
+  return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
+                        qlp, keep, nullptr, false);
+}
+
+int mv_op_sample_step_masked(int device, const float* logits, const uint8_t* allowed, int32_t R,
+                             int32_t S, int32_t K, int32_t t, float temperature, uint32_t seed,
+                             int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
+                             float* qlp, uint8_t* keep) {
+  return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
+                        qlp, keep, allowed, true);
 }
 
 int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,

@@ -36,16 +36,27 @@ void with_rank_j(int K, F&& fn) {
   else fn(std::integral_constant<int, mv::kBeamRankJ>{});
 }
 
+// The allowed cells of one decode step (mv_set_cell_mask): sample n's plane [K] is p + n * stride.
+// p == nullptr: no mask, and every launch is the unmasked one.
+struct StepMask {
+  const uint8_t* p = nullptr;
+  int64_t stride = 0;
+};
+
 // One beam step (log-softmax + diversity penalty + top-B).  K <= 1024: the rank count on
 // one wave per (n, b) row over the whole chip, then the per-sample selection; larger K
-// (or MV_BEAM_STEP=v1): the single-launch kernel.  `cand` = [N*B, K] scratch.
+// (or MV_BEAM_STEP=v1): the single-launch kernel.  `cand` = [N*B, K] scratch.  With a mask the
+// step always takes the two-launch form (K <= 1024), whatever MV_BEAM_STEP says.
 void launch_beam_step(hipStream_t stream, const float* logits, const float* prev_lp,
                       float* cand, int N, int B, int K, int time, int diverse,
                       float log_gamma, int fix_num_timestep, float* new_lp, int32_t* ids,
                       int32_t* parents, int32_t* src_row, int rows_per_sample,
-                      int32_t* row_ref = nullptr) {
+                      int32_t* row_ref = nullptr, StepMask mask = StepMask{}) {
   static const bool v1 = getenv("MV_BEAM_STEP") && strcmp(getenv("MV_BEAM_STEP"), "v1") == 0;
-  if (v1 || K > 64 * mv::kBeamRankJ || !cand) {
+  if (mask.p)
+    MV_REQUIRE(K <= 64 * mv::kBeamRankJ && cand, "beam step under a cell mask: grid of %d cells "
+               "(one wave holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
+  if (!mask.p && (v1 || K > 64 * mv::kBeamRankJ || !cand)) {
     hipLaunchKernelGGL(mv::beam_step_kernel, dim3(N), dim3(512),
                        ((size_t)2 * B * K + 512) * sizeof(float), stream, logits, prev_lp, B,
                        K, time, diverse, log_gamma, fix_num_timestep, new_lp, ids, parents,
@@ -56,8 +67,14 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   const int R = N * B;
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
-    hipLaunchKernelGGL(mv::beam_rank_kernel<decltype(j)::value>, grid, block, 0, stream, logits,
-                       prev_lp, R, B, K, time, diverse, log_gamma, cand);
+    constexpr int J = decltype(j)::value;
+    if (mask.p)
+      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true>), grid, block, 0, stream, logits, prev_lp,
+                         R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride);
+    else
+      hipLaunchKernelGGL((mv::beam_rank_kernel<J, false>), grid, block, 0, stream, logits,
+                         prev_lp, R, B, K, time, diverse, log_gamma, cand,
+                         (const uint8_t*)nullptr, (int64_t)0);
   });
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
@@ -74,7 +91,8 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
                      const float* prev_lp, const float* prev_g, float* cand, float* lp_plane,
                      float* q_plane, const uint32_t* params, int N, int B, int K, int t,
                      float* new_phi, float* new_lp, float* new_g, int32_t* ids, int32_t* parents,
-                     int32_t* src_row, int rows_per_sample, int32_t* row_ref = nullptr) {
+                     int32_t* src_row, int rows_per_sample, int32_t* row_ref = nullptr,
+                     StepMask mask = StepMask{}) {
   MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampling without replacement: grid of %d cells (one wave "
              "holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
   MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first step "
@@ -82,15 +100,41 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
   const int R = N * B;
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
-    hipLaunchKernelGGL(mv::sbs_perturb_kernel<decltype(j)::value>, grid, block, 0, stream, logits,
-                       prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                       q_plane);
+    constexpr int J = decltype(j)::value;
+    if (mask.p)
+      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true>), grid, block, 0, stream, logits,
+                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
+                         q_plane, mask.p, mask.stride);
+    else
+      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, false>), grid, block, 0, stream, logits,
+                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
+                         q_plane, (const uint8_t*)nullptr, (int64_t)0);
   });
   hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
                      prev_phi, prev_lp, B, K, t, new_phi, new_lp, new_g, ids, parents, src_row,
-                     rows_per_sample, row_ref);
+                     rows_per_sample, row_ref, mask.p ? 1 : 0);
   HIP_CHECK(hipGetLastError());
+}
+
+// One step of the independent sampler (sample_step_kernel), masked or not; arguments as the
+// kernel's.
+void launch_sample_step(hipStream_t stream, float* logits, int64_t row_stride, int R, int S,
+                        int K, int t, int shared, const uint32_t* params, int floor,
+                        const int32_t* lens, float* lp_acc, float* lq_acc, int32_t* ids,
+                        int ids_stride, int32_t* src_row, uint8_t* keep_out, StepMask mask) {
+  const dim3 grid(cdiv((size_t)R, 4)), block(256);
+  with_rank_j(K, [&](auto j) {
+    constexpr int J = decltype(j)::value;
+    if (mask.p)
+      hipLaunchKernelGGL((mv::sample_step_kernel<J, true>), grid, block, 0, stream, logits,
+                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
+                         ids_stride, src_row, keep_out, mask.p, mask.stride);
+    else
+      hipLaunchKernelGGL((mv::sample_step_kernel<J, false>), grid, block, 0, stream, logits,
+                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
+                         ids_stride, src_row, keep_out, (const uint8_t*)nullptr, (int64_t)0);
+  });
 }
 
 // MV_CHAIN_STREAMS=1 keeps the whole greedy forward on one stream (the order before the chain

@@ -266,7 +266,7 @@ struct mv_engine {
   // rows of every ConvLSTM problem of every grouped gate launch of the last forward
   // (mv_last_forward_gate_rows); a replayed graph carries the count of its capture
   int64_t gate_rows = 0;
-  std::map<std::tuple<ForwardKind, int, int>, int64_t> graph_gate_rows;
+  std::map<std::tuple<ForwardKind, int, int, int>, int64_t> graph_gate_rows;
   // beam
   DevBuf<float> bm_logits;         // [T, N, B, K] per-step logits
   DevBuf<int32_t> bm_ids, bm_parents;  // [T, N, B]
@@ -301,6 +301,17 @@ struct mv_engine {
   // [N, B] log-probability of each future under the PROPOSAL (tempered, truncated):
   // the independent sampler accumulates it beside bm_lp[0]; without replacement it is the final phi
   DevBuf<float> lq_acc;
+  // caller-given allowed cells (mv_set_cell_mask; sticky until cleared).  The
+  // device copy has ONE address and one of two layouts, so that a captured forward follows a
+  // later mask: [N, 1, K] for Tm == 1, [N, max_pred_len, K] for Tm > 1 (planes past max_pred_len
+  // are never read and not kept).  cmask_count [N, Tm]: allowed cells per plane, taken on the
+  // host when the mask is set and checked at the forward.
+  DevBuf<uint8_t> cmask_dev;
+  std::vector<int32_t> cmask_count;
+  int cmask_tm = 0;                // 0 = no mask
+  bool cmask_set() const { return cmask_tm > 0; }
+  int64_t cmask_stride(int K) const { return cmask_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
+  int64_t cmask_step(int K) const { return cmask_tm > 1 ? K : 0; }
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps
@@ -356,9 +367,11 @@ struct mv_engine {
     auto it = planes.find(dst);
     if (it != planes.end()) it->second.valid = false;
   }
-  // hipGraph replay of the forward (one graph per (kind, T_pred, U))
+  // hipGraph replay of the forward (one graph per (kind, T_pred, U, cell mask: 0 none, 1 one
+  // plane, 2 a plane per step))
   bool graph_mode = false;
-  std::map<std::tuple<ForwardKind, int, int>, hipGraphExec_t> graphs;
+  std::map<std::tuple<ForwardKind, int, int, int>, hipGraphExec_t> graphs;
+  int64_t graph_captures = 0;        // forwards captured so far (mv_graph_captures)
   void drop_graphs() {
     for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
     graphs.clear();

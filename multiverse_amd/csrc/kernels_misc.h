@@ -1322,15 +1322,47 @@ void beam_step_kernel(const float* __restrict__ logits,
 //                       owner rescans.  One barrier per round.
 constexpr int kBeamRankJ = 16;   // K <= 1024
 
+// Caller-given allowed cells (include/multiverse_hip.h mv_set_cell_mask): the kernels that hold a
+// row in one wave's registers come in a MASKED form, instantiated beside the unmasked one, whose
+// in-row predicate `lane + 64 j < K` is "in row AND allowed".  The row's mask plane [K] (one
+// byte per cell, non-zero = allowed) is read once per wave into one bit per owned cell (bit j:
+// k = lane + 64 j); a cell past the row is not allowed.  No LDS, no scratch, no indexed arrays.
 template <int J>
+__device__ __forceinline__ uint32_t step_row_allowed_bits(const uint8_t* __restrict__ plane,
+                                                          int K, int lane) {
+  static_assert(J <= 32, "one bit per owned cell");
+  uint32_t am = 0u;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    if (k < K && plane[k] != 0) am |= 1u << j;
+  }
+  return am;
+}
+
+// the in-row predicate of owned cell j; the unmasked form does not read `am`
+template <bool MASKED>
+__device__ __forceinline__ bool step_cell_in(uint32_t am, int lane, int j, int K) {
+  if constexpr (MASKED) return ((am >> j) & 1u) != 0u;   // (a set bit is in the row)
+  else return lane + 64 * j < K;
+}
+
+// MASKED: amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A cell
+// outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
+// nothing, so an allowed cell's rank counts allowed cells only.
+template <int J, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict__ prev_lp,
                       int R, int B, int K, int time, int diverse, float log_gamma,
-                      float* __restrict__ cand) {
+                      float* __restrict__ cand, const uint8_t* __restrict__ amask = nullptr,
+                      int64_t mask_stride = 0) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   if (time <= 1 && (r % B) != 0) return;   // only beam 0 is a candidate at the first step
+  uint32_t am = 0u;
+  if constexpr (MASKED)
+    am = step_row_allowed_bits<J>(amask + (size_t)(r / B) * mask_stride, K, lane);
   const float* row = logits + (size_t)r * K;
   float v[J];
   float mx = -INFINITY;
@@ -1351,6 +1383,11 @@ void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict_
   const float pl = prev_lp[r];
 #pragma unroll
   for (int j = 0; j < J; ++j) v[j] = pl + ((v[j] - mx) - lse);
+  if constexpr (MASKED) {
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (!step_cell_in<true>(am, lane, j, K)) v[j] = -INFINITY;
+  }
   if (diverse) {
     int rank[J];
 #pragma unroll
@@ -1490,9 +1527,10 @@ __device__ __forceinline__ void step_row_log_softmax(const float* __restrict__ r
 
 // log_softmax terms of a row already in registers (-inf past K): step_row_log_softmax's
 // arithmetic in its order
-template <int J>
+// MASKED: v is -inf outside the allowed cells too, and the sum runs over the allowed cells
+template <int J, bool MASKED = false>
 __device__ __forceinline__ void step_regs_log_softmax(const float (&v)[J], int K, int lane,
-                                                      float& mx, float& lse) {
+                                                      float& mx, float& lse, uint32_t am = 0u) {
   mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < J; ++j) mx = fmaxf(mx, v[j]);
@@ -1501,7 +1539,7 @@ __device__ __forceinline__ void step_regs_log_softmax(const float (&v)[J], int K
   float sum = 0.f;
 #pragma unroll
   for (int j = 0; j < J; ++j)
-    if (lane + 64 * j < K) sum += expf(v[j] - mx);
+    if (step_cell_in<MASKED>(am, lane, j, K)) sum += expf(v[j] - mx);
   sum = wave_sum(sum);
   lse = logf(sum);
 }
@@ -1527,17 +1565,20 @@ __device__ __forceinline__ uint32_t float_order_key(float x) {
 // count and sum over j and two butterflies.  No LDS, no scratch, no indexed register arrays.
 // -> the threshold (keep(k) <=> float_order_key(v[k]) >= threshold); lse_kept = logf of the kept
 // cells' sum of e, taken in the same order.
-template <int J>
+// MASKED (mv_set_cell_mask): a cell outside the allowed set `am` is absent, as a cell past K is:
+// e, sum_e, c(k), m(k) and the floor run over the allowed cells, and mxq is their maximum.
+template <int J, bool MASKED = false>
 __device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
                                                             const float (&w)[J], float mxq, int K,
                                                             int lane, int top_k, float top_p,
-                                                            int floor, float& lse_kept) {
+                                                            int floor, float& lse_kept,
+                                                            uint32_t am = 0u) {
   uint32_t key[J];
   float e[J];
   float sum_e = 0.f;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
-    const bool in = lane + 64 * j < K;
+    const bool in = step_cell_in<MASKED>(am, lane, j, K);
     key[j] = in ? float_order_key(v[j]) : 0u;     // (a pad never counts: masked by e and `in`)
     e[j] = in ? expf(w[j] - mxq) : 0.f;
     if (in) sum_e += e[j];
@@ -1554,7 +1595,7 @@ __device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
     float m = 0.f;
 #pragma unroll
     for (int j = 0; j < J; ++j) {
-      const bool above = lane + 64 * j < K && key[j] > probe;
+      const bool above = step_cell_in<MASKED>(am, lane, j, K) && key[j] > probe;
       cnt += above ? 1 : 0;
       if (above) m += e[j];
     }
@@ -1567,7 +1608,7 @@ __device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
   float sum_kept = 0.f;
 #pragma unroll
   for (int j = 0; j < J; ++j)
-    if (lane + 64 * j < K && key[j] >= thr) sum_kept += e[j];
+    if (step_cell_in<MASKED>(am, lane, j, K) && key[j] >= thr) sum_kept += e[j];
   lse_kept = logf(wave_sum(sum_kept));
   return thr;
 }
@@ -1596,13 +1637,18 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // state row the S rows of sample n continue from.  params: {seed, temperature bits, top_k,
 // top_p bits}, read on the device so that a replayed graph follows mv_set_sampling and
 // mv_set_sampling_truncation.  keep_out (mv_op_sample_step only): the kept set [R, K].
-template <int J>
+// MASKED (mv_set_cell_mask): amask + n * mask_stride is the sample's plane at this step.  lp stays
+// the log-softmax over ALL cells; the proposal treats a cell outside the plane as absent: w is
+// -inf there, mxq and the sums run over the allowed cells (also at temperature 1 with no limit:
+// the proposal differs from the model), and keep(k) = allowed and the limits' predicate.
+template <int J, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
                         int t, int shared, const uint32_t* __restrict__ params, int floor,
                         const int32_t* __restrict__ lens, float* __restrict__ lp_acc,
                         float* __restrict__ lq_acc, int32_t* __restrict__ ids, int ids_stride,
-                        int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out) {
+                        int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out,
+                        const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1621,15 +1667,24 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   float w[J];
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
-  if (tempered) step_regs_log_softmax<J>(w, K, lane, mxq, lseq);
-  if (limited) thr = step_row_keep_threshold<J>(v, w, mxq, K, lane, top_k, top_p, floor, lseq);
+  uint32_t am = 0u;
+  if constexpr (MASKED) {
+    am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (!step_cell_in<true>(am, lane, j, K)) w[j] = -INFINITY;
+  }
+  if (tempered || MASKED) step_regs_log_softmax<J, MASKED>(w, K, lane, mxq, lseq, am);
+  if (limited)
+    thr = step_row_keep_threshold<J, MASKED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq, am);
   float best = -INFINITY, blp = 0.f, blq = 0.f;
   int bi = 0x7fffffff;
 #pragma unroll
   for (int j = 0; j < J; ++j) {
     const int k = lane + 64 * j;
     if (k < K) {
-      const bool kept = !limited || float_order_key(v[j]) >= thr;
+      const bool kept = step_cell_in<MASKED>(am, lane, j, K) &&
+                        (!limited || float_order_key(v[j]) >= thr);
       if (keep_out) keep_out[(size_t)r * K + k] = kept ? 1 : 0;
       if (kept) {
         const float lp = (v[j] - mx) - lse;
@@ -1725,13 +1780,17 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 // With a top-k / nucleus limit on (step_row_keep_threshold; floor = B at t == 0, else 1), q is
 // renormalised over the kept cells and a dropped cell is the candidate -inf, never selected.
 
-template <int J>
+// MASKED (mv_set_cell_mask; amask + n * mask_stride = the sample's plane at this step): a cell
+// outside the plane is absent from the proposal as in sample_step_kernel -- q = cand = -inf -- and
+// the q plane is always written (sbs_select_kernel's force_q).
+template <int J, bool MASKED = false>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
                         const uint32_t* __restrict__ params, int floor,
                         float* __restrict__ cand, float* __restrict__ lp_plane,
-                        float* __restrict__ q_plane) {
+                        float* __restrict__ q_plane, const uint8_t* __restrict__ amask = nullptr,
+                        int64_t mask_stride = 0) {
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1746,14 +1805,22 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
   float w[J];
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
-  if (tempered) step_regs_log_softmax<J>(w, K, lane, mxq, lseq);
+  uint32_t am = 0u;
+  if constexpr (MASKED) {
+    am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+      if (!step_cell_in<true>(am, lane, j, K)) w[j] = -INFINITY;
+  }
+  if (tempered || MASKED) step_regs_log_softmax<J, MASKED>(w, K, lane, mxq, lseq, am);
   // top-k / nucleus limits (mv_set_sampling_truncation): q renormalised over the kept cells; a
   // dropped cell is no candidate (q = cand = -inf, written as such, not computed)
   const int top_k = (int)params[2];
   const float top_p = __builtin_bit_cast(float, params[3]);
   const bool limited = top_k > 0 || top_p < 1.f;   // uniform
   uint32_t thr = 0u;
-  if (limited) thr = step_row_keep_threshold<J>(v, w, mxq, K, lane, top_k, top_p, floor, lseq);
+  if (limited)
+    thr = step_row_keep_threshold<J, MASKED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq, am);
   const float phi = prev_phi[r], G = prev_g[r];
   float* lp_out = lp_plane + (size_t)r * K;
   float* q_out = q_plane + (size_t)r * K;
@@ -1763,11 +1830,12 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
     const int k = lane + 64 * j;
     if (k < K) {
       const float lp = (v[j] - mx) - lse;
-      const bool kept = !limited || float_order_key(v[j]) >= thr;
+      const bool kept = step_cell_in<MASKED>(am, lane, j, K) &&
+                        (!limited || float_order_key(v[j]) >= thr);
       // == lp bit for bit at temperature 1 with the limits off
       const float q = kept ? (w[j] - mxq) - lseq : -INFINITY;
       lp_out[k] = lp;
-      if (tempered || limited) q_out[k] = q;
+      if (tempered || limited || MASKED) q_out[k] = q;
       const float u = sample_uniform((uint32_t)b * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
       w[j] = kept ? (phi + q) + (-logf(-logf(u))) : -INFINITY;
       Z = fmaxf(Z, w[j]);
@@ -1796,7 +1864,7 @@ void sbs_select_kernel(const float* __restrict__ cand, const float* __restrict__
                        float* __restrict__ new_lp, float* __restrict__ new_g,
                        int32_t* __restrict__ ids, int32_t* __restrict__ parents,
                        int32_t* __restrict__ state_src_row, int state_rows_per_sample,
-                       int32_t* __restrict__ row_ref) {
+                       int32_t* __restrict__ row_ref, int force_q = 0) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ncand = (t > 0) ? B * K : K;
@@ -1837,8 +1905,10 @@ void sbs_select_kernel(const float* __restrict__ cand, const float* __restrict__
       const int par = flat / K;
       const size_t o = (size_t)n * B + sel, pr = (size_t)n * B + par;
       const size_t cell = (size_t)n * B * K + flat;
-      // the q plane exists when the proposal differs from the model: tempered or truncated
-      const bool has_q = __builtin_bit_cast(float, params[1]) != 1.f || (int)params[2] > 0 ||
+      // the q plane exists when the proposal differs from the model: tempered, truncated or
+      // (force_q) under a cell mask
+      const bool has_q = force_q != 0 ||
+                         __builtin_bit_cast(float, params[1]) != 1.f || (int)params[2] > 0 ||
                          __builtin_bit_cast(float, params[3]) < 1.f;
       const float lpk = lp_plane[cell];
       new_g[o] = wv;

@@ -137,12 +137,30 @@ __device__ __forceinline__ void occ_beam_weight_norm(const float* __restrict__ l
 // cost two barriers each.  Reductions in a fixed order, no atomics: the map is bitwise
 // reproducible, and a row's result depends on that row alone.
 // RAGGED (per-row lengths): the map of a step past its sample's end (t >= lens[n]) is 0.
-template <int CPT, bool RAGGED>
+// MASKED (mv_set_cell_mask): every future's step map is the softmax over the allowed cells of
+// (n, t) -- maximum and sum over them, a cell outside exactly 0.0f; the plane is
+// amask + n * mask_stride + t * mask_step, read once into one bit per owned cell.
+template <int CPT, bool RAGGED, bool MASKED = false>
 __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens) {
+    int B, int T, int K, const int32_t* __restrict__ lens,
+    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0) {
   __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
+  uint32_t am = 0u;                                // MASKED: bit c = cell tid + c * 256 is allowed
+  if constexpr (MASKED) {
+    const uint8_t* plane = amask + (size_t)n * mask_stride + (size_t)t * mask_step;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+      const int k = tid + c * kMfBlock;
+      if (k < K && plane[k] != 0) am |= 1u << c;
+    }
+  }
+  // cell c of this thread takes part in the softmax (the unmasked form does not read `am`)
+  auto in = [&](int c) {
+    if constexpr (MASKED) return ((am >> c) & 1u) != 0u;
+    else return tid + c * kMfBlock < K;
+  };
   if constexpr (RAGGED) {
     if (t >= lens[n]) {                            // block-uniform, before any barrier
       for (int k = tid; k < K; k += kMfBlock) out[(size_t)blockIdx.x * K + k] = 0.f;
@@ -168,7 +186,7 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
         const int k = tid + c * kMfBlock;
         // a cell past the row reads the row's last one (no divergent load) and is masked
         const float xv = live ? x[min(k, K - 1)] : 0.f;
-        v[j][c] = (live && k < K) ? xv : -INFINITY;
+        v[j][c] = (live && in(c)) ? xv : -INFINITY;
         mx[j] = fmaxf(mx[j], v[j][c]);
       }
     }
@@ -178,8 +196,7 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
       sm[j] = 0.f;
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const int k = tid + c * kMfBlock;
-        v[j][c] = (b0 + j < B && k < K) ? expf(v[j][c] - mx[j]) : 0.f;
+        v[j][c] = (b0 + j < B && in(c)) ? expf(v[j][c] - mx[j]) : 0.f;
         sm[j] += v[j][c];
       }
     }
@@ -203,10 +220,12 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
 // k = tid, tid + 256, ...  The row is read three times (maximum, sum, accumulation), the second
 // and third time from cache; the running map lives in the output row, which only this
 // workgroup -- and each cell only its own thread -- touches.
-template <bool RAGGED>
+// MASKED as above; the plane is read beside the row in every pass.
+template <bool RAGGED, bool MASKED = false>
 __global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
-    int B, int T, int K, const int32_t* __restrict__ lens) {
+    int B, int T, int K, const int32_t* __restrict__ lens,
+    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0) {
   __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
   if constexpr (RAGGED) {
@@ -218,17 +237,20 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
   float wm, ws;
   occ_beam_weight_norm(lp + (size_t)n * B, B, &wm, &ws);
   float* o = out + (size_t)blockIdx.x * K;
+  const uint8_t* am = nullptr;
+  if constexpr (MASKED) am = amask + (size_t)n * mask_stride + (size_t)t * mask_step;
+  auto in = [&](int k) { if constexpr (MASKED) return am[k] != 0; else return true; };
   for (int b = 0; b < B; ++b) {
     const float* x = logits + (((size_t)n * B + b) * T + t) * K;
     float mx[1] = {-INFINITY};
-    for (int k = tid; k < K; k += kMfBlock) mx[0] = fmaxf(mx[0], x[k]);
+    for (int k = tid; k < K; k += kMfBlock) if (in(k)) mx[0] = fmaxf(mx[0], x[k]);
     occ_block_reduce<true>(mx, red);
     float sm[1] = {0.f};
-    for (int k = tid; k < K; k += kMfBlock) sm[0] += expf(x[k] - mx[0]);
+    for (int k = tid; k < K; k += kMfBlock) if (in(k)) sm[0] += expf(x[k] - mx[0]);
     occ_block_reduce<false>(sm, red);
     const float w = expf(lp[(size_t)n * B + b] - wm) / ws;
     for (int k = tid; k < K; k += kMfBlock) {
-      const float p = (expf(x[k] - mx[0]) / sm[0]) * w;
+      const float p = in(k) ? (expf(x[k] - mx[0]) / sm[0]) * w : 0.f;
       o[k] = b == 0 ? p : o[k] + p;
     }
   }

@@ -223,6 +223,26 @@ def plan_ragged_batches(lengths, N, obs_lengths=None):
   return RaggedPlan(batches, sum(lengths), grouped)
 
 
+def cell_mask_from_scene(args, scene_onehot_last_frame, allowed_classes, min_share=0.0):
+  """The cells of the used grid a future may enter, from one frame of scene semantics (not in
+  the reference; include/multiverse_hip.h mv_set_cell_mask): scene_onehot_last_frame
+  [scene_h, scene_w, scene_class] one-hot over the NEW class ids of the scene_id2name map ->
+  bool [h, w].  Pixel row i belongs to grid row floor(i * h / H), columns likewise; a cell is
+  allowed iff the count of its pixels whose class is in `allowed_classes` is at least
+  max(1, ceil(min_share * pixels of the cell))."""
+  h, w = args.scene_grids[list(args.use_grids).index(True)]
+  sf = np.asarray(scene_onehot_last_frame)
+  H, W = sf.shape[:2]
+  ok = sf[..., [int(c) for c in allowed_classes]].any(axis=-1)
+  rows = (np.arange(H) * h) // H
+  cols = (np.arange(W) * w) // W
+  cell = rows[:, None] * w + cols[None, :]
+  total = np.bincount(cell.reshape(-1), minlength=h * w)
+  count = np.bincount(cell.reshape(-1), weights=ok.reshape(-1), minlength=h * w)
+  need = np.maximum(1, np.ceil(float(min_share) * total))
+  return (count >= need).reshape(h, w)
+
+
 def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_length=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
@@ -236,7 +256,12 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   Short tracks (`get_inputs` with args.allow_short_obs): a sample with fewer than obs_length
   frames is RIGHT-ALIGNED, the columns in front of it repeat its first observation (label,
   frame index, regress map: in range and finite, and ignored by the engine), and the feed
-  carries "obs_lengths" [N] -- only when some row of the batch is short."""
+  carries "obs_lengths" [N] -- only when some row of the batch is short.
+  args.allowed_classes (a list of new scene class ids; not in the reference): the feed carries
+  "cell_mask" [N, K] for the used grid, row n built by `cell_mask_from_scene` from the row's
+  LAST observed frame with args.allowed_min_share.  A row with fewer than num_out allowed cells
+  gets the all-ones row (a beam of num_out needs that many first cells) and is listed in
+  "cell_mask_fallback" (positions in `idxs`); padding rows get all ones."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
@@ -293,6 +318,21 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
     scene_feat[new] = inputs["scene_feats"][old]
   feed["obs_scene"] = obs_scene
   feed["scene_feat"] = scene_feat
+  allowed_classes = getattr(args, "allowed_classes", None)
+  if allowed_classes:
+    h, w = args.scene_grids[list(args.use_grids).index(True)]
+    mask = np.ones((N, h * w), dtype="uint8")
+    fallback = []
+    for r in range(n_real):
+      last = inputs["scene_feats"][int(np.asarray(inputs["obs_scene"][idxs[r]])[-1][0])]
+      m = cell_mask_from_scene(args, last, allowed_classes,
+                               float(getattr(args, "allowed_min_share", 0.0))).reshape(-1)
+      if int(m.sum()) < int(args.num_out):
+        fallback.append(r)
+      else:
+        mask[r] = m
+    feed["cell_mask"] = mask
+    feed["cell_mask_fallback"] = fallback
   return feed, n_real
 
 
@@ -365,6 +405,13 @@ def _inference_batches(args, inputs, n, N):
           for lo in range(0, len(by_len[T]), N)]
 
 
+def _note_unconstrained(args, feed, idxs, traj_ids):
+  """args.unconstrained (a list, when the caller keeps one) collects the trajectory ids whose
+  row fell back to the all-ones cell mask (`inference_feed`)."""
+  if getattr(args, "unconstrained", None) is not None:
+    args.unconstrained.extend(traj_ids[idxs[r]] for r in feed.get("cell_mask_fallback", []))
+
+
 def run_inference(args, model, inputs, traj_ids):
   """The per-sample loop of code/multifuture_inference.py:458-523 ->
   (output_data {traj_id: [num_out][T][2]}, beam_prob {traj_id: (logits
@@ -376,6 +423,7 @@ def run_inference(args, model, inputs, traj_ids):
   output_data, beam_prob = {}, {}
   for idxs, lengths in _inference_batches(args, inputs, len(traj_ids), N):
     feed, n_real = inference_feed(inputs, args, idxs, batch_size=N, lengths=lengths)
+    _note_unconstrained(args, feed, idxs, traj_ids)
     cls, reg, beam = model.run_forward(feed)
     # --use_single_decoder with beam search: the offsets come per beam, [N*B, T, H, W, 2]
     # (code/pred_models.py:287-296); the reference's script reshapes the B rows of its one
@@ -413,6 +461,7 @@ def run_inference_device(args, model, inputs, traj_ids):
   output_data, beam_prob, occupancy = {}, {}, {}
   for idxs, lengths in _inference_batches(args, inputs, len(traj_ids), N):
     feed, n_real = inference_feed(inputs, args, idxs, batch_size=N, lengths=lengths)
+    _note_unconstrained(args, feed, idxs, traj_ids)
     dec = model.run_forward_decoded(feed, center_only=bool(args.center_only),
                                     occupancy=want_occ,
                                     grid_centers=args.scene_grid_centers,
