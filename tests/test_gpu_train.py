@@ -26,12 +26,44 @@ def _rel(a, b):
   return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
-@pytest.mark.parametrize("Cx,zero", [(32, False), (64, False), (2, False), (64, True)])
-def test_convlstm_backward_op(built_lib, Cx, zero):
+def _kernel_slices(a, Cx):
+  """A gate kernel [3,3,Cx+C,4C] (or its gradient) per tap and x rows / h rows."""
+  out = []
+  for ky in range(3):
+    for kx in range(3):
+      if Cx > 0:
+        out.append(("tap %d,%d x rows" % (ky, kx), a[ky, kx, :Cx]))
+      out.append(("tap %d,%d h rows" % (ky, kx), a[ky, kx, Cx:]))
+  return out
+
+
+def _cell_grads(x, c, h, k, b, dhn, dcn, dtype):
+  """torch.autograd through the oracle's cell -> [dx, dc, dh, dkernel, dbiases]."""
+  ts = [torch.tensor(v, dtype=dtype, requires_grad=True) for v in (x, c, h, k, b)]
+  nc, nh = oracle.convlstm_cell(*ts)
+  loss = (nh * torch.tensor(dhn, dtype=dtype)).sum() + \
+      (nc * torch.tensor(dcn, dtype=dtype)).sum()
+  return [g.numpy() for g in torch.autograd.grad(loss, ts)]
+
+
+# (3,9,16): the default coarse grid.  (1,5,7) one partial 64-cell block, a width
+# that divides nothing; (5,2,7) M*K = 70, image rows and images ending inside a block, the
+# 2-channel x chunk; (2,18,9) the literal coarse grid; zero state at a ragged and a small grid
+# (the four (3,9,16) cases keep the ids they had when Cx and zero were the only parameters)
+@pytest.mark.parametrize("M,H,W,Cx,zero", [pytest.param(3, 9, 16, 32, False, id="32-False"),
+                                            pytest.param(3, 9, 16, 64, False, id="64-False"),
+                                            pytest.param(3, 9, 16, 2, False, id="2-False"),
+                                            pytest.param(3, 9, 16, 64, True, id="64-True"),
+                                            (1, 5, 7, 32, False), (5, 2, 7, 2, False),
+                                            (2, 18, 9, 64, False), (1, 5, 7, 64, True),
+                                            (3, 4, 8, 2, True)])
+def test_convlstm_backward_op(built_lib, M, H, W, Cx, zero):
   """One ConvLSTMCell step: gate backward + MFMA dgrad + MFMA wgrad + bias
-  column sums vs torch.autograd through the oracle's cell."""
+  column sums vs torch.autograd through the oracle's cell.  d kernel is held per tap and per
+  x rows / h rows (each slice to 2e-4 of ITS max): a tap that is wrong only at an image edge
+  would otherwise hide behind the other eight."""
   rng = np.random.default_rng(100 + Cx)
-  M, H, W, C = 3, 9, 16, 256
+  C = 256
   x = rng.normal(0, 1, (M, H, W, Cx)).astype("float32")
   c = rng.normal(0, 0.5, (M, H, W, C)).astype("float32")
   h = np.tanh(rng.normal(0, 1, (M, H, W, C))).astype("float32")
@@ -44,28 +76,81 @@ def test_convlstm_backward_op(built_lib, Cx, zero):
     h = np.zeros_like(h)
   got = built_lib.op_convlstm_bwd(x, None if zero else c, None if zero else h, k, b,
                                   dhn, dcn)
-
-  def ref(dtype):
-    ts = [torch.tensor(v, dtype=dtype, requires_grad=True) for v in (x, c, h, k, b)]
-    nc, nh = oracle.convlstm_cell(*ts)
-    loss = (nh * torch.tensor(dhn, dtype=dtype)).sum() + \
-        (nc * torch.tensor(dcn, dtype=dtype)).sum()
-    gs = torch.autograd.grad(loss, ts)
-    return [g.numpy() for g in gs]
-
-  r32, r64 = ref(torch.float32), ref(torch.float64)
+  r32 = _cell_grads(x, c, h, k, b, dhn, dcn, torch.float32)
+  r64 = _cell_grads(x, c, h, k, b, dhn, dcn, torch.float64)
   names = ["dx", "dc", "dh", "dkernel", "dbiases"]   # autograd order (x, c, h, k, b)
+  tag = "convlstm_bwd %dx%dx%d Cx=%d zero=%s" % (M, H, W, Cx, zero)
   # the op returns (dx, dh, dc, dkernel, dbiases)
   for nm, gi, ri in zip(names, [got[0], got[2], got[1], got[3], got[4]], range(5)):
     e_gpu, e_cpu = _rel(gi, r64[ri]), _rel(r32[ri], r64[ri])
-    print("convlstm_bwd Cx=%d zero=%s %-8s rel err gpu %.2e (cpu fp32 %.2e)"
-          % (Cx, zero, nm, e_gpu, e_cpu))
+    print("%s %-8s rel err gpu %.2e (cpu fp32 %.2e)" % (tag, nm, e_gpu, e_cpu))
     assert e_gpu < 2e-4, nm
+  worst, worst_cpu = 0.0, 0.0
+  for (what, g), (_, r), (_, r4) in zip(_kernel_slices(got[3], Cx), _kernel_slices(r64[3], Cx),
+                                        _kernel_slices(r32[3], Cx)):
+    if not np.abs(r).max() > 0:      # zero state: the h rows' gradient is identically zero
+      assert zero and what.endswith("h rows") and (g == 0.0).all(), what
+      continue
+    worst, worst_cpu = max(worst, _rel(g, r)), max(worst_cpu, _rel(r4, r))
+    assert _rel(g, r) < 2e-4, what
+  print("%s dkernel worst tap slice rel err gpu %.2e (cpu fp32 %.2e)" % (tag, worst, worst_cpu))
 
 
-def test_gnn_backward_op(built_lib):
+@pytest.mark.parametrize("hot", [(5, 7), (3, 4)])
+@pytest.mark.parametrize("hrow", [False, True])
+def test_convlstm_backward_op_transpose_detecting(built_lib, hot, hrow):
+  """The backward twin of test_convlstm_step_transpose_detecting: ONE hot d h' cell, ONE non-zero
+  weight -- tap (ky=0, kx=2), input channel 3 of x (or of h), gate j, channel 17 -- zero biases,
+  dense x, c, h on the 6 x 8 grid.  out(y,x) sees in(y-1, x+1) through that tap, so d x (d h) has
+  one non-zero cell, (hot y - 1, hot x + 1), and d kernel is non-zero in the four gate columns of
+  channel 17 only, at the taps whose input cell lies inside the grid.  With the hot cell in the
+  last row AND last column, (4, 8) is outside: d x and d h vanish entirely, and the taps ky = 2 /
+  kx = 2 of d kernel too (a kernel that runs on into the next image row or the next row of cells
+  shows there).  Non-zero entries where autograd has them, to 1e-6; everything else 0.0 exactly."""
+  M, H, W, Cx, C = 1, 6, 8, 32, 256
+  rng = np.random.default_rng(5)
+  x = rng.normal(0, 1, (M, H, W, Cx)).astype("f4")
+  c = rng.normal(0, 0.5, (M, H, W, C)).astype("f4")
+  h = np.tanh(rng.normal(0, 1, (M, H, W, C))).astype("f4")
+  kernel = np.zeros((3, 3, Cx + C, 4 * C), "f4")
+  kernel[0, 2, (Cx if hrow else 0) + 3, 1 * C + 17] = 2.0
+  biases = np.zeros(4 * C, "f4")
+  dhn = np.zeros((M, H, W, C), "f4")
+  dhn[0, hot[0], hot[1], 17] = 1.0
+  dcn = np.zeros_like(dhn)
+  dx, dh, dc, dk, db = built_lib.op_convlstm_bwd(x, c, h, kernel, biases, dhn, dcn)
+  rx, rc, rh, rk, rb = _cell_grads(x, c, h, kernel, biases, dhn, dcn, torch.float64)
+  # the reference itself has the structure the docstring states
+  src = (hot[0] - 1, hot[1] + 1)
+  moved = rh if hrow else rx
+  if src[1] < W:
+    assert np.count_nonzero(moved) == 1 and moved[0, src[0], src[1], 3] != 0
+  else:
+    assert not rx.any() and not rh.any()
+  assert not (rx if hrow else rh).any()
+  taps = {(ky, kx) for ky in range(3) for kx in range(3) if rk[ky, kx].any()}
+  assert taps == {(ky, kx) for ky in range(3) for kx in range(3)
+                  if 0 <= hot[0] + ky - 1 < H and 0 <= hot[1] + kx - 1 < W}
+  assert set(np.nonzero(rk)[3]) <= {17, C + 17, 2 * C + 17, 3 * C + 17}
+  for nm, g, r in (("dx", dx, rx), ("dh", dh, rh), ("dc", dc, rc), ("dkernel", dk, rk),
+                   ("dbiases", db, rb)):
+    nz = r != 0
+    print("convlstm_bwd one-hot hot=%s hrow=%s %-8s %d non-zero, max |gpu - ref| %.2e"
+          % (hot, hrow, nm, nz.sum(), np.abs(g - r).max()))
+    assert (g[~nz] == 0.0).all(), nm
+    assert np.abs(g[nz] - r[nz]).max(initial=0.0) < 1e-6, nm
+    assert (g[nz] != 0).all(), nm
+
+
+# (2,9,16) the default coarse grid.  (1,4,5) / (1,3,31) / (5,2,7): odd cell counts, widths that divide
+# nothing, image rows and images ending inside a group of cells; (3,18,9) the literal coarse
+# grid; C = 512: the <2> instances of both kernels; C = 128: half a wave's channels
+@pytest.mark.parametrize("M,H,W,C", [(2, 9, 16, 256), (1, 4, 5, 256), (1, 3, 31, 256),
+                                     (5, 2, 7, 256), (3, 18, 9, 256), (1, 4, 5, 512),
+                                     (2, 4, 5, 128)])
+def test_gnn_backward_op(built_lib, M, H, W, C):
   rng = np.random.default_rng(7)
-  M, H, W, C, D = 2, 9, 16, 256, 64
+  D = 64
   h = np.tanh(rng.normal(0, 1, (M, H, W, C))).astype("float32")
   s = np.tanh(rng.normal(0, 1, (M, H, W, D))).astype("float32")
   g = rng.normal(0, 1, (M, H, W, C)).astype("float32")
@@ -80,8 +165,8 @@ def test_gnn_backward_op(built_lib):
 
   r32, r64 = ref(torch.float32), ref(torch.float64)
   for nm, a, i in (("dh", dh, 0), ("dscene_mean", ds, 1)):
-    print("gnn_bwd %-12s rel err gpu %.2e (cpu fp32 %.2e)"
-          % (nm, _rel(a, r64[i]), _rel(r32[i], r64[i])))
+    print("gnn_bwd %dx%dx%d C=%d %-12s rel err gpu %.2e (cpu fp32 %.2e)"
+          % (M, H, W, C, nm, _rel(a, r64[i]), _rel(r32[i], r64[i])))
     assert _rel(a, r64[i]) < 1e-4, nm
 
 
@@ -101,7 +186,8 @@ def _train_case(use_grids, N, seed, gnn=True):
 def test_gradients_match_oracle(built_lib, use_grids, N, gnn, mode):
   """tf.gradients(loss, trainable_variables): every parameter tensor.  mode f16x3:
   the training forward's gate convolutions run on the fp16 matrix pipe (same
-  tolerances), the backward on the fp32 MFMA."""
+  tolerances), and so does the backward: dgrad and wgrad on two scaled fp16 planes per
+  operand (run_dgrad_group, run_wgrad)."""
   cfg, params, feed = _train_case(use_grids, N, 1, gnn)
   eng = built_lib.Engine(cfg, device=0)
   eng.set_params(params)

@@ -113,10 +113,22 @@ def test_two_rank_gradient_allreduce_matches_single_process(tmp_path):
 # ---- the shared-memory RCCL stand-in of the two-ranks-on-one-GPU test (tests/fake_rccl)
 
 _FAKE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fake_rccl", "libfakerccl.so")
+_HOOKS = os.path.join(os.path.dirname(_FAKE), "libmultiverse_hip_testhooks.so")
 
 
-@pytest.mark.skipif(not os.path.exists(_FAKE), reason="tests/fake_rccl not built (__graft_entry__.build())")
-def test_fake_rccl_exports_what_comm_h_binds():
+@pytest.fixture(scope="module")
+def fake_rccl_built():
+  """The stand-in and the test-hooks copy of the library are build products: where they are
+  missing when the test starts they are built here (__graft_entry__.build()), and a stand-in
+  that does not build FAILS the two tests below -- they never skip."""
+  if not (os.path.exists(_FAKE) and os.path.exists(_HOOKS)):
+    import __graft_entry__ as g
+    g.build()
+  assert os.path.exists(_FAKE), "tests/fake_rccl/libfakerccl.so did not build"
+  assert os.path.exists(_HOOKS), "the -DMV_TEST_HOOKS copy of the library did not build"
+
+
+def test_fake_rccl_exports_what_comm_h_binds(fake_rccl_built):
   """TEST INFRASTRUCTURE check: the stand-in carries the seven entry points
   multiverse_amd/csrc/comm.h resolves by dlsym, ids are unique and tagged, group calls nest,
   a world of one attaches without a peer, and foreign ids / dtypes are refused."""
@@ -151,12 +163,7 @@ def test_fake_rccl_exports_what_comm_h_binds():
   assert lib.ncclCommInitRank(C.byref(comm), 2, uid, 2) != 0      # rank out of range
 
 
-_HOOKS = os.path.join(os.path.dirname(_FAKE), "libmultiverse_hip_testhooks.so")
-
-
-@pytest.mark.skipif(not (os.path.exists(_FAKE) and os.path.exists(_HOOKS)),
-                    reason="tests/fake_rccl not built (__graft_entry__.build())")
-def test_mv_rccl_lib_is_a_hook_of_the_test_build_only():
+def test_mv_rccl_lib_is_a_hook_of_the_test_build_only(fake_rccl_built):
   """MV_RCCL_LIB (comm.h) exists ONLY in the -DMV_TEST_HOOKS copy of the library (selected
   with MV_LIB_PATH): there it binds exactly the named RCCL -- here the stand-in, recognisable
   by the tag in the unique id it hands out -- and reports a missing file.  The SHIPPED library
