@@ -675,6 +675,11 @@ int  mv_op_convlstm_step16(int device, int32_t variant, const float* x, const fl
  * h [M,H,W,C], scene_mean [M,H,W,D]. */
 int  mv_op_gnn(int device, const float* h, const float* scene_mean, int32_t M,
                int32_t H, int32_t W, int32_t C, int32_t D, float* out);
+/* The same with the kernel version asked for: 0 = the library's choice (mv_op_gnn), 1 = one wave
+ * per cell, 2 = LDS-tiled, 3 = register-blocked.  A version whose kernel does not take the shape
+ * runs the next one down that does (csrc/step_plan.h gnn_form), as in an engine. */
+int  mv_op_gnn_variant(int device, const float* h, const float* scene_mean, int32_t M,
+                       int32_t H, int32_t W, int32_t C, int32_t D, int32_t version, float* out);
 /* hidden2grid (pred_models.py:925-959): h [M,H,W,C], w [3,3,C,P] -> [M,H,W,P] */
 int  mv_op_hidden2grid(int device, const float* h, const float* w, int32_t M,
                        int32_t H, int32_t W, int32_t C, int32_t P, float* out);

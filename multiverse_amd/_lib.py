@@ -30,7 +30,8 @@ EXPORTED_SYMBOLS = [
     "mv_kernel_stat", "mv_kernel_stat_dense_flops", "mv_kernel_stat_mfma_flops",
     "mv_time_greedy_resident",
     "mv_time_beam_resident",
-    "mv_op_convlstm_step", "mv_op_convlstm_step16", "mv_op_gnn", "mv_op_hidden2grid", "mv_op_beam_step",
+    "mv_op_convlstm_step", "mv_op_convlstm_step16", "mv_op_gnn", "mv_op_gnn_variant",
+    "mv_op_hidden2grid", "mv_op_beam_step",
     "mv_train_init", "mv_train_step", "mv_train_forward_backward",
     "mv_upload_targets", "mv_grad_buffer", "mv_train_apply", "mv_get_grad", "mv_get_global_step",
     "mv_set_global_step", "mv_get_opt_slot", "mv_set_opt_slot",
@@ -274,6 +275,8 @@ def load():
   lib.mv_op_convlstm_step16.argtypes = [C.c_int, C.c_int32, _fp, _fp, _fp, _fp, _fp] + \
       [C.c_int32] * 5 + [_fp, _fp, _fp]
   lib.mv_op_gnn.argtypes = [C.c_int, _fp, _fp] + [C.c_int32] * 5 + [_fp]
+  if hasattr(lib, "mv_op_gnn_variant"):     # (an A/B build through MV_LIB_PATH may predate it)
+    lib.mv_op_gnn_variant.argtypes = [C.c_int, _fp, _fp] + [C.c_int32] * 6 + [_fp]
   lib.mv_op_hidden2grid.argtypes = [C.c_int, _fp, _fp] + [C.c_int32] * 5 + [_fp]
   lib.mv_op_beam_step.argtypes = [C.c_int, _fp, _fp, C.c_int32, C.c_int32,
                                   C.c_int32, C.c_int32, C.c_int32, C.c_float,
@@ -1309,13 +1312,15 @@ def op_convlstm_step16(x, c, h, kernel, biases, variant, device=0):
   return c_out, h_out, h16
 
 
-def op_gnn(h, scene_mean, device=0):
+def op_gnn(h, scene_mean, device=0, version=0):
+  """version: 0 = the library's choice, 1 / 2 / 3 = that kernel version where it takes the shape
+  (mv_op_gnn_variant)."""
   lib = load()
   h, scene_mean = f32(h), f32(scene_mean)
   M, H, W, Cc = h.shape
   out = np.empty_like(h)
-  check(lib.mv_op_gnn(device, fptr(h), fptr(scene_mean), M, H, W, Cc,
-                      scene_mean.shape[-1], fptr(out)))
+  check(lib.mv_op_gnn_variant(device, fptr(h), fptr(scene_mean), M, H, W, Cc,
+                              scene_mean.shape[-1], int(version), fptr(out)))
   return out
 
 

@@ -39,6 +39,7 @@
 
 #include "engine_state.h"
 #include "gate_plan.h"
+#include "step_plan.h"
 #include "engine_setup.h"
 #include "engine_forward.h"
 #include "engine_io.h"
@@ -112,8 +113,7 @@ int mv_create(const mv_config* cfg, int device, mv_handle* out) {
     build_param_table(e);
     alloc_buffers(e);
     if (cfg->beam_size > 1) {
-      const size_t K = e->sc[beam_scale(e)].K;
-      ensure_beam_step_lds(device, ((size_t)2 * cfg->beam_size * K + 512) * sizeof(float));
+      ensure_beam_step_lds(device, beam_step_lds_bytes(cfg->beam_size, e->sc[beam_scale(e)].K));
     }
   });
   if (rc != 0) {

@@ -427,13 +427,6 @@ struct Cursors {                 // which ping-pong buffer holds the live state
   int reg[MV_MAX_SCALES] = {0, 0};
 };
 
-// MV_BEAM_SHARED_FIRST=0 restores the tiled first beam step for A/B runs (run_decoders_beam)
-static bool beam_shared_first() {
-  static const bool on =
-      !(getenv("MV_BEAM_SHARED_FIRST") && atoi(getenv("MV_BEAM_SHARED_FIRST")) == 0);
-  return on;
-}
-
 // Encoders of every enabled scale (dynamic_rnn from the zero state, T_o steps;
 // code/pred_models.py:212-215, 232-234), all chains advanced in lockstep: step t's input
 // launches (on e->issue) and gate problems for the chains in `chains`.
@@ -532,7 +525,7 @@ void encoder_step_problems(mv_engine* e, Cursors& cur, int t, int chains,
       // first decoder step (and by the tiled-first-step A/B path of the beam decoder); the
       // regression encoder's never
       probs.back().skip_h32 =
-          (t + 1 < T || (!c.use_gnn && (c.beam_size == 1 || beam_shared_first()))) ? 1 : 0;
+          (t + 1 < T || (!c.use_gnn && (c.beam_size == 1 || step_knobs().beam_shared_first))) ? 1 : 0;
       if (sparse && e->no_scene()) {   // the decoder's by-class form, radius 2
         set_sparse_x(e, S, probs.back(), true, S.labels.p + t, T, 1);
         probs.back().sx_bias = S.sx_enc_bias.p;
@@ -586,18 +579,45 @@ void run_encoders(mv_engine* e, Cursors& cur, bool pairs) {
   }
 }
 
-// One attention pass per job; the LDS-tiled kernel takes up to two jobs per launch (the
-// two grid scales of a greedy step are 62 + 22 us back to back, one round of workgroups
-// each: together they fill the chip better).
-// MV_GNN = v1 (one wave per cell) / v2 (LDS-tiled, one cell per thread) select the earlier
-// kernels for A/B runs; default: the register-blocked third version.
-static int gnn_version() {
-  const char* v = getenv("MV_GNN");
-  if (v && strcmp(v, "v1") == 0) return 1;
-  if (v && strcmp(v, "v2") == 0) return 2;
-  return 3;
+// One attention launch in the form step_plan.h's gnn_form chose: the one or (tiled forms) two
+// problems of `group`, whose block counts are filled in here.  PerCell carries one problem.
+void launch_gnn(hipStream_t stream, GnnForm form, const mv::GnnGroup& group, int njobs, int C,
+                int D) {
+  if (form == GnnForm::PerCell) {
+    MV_REQUIRE(njobs == 1, "internal: the per-cell attention carries one job per launch");
+    const mv::GnnProblem& P = group.p[0];
+    const size_t cells = (size_t)P.M * P.H * P.W;
+    if (C <= 256)
+      hipLaunchKernelGGL(mv::gnn_attend_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0, stream,
+                         P.h, P.scene_mean, P.src_row, P.out, P.M, P.H, P.W, C, D, P.sm_div,
+                         P.p16, P.p16_stride);
+    else
+      hipLaunchKernelGGL(mv::gnn_attend_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0, stream,
+                         P.h, P.scene_mean, P.src_row, P.out, P.M, P.H, P.W, C, D, P.sm_div,
+                         P.p16, P.p16_stride);
+    return;
+  }
+  mv::GnnGroup grp = group;
+  unsigned nblocks = 0;
+  for (int j = 0; j < njobs; ++j) {
+    mv::GnnProblem& P = grp.p[j];
+    const size_t cells = (size_t)P.M * P.H * P.W;
+    const unsigned nb = form == GnnForm::Blocked ? mv::gnn_v3_blocks(cells, &P.ngroups)
+                                                 : mv::gnn_v2_blocks(cells, &P.ngroups);
+    if (j == 0) grp.nblocks0 = nb;
+    nblocks += nb;
+  }
+  if (form == GnnForm::Blocked)
+    hipLaunchKernelGGL(mv::gnn_attend_v3_kernel, dim3(nblocks), dim3(mv::kGnn3Threads), 0, stream,
+                       grp, C, D);
+  else
+    hipLaunchKernelGGL(mv::gnn_attend_v2_kernel, dim3(nblocks), dim3(mv::kGnnThreads), 0, stream,
+                       grp, C, D);
 }
 
+// One attention pass per job; the tiled forms take up to two jobs per launch (the two grid
+// scales of a greedy step are 62 + 22 us back to back, one round of workgroups each: together
+// they fill the chip better).  The form: step_plan.h gnn_form, the weaker of a pair's two.
 struct GnnJob {
   ScaleState* S; const float* h; const int32_t* src_row; float* out; int rows, sm_div;
   const int32_t* row_ref = nullptr;
@@ -605,24 +625,26 @@ struct GnnJob {
 
 void run_gnn_jobs(mv_engine* e, const std::vector<GnnJob>& jobs) {
   const mv_config& c = e->cfg;
-  static const int env_ver = gnn_version();
-  // The third version addresses h, the scene means and nothing else through 32-bit byte
-  // offsets and takes the scene channels in one 64-channel chunk; anything else runs on
-  // the second.
+  const int C = c.hidden_size, D = gnn_scene_dim(e);
+  // The kernels see D = gnn_scene_dim channels; a model of more than 64 scene channels keeps the
+  // per-cell form even where its attention reads none of them (SimAug's greedy graph).
+  const int D_form = c.scene_conv_dim > 64 ? c.scene_conv_dim : D;
+  // worst case of the engine, not this step's rows: one form per scale
   const size_t max_rows = (size_t)c.batch_size * (size_t)std::max(1, c.beam_size);
-  auto v3_ok = [&](const GnnJob& J) {
-    return (gnn_scene_dim(e) == 0 || gnn_scene_dim(e) == 64) &&
-           max_rows * J.S->K * c.hidden_size * 4 < ((size_t)1 << 32);
+  auto form_of = [&](const GnnJob& J) {
+    return gnn_form(0, J.S->W, C, D_form, max_rows * J.S->K * C * 4);
   };
   for (size_t j0 = 0; j0 < jobs.size();) {
-    const GnnJob& A = jobs[j0];
-    const bool tiled = env_ver >= 2 && A.S->W <= 32 && c.hidden_size == 256 && c.scene_conv_dim <= 64;
+    GnnForm form = form_of(jobs[j0]);
     size_t nj = 1;
-    if (tiled && j0 + 1 < jobs.size() && jobs[j0 + 1].S->W <= 32) nj = 2;
-    const int ver = env_ver >= 3 && !(v3_ok(A) && (nj == 1 || v3_ok(jobs[j0 + 1]))) ? 2 : env_ver;
+    if (form != GnnForm::PerCell && j0 + 1 < jobs.size() &&
+        form_of(jobs[j0 + 1]) != GnnForm::PerCell) {
+      nj = 2;
+      form = weaker(form, form_of(jobs[j0 + 1]));
+    }
+    const bool tiled = form != GnnForm::PerCell;
     mv::GnnGroup grp{};
     double flops = 0, bytes = 0;
-    unsigned nblocks = 0;
     for (size_t j = 0; j < nj; ++j) {
       const GnnJob& J = jobs[j0 + j];
       const size_t cells = (size_t)J.rows * J.S->K;
@@ -631,42 +653,17 @@ void run_gnn_jobs(mv_engine* e, const std::vector<GnnJob>& jobs) {
       // f16x3 inference: the only consumer of h + GNN(h) is the gate convolution, which
       // reads the operand planes -- the fp32 copy is not written at all
       const bool need_f32 = !(tiled && p16 && !e->train && e->compute_mode != 0);
-      flops += cells * (9.0 * 2 * 2 * (c.hidden_size + gnn_scene_dim(e)) +
-                        9.0 * 2 * c.hidden_size);
-      bytes += 4.0 * cells * c.hidden_size *
-                   (1.0 + (need_f32 ? 1.0 : 0.0) + (p16 ? 1.0 : 0.0)) +
-               4.0 * (cells / J.sm_div) * gnn_scene_dim(e);
-      int ng = 0;
-      const unsigned nb = ver >= 3 ? mv::gnn_v3_blocks(cells, &ng) : mv::gnn_v2_blocks(cells, &ng);
+      flops += cells * (9.0 * 2 * 2 * (C + D) + 9.0 * 2 * C);
+      bytes += 4.0 * cells * C * (1.0 + (need_f32 ? 1.0 : 0.0) + (p16 ? 1.0 : 0.0)) +
+               4.0 * (cells / J.sm_div) * D;
       mv::GnnProblem& P = grp.p[j];
       P.h = J.h; P.scene_mean = J.S->scene_mean.p; P.src_row = J.src_row;
       P.out = need_f32 ? J.out : nullptr; P.p16 = p16; P.p16_stride = pst;
-      P.M = J.rows; P.H = J.S->H; P.W = J.S->W; P.sm_div = J.sm_div; P.ngroups = ng;
+      P.M = J.rows; P.H = J.S->H; P.W = J.S->W; P.sm_div = J.sm_div;
       P.row_ref = J.row_ref;
-      if (j == 0) grp.nblocks0 = nb;
-      nblocks += nb;
     }
-    if (nj == 1) grp.nblocks0 = nblocks;
     launch(e, "gnn_attend", flops, bytes, [&] {
-      if (tiled && ver >= 3) {
-        hipLaunchKernelGGL(mv::gnn_attend_v3_kernel, dim3(nblocks), dim3(mv::kGnn3Threads), 0,
-                           e->issue, grp, c.hidden_size, gnn_scene_dim(e));
-      } else if (tiled) {
-        hipLaunchKernelGGL(mv::gnn_attend_v2_kernel, dim3(nblocks), dim3(mv::kGnnThreads), 0, e->issue,
-                           grp, c.hidden_size, gnn_scene_dim(e));
-      } else {
-        const size_t cells = (size_t)A.rows * A.S->K;
-        size_t pst = 0;
-        _Float16* p16 = e->plane_out(A.out, &pst);
-        if (c.hidden_size <= 256)
-          hipLaunchKernelGGL(mv::gnn_attend_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                             e->issue, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
-                             A.S->H, A.S->W, c.hidden_size, gnn_scene_dim(e), A.sm_div, p16, pst);
-        else
-          hipLaunchKernelGGL(mv::gnn_attend_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                             e->issue, A.h, A.S->scene_mean.p, A.src_row, A.out, A.rows,
-                             A.S->H, A.S->W, c.hidden_size, gnn_scene_dim(e), A.sm_div, p16, pst);
-      }
+      launch_gnn(e->issue, form, grp, (int)nj, C, D);
     });
     j0 += nj;
   }
@@ -688,11 +685,12 @@ void run_hidden2grid(mv_engine* e, ScaleState& S, const float* h, const float* w
   });
 }
 
-// MV_TAIL=v1 selects the first-round decoder tail (hidden2grid convolved in place,
-// separate argmax / embedding launches) for A/B runs
-static bool tail_v2() {
-  static const bool on = !(getenv("MV_TAIL") && strcmp(getenv("MV_TAIL"), "v1") == 0);
-  return on;
+// Does this engine's forward take the grouped decoder tail (step_plan.h tail_form)?
+bool tail_grouped(const mv_engine* e, bool training = false) {
+  int Kmax = 0;
+  for (int s = 0; s < e->cfg.num_scales; ++s)
+    if (e->sc[s].use) Kmax = std::max(Kmax, e->sc[s].K);
+  return tail_form(training, e->cfg.emb_size, Kmax) == TailForm::Grouped;
 }
 
 void run_emb_onehot(mv_engine* e, ScaleState& S, const int32_t* ids, int stride,
@@ -702,7 +700,7 @@ void run_emb_onehot(mv_engine* e, ScaleState& S, const int32_t* ids, int stride,
   launch(e, "grid_emb_onehot", (double)total, 4.0 * total, [&] {
     size_t pst = 0;
     _Float16* p16 = e->plane_out(out, &pst);
-    if (tail_v2() && E % 8 == 0)
+    if (step_knobs().tail_grouped && E % 8 == 0)   // (the 8-channel form came with that tail)
       hipLaunchKernelGGL(mv::grid_emb_onehot8_kernel, dim3(cdiv(total / 8, 256)), dim3(256), 0,
                          e->issue, ids, stride, ids_div, S.emb_cls_W->dev.p,
                          S.emb_cls_b->dev.p, out, rows, S.H, S.W, E, p16, pst, e->cfg.activation);
@@ -785,8 +783,7 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
   double qbytes = 0, qflops = 0, tbytes = 0;
   for (const TailPlan& pl : plans) {
     ScaleState& S = e->sc[pl.s];
-    MV_REQUIRE((size_t)S.K * 2 <= 2048 && E % 16 == 0 && E <= 512,
-               "decode tail: K %d / emb_size %d", S.K, E);
+    MV_REQUIRE(tail_grouped_fits(E, S.K), "decode tail: K %d / emb_size %d", S.K, E);
     const int reg_rows = pl.reg_rows ? pl.reg_rows : N;
     const size_t cc = (size_t)pl.cls_rows * S.K, cr = (size_t)reg_rows * S.K;
     if (pl.do_cls) {
@@ -893,7 +890,7 @@ ConvLstmArgs beam_cls_problem(mv_engine* e, int s, Cursors& cur, int time, int r
 void run_decoders_greedy(mv_engine* e, Cursors& cur, int Tp, bool pairs) {
   const mv_config& c = e->cfg;
   const int T = c.obs_len;
-  const bool v2 = tail_v2();
+  const bool v2 = tail_grouped(e);
   MV_REQUIRE(!pairs || (v2 && !c.use_single_decoder), "internal: chain pairs need the grouped "
              "decoder tail and a regression decoder");
   // ragged forward: max L steps, step t on the rows_at(t) rows of its active prefix
@@ -1124,7 +1121,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
   // per sample on the N encoder rows (bit-identical to the tiled computation): its logits
   // are copied to the B beam rows, and the first selection hands out state rows n instead
   // of n * B + parent.  MV_BEAM_SHARED_FIRST=0 restores the tiled first step for A/B runs.
-  const bool shared_first = beam_shared_first();
+  const bool shared_first = step_knobs().beam_shared_first;
   if (!shared_first) {
     const int cc = cur.cls[s];
     const size_t row4 = (size_t)K * C / 4, total4 = (size_t)R * row4;
@@ -1141,8 +1138,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
   if (wor) {
     MV_REQUIRE(!c.use_single_decoder, "sampling without replacement: use_single_decoder is not "
                "supported");
-    MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampling without replacement: grid of %d cells (one "
-               "wave holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
+    require_row_fits_wave("sampling without replacement", K);
     MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first "
                "step has only K distinct candidates)", B, K);
     HIP_CHECK(hipMemsetAsync(e->bm_phi[0].p, 0, (size_t)R * sizeof(float), e->issue));
@@ -1166,12 +1162,9 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
   // the B beams of a sample descend from few distinct parents, so it is computed once per
   // state row that some surviving beam continues (beam_select marks them in bm_ref; the rest
   // are skipped) and the next cell step reads it through the parent indirection, like c.
-  // Bit-identical to attention after the gather.  MV_BEAM_GNN_DEDUPE=0 gathers first.
-  static const bool dedupe_env =
-      !(getenv("MV_BEAM_GNN_DEDUPE") && atoi(getenv("MV_BEAM_GNN_DEDUPE")) == 0);
-  const bool dedupe = dedupe_env && shared_first && c.use_gnn && K <= 64 * mv::kBeamRankJ &&
-                      !(getenv("MV_BEAM_STEP") && strcmp(getenv("MV_BEAM_STEP"), "v1") == 0) &&
-                      !(getenv("MV_GNN") && strcmp(getenv("MV_GNN"), "v1") == 0);
+  // Bit-identical to attention after the gather.  MV_BEAM_GNN_DEDUPE=0 gathers first; when
+  // else: step_plan.h beam_gnn_dedupe.
+  const bool dedupe = beam_gnn_dedupe(c, K, shared_first);
   for (int time = 0; time <= Tsteps && Tsteps > 0; ++time) {
     // samples of this iteration's cell step / of the next one (uniform forward: N both)
     const int n_now = e->rows_at(std::max(time - 1, 0)), n_next = e->rows_at(time);
@@ -1186,7 +1179,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
                                        (c.use_gnn && !dedupe) ? nullptr : src, src,
                                        one_per_sample ? 1 : B,
                                        e->bm_ids.p + (size_t)std::max(time - 2, 0) * R, 1));
-      const bool v2 = tail_v2();
+      const bool v2 = tail_grouped(e);
       const bool single = c.use_single_decoder != 0;
       MV_REQUIRE(!single || v2, "use_single_decoder with beam search needs the v2 decoder tail");
       if (!single) probs.push_back(reg_decoder_problem(e, s, cur, time - 1, Tp, !v2));
@@ -1325,10 +1318,9 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
   const int N = c.batch_size, T = c.obs_len, B = c.beam_size, K = S.K;
   const int R = N * B;
   const char* who = scored ? "scoring forward" : "sampled decode";
-  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "%s: grid of %d cells (one wave holds a row "
-             "of at most %d)", who, K, 64 * mv::kBeamRankJ);
+  require_row_fits_wave(who, K);
   MV_REQUIRE(!c.use_single_decoder, "%s: use_single_decoder is not supported", who);
-  MV_REQUIRE(tail_v2(), "%s needs the v2 decoder tail", who);
+  MV_REQUIRE(tail_grouped(e), "%s needs the v2 decoder tail", who);
   HIP_CHECK(hipMemsetAsync(e->bm_lp[0].p, 0, (size_t)R * sizeof(float), e->issue));
   if (!scored) HIP_CHECK(hipMemsetAsync(e->lq_acc.p, 0, (size_t)R * sizeof(float), e->issue));
   if (scored) {
@@ -1407,23 +1399,6 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
   }
 }
 
-// The four chains of a greedy forward (class / regression x two scales) exchange nothing between
-// the scene stage and the end of the decode, and want different things from the chip: a gate
-// launch the matrix pipe, the attention / transform / tail kernels HBM and L2.  So the greedy
-// inference forward issues them as two chain pairs -- the class chains on the engine's stream,
-// the regression chains on a second one -- that meet once per forward: the second stream starts
-// after everything queued before the forward (uploads, weight packs), the engine's stream
-// continues after both.  The regression pair does not read the scene stage, which thereby runs
-// under its first encoder steps.  One stream, in the order of before: MV_CHAIN_STREAMS=1;
-// profiling (event brackets around overlapped launches time nothing); hipGraph capture (a
-// captured fork / join becomes parallel branches of the graph); beam search; a model with one
-// decoder (no regression chains); MV_TAIL=v1; batches above kChainPairMaxBatch -- measured on one
-// box, alternating fresh processes: batch 64 +0.7 % (bf16 mode +2.1 %), batch 256 -2.6 % (the
-// two gate launches of a step run side by side rather than against the other pair's small
-// kernels, and at 256 rows a launch of its own per pair costs more than the small kernels
-// hide); sizes in between are unmeasured and stay on one stream.
-constexpr int kChainPairMaxBatch = 64;
-
 // "The last enabled scale": the one a beam handle decodes on.
 int beam_scale(const mv_engine* e) {
   int s = 0;
@@ -1435,8 +1410,9 @@ void enqueue_forward(mv_engine* e, ForwardKind kind, bool capturing = false) {
   const mv_config& c = e->cfg;
   const int Tp = e->pred_len;
   const bool beam = kind != ForwardKind::Greedy;
-  const bool pairs = !beam && e->stream_b && !e->profiling && !capturing && c.beam_size == 1 &&
-                     !c.use_single_decoder && tail_v2() && c.batch_size <= kChainPairMaxBatch;
+  // the greedy forward as two chain pairs on two streams, or everything on one (step_plan.h)
+  const bool pairs = chain_pairs_planned(c, !beam, e->stream_b != nullptr, e->profiling,
+                                         capturing, tail_grouped(e));
   Cursors cur;
   auto decode_on_beams = [&] {
     if (kind == ForwardKind::Beam || kind == ForwardKind::SampledWor)
@@ -1574,9 +1550,7 @@ void run_forward(mv_engine* e, ForwardKind kind) {
   MV_REQUIRE(e->inputs_ready, "no inputs uploaded (mv_upload_inputs)");
   // a masked step holds a row in one wave: refused before anything is launched
   if (beam && kind != ForwardKind::Scored && e->cmask_set())
-    MV_REQUIRE(e->sc[beam_scale(e)].K <= 64 * mv::kBeamRankJ, "mv_set_cell_mask: grid of %d "
-               "cells (under a mask one wave holds a row of at most %d)",
-               e->sc[beam_scale(e)].K, 64 * mv::kBeamRankJ);
+    require_row_fits_wave("mv_set_cell_mask: a masked step", e->sc[beam_scale(e)].K);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");

@@ -194,44 +194,32 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
   });
 }
 
-int mv_op_gnn(int device, const float* h, const float* scene_mean, int32_t M,
-              int32_t H, int32_t W, int32_t C, int32_t D, float* out) {
+// version: 0 = step_plan.h's choice (the MV_GNN knob), 1 / 2 / 3 = at most that kernel version;
+// gnn_form's demotions apply to a version asked for as to the knob's.
+int mv_op_gnn_variant(int device, const float* h, const float* scene_mean, int32_t M,
+                      int32_t H, int32_t W, int32_t C, int32_t D, int32_t version, float* out) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(C % 64 == 0 && C <= 512 && D >= 0 && D <= 128,
                "gnn: C a multiple of 64 up to 512, D <= 128");
+    MV_REQUIRE(version >= 0 && version <= 3, "gnn: version %d not in [0, 3]", (int)version);
     OpCtx ctx(device);
     const size_t cells = (size_t)M * H * W;
     DevBuf<float> dh, ds, dout;
     ctx.up(dh, h, cells * C);
     ctx.up(ds, scene_mean, cells * D);
     dout.alloc(cells * C);
-    int ver = gnn_version();              // read per call: the kernel test runs every version
-    if (ver >= 3 && !((D == 0 || D == 64) && cells * C * 4 < ((size_t)1 << 32))) ver = 2;
-    if (ver >= 2 && W <= 32 && C == 256) {
-      int ng = 0;
-      const unsigned nb = ver >= 3 ? mv::gnn_v3_blocks(cells, &ng) : mv::gnn_v2_blocks(cells, &ng);
-      mv::GnnGroup grp{};
-      grp.p[0] = mv::GnnProblem{dh.p, ds.p, nullptr, dout.p, nullptr, 0, M, H, W, 1, ng, nullptr};
-      grp.nblocks0 = nb;
-      if (ver >= 3)
-        hipLaunchKernelGGL(mv::gnn_attend_v3_kernel, dim3(nb), dim3(mv::kGnn3Threads), 0, ctx.stream,
-                           grp, C, D);
-      else
-        hipLaunchKernelGGL(mv::gnn_attend_v2_kernel, dim3(nb), dim3(mv::kGnnThreads), 0, ctx.stream,
-                           grp, C, D);
-    } else {
-      if (C <= 256)
-        hipLaunchKernelGGL(mv::gnn_attend_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                           ctx.stream, dh.p, ds.p, (const int32_t*)nullptr, dout.p, M, H,
-                           W, C, D, 1, (_Float16*)nullptr, (size_t)0);
-      else
-        hipLaunchKernelGGL(mv::gnn_attend_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0,
-                           ctx.stream, dh.p, ds.p, (const int32_t*)nullptr, dout.p, M, H,
-                           W, C, D, 1, (_Float16*)nullptr, (size_t)0);
-    }
+    mv::GnnGroup grp{};
+    grp.p[0] = mv::GnnProblem{dh.p, ds.p, nullptr, dout.p, nullptr, 0, M, H, W, 1, 0, nullptr};
+    // (the bytes this call addresses, not an engine's worst case)
+    launch_gnn(ctx.stream, gnn_form(version, W, C, D, cells * C * 4), grp, 1, C, D);
     HIP_CHECK(hipGetLastError());
     ctx.down(out, dout, cells * C);
   });
+}
+
+int mv_op_gnn(int device, const float* h, const float* scene_mean, int32_t M,
+              int32_t H, int32_t W, int32_t C, int32_t D, float* out) {
+  return mv_op_gnn_variant(device, h, scene_mean, M, H, W, C, D, 0, out);
 }
 
 int mv_op_hidden2grid(int device, const float* h, const float* w, int32_t M,
@@ -259,8 +247,7 @@ int mv_op_hidden2grid(int device, const float* h, const float* w, int32_t M,
 static StepMask op_mask_up(OpCtx& ctx, DevBuf<uint8_t>& dm, const uint8_t* allowed, size_t samples,
                            int K, const char* who) {
   MV_REQUIRE(allowed, "%s: NULL allowed", who);
-  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "%s: K = %d cells (under a mask one wave holds a row of at "
-             "most %d)", who, K, 64 * mv::kBeamRankJ);
+  require_row_fits_wave(who, K);
   ctx.up(dm, allowed, samples * K);
   StepMask m;
   m.p = dm.p;
@@ -277,8 +264,7 @@ static int op_beam_step(int device, const float* logits, const float* prev_logpr
     DevBuf<uint8_t> dm;
     StepMask mask;
     if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
-    const size_t lds = ((size_t)2 * B * K + 512) * sizeof(float);
-    ensure_beam_step_lds(device, lds);
+    ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     DevBuf<float> dl, dp, dn;
     DevBuf<int32_t> di, dpa;
     ctx.up(dl, logits, (size_t)N * B * K);
@@ -323,7 +309,7 @@ static int op_sbs_step(int device, const float* logits, const float* prev_phi,
     DevBuf<uint8_t> dm;
     StepMask mask;
     if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
-    ensure_beam_step_lds(device, ((size_t)2 * B * K + 512) * sizeof(float));
+    ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     const size_t R = (size_t)N * B;
     DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
     DevBuf<int32_t> di, dpa;
@@ -367,8 +353,7 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
                (int)R, (int)S);
-    MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "mv_op_sample_step: K = %d cells (one wave holds a row "
-               "of at most %d)", (int)K, 64 * mv::kBeamRankJ);
+    require_row_fits_wave("mv_op_sample_step", K);
     MV_REQUIRE(temperature > 0.f, "mv_op_sample_step: temperature %g must be > 0",
                (double)temperature);
     MV_REQUIRE(top_k >= 0, "mv_op_sample_step: top_k %d must be >= 0 (0 = off)", (int)top_k);
@@ -534,17 +519,7 @@ int mv_op_gnn_bwd(int device, const float* h, const float* scene_mean, const flo
     ctx.up(dg_, g, cells * C);
     a.alloc(cells * 9); de.alloc(cells * 9); n.alloc(cells);
     odh.alloc(cells * C); ods.alloc(cells * (D ? D : 1));
-    if (C <= 256) {
-      hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0, ctx.stream,
-                         dh_.p, ds_.p, dg_.p, a.p, de.p, n.p, M, H, W, C, D);
-      hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0, ctx.stream,
-                         dh_.p, ds_.p, dg_.p, a.p, de.p, n.p, odh.p, ods.p, M, H, W, C, D, 0);
-    } else {
-      hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0, ctx.stream,
-                         dh_.p, ds_.p, dg_.p, a.p, de.p, n.p, M, H, W, C, D);
-      hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0, ctx.stream,
-                         dh_.p, ds_.p, dg_.p, a.p, de.p, n.p, odh.p, ods.p, M, H, W, C, D, 0);
-    }
+    launch_gnn_bwd(ctx.stream, dh_.p, ds_.p, dg_.p, a.p, de.p, n.p, odh.p, ods.p, M, H, W, C, D, 0);
     HIP_CHECK(hipGetLastError());
     ctx.down(dh, odh, cells * C);
     if (dscene_mean && D) ctx.down(dscene_mean, ods, cells * D);

@@ -43,24 +43,21 @@ struct StepMask {
   int64_t stride = 0;
 };
 
-// One beam step (log-softmax + diversity penalty + top-B).  K <= 1024: the rank count on
-// one wave per (n, b) row over the whole chip, then the per-sample selection; larger K
-// (or MV_BEAM_STEP=v1): the single-launch kernel.  `cand` = [N*B, K] scratch.  With a mask the
-// step always takes the two-launch form (K <= 1024), whatever MV_BEAM_STEP says.
+// One beam step (log-softmax + diversity penalty + top-B) in the form step_plan.h's
+// beam_step_form chooses.  `cand` = [N*B, K] scratch of the two-launch form.
 void launch_beam_step(hipStream_t stream, const float* logits, const float* prev_lp,
                       float* cand, int N, int B, int K, int time, int diverse,
                       float log_gamma, int fix_num_timestep, float* new_lp, int32_t* ids,
                       int32_t* parents, int32_t* src_row, int rows_per_sample,
                       int32_t* row_ref = nullptr, StepMask mask = StepMask{}) {
-  static const bool v1 = getenv("MV_BEAM_STEP") && strcmp(getenv("MV_BEAM_STEP"), "v1") == 0;
-  if (mask.p)
-    MV_REQUIRE(K <= 64 * mv::kBeamRankJ && cand, "beam step under a cell mask: grid of %d cells "
-               "(one wave holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
-  if (!mask.p && (v1 || K > 64 * mv::kBeamRankJ || !cand)) {
-    hipLaunchKernelGGL(mv::beam_step_kernel, dim3(N), dim3(512),
-                       ((size_t)2 * B * K + 512) * sizeof(float), stream, logits, prev_lp, B,
-                       K, time, diverse, log_gamma, fix_num_timestep, new_lp, ids, parents,
-                       src_row, rows_per_sample, row_ref);
+  if (mask.p) {
+    require_row_fits_wave("beam step under a cell mask", K);
+    MV_REQUIRE(cand, "internal: beam step under a cell mask without the candidate scratch");
+  }
+  if (beam_step_form(K, cand != nullptr, mask.p != nullptr) == BeamStepForm::Single) {
+    hipLaunchKernelGGL(mv::beam_step_kernel, dim3(N), dim3(512), beam_step_lds_bytes(B, K),
+                       stream, logits, prev_lp, B, K, time, diverse, log_gamma,
+                       fix_num_timestep, new_lp, ids, parents, src_row, rows_per_sample, row_ref);
     HIP_CHECK(hipGetLastError());   // a refused LDS size must not pass silently
     return;
   }
@@ -93,8 +90,7 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
                      float* new_phi, float* new_lp, float* new_g, int32_t* ids, int32_t* parents,
                      int32_t* src_row, int rows_per_sample, int32_t* row_ref = nullptr,
                      StepMask mask = StepMask{}) {
-  MV_REQUIRE(K <= 64 * mv::kBeamRankJ, "sampling without replacement: grid of %d cells (one wave "
-             "holds a row of at most %d)", K, 64 * mv::kBeamRankJ);
+  require_row_fits_wave("sampling without replacement", K);
   MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first step "
              "has only K distinct candidates)", B, K);
   const int R = N * B;
@@ -138,21 +134,12 @@ void launch_sample_step(hipStream_t stream, float* logits, int64_t row_stride, i
 }
 
 // MV_CHAIN_STREAMS=1 keeps the whole greedy forward on one stream (the order before the chain
-// pairs, for A/B runs); default 2.  MV_CHAIN_PRIORITY=1 creates the regression pair's stream at
-// the lowest priority, so that the class pair (attention + transform + gate + tail: the longer
-// critical path of a step) is dispatched first; default 0, plain streams.
-static int chain_streams() {
-  static const int n = (getenv("MV_CHAIN_STREAMS") && atoi(getenv("MV_CHAIN_STREAMS")) == 1) ? 1 : 2;
-  return n;
-}
-static bool chain_priority() {
-  static const bool on = getenv("MV_CHAIN_PRIORITY") && atoi(getenv("MV_CHAIN_PRIORITY")) == 1;
-  return on;
-}
-
+// pairs, for A/B runs).  MV_CHAIN_PRIORITY=1 creates the regression pair's stream at the lowest
+// priority, so that the class pair (attention + transform + gate + tail: the longer critical
+// path of a step) is dispatched first; default: plain streams.
 void create_chain_streams(mv_engine* e) {
-  if (chain_streams() != 2) return;
-  if (chain_priority()) {
+  if (step_knobs().chain_streams != 2) return;
+  if (step_knobs().chain_priority) {
     int least = 0, greatest = 0;
     HIP_CHECK(hipDeviceGetStreamPriorityRange(&least, &greatest));
     HIP_CHECK(hipStreamCreateWithPriority(&e->stream_b, hipStreamDefault, least));
@@ -613,9 +600,8 @@ int gnn_scene_dim(const mv_engine* e) {
 }
 
 bool sparse_x_on(const mv_engine* e, const ScaleState& S) {
-  static const bool off = getenv("MV_SPARSE_X") && atoi(getenv("MV_SPARSE_X")) == 0;
   const mv_config& c = e->cfg;
-  return !off && e->compute_mode != 0 && !e->train && S.use && S.H >= 3 && S.W >= 3 &&
+  return step_knobs().sparse_x && e->compute_mode != 0 && !e->train && S.use && S.H >= 3 && S.W >= 3 &&
          S.dec_cls.Cx == c.emb_size && c.emb_size % 16 == 0 && c.scene_conv_dim % 16 == 0 &&
          c.scene_conv_dim <= 64;
 }

@@ -670,13 +670,9 @@ void train_forward(mv_engine* e) {
     // (decode_tail) instead of two hidden2grid convolutions, an argmax and two embedding
     // launches per scale.  The embeddings of step ts+1 land in the time-major x buffers the
     // backward pass reads; dense class feedback and teacher forcing keep their own embedding
-    // launches at the head of the next iteration.  MV_TRAIN_TAIL=v1 restores the old launches.
-    static const bool tail2 = tail_v2() &&
-        !(getenv("MV_TRAIN_TAIL") && strcmp(getenv("MV_TRAIN_TAIL"), "v1") == 0);
-    bool tail_fits = E % 16 == 0 && E <= 512;   // run_tail's own limits (decode_tail LDS)
-    for (int s = 0; s < c.num_scales; ++s)
-      if (e->sc[s].use && (size_t)e->sc[s].K * 2 > 2048) tail_fits = false;
-    if (tail2 && tail_fits) {
+    // launches at the head of the next iteration.  MV_TRAIN_TAIL=v1, or a grid the grouped tail
+    // does not fit, restores the old launches (step_plan.h tail_form).
+    if (tail_grouped(e, /*training=*/true)) {
       std::vector<TailPlan> plans;
       for (int s = 0; s < c.num_scales; ++s) {
         ScaleState& S = e->sc[s];
@@ -1221,6 +1217,26 @@ void run_wgrad(mv_engine* e, TrainChain& ch, const float* hin, int Tsteps, int H
   });
 }
 
+// Backward of the graph attention on M rows of an H x W grid: pass a (softmax weights, d e and
+// norms into the [cells, 9] / [cells] scratch a / de / n), then pass b (d h, d scene_mean;
+// `accumulate`: dsmean += instead of =).  One wave per cell; C > 256 takes the two-register form.
+void launch_gnn_bwd(hipStream_t stream, const float* h, const float* scene_mean, const float* g,
+                    float* a, float* de, float* n, float* dh, float* dsmean, int M, int H, int W,
+                    int C, int D, int accumulate) {
+  const dim3 grid(cdiv((size_t)M * H * W, 4)), block(256);
+  if (C <= 256) {
+    hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<1>, grid, block, 0, stream, h, scene_mean, g, a, de,
+                       n, M, H, W, C, D);
+    hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<1>, grid, block, 0, stream, h, scene_mean, g, a, de,
+                       n, dh, dsmean, M, H, W, C, D, accumulate);
+  } else {
+    hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<2>, grid, block, 0, stream, h, scene_mean, g, a, de,
+                       n, M, H, W, C, D);
+    hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<2>, grid, block, 0, stream, h, scene_mean, g, a, de,
+                       n, dh, dsmean, M, H, W, C, D, accumulate);
+  }
+}
+
 void train_backward(mv_engine* e) {
   const mv_config& c = e->cfg;
   TrainState& t = TS(e);
@@ -1294,23 +1310,8 @@ void train_backward(mv_engine* e) {
         const float* hsrc = R.hs[0].p + slot * NKC;
         launch(e, "gnn_bwd", NK * (9.0 * 2 * 3 * (C + D) + 9.0 * 4 * C),
                4.0 * NK * (4.0 * C + 2.0 * D), [&] {
-          if (C <= 256) {
-          hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<1>, dim3(cdiv(NK, 4)), dim3(256), 0,
-                             e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p,
-                             R.gnn_de.p, R.gnn_n.p, N, S.H, S.W, C, gnn_scene_dim(e));
-          hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<1>, dim3(cdiv(NK, 4)), dim3(256), 0,
-                             e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p,
-                             R.gnn_de.p, R.gnn_n.p, dh_a[s][0], R.dsmean.p, N, S.H, S.W,
-                             C, gnn_scene_dim(e), 1);
-          } else {
-          hipLaunchKernelGGL(mv::gnn_bwd_a_kernel<2>, dim3(cdiv(NK, 4)), dim3(256), 0,
-                             e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p,
-                             R.gnn_de.p, R.gnn_n.p, N, S.H, S.W, C, gnn_scene_dim(e));
-          hipLaunchKernelGGL(mv::gnn_bwd_b_kernel<2>, dim3(cdiv(NK, 4)), dim3(256), 0,
-                             e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p,
-                             R.gnn_de.p, R.gnn_n.p, dh_a[s][0], R.dsmean.p, N, S.H, S.W,
-                             C, gnn_scene_dim(e), 1);
-          }
+          launch_gnn_bwd(e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p, R.gnn_de.p,
+                         R.gnn_n.p, dh_a[s][0], R.dsmean.p, N, S.H, S.W, C, gnn_scene_dim(e), 1);
         });
       } else {
         std::swap(dh_a[s][0], dh_b[s][0]);

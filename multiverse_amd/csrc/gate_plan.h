@@ -10,7 +10,8 @@ namespace {
 
 // ------------------------------------------------------------------ the A/B switches
 // Every environment switch that takes part in choosing or shaping a gate launch, read once per
-// process (DESIGN.md carries the table).  Other subsystems' switches stay with their code.
+// process (DESIGN.md carries the table).  The decode step's and the chain streams' switches:
+// step_plan.h.
 struct GateKnobs {
   bool wino, wino3, bf16t, wino_dgrad;      // MV_WINO, MV_WINO3, MV_BF16T, MV_WINO_DGRAD (=0: off)
   // MV_WINO_MAP, block -> column block map; each kernel has its own measured default
@@ -36,13 +37,17 @@ struct GateKnobs {
                         // light cone from kEncConeMinBatch rows on; 2 at any batch size
 };
 
+// (the two readers, shared with step_plan.h's switches)
+inline int env_num(const char* name, int unset) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : unset;
+}
+inline bool env_on(const char* name) { return env_num(name, 1) != 0; }     // off only by NAME=0
+
 inline const GateKnobs& gate_knobs() {
   static const GateKnobs k = [] {
-    auto num = [](const char* name, int unset) {
-      const char* v = getenv(name);
-      return v ? atoi(v) : unset;
-    };
-    auto on = [&](const char* name) { return num(name, 1) != 0; };     // off only by NAME=0
+    const auto num = env_num;
+    const auto on = env_on;
     GateKnobs g{};
     g.wino = on("MV_WINO"); g.wino3 = on("MV_WINO3"); g.bf16t = on("MV_BF16T");
     g.wino_dgrad = on("MV_WINO_DGRAD");

@@ -86,9 +86,9 @@ def test_gnn(built_lib, M, H, W):
     assert np.abs(out - twin).max() < 2e-6
 
 
-def test_gnn_kernel_versions_and_position_independence(built_lib, monkeypatch):
-  """The three kernels of the graph attention (MV_GNN=v1 one wave per cell, v2 LDS-tiled,
-  default: register-blocked + LDS-DMA) against the oracle on the same input; and the
+def test_gnn_kernel_versions_and_position_independence(built_lib):
+  """The three kernels of the graph attention (version 1 one wave per cell, 2 LDS-tiled,
+  0 = the default: register-blocked + LDS-DMA) against the oracle on the same input; and the
   default one gives a row the same bits wherever the row sits in its 64-cell groups
   (the engine's layout A/B tests rely on that)."""
   rng = _rng(77)
@@ -97,17 +97,41 @@ def test_gnn_kernel_versions_and_position_independence(built_lib, monkeypatch):
   sm = np.tanh(rng.normal(size=(M, H, W, 64))).astype("f4")
   ref = oracle.gnn_np(h, sm)
   outs = {}
-  for ver in ("v1", "v2", ""):
-    if ver:
-      monkeypatch.setenv("MV_GNN", ver)
-    else:
-      monkeypatch.delenv("MV_GNN", raising=False)
-    outs[ver] = built_lib.op_gnn(h, sm)
+  for ver in (1, 2, 0):
+    outs[ver] = built_lib.op_gnn(h, sm, version=ver)
     assert np.abs(outs[ver] - ref).max() < 2e-6, ver
-  assert np.abs(outs[""] - outs["v2"]).max() < 1e-6
+  assert np.abs(outs[0] - outs[2]).max() < 1e-6
   for lo in (1, 2, 3):
     part = built_lib.op_gnn(h[lo:], sm[lo:])
-    assert (part == outs[""][lo:]).all(), lo
+    assert (part == outs[0][lo:]).all(), lo
+
+
+def test_gnn_128_scene_channels_take_the_per_cell_kernel(built_lib):
+  """D = 128 at C = 256, W <= 32: the tiled kernels stage one 64-channel scene chunk, so the op
+  -- like an engine of that model -- runs the per-cell kernel (csrc/step_plan.h gnn_form).  A
+  tiled kernel here would drop scene channels 64 .. 127."""
+  rng = _rng(128)
+  M, H, W = 1, 3, 5
+  h = np.tanh(rng.normal(size=(M, H, W, 256))).astype("f4")
+  sm = np.tanh(rng.normal(size=(M, H, W, 128))).astype("f4")
+  ref = oracle.gnn_np(h, sm)
+  # the upper scene channels matter at this tolerance (else the case would check nothing)
+  assert np.abs(oracle.gnn_np(h, sm[..., :64]) - ref).max() > 1e-3
+  assert np.abs(built_lib.op_gnn(h, sm) - ref).max() < 2e-6
+
+
+@pytest.mark.parametrize("M,H,W", [(1, 3, 5), (3, 9, 16)])
+def test_gnn_version_3_demotes_to_2_at_a_partial_scene_chunk(built_lib, M, H, W):
+  """D = 32: the register-blocked kernel takes the scene channels as no chunk or one whole
+  64-channel chunk, so version 3 runs what version 2 runs (gnn_form), bit for bit."""
+  rng = _rng(32 + H)
+  h = np.tanh(rng.normal(size=(M, H, W, 256))).astype("f4")
+  sm = np.tanh(rng.normal(size=(M, H, W, 32))).astype("f4")
+  ref = oracle.gnn_np(h, sm)
+  v3 = built_lib.op_gnn(h, sm, version=3)
+  v2 = built_lib.op_gnn(h, sm, version=2)
+  assert v3.tobytes() == v2.tobytes()
+  assert np.abs(v3 - ref).max() < 2e-6
 
 
 @pytest.mark.parametrize("P", [1, 2])
@@ -140,3 +164,21 @@ def test_beam_step(built_lib, time, diverse):
     assert (ids[n] == ri).all(), (n, ids[n], ri)
     assert (parents[n] == rp).all()
     assert np.abs(new_lp[n] - rl).max() < 1e-4
+
+
+@pytest.mark.parametrize("time", [1, 2])
+@pytest.mark.parametrize("diverse", [True, False])
+def test_beam_step_single_launch_above_1024_cells(built_lib, time, diverse):
+  """K = 1100 > 1024: a row no longer fits one wave, so the unmasked step takes the single-launch
+  kernel (csrc/step_plan.h beam_step_form).  Same comparison as test_beam_step."""
+  rng = _rng(1100 + time)
+  N, B, K = 1, 2, 1100
+  logits = rng.normal(size=(N, B, K)).astype("f4")
+  # an exact tie inside a row, one of the pair past cell 1024
+  logits[0, 0, 10] = logits[0, 0, 1090] = logits[0, 0].max() + 1.0
+  prev = (rng.normal(size=(N, B)) * (time > 1)).astype("f4")
+  new_lp, ids, parents = built_lib.op_beam_step(logits, prev, time, diverse, 0.01, 1)
+  rl, ri, rp = naive_twin.beam_step_naive(logits[0], prev[0], time, 0.01, 1, diverse=diverse)
+  assert (ids[0] == ri).all(), (ids[0], ri)
+  assert (parents[0] == rp).all()
+  assert np.abs(new_lp[0] - rl).max() < 1e-4

@@ -20,8 +20,10 @@ exponent: F(2,3) forward, three-pass bf16 x); the literal 36 x 18 / 18 x 9 grids
 fp32 wgrad on the 9-wide grid); --convlstm_kernel 5 (generic loops); hidden sizes 128 and 512
 (every hidden size the engine accepts is a multiple of the Winograd channel block, so none can
 fail the packs' channel-block test); emb_size 128 (x rows of the wgrad in whole 64-channel
-groups); and weights with outliers (no Winograd form).  Environment switches are inherited: run
-it under MV_WINO3=0 etc. to table what a switch selects."""
+groups); weights with outliers (no Winograd form); and three shapes for the decode-step forms of
+csrc/step_plan.h (see configurations()).  The table cannot tell the two beam-step forms apart, nor
+the tiled from the blocked attention: same launch name, same accounted flops.  Environment
+switches are inherited: run it under MV_WINO3=0 etc. to table what a switch selects."""
 
 from __future__ import annotations
 
@@ -68,6 +70,18 @@ def configurations():
   out.append(("ck5/train", "train", "f32", ck5, None))
   out.append(("outliers/greedy", "greedy", "f16x3", dict(batch_size=2, use_grids=(0, 1)),
               "outliers"))
+  # the decode-step forms of csrc/step_plan.h the list above does not reach: 32 scene channels
+  # (the blocked attention demoted to the tiled one); the second scale alone of a 36 x 32 /
+  # 18 x 16 pyramid; a beam handle on 1152 cells (single-launch beam step, no attention dedupe;
+  # the grouped tail refuses that grid, so the table is the error text unless MV_TAIL=v1)
+  out.append(("scd32/greedy", "greedy", "f16x3",
+              dict(batch_size=2, use_grids=(1, 1), scene_conv_dim=32), None))
+  big = dict(scene_h=72, scene_w=64, scene_grids=[(36, 32), (18, 16)])
+  out.append(("grid36x32/greedy_scale1", "greedy", "f16x3",
+              dict(batch_size=2, use_grids=(0, 1), **big), None))
+  out.append(("grid36x32/beam2_hidden128", "beam", "f16x3",
+              dict(batch_size=1, use_grids=(1, 0), beam_size=2, enc_hidden_size=128,
+                   dec_hidden_size=128, **big), None))
   return out
 
 
