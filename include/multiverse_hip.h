@@ -538,6 +538,57 @@ int  mv_train_forward_backward(mv_handle h, const mv_inputs* in,
 int  mv_upload_targets(mv_handle h, const mv_targets* tg);
 int  mv_grad_buffer(mv_handle h, float** device_ptr, int64_t* elems);
 int  mv_train_apply(mv_handle h, float grad_scale);
+/* Per-row TRAINING lengths: one training step over rows of different history and horizon.
+ * obs_lengths[n] = Lo[n] in [1, obs_len], pred_lengths[n] = L[n] in [0, pred_len] (pred_len is
+ * the step's mv_inputs.pred_len); both are checked at the step, whose message names n and the
+ * value.  Either pointer NULL means that side is uniform (obs_len / pred_len for every row);
+ * both NULL clears.  Sticky until cleared.  Read ONLY by mv_train_step and
+ * mv_train_forward_backward (their resident forms included): no inference forward reads it, and
+ * mv_set_pred_lengths / mv_set_obs_lengths stay the forward's and keep refusing training.
+ * L[n] = 0 is a padding row: it contributes nothing, whatever its inputs hold.  At least one
+ * row must have L[n] > 0.
+ * Row layout (the forward's): observations RIGHT-ALIGNED in columns obs_len - Lo[n] ..
+ * obs_len - 1; targets (grid_pred_labels, grid_pred_regress, pred_xy of the compact upload, the
+ * soft maps made from them) LEFT-ALIGNED in columns 0 .. L[n] - 1.  The ignored columns must
+ * hold in-range labels / frame indices and finite floats (the upload checks read them); no loss
+ * and no gradient bit depends on them.
+ * Model per row: row n is the reference's model at obs_len = Lo[n], pred_len = L[n].  The
+ * encoders start from the zero state at the row's first observation; scene_mean is taken over
+ * the row's own frames, summed in ascending time order and divided by (float)Lo[n]; the
+ * decoders' first inputs are the last observed column; decode steps t >= L[n] do not exist for
+ * the row.
+ * Loss: with M = sum_n L[n], per used scale
+ *   cls_loss = grid_loss_weight * (1/M) sum_n sum_{t < L[n]} ce(n, t)
+ *   reg_loss = grid_reg_loss_weight * (1/(2 K M)) sum of the Huber elements of the valid (n, t)
+ * and with mask_grid_regression reg_loss is the foreground-masked mean over the valid (n, t)
+ * only (the foreground count is taken over them).  wd_loss is unchanged.  This is the mean over
+ * what exists; with every length full it is the uniform loss, and the step is the uniform one,
+ * launch for launch and bit for bit.  No operation couples batch rows, so (wd = 0) losses and
+ * gradients are the sums over the groups of rows with equal (Lo, L) of the uniform model's at
+ * (obs_len = Lo, pred_len = L) on the group, weighted |g| L / M (masked regression: by the
+ * group's foreground count over the total); wd > 0 adds wd * W once.
+ * Launches: encoder step t issues every launch of the step (input builders, dropout, gate
+ * group and their backward counterparts) on the prefix of 1 + max{n : L[n] > 0, Lo[n] >=
+ * obs_len - t} rows, decoder step t (the graph attention, tail and hidden2grid included) on the
+ * prefix of 1 + max{n : L[n] > t} rows; a step with no row is not issued.  Any row order is
+ * correct; rows sorted by L descending (ties by Lo descending) launch no finished and no padding
+ * row, and an unstarted row only in front of a row with a longer history.  The weight-gradient
+ * GEMMs run at full extent over rows whose gate gradients are cleared.
+ * Dropout (keep_prob < 1): the draw of an element is the uniform step's -- the same seed, the
+ * stream number computed from the uniform obs_len / pred_len, the element's index within the
+ * full [N, ..] step tensor -- so a row's mask does not depend on the other rows' lengths.
+ * With the in-library all-reduce (and mv_train_forward_backward + the caller's) the mean is
+ * the LOCAL one, as for uniform steps: ranks with different M are averaged, not M-weighted.
+ * A step whose lengths are not all full fails, with a message naming the call and the reason,
+ * in bf16 compute mode, for use_single_decoder models, models without the scene encoder,
+ * convlstm_kernel != 3 and under label mixup; mv_attack_begin / mv_attack_step and a training
+ * step inside an attack pass fail while training lengths are set at all. */
+int  mv_set_train_lengths(mv_handle h, const int32_t* obs_lengths /* [N] or NULL */,
+                          const int32_t* pred_lengths /* [N] or NULL */);
+/* the row counts of the last training step, summed over every ConvLSTM problem of every grouped
+ * gate launch: forward_rows as mv_last_forward_gate_rows counts a forward, dgrad_rows over the
+ * backward's dgrad groups.  With no training lengths set: the uniform counts. */
+int  mv_last_train_gate_rows(mv_handle h, int64_t* forward_rows, int64_t* dgrad_rows);
 /* -- in-library gradient all-reduce (RCCL over xGMI) ----
  * One process per GPU.  Rank 0 draws an id (mv_comm_unique_id) and hands its 128 bytes to
  * the other ranks out of band (any bootstrap: a file, MPI, torch.distributed); every rank

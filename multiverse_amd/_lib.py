@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_obs_lengths",
     "mv_set_cell_mask", "mv_graph_captures", "mv_op_beam_step_masked", "mv_op_sbs_step_masked",
     "mv_op_sample_step_masked",
+    "mv_set_train_lengths", "mv_last_train_gate_rows",
 ]
 
 
@@ -288,6 +289,9 @@ def load():
   lib.mv_upload_targets.argtypes = [h, C.POINTER(mv_targets)]
   lib.mv_grad_buffer.argtypes = [h, C.POINTER(_fp), C.POINTER(C.c_int64)]
   lib.mv_train_apply.argtypes = [h, C.c_float]
+  if hasattr(lib, "mv_set_train_lengths"):  # (an A/B build through MV_LIB_PATH may predate it)
+    lib.mv_set_train_lengths.argtypes = [h, _ip, _ip]
+    lib.mv_last_train_gate_rows.argtypes = [h, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
   lib.mv_get_grad.argtypes = [h, C.c_char_p, _fp, C.c_int64]
   lib.mv_get_global_step.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_global_step.argtypes = [h, C.c_int64]
@@ -903,6 +907,8 @@ class Engine(object):
         keep.append(lab)
         tg.grid_pred_labels[s] = iptr(lab)
       check(self.lib.mv_upload_targets_compact(self.handle, C.byref(tg)), self.handle)
+      self._set_feed_train_lengths(feed.get("train_obs_lengths"),
+                                   feed.get("train_pred_lengths"))
     del keep      # both calls copy synchronously
 
   # ---- pipelined greedy forward: feed of batch k+1 / fetch of batch k-1 under batch k
@@ -1073,7 +1079,46 @@ class Engine(object):
       tg.grid_pred_labels[s] = iptr(lab)
       tg.grid_pred_regress[s] = fptr(reg)
     self._keep_t = keep
+    self._set_feed_train_lengths(feed.get("train_obs_lengths"), feed.get("train_pred_lengths"))
     return tg
+
+  def _set_feed_train_lengths(self, obs_lengths, pred_lengths):
+    """feed["train_obs_lengths"] / feed["train_pred_lengths"], handled as feed["obs_lengths"]
+    is: set when present; a feed without them clears what an earlier FEED set.  Lengths set
+    through set_train_lengths stay (sticky until set_train_lengths(None, None))."""
+    if obs_lengths is None and pred_lengths is None:
+      if getattr(self, "_feed_train_lengths", False):
+        self.set_train_lengths(None, None)
+        self._feed_train_lengths = False
+      return
+    self.set_train_lengths(obs_lengths, pred_lengths)
+    self._feed_train_lengths = True
+
+  def set_train_lengths(self, obs_lengths=None, pred_lengths=None):
+    """Per-row lengths of the TRAINING step (include/multiverse_hip.h mv_set_train_lengths):
+    obs_lengths int [N] in [1, obs_len] (observations right-aligned), pred_lengths int [N] in
+    [0, pred_len] (targets left-aligned; 0 = padding row).  None = that side uniform; both None
+    clears.  Sticky; read by train_step / train_forward_backward only."""
+    arrs = []
+    for name, lengths in (("train_obs_lengths", obs_lengths), ("train_pred_lengths", pred_lengths)):
+      if lengths is None:
+        arrs.append(None)
+        continue
+      lens = i32(lengths).reshape(-1)
+      if lens.size != self.cfg.batch_size:
+        raise MvError("%s: %d values for batch_size %d" % (name, lens.size, self.cfg.batch_size))
+      arrs.append(lens)
+    check(self.lib.mv_set_train_lengths(self.handle,
+                                        iptr(arrs[0]) if arrs[0] is not None else None,
+                                        iptr(arrs[1]) if arrs[1] is not None else None),
+          self.handle)
+
+  def last_train_gate_rows(self):
+    """(forward_rows, dgrad_rows) of the last training step: the row counts summed over every
+    ConvLSTM problem of its grouped gate launches / dgrad groups."""
+    f, d = C.c_int64(), C.c_int64()
+    check(self.lib.mv_last_train_gate_rows(self.handle, C.byref(f), C.byref(d)), self.handle)
+    return int(f.value), int(d.value)
 
   @staticmethod
   def _losses(L):

@@ -632,7 +632,33 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_forward_backward: give both inputs and targets, or neither "
                "(resident)");
-    train_fwd_bwd(h, in, tg, out);
+    train_fwd_bwd(h, in, tg, out, "mv_train_forward_backward");
+  });
+}
+
+int mv_set_train_lengths(mv_handle h, const int32_t* obs_lengths, const int32_t* pred_lengths) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    const size_t N = (size_t)h->cfg.batch_size;
+    TrainLens& tl = h->tl;
+    // (the bounds are checked at the step, which knows pred_len)
+    tl.obs_host.clear(); tl.pred_host.clear();
+    if (obs_lengths) tl.obs_host.assign(obs_lengths, obs_lengths + N);
+    if (pred_lengths) tl.pred_host.assign(pred_lengths, pred_lengths + N);
+    tl.set = obs_lengths || pred_lengths;
+    tl.dirty = true;
+    tl.ragged = false;
+  });
+}
+
+int mv_last_train_gate_rows(mv_handle h, int64_t* forward_rows, int64_t* dgrad_rows) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(forward_rows && dgrad_rows, "mv_last_train_gate_rows: NULL argument");
+    MV_REQUIRE(h->train && TS(h).have_grads, "mv_last_train_gate_rows: no training step has run "
+               "on this handle");
+    *forward_rows = TS(h).fwd_gate_rows;
+    *dgrad_rows = TS(h).dgrad_rows;
   });
 }
 
@@ -688,7 +714,7 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
                "them first", "mv_train_step");
     MV_REQUIRE((in == nullptr) == (tg == nullptr),
                "mv_train_step: give both inputs and targets, or neither (resident)");
-    train_fwd_bwd(h, in, tg, out);
+    train_fwd_bwd(h, in, tg, out, "mv_train_step");
     // with a communicator the gradients are the SUM over the ranks (reduced inside
     // train_fwd_bwd, overlapped with the backward pass): mean, then clip + optimizer
     train_apply(h, h->comm ? 1.0f / (float)h->comm->world : 1.0f);
@@ -791,6 +817,8 @@ int mv_attack_begin(mv_handle h) {
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
                "(mv_set_obs_lengths); the attack runs the training forward, which encodes every "
                "row over obs_len frames -- clear them first", "mv_attack_begin");
+    MV_REQUIRE(!h->tl.set, "%s: per-row training lengths are set (mv_set_train_lengths); the "
+               "attacks train full-length rows -- clear them first", "mv_attack_begin");
     TrainState& t = TS(h);
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;
     t.scene_clean.alloc((size_t)h->cfg.batch_size * h->cfg.obs_len * h->cfg.scene_h *
@@ -852,6 +880,8 @@ int mv_attack_step(mv_handle h, float epsilon, float step) {
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
                "(mv_set_obs_lengths); the attack runs the training forward, which encodes every "
                "row over obs_len frames -- clear them first", "mv_attack_step");
+    MV_REQUIRE(!h->tl.set, "%s: per-row training lengths are set (mv_set_train_lengths); the "
+               "attacks train full-length rows -- clear them first", "mv_attack_step");
     MV_REQUIRE(h->train && TS(h).have_dscene && TS(h).scene_clean.p,
                "mv_attack_step: mv_attack_begin + mv_train_forward_backward first");
     const size_t n = (size_t)h->num_frames * h->cfg.scene_h * h->cfg.scene_w * h->cfg.scene_class;

@@ -98,6 +98,11 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
     q.wp16 = bf16 ? cells[i]->wpb.p : cells[i]->wp16.p;
     q.wx32 = bf16 ? cells[i]->wx32u.p : cells[i]->wx32.p;
     const size_t ncell = (size_t)a.rows * a.H * a.W;
+    // A ragged TRAINING step (TrainLens) changes a.rows from launch to launch, and its operands
+    // always take the slot's scratch: the second plane keeps the place it has at full batch, so
+    // that the zero halves in front of it (kPlanePad, which no split writes) are never inside
+    // what an earlier launch of another row count left there.
+    const size_t ncell_st = e->tl.issuing ? (size_t)e->cfg.batch_size * a.H * a.W : ncell;
     // bf16 mode, unbounded activations: three x passes (convlstm_f16x3.h xpasses)
     const int xpass = bf16_x_passes(e->compute_mode, e->dyn_x(), a.x_small);
     q.n_xk = a.x_small ? 0 : xpass * mv::f16x3_xksteps(a.Cx);
@@ -129,7 +134,7 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
       if (const auto* pb = ready(a.x)) {
         q.x16 = pb->p; q.x_plane_stride = (int64_t)pb->n;
       } else {
-        const size_t pst = ncell * a.Cx + mv::kPlaneSlack + mv::kPlanePad;
+        const size_t pst = ncell_st * a.Cx + mv::kPlaneSlack + mv::kPlanePad;
         MV_REQUIRE(e->px16[sl].n >= 2 * pst, "internal: f16x3 x plane scratch");
         _Float16* p0 = e->px16[sl].p + mv::kPlanePad;
         q.x16 = p0; q.x_plane_stride = (int64_t)pst;
@@ -150,7 +155,7 @@ void prepare_gate_operands(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
       if (const auto* pb = ready(a.h)) {
         q.h16 = pb->p; q.h_plane_stride = (int64_t)pb->n;
       } else {
-        const size_t pst = ncell * a.C + mv::kPlaneSlack + mv::kPlanePad;
+        const size_t pst = ncell_st * a.C + mv::kPlaneSlack + mv::kPlanePad;
         MV_REQUIRE(e->ph16[sl].n >= 2 * pst, "internal: f16x3 h plane scratch");
         _Float16* p0 = e->ph16[sl].p + mv::kPlanePad;
         q.h16 = p0; q.h_plane_stride = (int64_t)pst;
@@ -376,7 +381,9 @@ void run_conv_pairs(mv_engine* e, const std::vector<ConvLstmArgs>& a,
   { IssueOn on(e, 1); issue_gate_group(e, gb, pl); }
 }
 
-void run_scene(mv_engine* e) {
+// mean_lens (the training step's per-row observation lengths, engine_train.h): the window of
+// the scene mean when the forward's own obs plan is not in force
+void run_scene(mv_engine* e, const int32_t* mean_lens = nullptr) {
   const mv_config& c = e->cfg;
   const int U = e->num_frames;
   const float* in = e->scene_feat.p;
@@ -417,7 +424,8 @@ void run_scene(mv_engine* e) {
                          0, e->issue, e->scene_conv[s].p, e->obs_scene.p,
                          S.scene_mean.p, rows, c.obs_len, S.K,
                          c.scene_conv_dim,
-                         e->obs.ragged ? e->obs_lens_dev.p : (const int32_t*)nullptr);
+                         mean_lens ? mean_lens
+                                   : e->obs.ragged ? e->obs_lens_dev.p : (const int32_t*)nullptr);
     });
   }
 }

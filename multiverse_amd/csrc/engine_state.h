@@ -165,6 +165,48 @@ struct ObsPlan {
   }
 };
 
+// Per-row TRAINING lengths (mv_set_train_lengths): the two plans above for a
+// training step.  Row n is the model at obs_len = Lo[n], pred_len = L[n]; L[n] == 0 is a padding
+// row.  A step whose lengths are not all full is RAGGED: encoder step t issues its launches on
+// the prefix of enc_rows[t] = 1 + max{n : L[n] > 0, Lo[n] >= obs_len - t} rows, decoder step t on
+// dec_rows[t] = 1 + max{n : L[n] > t}; a step without rows is not issued.  live [obs_len +
+// pred_len][N] says per step which rows of [0, N) the step runs for their own model -- the
+// others (outside the prefix, not yet joined, finished, padding) are cleared by
+// zero_dead_rows_kernel.  Otherwise the step is the uniform one, launch for launch.
+struct TrainLens {
+  bool set = false;                  // mv_set_train_lengths holds a value
+  std::vector<int32_t> obs_host, pred_host;   // as given ([N]); empty: that side is uniform
+  bool dirty = true;                 // the device copy predates the setting
+  int built_pred_len = -1;
+  // the step being issued / issued last
+  bool ragged = false;
+  bool issuing = false;              // ... and its launches are being issued right now
+  std::vector<int32_t> Lo, L;        // [N] with the uniform side filled in
+  std::vector<int> enc_rows, dec_rows;   // [obs_len], [pred_len]
+  int64_t M = 0;                     // sum of L: the valid (n, t) of the losses
+  DevBuf<int32_t> dev;               // Lo [N] | L [N] | live [obs_len + pred_len][N]
+  int N = 0, To = 0;
+  const int32_t* d_obs() const { return dev.p; }
+  const int32_t* d_pred() const { return dev.p + N; }
+  const int32_t* d_enc_live(int t) const { return dev.p + (size_t)(2 + t) * N; }
+  const int32_t* d_dec_live(int t) const { return dev.p + (size_t)(2 + To + t) * N; }
+  void build(int n_rows, int obs_len, int pred_len, std::vector<int32_t>& live) {
+    N = n_rows; To = obs_len;
+    enc_rows.assign((size_t)obs_len, 0);
+    dec_rows.assign((size_t)pred_len, 0);
+    live.assign((size_t)(obs_len + pred_len) * N, 0);
+    M = 0;
+    for (int n = 0; n < N; ++n) {      // n ascending: the max
+      M += L[n];
+      for (int t = 0; t < L[n]; ++t) { dec_rows[t] = n + 1; live[(size_t)(To + t) * N + n] = 1; }
+      if (L[n] > 0)
+        for (int t = obs_len - Lo[n]; t < obs_len; ++t) {
+          enc_rows[t] = n + 1; live[(size_t)t * N + n] = 1;
+        }
+    }
+  }
+};
+
 struct ScaleState {
   int H = 0, W = 0, K = 0;
   bool use = false;
@@ -395,6 +437,9 @@ struct mv_engine {
   size_t pipe_head = 0, pipe_tail = 0;      // next slot to submit into / to collect from
   // in-library gradient all-reduce (mv_allreduce_init, comm.h); null: single device
   mv::Comm* comm = nullptr;
+  // per-row training lengths (mv_set_train_lengths; sticky until cleared): read by the training
+  // step alone, never by an inference forward
+  TrainLens tl;
   // training state (mv_train_init)
   mv_train_holder* train = nullptr;
   bool train_packs_valid = false;

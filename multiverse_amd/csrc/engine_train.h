@@ -95,6 +95,9 @@ struct TrainState {
   bool wgrad16_attr = false;
   bool have_grads = false;
   bool targets_ready = false;
+  // rows of every ConvLSTM problem of the last step's grouped gate launches / dgrad groups
+  // (mv_last_train_gate_rows)
+  int64_t fwd_gate_rows = 0, dgrad_rows = 0;
   mv_losses last{};
   uint32_t dropout_seed = 0;      // keep_prob < 1: seed of the next step's masks
   float beta1_power = 0.9f, beta2_power = 0.999f;   // Adam (TF non-slot variables)
@@ -474,9 +477,9 @@ void upload_targets_compact(mv_engine* e, const mv_targets_compact* tg) {
 
 ConvLstmArgs train_problem(mv_engine* e, TrainChain& ch, const float* x, const float* h,
                            const float* c, float* h_out, float* c_out, float* gates,
-                           int H, int W, bool zero_state) {
+                           int H, int W, bool zero_state, int rows = 0 /* 0: the batch */) {
   ConvLstmArgs a = conv_problem(e, *ch.cell, x, h, c, nullptr, nullptr, h_out, c_out,
-                                e->cfg.batch_size, H, W, zero_state);
+                                rows ? rows : e->cfg.batch_size, H, W, zero_state);
   a.gates_out = gates;
   return a;
 }
@@ -508,6 +511,85 @@ void run_dropout(mv_engine* e, float* x, size_t n, int s, int chain, int step) {
   });
 }
 
+// ---- per-row training lengths (mv_set_train_lengths; TrainLens in engine_state.h)
+// The setting against this step's obs_len / pred_len: range checks, what a ragged step does
+// not support, the two plans and their device copy.  A setting whose lengths are all full
+// leaves the step the uniform one.
+void train_lens_prepare(mv_engine* e, const char* call) {
+  TrainLens& tl = e->tl;
+  tl.ragged = false;
+  if (!tl.set) return;
+  const mv_config& c = e->cfg;
+  TrainState& t = TS(e);
+  const int N = c.batch_size, To = c.obs_len, Tp = e->pred_len;
+  tl.Lo.assign((size_t)N, To);
+  tl.L.assign((size_t)N, Tp);
+  if (!tl.obs_host.empty()) tl.Lo = tl.obs_host;
+  if (!tl.pred_host.empty()) tl.L = tl.pred_host;
+  bool full = true, any = false;
+  for (int n = 0; n < N; ++n) {
+    MV_REQUIRE(tl.Lo[n] >= 1 && tl.Lo[n] <= To, "%s: training observation length of row %d is "
+               "%d, not in [1, obs_len = %d] (mv_set_train_lengths)", call, n, tl.Lo[n], To);
+    MV_REQUIRE(tl.L[n] >= 0 && tl.L[n] <= Tp, "%s: training prediction length of row %d is %d, "
+               "not in [0, pred_len = %d] (mv_set_train_lengths)", call, n, tl.L[n], Tp);
+    full = full && tl.Lo[n] == To && tl.L[n] == Tp;
+    any = any || tl.L[n] > 0;
+  }
+  MV_REQUIRE(any, "%s: every training prediction length is 0 (mv_set_train_lengths): at least "
+             "one row must have a step to learn from", call);
+  MV_REQUIRE(!t.want_dscene, "%s: per-row training lengths are set (mv_set_train_lengths) inside "
+             "an attack pass (mv_attack_begin); the attacks train full-length rows -- clear them "
+             "first", call);
+  if (full) return;
+  MV_REQUIRE(e->compute_mode != 2, "%s: per-row training lengths (mv_set_train_lengths) are not "
+             "built for the bf16 compute mode; use f32 or f16x3", call);
+  MV_REQUIRE(!c.use_single_decoder, "%s: per-row training lengths (mv_set_train_lengths) are not "
+             "built for use_single_decoder models", call);
+  MV_REQUIRE(!e->no_scene(), "%s: per-row training lengths (mv_set_train_lengths) are not built "
+             "for a model without the scene encoder (scene_conv_dim 0)", call);
+  MV_REQUIRE(c.convlstm_kernel == 3, "%s: per-row training lengths (mv_set_train_lengths) are "
+             "not built for convlstm_kernel %d (3 only)", call, c.convlstm_kernel);
+  MV_REQUIRE(!t.mix_on, "%s: per-row training lengths (mv_set_train_lengths) are not built for "
+             "label mixup (mv_set_label_mixup); clear one of the two", call);
+  if (tl.dirty || tl.built_pred_len != Tp) {
+    std::vector<int32_t> live, up;
+    tl.build(N, To, Tp, live);
+    up.insert(up.end(), tl.Lo.begin(), tl.Lo.end());
+    up.insert(up.end(), tl.L.begin(), tl.L.end());
+    up.insert(up.end(), live.begin(), live.end());
+    // behind whatever of the previous step still reads the old copy
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    tl.dev.alloc((size_t)(2 + c.obs_len + c.max_pred_len) * N);
+    HIP_CHECK(hipMemcpy(tl.dev.p, up.data(), up.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    tl.dirty = false;
+    tl.built_pred_len = Tp;
+  }
+  tl.ragged = true;
+}
+
+// the dead rows of a step's tensors (zero_dead_rows_kernel), one launch per step and pass
+struct DeadRows {
+  mv::ZeroDeadArgs a{};
+  int n = 0;
+  uint32_t widest = 0;
+  void add(void* p, size_t row_elems) {
+    if (!p || row_elems == 0) return;
+    if (n >= 20) throw HipError{"internal: dead-row segments"};
+    a.p[n] = (float*)p; a.row_elems[n] = (uint32_t)row_elems;
+    widest = std::max(widest, (uint32_t)row_elems);
+    ++n;
+  }
+};
+void run_zero_dead(mv_engine* e, DeadRows& z, const int32_t* live) {
+  if (!z.n) return;
+  z.a.live = live;
+  const unsigned gx = std::min<unsigned>(cdiv(z.widest, 256), 32);
+  launch(e, "zero_dead_rows", 0, 0, [&] {
+    hipLaunchKernelGGL(mv::zero_dead_rows_kernel, dim3(gx, z.n, e->cfg.batch_size), dim3(256), 0,
+                       e->stream, z.a);
+  });
+}
+
 // ground-truth class maps / teacher-forcing inputs / fg count of this batch's targets
 void train_prepare_targets(mv_engine* e) {
   const mv_config& c = e->cfg;
@@ -522,6 +604,11 @@ void train_prepare_targets(mv_engine* e) {
       mv::SoftKernel sk{};
       const int ks = t.tc.use_soft_grid_class ? t.tc.soft_kernel_size : 0;
       for (int i = 0; i < ks * ks; ++i) sk.k[i] = t.tc.soft_kernel[i];
+      if (e->tl.ragged)     // all-zero maps where the row has no step: no foreground there
+        hipLaunchKernelGGL(mv::gt_class_maps_len_kernel, dim3(cdiv((size_t)Tp * NK, 256)),
+                           dim3(256), 0, e->stream, R.pred_labels.p, R.gt_cls.p, Tp, N, S.H, S.W,
+                           ks, sk, e->tl.d_pred());
+      else
       hipLaunchKernelGGL(mv::gt_class_maps_kernel, dim3(cdiv((size_t)Tp * NK, 256)), dim3(256),
                          0, e->stream, R.pred_labels.p, R.gt_cls.p, Tp, N, S.H, S.W, ks, sk);
     }
@@ -546,8 +633,11 @@ void train_forward(mv_engine* e) {
   const int cls_fb = t.tc.class_feedback;        // 0 one-hot, 1 dense logits, 2 ground truth
   const bool reg_tf = t.tc.reg_teacher_forcing != 0;
   const int nb = c.use_single_decoder ? 1 : 2;   // branches run: class (+ regression)
+  // per-row training lengths: the step's launches take the prefix the plan gives (N: uniform)
+  const TrainLens& tl = e->tl;
+  const bool rag = tl.ragged;
   train_prepare_targets(e);
-  if (!e->no_scene()) run_scene(e);
+  if (!e->no_scene()) run_scene(e, rag ? tl.d_obs() : nullptr);
   else {
     // no scene encoder: the class encoders' x of all T_o steps, time-major, in one launch per
     // scale (the shared person_pred/grid_emb; dropout below, per step)
@@ -576,6 +666,8 @@ void train_forward(mv_engine* e) {
   // encoders, all chains in lockstep (dynamic_rnn from the zero state)
   for (int ts = 0; ts < To; ++ts) {
     std::vector<ConvLstmArgs> probs;
+    const int P = rag ? tl.enc_rows[ts] : N;     // rows of the step
+    DeadRows zx, zo;      // ragged: dead rows of the step's x operands / of what it writes
     for (int s = 0; s < c.num_scales; ++s) {
       ScaleState& S = e->sc[s];
       if (!S.use) continue;
@@ -583,41 +675,68 @@ void train_forward(mv_engine* e) {
       const size_t NKC = (size_t)N * S.K * C;
       const int Cx = R.enc[0].Cx;          // D, or E without the scene encoder
       float* xc = R.enc[0].xs.p + (size_t)ts * N * S.K * Cx;
-      const size_t total = (size_t)N * S.K * Cx;
+      const size_t total = (size_t)P * S.K * Cx;
+      if (rag) {
+        zx.add(xc, (size_t)S.K * Cx);
+        zx.add(R.enc[1].xs.p + (size_t)ts * N * S.K * 2, (size_t)S.K * 2);
+        for (int b = 0; b < nb; ++b) {
+          // (slot ts + 1 cleared: a row that joins at step ts + 1 reads the zero state there)
+          zo.add(R.hs[b].p + (ts + 1) * NKC, (size_t)S.K * C);
+          zo.add(R.cs[b].p + (ts + 1) * NKC, (size_t)S.K * C);
+          zo.add(R.enc[b].gates.p + (size_t)ts * 4 * NKC, (size_t)S.K * 4 * C);
+        }
+      }
+      if (P == 0) continue;                // no row has joined yet: the step is not issued
       if (!e->no_scene())
       launch(e, "enc_class_input", 0, 4.0 * total, [&] {
         hipLaunchKernelGGL(mv::enc_class_input_kernel, dim3(cdiv(total, 256)), dim3(256),
                            0, e->stream, e->scene_conv[s].p, e->obs_scene.p, S.labels.p,
-                           xc, N, To, ts, S.K, D, (_Float16*)nullptr, (size_t)0,
+                           xc, P, To, ts, S.K, D, (_Float16*)nullptr, (size_t)0,
                            t.mix_on ? R.obs_labels2.p : (const int32_t*)nullptr, t.mix_w);
       });
       run_dropout(e, xc, total, s, 0, ts);
       if (nb == 2)
-        run_dropout(e, R.enc[1].xs.p + (size_t)ts * N * S.K * 2, (size_t)N * S.K * 2, s, 1, ts);
+        run_dropout(e, R.enc[1].xs.p + (size_t)ts * N * S.K * 2, (size_t)P * S.K * 2, s, 1, ts);
       for (int b = 0; b < nb; ++b) {
         const float* x = b == 0 ? xc : R.enc[1].xs.p + (size_t)ts * N * S.K * 2;
         probs.push_back(train_problem(
             e, R.enc[b], x, R.hs[b].p + ts * NKC, R.cs[b].p + ts * NKC,
             R.hs[b].p + (ts + 1) * NKC, R.cs[b].p + (ts + 1) * NKC,
-            R.enc[b].gates.p + (size_t)ts * 4 * NKC, S.H, S.W, ts == 0));
+            R.enc[b].gates.p + (size_t)ts * 4 * NKC, S.H, S.W, ts == 0, P));
       }
     }
+    if (rag) run_zero_dead(e, zx, tl.d_enc_live(ts));
     run_conv_group(e, probs);
+    if (rag) run_zero_dead(e, zo, tl.d_enc_live(ts));
   }
   // decoders (grid_decoder under raw_rnn, input_onehot for the class decoder)
   bool tail_embedded = false;      // the previous step's tail wrote this step's embeddings
   for (int ts = 0; ts < Tp; ++ts) {
     std::vector<ConvLstmArgs> probs;
+    const int P = rag ? tl.dec_rows[ts] : N;     // rows of the step
+    DeadRows zx, zo;      // ragged: dead rows of the step's operands / of what it writes
     for (int s = 0; s < c.num_scales; ++s) {
       ScaleState& S = e->sc[s];
       if (!S.use) continue;
       TrainScale& R = t.sc[s];
       const size_t NK = (size_t)N * S.K, NKC = NK * C;
+      const size_t PK = (size_t)P * S.K;         // cells of the step
       const int slot = To + ts;
+      if (rag) {
+        zx.add(R.dec[0].xs.p + (size_t)ts * NK * E, (size_t)S.K * E);
+        zx.add(R.dec[1].xs.p + (size_t)ts * NK * E, (size_t)S.K * E);
+        if (c.use_gnn) zx.add(R.hg.p + ts * NKC, (size_t)S.K * C);
+        for (int b = 0; b < nb; ++b) {
+          zo.add(R.hs[b].p + (slot + 1) * NKC, (size_t)S.K * C);
+          zo.add(R.cs[b].p + (slot + 1) * NKC, (size_t)S.K * C);
+          zo.add(R.dec[b].gates.p + (size_t)ts * 4 * NKC, (size_t)S.K * 4 * C);
+        }
+      }
+      if (P == 0) continue;                      // every row has finished: not issued
       // class decoder
       const float* hin = R.hs[0].p + slot * NKC;
       if (c.use_gnn) {
-        run_gnn(e, S, hin, nullptr, R.hg.p + ts * NKC, N, 1);
+        run_gnn(e, S, hin, nullptr, R.hg.p + ts * NKC, P, 1);
         hin = R.hg.p + ts * NKC;
       }
       float* xc = R.dec[0].xs.p + (size_t)ts * NK * E;
@@ -629,20 +748,20 @@ void train_forward(mv_engine* e) {
                            S.labels.p + (To - 1), R.obs_labels2.p + (To - 1), To, 0, t.mix_w,
                            R.onehot.p, 1, N, S.K);
         run_emb_dense(e, S, R.onehot.p, (size_t)S.K, xc, N, S.emb_cls_W, S.emb_cls_b, 1);
-      } else if (ts == 0) run_emb_onehot(e, S, S.labels.p + (To - 1), To, xc, N);
+      } else if (ts == 0) run_emb_onehot(e, S, S.labels.p + (To - 1), To, xc, P);
       else if (cls_fb == 0) {
-        if (!tail_embedded) run_emb_onehot(e, S, R.ids.p + (size_t)ts * N, 1, xc, N);
+        if (!tail_embedded) run_emb_onehot(e, S, R.ids.p + (size_t)ts * N, 1, xc, P);
       }
       else   // dense input map: the previous step's logits, or the step's ground truth
         run_emb_dense(e, S, cls_fb == 1 ? R.logits.p + (size_t)(ts - 1) * NK
                                         : R.gt_cls.p + (size_t)ts * NK,
-                      (size_t)S.K, xc, N, S.emb_cls_W, S.emb_cls_b, 1);
-      run_dropout(e, xc, NK * E, s, 2, ts);
+                      (size_t)S.K, xc, P, S.emb_cls_W, S.emb_cls_b, 1);
+      run_dropout(e, xc, PK * E, s, 2, ts);
       probs.push_back(train_problem(e, R.dec[0], xc, hin, R.cs[0].p + slot * NKC,
                                     R.hs[0].p + (slot + 1) * NKC,
                                     R.cs[0].p + (slot + 1) * NKC,
                                     R.dec[0].gates.p + (size_t)ts * 4 * NKC, S.H, S.W,
-                                    false));
+                                    false, P));
       if (nb == 1) continue;       // single decoder: offsets come from the class states
       // regression decoder
       float* xr = R.dec[1].xs.p + (size_t)ts * NK * E;
@@ -654,17 +773,32 @@ void train_forward(mv_engine* e) {
                                    N, hipMemcpyDeviceToDevice, e->stream));
       }
       if (reg_tf && ts > 0)       // teacher forcing: grid_pred_regress[:, ts] (:398)
-        run_emb_dense(e, S, R.reg_in.p + (size_t)ts * NK * 2, (size_t)S.K * 2, xr, N);
+        run_emb_dense(e, S, R.reg_in.p + (size_t)ts * NK * 2, (size_t)S.K * 2, xr, P);
       else if (!(tail_embedded && ts > 0))
-        run_emb_dense(e, S, R.regio.p + (size_t)ts * NK * 2, (size_t)S.K * 2, xr, N);
-      run_dropout(e, xr, NK * E, s, 3, ts);
+        run_emb_dense(e, S, R.regio.p + (size_t)ts * NK * 2, (size_t)S.K * 2, xr, P);
+      run_dropout(e, xr, PK * E, s, 3, ts);
       probs.push_back(train_problem(e, R.dec[1], xr, R.hs[1].p + slot * NKC,
                                     R.cs[1].p + slot * NKC, R.hs[1].p + (slot + 1) * NKC,
                                     R.cs[1].p + (slot + 1) * NKC,
                                     R.dec[1].gates.p + (size_t)ts * 4 * NKC, S.H, S.W,
-                                    false));
+                                    false, P));
     }
+    if (rag) run_zero_dead(e, zx, tl.d_dec_live(ts));
     run_conv_group(e, probs);
+    if (rag) {
+      // the step's outputs of the dead rows: logits, offsets and the next step's input ids are
+      // operands of the full-extent wgrads (no tail launch of this step writes them)
+      for (int s = 0; s < c.num_scales; ++s) {
+        ScaleState& S = e->sc[s];
+        if (!S.use) continue;
+        TrainScale& R = t.sc[s];
+        const size_t NK = (size_t)N * S.K;
+        zo.add(R.logits.p + (size_t)ts * NK, (size_t)S.K);
+        zo.add(R.regio.p + (size_t)(ts + 1) * NK * 2, (size_t)S.K * 2);
+        if (ts + 1 < Tp) zo.add(R.ids.p + (size_t)(ts + 1) * N, 1);
+      }
+      if (P == 0) { run_zero_dead(e, zo, tl.d_dec_live(ts)); continue; }
+    }
     // Decoder tail of the step on the inference kernels (round 3): hidden2grid of every chain
     // as ONE grouped GEMM launch (h2g_q) + one gather / argmax / next-embedding kernel
     // (decode_tail) instead of two hidden2grid convolutions, an argmax and two embedding
@@ -683,7 +817,7 @@ void train_forward(mv_engine* e) {
         const bool more = ts + 1 < Tp;
         TailPlan pl{};
         pl.s = s;
-        pl.cls_h = R.hs[0].p + slot * NKC; pl.cls_rows = N;
+        pl.cls_h = R.hs[0].p + slot * NKC; pl.cls_rows = P; pl.reg_rows = P;
         pl.cls_out = R.logits.p + (size_t)ts * NK; pl.cls_stride = (int64_t)S.K;
         pl.cls_next = more && cls_fb == 0;
         pl.cls_ids_out = R.ids.p + (size_t)(ts + 1) * N;
@@ -696,6 +830,7 @@ void train_forward(mv_engine* e) {
       }
       run_tail(e, plans);
       tail_embedded = true;
+      if (rag) run_zero_dead(e, zo, tl.d_dec_live(ts));
       continue;
     }
     for (int s = 0; s < c.num_scales; ++s) {
@@ -706,16 +841,17 @@ void train_forward(mv_engine* e) {
       const int slot = To + ts + 1;
       float* lg = R.logits.p + (size_t)ts * NK;
       run_hidden2grid<1>(e, S, R.hs[0].p + slot * NKC, S.out_cls_W->dev.p, lg,
-                         (size_t)S.K, N);
+                         (size_t)S.K, P);
       if (ts + 1 < Tp && cls_fb == 0) {
         launch(e, "argmax_rows", 0, 4.0 * NK, [&] {
-          hipLaunchKernelGGL(mv::argmax_rows_kernel, dim3(N), dim3(64), 0, e->stream, lg,
-                             (size_t)S.K, R.ids.p + (size_t)(ts + 1) * N, N, S.K);
+          hipLaunchKernelGGL(mv::argmax_rows_kernel, dim3(P), dim3(64), 0, e->stream, lg,
+                             (size_t)S.K, R.ids.p + (size_t)(ts + 1) * N, P, S.K);
         });
       }
       run_hidden2grid<2>(e, S, R.hs[nb - 1].p + slot * NKC, S.out_reg_W->dev.p,
-                         R.regio.p + (size_t)(ts + 1) * NK * 2, (size_t)S.K * 2, N);
+                         R.regio.p + (size_t)(ts + 1) * NK * 2, (size_t)S.K * 2, P);
     }
+    if (rag) run_zero_dead(e, zo, tl.d_dec_live(ts));
   }
 }
 
@@ -730,9 +866,18 @@ void train_losses(mv_engine* e) {
     if (!S.use) continue;
     TrainScale& R = t.sc[s];
     const size_t NK = (size_t)N * S.K;
-    const float cs = t.tc.grid_loss_weight / (float)((size_t)N * Tp);
+    // per-row training lengths: the mean over the M = sum of L valid (n, t) -- with every
+    // length full M is N * Tp and both factors are the uniform ones
+    const bool rag = e->tl.ragged;
+    const size_t Mv = rag ? (size_t)e->tl.M : (size_t)N * Tp;
+    const float cs = t.tc.grid_loss_weight / (float)Mv;
     launch(e, "ce_loss", 0, 8.0 * Tp * NK, [&] {
-      if (t.mix_on) {
+      if (rag)
+        hipLaunchKernelGGL(mv::ce_loss_len_kernel, dim3(Tp * N), dim3(64), 0, e->stream,
+                           R.logits.p, R.pred_labels.p,
+                           t.tc.use_soft_grid_class ? R.gt_cls.p : (const float*)nullptr,
+                           R.loss_row.p, R.dlogits.p, Tp, N, S.K, cs, e->tl.d_pred());
+      else if (t.mix_on) {
         // mixed-up targets w * one_hot(label) + one_hot(extra view's label) * (1 - w)
         // (SimAug/code/pred_models.py:1371-1390), optionally weighted per sample (:1391-1398)
         hipLaunchKernelGGL(mv::twohot_map_kernel, dim3(cdiv((size_t)Tp * NK, 256)), dim3(256), 0,
@@ -755,7 +900,7 @@ void train_losses(mv_engine* e) {
                          R.loss_row.p, (size_t)Tp * N, t.losses.p + li, cs, 0);
     });
     const size_t nel = (size_t)Tp * NK * 2;
-    const float rs = t.tc.grid_reg_loss_weight / (float)nel;
+    const float rs = t.tc.grid_reg_loss_weight / (float)(Mv * S.K * 2);
     launch(e, "huber_loss", 0, 16.0 * nel, [&] {
       if (t.tc.mask_grid_regression) {
         hipLaunchKernelGGL(mv::huber_masked_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
@@ -766,6 +911,11 @@ void train_losses(mv_engine* e) {
         hipLaunchKernelGGL(mv::masked_mean_kernel, dim3(1), dim3(64), 0, e->stream,
                            t.scratch.p, R.fg_count.p, t.losses.p + li + 1,
                            t.tc.grid_reg_loss_weight);
+      } else if (rag) {
+        hipLaunchKernelGGL(mv::huber_loss_len_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
+                           e->stream, R.regio.p + NK * 2, R.pred_reg.p, R.loss_elem.p,
+                           R.dreg.p, Tp, N, S.K * 2, rs, e->tl.d_pred());
+        run_long_sum(e, t, R.loss_elem.p, nel, t.losses.p + li + 1, rs);
       } else {
         hipLaunchKernelGGL(mv::huber_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
                            e->stream, R.regio.p + NK * 2, R.pred_reg.p, R.loss_elem.p,
@@ -831,7 +981,10 @@ void run_dgrad_group_f16x3(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
     q.f = a;
     const size_t M = (size_t)a.rows * a.H * a.W;
     const size_t nel = M * a.C;                               // a.C == 4C here
-    const size_t pst = nel + mv::kPlaneSlack + mv::kPlanePad;
+    // (ragged step: the second plane stays where it is at full batch -- its zero pad must not
+    // lie inside what a step of another row count wrote; engine_forward.h prepare_gate_operands)
+    const size_t pst = (e->tl.issuing ? (size_t)e->cfg.batch_size * a.H * a.W * a.C : nel) +
+                       mv::kPlaneSlack + mv::kPlanePad;
     MV_REQUIRE(t.g16[i].n >= 2 * pst, "internal: G plane scratch");
     _Float16* p0 = t.g16[i].p + mv::kPlanePad;
     const bool fused = bf && t.g16_fused[i];       // the plane came out of lstm_gate_bwd
@@ -914,6 +1067,7 @@ void run_dgrad_group(mv_engine* e, const std::vector<ConvLstmArgs>& probs,
   if (probs.empty()) return;
   double fl = 0, by = 0;
   for (size_t i = 0; i < probs.size(); ++i) {
+    TS(e).dgrad_rows += probs[i].rows;           // mv_last_train_gate_rows
     fl += flops[i];
     by += (double)probs[i].rows * probs[i].H * probs[i].W * (probs[i].C + 288.0) * 4.0;
   }
@@ -1244,6 +1398,10 @@ void train_backward(mv_engine* e) {
             D = c.scene_conv_dim, E = c.emb_size;
   float* dh_a[MV_MAX_SCALES][2];
   float* dh_b[MV_MAX_SCALES][2];
+  // per-row training lengths: every launch of a step takes the step's prefix, as the forward's
+  const TrainLens& tl = e->tl;
+  const bool rag = tl.ragged;
+  t.dgrad_rows = 0;
   for (int s = 0; s < c.num_scales; ++s) {
     if (!e->sc[s].use) continue;
     TrainScale& R = t.sc[s];
@@ -1251,6 +1409,9 @@ void train_backward(mv_engine* e) {
     for (int b = 0; b < 2; ++b) {
       dh_a[s][b] = R.dh_a[b].p; dh_b[s][b] = R.dh_b[b].p;
       HIP_CHECK(hipMemsetAsync(R.dh_a[b].p, 0, NKC * sizeof(float), e->stream));
+      // (ragged: the decoder prefixes grow towards step 0, so a row enters with whatever the
+      // other buffer of the ping-pong holds: zero, too)
+      if (rag) HIP_CHECK(hipMemsetAsync(R.dh_b[b].p, 0, NKC * sizeof(float), e->stream));
       HIP_CHECK(hipMemsetAsync(R.dc[b].p, 0, NKC * sizeof(float), e->stream));
     }
     if (c.use_gnn)
@@ -1270,32 +1431,45 @@ void train_backward(mv_engine* e) {
     std::vector<double> flops;
     std::vector<TrainChain*> chains;
     std::vector<int> slots;
+    const int P = rag ? tl.dec_rows[ts] : N;     // rows of the step
+    if (rag) {
+      // d x of the rows the step does not run: operands of the full-extent wgrads / column sums
+      DeadRows zd;
+      for (int s = 0; s < c.num_scales; ++s) {
+        if (!e->sc[s].use) continue;
+        const size_t KE = (size_t)e->sc[s].K * E;
+        for (int b = 0; b < nb; ++b) zd.add(t.sc[s].dec[b].dxs.p + (size_t)ts * N * KE, KE);
+      }
+      run_zero_dead(e, zd, tl.d_dec_live(ts));
+      if (P == 0) continue;                      // the step was not issued
+    }
     for (int s = 0; s < c.num_scales; ++s) {
       ScaleState& S = e->sc[s];
       if (!S.use) continue;
       TrainScale& R = t.sc[s];
       const size_t NK = (size_t)N * S.K, NKC = NK * C;
+      const size_t PK = (size_t)P * S.K;
       const int slot = To + ts;
       // d logits / d out_reg of this step -> d h'  (hidden2grid backward)
       run_small_dgrad(e, R.dlogits.p + (size_t)ts * NK, (size_t)S.K, S.out_cls_W->dev.p,
-                      dh_a[s][0], (size_t)S.K * C, N, S.H, S.W, C, 1, true);
+                      dh_a[s][0], (size_t)S.K * C, P, S.H, S.W, C, 1, true);
       run_small_dgrad(e, R.dreg.p + (size_t)ts * NK * 2, (size_t)S.K * 2,
-                      S.out_reg_W->dev.p, dh_a[s][nb - 1], (size_t)S.K * C, N, S.H, S.W, C, 2,
+                      S.out_reg_W->dev.p, dh_a[s][nb - 1], (size_t)S.K * C, P, S.H, S.W, C, 2,
                       true);
       for (int b = 0; b < nb; ++b) {
         float* G = R.dec[b].gates.p + (size_t)ts * 4 * NKC;
         const int gs = (2 * s + b) * 64 + ts;
         run_gate_bwd(e, G, R.cs[b].p + slot * NKC, R.cs[b].p + (slot + 1) * NKC,
-                     dh_a[s][b], R.dc[b].p, NK, C, f16 ? t.gmax.p + (size_t)gs * 64 : nullptr,
+                     dh_a[s][b], R.dc[b].p, PK, C, f16 ? t.gmax.p + (size_t)gs * 64 : nullptr,
                      (int)probs.size());
         chains.push_back(&R.dec[b]);
         slots.push_back(gs);
         ConvLstmArgs a;
         mv::convlstm_dgrad_args(a, G, R.dec[b].wdpack.p, dh_b[s][b],
-                                R.dec[b].dxs.p + (size_t)ts * NK * E, N, S.H, S.W, E, C,
+                                R.dec[b].dxs.p + (size_t)ts * NK * E, P, S.H, S.W, E, C,
                                 true, true);
         probs.push_back(a);
-        flops.push_back(2.0 * NK * 9 * (E + C) * 4.0 * C);
+        flops.push_back(2.0 * PK * 9 * (E + C) * 4.0 * C);
       }
     }
     run_dgrad_group(e, probs, flops, chains, slots);
@@ -1304,14 +1478,15 @@ void train_backward(mv_engine* e) {
       if (!S.use) continue;
       TrainScale& R = t.sc[s];
       const size_t NK = (size_t)N * S.K, NKC = NK * C;
+      const size_t PK = (size_t)P * S.K;
       const int slot = To + ts;
       // class branch: d(h + GNN(h)) -> d h, d scene_mean
       if (c.use_gnn) {
         const float* hsrc = R.hs[0].p + slot * NKC;
-        launch(e, "gnn_bwd", NK * (9.0 * 2 * 3 * (C + D) + 9.0 * 4 * C),
-               4.0 * NK * (4.0 * C + 2.0 * D), [&] {
+        launch(e, "gnn_bwd", PK * (9.0 * 2 * 3 * (C + D) + 9.0 * 4 * C),
+               4.0 * PK * (4.0 * C + 2.0 * D), [&] {
           launch_gnn_bwd(e->stream, hsrc, S.scene_mean.p, dh_b[s][0], R.gnn_a.p, R.gnn_de.p,
-                         R.gnn_n.p, dh_a[s][0], R.dsmean.p, N, S.H, S.W, C, gnn_scene_dim(e), 1);
+                         R.gnn_n.p, dh_a[s][0], R.dsmean.p, P, S.H, S.W, C, gnn_scene_dim(e), 1);
         });
       } else {
         std::swap(dh_a[s][0], dh_b[s][0]);
@@ -1320,7 +1495,7 @@ void train_backward(mv_engine* e) {
       // decoder input embeddings: d x -> d pre-activation (in place)
       for (int b = 0; b < nb; ++b) {
         float* dx = R.dec[b].dxs.p + (size_t)ts * NK * E;
-        const size_t total = NK * E;
+        const size_t total = PK * E;
         run_dropout(e, dx, total, s, 2 + b, ts);       // backward of the input dropout
         launch(e, "tanh_bwd", 3.0 * total, 12.0 * total, [&] {
           // xs holds the DROPPED input; where the mask is zero d x is zero too, elsewhere
@@ -1340,13 +1515,13 @@ void train_backward(mv_engine* e) {
       if (ts > 0 && !t.tc.reg_teacher_forcing && nb == 2)
         run_small_dgrad(e, R.dec[1].dxs.p + (size_t)ts * NK * E, (size_t)S.K * E,
                         S.emb_reg_W->dev.p, R.dreg.p + (size_t)(ts - 1) * NK * 2,
-                        (size_t)S.K * 2, N, S.H, S.W, 2, E, true);
+                        (size_t)S.K * 2, P, S.H, S.W, 2, E, true);
       // class decoder fed its own logits (training without --train_w_onehot): the same
       // path into d logits[t-1]
       if (ts > 0 && t.tc.class_feedback == 1)
         run_small_dgrad(e, R.dec[0].dxs.p + (size_t)ts * NK * E, (size_t)S.K * E,
                         S.emb_cls_W->dev.p, R.dlogits.p + (size_t)(ts - 1) * NK,
-                        (size_t)S.K, N, S.H, S.W, 1, E, true);
+                        (size_t)S.K, P, S.H, S.W, 1, E, true);
     }
   }
   // ---- encoders, t = To-1 .. 0
@@ -1355,17 +1530,29 @@ void train_backward(mv_engine* e) {
     std::vector<double> flops;
     std::vector<TrainChain*> chains;
     std::vector<int> slots;
+    const int P = rag ? tl.enc_rows[ts] : N;     // rows of the step
+    if (rag) {
+      DeadRows zd;      // d x of the class encoder: scene_grad_gather reads [To][N]
+      for (int s = 0; s < c.num_scales; ++s) {
+        if (!e->sc[s].use) continue;
+        const size_t KX = (size_t)e->sc[s].K * t.sc[s].enc[0].Cx;
+        zd.add(t.sc[s].enc[0].dxs.p + (size_t)ts * N * KX, KX);
+      }
+      run_zero_dead(e, zd, tl.d_enc_live(ts));
+      if (P == 0) continue;                      // the step was not issued
+    }
     for (int s = 0; s < c.num_scales; ++s) {
       ScaleState& S = e->sc[s];
       if (!S.use) continue;
       TrainScale& R = t.sc[s];
       const size_t NK = (size_t)N * S.K, NKC = NK * C;
+      const size_t PK = (size_t)P * S.K;
       for (int b = 0; b < nb; ++b) {
         float* G = R.enc[b].gates.p + (size_t)ts * 4 * NKC;
         const int gs = (2 * s + b) * 64 + 32 + ts;    // encoder steps: 32..
         const bool need_dh = ts > 0, need_dx = (b == 0);
         run_gate_bwd(e, G, R.cs[b].p + ts * NKC, R.cs[b].p + (ts + 1) * NKC, dh_a[s][b],
-                     R.dc[b].p, NK, C,
+                     R.dc[b].p, PK, C,
                      f16 ? t.gmax.p + (size_t)gs * 64 : nullptr,
                      (need_dh || need_dx) ? (int)probs.size() : -1);
         if (!need_dh && !need_dx) continue;
@@ -1375,19 +1562,28 @@ void train_backward(mv_engine* e) {
         mv::convlstm_dgrad_args(a, G, R.enc[b].wdpack.p, dh_b[s][b],
                                 need_dx ? R.enc[b].dxs.p + (size_t)ts * NK * R.enc[b].Cx
                                         : nullptr,
-                                N, S.H, S.W, R.enc[b].Cx, C, need_dh, need_dx);
+                                P, S.H, S.W, R.enc[b].Cx, C, need_dh, need_dx);
         probs.push_back(a);
-        flops.push_back(2.0 * NK * 9 * ((need_dx ? R.enc[b].Cx : 0) + C) * 4.0 * C);
+        flops.push_back(2.0 * PK * 9 * ((need_dx ? R.enc[b].Cx : 0) + C) * 4.0 * C);
       }
     }
     run_dgrad_group(e, probs, flops, chains, slots);
+    DeadRows zj;
     for (int s = 0; s < c.num_scales; ++s) {
       if (!e->sc[s].use) continue;
       for (int b = 0; b < 2; ++b) std::swap(dh_a[s][b], dh_b[s][b]);
       const int Cx = t.sc[s].enc[0].Cx;
       run_dropout(e, t.sc[s].enc[0].dxs.p + (size_t)ts * N * e->sc[s].K * Cx,
-                  (size_t)N * e->sc[s].K * Cx, s, 0, ts);
+                  (size_t)P * e->sc[s].K * Cx, s, 0, ts);
+      if (rag && ts > 0)
+        for (int b = 0; b < nb; ++b) {
+          zj.add(dh_a[s][b], (size_t)e->sc[s].K * C);
+          zj.add(t.sc[s].dc[b].p, (size_t)e->sc[s].K * C);
+        }
     }
+    // a row that joined at this step started from the CONSTANT zero state: nothing flows into
+    // the steps in front of it, which then see G = 0 for the row
+    if (rag && ts > 0) run_zero_dead(e, zj, tl.d_enc_live(ts - 1));
   }
   // ---- parameter gradients
   bool single_first_done = false;
@@ -1499,6 +1695,12 @@ void train_backward(mv_engine* e) {
     if (e->sc[i].use) {
       TrainScale& R = t.sc[i];
       launch(e, "scene_grad_gather", 0, 4.0 * n * N, [&] {
+        if (rag)
+          hipLaunchKernelGGL(mv::scene_grad_gather_len_kernel, dim3(cdiv(n, 256)), dim3(256), 0,
+                             e->stream, (c.use_gnn && gnn_scene_dim(e) > 0) ? R.dsmean.p : (const float*)nullptr,
+                             R.enc[0].dxs.p, e->obs_scene.p, e->sc[i].labels.p, t.dys[i].p,
+                             U, N, To, Ho * Wo, D, tl.d_obs(), tl.d_pred());
+        else
         hipLaunchKernelGGL(mv::scene_grad_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0,
                            e->stream, (c.use_gnn && gnn_scene_dim(e) > 0) ? R.dsmean.p : (const float*)nullptr,
                            R.enc[0].dxs.p, e->obs_scene.p, e->sc[i].labels.p, t.dys[i].p,
@@ -1583,7 +1785,8 @@ float train_learning_rate(const TrainState& t) {
   return (float)(lr * c.emb_lr);
 }
 
-void train_fwd_bwd(mv_engine* e, const mv_inputs* in, const mv_targets* tg, mv_losses* out) {
+void train_fwd_bwd(mv_engine* e, const mv_inputs* in, const mv_targets* tg, mv_losses* out,
+                   const char* call) {
   MV_REQUIRE(e->train, "mv_train_init has not been called");
   MV_REQUIRE(e->cfg.beam_size == 1, "training needs a greedy (beam_size 1) engine");
   TrainState& t = TS(e);
@@ -1597,7 +1800,15 @@ void train_fwd_bwd(mv_engine* e, const mv_inputs* in, const mv_targets* tg, mv_l
     e->train_packs_valid = true;
   }
   if (e->comm) { e->comm->buckets_last = 0; e->comm->bytes_last = 0; }
+  train_lens_prepare(e, call);
+  struct Issuing {                   // (cleared on every way out: a failed launch throws)
+    TrainLens& tl;
+    explicit Issuing(TrainLens& l) : tl(l) { tl.issuing = tl.ragged; }
+    ~Issuing() { tl.issuing = false; }
+  } issuing(e->tl);
+  const int64_t rows0 = e->gate_rows;
   train_forward(e);
+  t.fwd_gate_rows = e->gate_rows - rows0;
   train_losses(e);
   train_backward(e);
   t.have_grads = true;

@@ -908,6 +908,156 @@ __global__ void scene_grad_gather_kernel(const float* __restrict__ dmean,
   dsc[idx] = acc;
 }
 
+// ------------------------------------------------------------ per-row training lengths
+// (mv_set_train_lengths).  Row n is the model at obs_len = obs_lens[n],
+// pred_len = pred_lens[n]: observations right-aligned, targets left-aligned.  The kernels below
+// are the length-aware forms of the loss / label-map / scene-gradient kernels above, picked on
+// the host for a step whose lengths are not all full; the arithmetic of a valid (n, t) is the
+// uniform kernel's, operation for operation, and an invalid one writes exactly 0.0f.
+
+// ce_loss_kernel / ce_soft_loss_kernel (soft != NULL: soft labels [T*N, K], labels unread).
+// scale = grid_loss_weight / M, M = sum of pred_lens.
+__global__ __launch_bounds__(64)
+void ce_loss_len_kernel(const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                        const float* __restrict__ soft, float* __restrict__ loss_row,
+                        float* __restrict__ dlogits, int T, int N, int K, float scale,
+                        const int32_t* __restrict__ pred_lens) {
+  const int r = blockIdx.x;          // t * N + n
+  const int t = r / N, n = r - t * N;
+  const int lane = threadIdx.x;
+  float* d = dlogits + (size_t)r * K;
+  if (t >= pred_lens[n]) {           // the step does not exist for the row
+    if (lane == 0) loss_row[r] = 0.f;
+    for (int k = lane; k < K; k += 64) d[k] = 0.f;
+    return;
+  }
+  const float* p = logits + (size_t)r * K;
+  float mx = -INFINITY;
+  for (int k = lane; k < K; k += 64) mx = fmaxf(mx, p[k]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off, 64));
+  float s = 0.f;
+  for (int k = lane; k < K; k += 64) s += expf(p[k] - mx);
+  s = wave_sum(s);
+  const float inv = 1.0f / s;
+  if (soft) {
+    const float* q = soft + (size_t)r * K;
+    const float ls = logf(s);
+    float acc = 0.f;
+    for (int k = lane; k < K; k += 64) acc += q[k] * ((p[k] - mx) - ls);
+    acc = wave_sum(acc);
+    if (lane == 0) loss_row[r] = -acc;
+    for (int k = lane; k < K; k += 64) d[k] = (expf(p[k] - mx) * inv - q[k]) * scale;
+    return;
+  }
+  const float lse = logf(s) + mx;
+  const int lab = labels[(size_t)n * T + t];
+  if (lane == 0) loss_row[r] = lse - p[lab];
+  for (int k = lane; k < K; k += 64) {
+    const float sm = expf(p[k] - mx) * inv;
+    d[k] = (sm - (k == lab ? 1.f : 0.f)) * scale;
+  }
+}
+
+// huber_loss_kernel over the valid (n, t); scale = grid_reg_loss_weight / (2 K M)
+__global__ void huber_loss_len_kernel(const float* __restrict__ pred,
+                                      const float* __restrict__ target,
+                                      float* __restrict__ loss_elem,
+                                      float* __restrict__ dpred, int T, int N, int KP,
+                                      float scale, const int32_t* __restrict__ pred_lens) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t total = (size_t)T * N * KP;
+  if (idx >= total) return;
+  const int kp = idx % KP;
+  const size_t r = idx / KP;
+  const int n = r % N;
+  const int t = r / N;
+  if (t >= pred_lens[n]) {
+    loss_elem[idx] = 0.f;
+    dpred[idx] = 0.f;
+    return;
+  }
+  const float e = pred[idx] - target[((size_t)n * T + t) * KP + kp];
+  const float ab = fabsf(e);
+  const float q = fminf(ab, 1.f);
+  loss_elem[idx] = 0.5f * q * q + (ab - q);
+  dpred[idx] = fminf(fmaxf(e, -1.f), 1.f) * scale;
+}
+
+// gt_class_maps_kernel with an all-zero map at every invalid (n, t): count_positive_kernel
+// then counts the foreground of the valid steps only, and huber_masked_loss_kernel, whose
+// mask this map is, writes zeros there -- both run unchanged on a ragged step.
+__global__ void gt_class_maps_len_kernel(const int32_t* __restrict__ labels,
+                                         float* __restrict__ out, int T, int N, int H, int W,
+                                         int ks, const SoftKernel sk,
+                                         const int32_t* __restrict__ pred_lens) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = H * W;
+  if (idx >= (size_t)T * N * K) return;
+  const int cell = (int)(idx % K);
+  const size_t r = idx / K;
+  const int n = (int)(r % N), t = (int)(r / N);
+  if (t >= pred_lens[n]) { out[idx] = 0.f; return; }
+  const int lab = labels[(size_t)n * T + t];
+  const int y = cell / W, x = cell - y * W, py = lab / W, px = lab - py * W;
+  float v;
+  if (ks == 0) {
+    v = (cell == lab) ? 1.f : 0.f;
+  } else {
+    const int rad = ks >> 1, dy = y - py, dx = x - px;
+    v = (dy >= -rad && dy <= rad && dx >= -rad && dx <= rad)
+            ? sk.k[(dy + rad) * ks + (dx + rad)] : 0.f;
+  }
+  out[idx] = v;
+}
+
+// scene_grad_gather_kernel with row n's own window: the obs_lens[n] last columns, each frame
+// of it 1 / obs_lens[n] of d scene_mean; a padding row (pred_lens[n] == 0) gives nothing.
+__global__ void scene_grad_gather_len_kernel(const float* __restrict__ dmean,
+                                             const float* __restrict__ dxenc,
+                                             const int32_t* __restrict__ obs_scene,
+                                             const int32_t* __restrict__ labels,
+                                             float* __restrict__ dsc, int U, int N, int T,
+                                             int K, int D,
+                                             const int32_t* __restrict__ obs_lens,
+                                             const int32_t* __restrict__ pred_lens) {
+  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t per = (size_t)K * D;
+  if (idx >= (size_t)U * per) return;
+  const int u = idx / per;
+  const size_t off = idx - (size_t)u * per;
+  const int cell = off / D;
+  float acc = 0.f;
+  for (int n = 0; n < N; ++n) {
+    if (pred_lens[n] <= 0) continue;
+    const int L = min(max(obs_lens[n], 1), T);      // (host-checked: in [1, T])
+    for (int t = T - L; t < T; ++t) {
+      if (obs_scene[n * T + t] != u) continue;
+      if (dmean) acc += dmean[(size_t)n * per + off] / (float)L;
+      if (labels[n * T + t] == cell) acc += dxenc[((size_t)t * N + n) * per + off];
+    }
+  }
+  dsc[idx] = acc;
+}
+
+// The rows of a step's [N][row_elems] tensors that the step does not run for the row's model
+// (live[n] == 0: outside the step's prefix, not yet joined, finished, padding) are cleared, so
+// that no later launch -- the join of a short track, the full-extent wgrads, an operand's
+// max |x| -- reads stale or ignored content there.  grid (x, segment, row).
+struct ZeroDeadArgs {
+  float* p[20];
+  uint32_t row_elems[20];
+  const int32_t* live;         // [N]
+};
+__global__ void zero_dead_rows_kernel(ZeroDeadArgs a) {
+  const int n = blockIdx.z;
+  if (a.live[n]) return;
+  const uint32_t ne = a.row_elems[blockIdx.y];
+  float* p = a.p[blockIdx.y] + (size_t)n * ne;
+  for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += gridDim.x * blockDim.x)
+    p[i] = 0.f;
+}
+
 // ------------------------------------------------------------ label mixup (SimAug, exp 3)
 // out [T][N][K] (time-major) = w * one_hot(l1[n * sn + t * st]) + one_hot(l2[..]) * (1 - w)
 __global__ void twohot_map_kernel(const int32_t* __restrict__ l1, const int32_t* __restrict__ l2,

@@ -223,6 +223,57 @@ def plan_ragged_batches(lengths, N, obs_lengths=None):
   return RaggedPlan(batches, sum(lengths), grouped)
 
 
+TrainRowOrder = collections.namedtuple(
+    "TrainRowOrder", ["order", "enc_rows", "dec_rows", "enc_rows_unsorted", "dec_rows_unsorted"])
+
+
+def sum_dec_prefix_rows(pred_lengths):
+  """Rows the decoders of a ragged step launch per chain: sum over the steps t of
+  1 + max{n : L[n] > t} = sum_n max(L[n:]) -- sum(L) when the lengths are sorted descending."""
+  total, m = 0, 0
+  for l in reversed([int(l) for l in pred_lengths]):
+    m = max(m, l)
+    total += m
+  return total
+
+
+def order_train_rows(obs_lengths, pred_lengths, obs_len=None):
+  """Row order of a mixed-length TRAINING batch (Engine.set_train_lengths; the training
+  counterpart of plan_ragged_batches' ordering): prediction length descending, ties by
+  observation length descending, then by index.  Padding rows (length 0) go last; the decoder
+  steps of a sorted batch launch no finished row, its encoder steps an unstarted row only in
+  front of a row with a longer history.  -> TrainRowOrder(order, enc_rows, dec_rows,
+  enc_rows_unsorted, dec_rows_unsorted): the permutation, and the rows one chain launches over
+  the encoder / decoder steps in that order and in the given one (Engine.last_train_gate_rows
+  counts them once per chain and used scale, forward and dgrad)."""
+  lo = [int(l) for l in obs_lengths]
+  lp = [int(l) for l in pred_lengths]
+  assert len(lo) == len(lp), "one observation and one prediction length per row"
+  if obs_len is None:
+    obs_len = max(lo)
+  order = sorted(range(len(lp)), key=lambda i: (-lp[i], -lo[i], i))
+
+  def sums(idx):
+    live = 0
+    for r, i in enumerate(idx):
+      if lp[i] > 0:
+        live = r + 1
+    head = idx[:live]
+    if all(lp[i] > 0 for i in head):
+      enc = sum_enc_prefix_rows([lo[i] for i in head], obs_len)
+    else:        # a padding row inside the prefix is launched, but extends no step's prefix
+      enc, m = 0, 0
+      for i in reversed(head):
+        if lp[i] > 0:
+          m = max(m, lo[i])
+        enc += m
+    return enc, sum_dec_prefix_rows([lp[i] for i in idx])
+
+  e1, d1 = sums(order)
+  e0, d0 = sums(list(range(len(lp))))
+  return TrainRowOrder(order, e1, d1, e0, d0)
+
+
 def cell_mask_from_scene(args, scene_onehot_last_frame, allowed_classes, min_share=0.0):
   """The cells of the used grid a future may enter, from one frame of scene semantics (not in
   the reference; include/multiverse_hip.h mv_set_cell_mask): scene_onehot_last_frame

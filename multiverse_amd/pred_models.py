@@ -79,6 +79,17 @@ def compact_inputs_consistent(cfg, batch):
   return True, ""
 
 
+def _hand_train_lengths(data, feed, is_train):
+  """Per-row training lengths of a mixed-length batch (data["train_obs_lengths"] /
+  data["train_pred_lengths"], int [N]; Engine.set_train_lengths): handed to the engine's feed
+  untouched, for training feeds only."""
+  if not is_train:
+    return
+  for key in ("train_obs_lengths", "train_pred_lengths"):
+    if key in data and data[key] is not None:
+      feed[key] = data[key]
+
+
 def build_compact_feed_dict(cfg, batch, is_train=False):
   """The same batch as `build_feed_dict`, handed over as labels + one (x, y) per
   step + the uint8 scene masks; the engine derives the dense regression maps in HBM
@@ -121,6 +132,7 @@ def build_compact_feed_dict(cfg, batch, is_train=False):
   feed["obs_scene"] = obs_scene
   feed["scene_feat"] = np.asarray(data["batch_scene_feat"]).astype("uint8", copy=False)
   feed["compact"] = True
+  _hand_train_lengths(data, feed, is_train)
   return feed
 
 
@@ -167,6 +179,7 @@ def build_feed_dict(cfg, batch, is_train=False):
     obs_scene[i, :len(row)] = row
   feed["obs_scene"] = obs_scene
   feed["scene_feat"] = np.asarray(data["batch_scene_feat"], dtype="float32")
+  _hand_train_lengths(data, feed, is_train)
   return feed
 
 
