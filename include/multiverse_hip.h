@@ -472,6 +472,46 @@ int  mv_set_cell_mask(mv_handle h, const uint8_t* allowed /* [N, Tm, K]; NULL cl
 /* forwards captured into a hipGraph on this handle so far (a replay does not count) */
 int  mv_graph_captures(mv_handle h, int64_t* captures);
 
+/* ---- cell costs: per-row additive logit bias (not in the reference; defined here) -------------
+ * bias [N, Tm, K] float32, K = the cells of the handle's one used grid: b[n, tm, k] is a
+ * log-potential, in nats, that row n's choice of cell k carries beside the model's own -- a map
+ * cost, a goal heat-map, another model's occupancy.  Negative = less likely.  Tm == 1: one plane
+ * for every decode step; otherwise step t reads plane t, and Tm must be at least the forward's
+ * pred_len (checked at the forward).  NULL clears.  Sticky until cleared.  It applies to the
+ * forwards that mv_set_cell_mask applies to, and to mv_beam_occupancy after them;
+ * mv_score_futures neither reads nor changes it.  A mask is the special case "cost = -inf", and
+ * stays the mask's job: every value here is finite.  Notation as above: l the step's logits, tau
+ * the temperature, A the allowed set (all K cells when no mask is set), b the row's plane.
+ *   lp = log_softmax(l) over ALL K cells, unchanged: the logits outputs and both samplers'
+ *        logprobs stay the model's, and scoring the returned ids with mv_score_futures reproduces
+ *        logprobs bit for bit.
+ * Beam search: the candidate is (prev_lp + lp) + b, formed BEFORE the mask's -inf and before the
+ * diversity ranks; ranks, penalty and selection run as they are.  The carried and returned beam
+ * score therefore includes the bias, as it includes the diversity penalty.  With a bias the step
+ * takes the two-launch rank + select form, as under a mask.
+ * Independent sampler and sampling without replacement: the proposal's
+ *   w[k]    = l[k] / tau + b[k], -inf outside A;  mxq = max of w over A
+ *   e, sum_e, c(k), m(k), the step-0 floor and q~ are as documented for the mask, over THIS w;
+ *             in particular the order of the top-k and nucleus limits is the order of w, not of l:
+ *             c(k) = #{j in A : w[j] > w[k]}, m(k) the sum of e over that set
+ *   the independent sampler's score is (lp[k] / tau + b[k]) + g[k]
+ * qlogprobs, and the without-replacement q plane, are written whenever a bias is set -- also at
+ * tau == 1 with no limit -- and mv_download_beam_proposal_logprobs returns them as under a limit.
+ * mv_beam_occupancy: each future's step map is the softmax of l + b over A; the mixture weights
+ * are unchanged.  It reads the bias that is set when it is called.
+ * Identity, in eager and in graph mode: with no bias set no launch differs (the same kernels, the
+ * same graph keys, mv_graph_captures unchanged); with an all-zero bias every output that both
+ * handles define is bit-identical to a handle that never had one.
+ * The bias lives in an engine-owned device buffer; this call synchronises the stream and rewrites
+ * it, so a replayed graph follows a new bias without re-capture (the graph key carries whether a
+ * bias is set and whether Tm > 1).  It combines with mv_set_cell_mask, mv_set_pred_lengths and
+ * mv_set_obs_lengths with no new rule: row n equals its own uniform forward under its own bias row.
+ * Errors: a greedy handle; Tm < 1; a value that is NaN or +-inf (checked on the host here; the
+ * message names n, tm and k); 1 < Tm < pred_len (at the forward); a grid of more than 1024 cells
+ * (at the forward); mv_train_* and mv_submit_greedy while a bias is set (the message names the
+ * call). */
+int  mv_set_cell_bias(mv_handle h, const float* bias /* [N, Tm, K]; NULL clears */, int32_t Tm);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -773,6 +813,27 @@ int  mv_op_sbs_step_masked(int device, const float* logits, const float* prev_ph
                            float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
 int  mv_op_sample_step_masked(int device, const float* logits /* [R, K] */,
                               const uint8_t* allowed /* [R / S, K] */, int32_t R, int32_t S,
+                              int32_t K, int32_t t, float temperature, uint32_t seed,
+                              int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
+                              float* qlp, uint8_t* keep /* [R, K] */);
+
+/* The biased forms of the three step ops (mv_set_cell_bias above): the masked prototype with
+ * bias [samples, K] float32, one plane per SAMPLE as `allowed`, directly behind it; `allowed` may
+ * be NULL (every cell allowed).  Every bias value is finite.  K <= 1024. */
+int  mv_op_beam_step_biased(int device, const float* logits, const float* prev_logprob,
+                            const uint8_t* allowed /* [N, K] or NULL */,
+                            const float* bias /* [N, K] */, int32_t N, int32_t B, int32_t K,
+                            int32_t time, int32_t diverse, float gamma, int32_t fix_num_timestep,
+                            float* new_logprob, int32_t* ids, int32_t* parents);
+int  mv_op_sbs_step_biased(int device, const float* logits, const float* prev_phi,
+                           const float* prev_logprob, const float* prev_gumbel,
+                           const uint8_t* allowed /* [N, K] or NULL */,
+                           const float* bias /* [N, K] */, int32_t N, int32_t B, int32_t K,
+                           int32_t t, float temperature, uint32_t seed, float* new_phi,
+                           float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
+int  mv_op_sample_step_biased(int device, const float* logits /* [R, K] */,
+                              const uint8_t* allowed /* [R / S, K] or NULL */,
+                              const float* bias /* [R / S, K] */, int32_t R, int32_t S,
                               int32_t K, int32_t t, float temperature, uint32_t seed,
                               int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
                               float* qlp, uint8_t* keep /* [R, K] */);

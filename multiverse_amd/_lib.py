@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "mv_set_cell_mask", "mv_graph_captures", "mv_op_beam_step_masked", "mv_op_sbs_step_masked",
     "mv_op_sample_step_masked",
     "mv_set_train_lengths", "mv_last_train_gate_rows",
+    "mv_set_cell_bias", "mv_op_beam_step_biased", "mv_op_sbs_step_biased",
+    "mv_op_sample_step_biased",
 ]
 
 
@@ -240,6 +242,17 @@ def load():
     lib.mv_op_sample_step_masked.argtypes = [C.c_int, _fp, _u8p, C.c_int32, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_float, C.c_uint32, C.c_int32,
                                              C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
+  if hasattr(lib, "mv_set_cell_bias"):      # (as above)
+    lib.mv_set_cell_bias.argtypes = [h, _fp, C.c_int32]
+    lib.mv_op_beam_step_biased.argtypes = [C.c_int, _fp, _fp, _u8p, _fp, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                           C.c_int32, _fp, _ip, _ip]
+    lib.mv_op_sbs_step_biased.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _u8p, _fp, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                          _fp, _fp, _fp, _ip, _ip]
+    lib.mv_op_sample_step_biased.argtypes = [C.c_int, _fp, _u8p, _fp, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                             C.c_int32, C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
@@ -555,6 +568,7 @@ class Engine(object):
     self._set_pred_lengths(feed.get("pred_lengths"))
     self._set_obs_lengths(feed.get("obs_lengths"))
     self._set_feed_cell_mask(feed.get("cell_mask"))
+    self._set_feed_cell_bias(feed.get("cell_bias"))
     return inp
 
   def _set_pred_lengths(self, lengths):
@@ -626,6 +640,43 @@ class Engine(object):
     self.set_cell_mask(mask)
     self._cell_mask_from_feed = True
 
+  def set_cell_bias(self, bias):
+    """A float32 log-potential per row, decode step and cell, added to the choice of cells
+    (include/multiverse_hip.h mv_set_cell_bias): [N, K] (one plane for every decode step) or
+    [N, Tm, K] (plane t for step t, Tm >= pred_len), in nats, negative = less likely, every value
+    finite; a grid-shaped [N, (Tm,) h, w] is taken as well.  None clears.  Sticky, with the rule
+    of set_cell_mask: a bias set here stays through every later feed that has no "cell_bias"
+    key; one that a feed brought is cleared by the next feed without the key.  The beam search,
+    both samplers and beam_occupancy read it, score_futures does not.  While sampling is on
+    under a bias, the forwards add "proposal_logprobs"."""
+    self._cell_bias_from_feed = False
+    if bias is None:
+      check(self.lib.mv_set_cell_bias(self.handle, None, 0), self.handle)
+      self._cell_bias_set = False
+      return
+    N = self.cfg.batch_size
+    h, w = self.cfg.scene_grids[self._beam_scale()]
+    b = np.asarray(bias)
+    if b.ndim >= 2 and b.shape[-2:] == (h, w) and b.shape[-1] != h * w:
+      b = b.reshape(b.shape[:-2] + (h * w,))
+    if b.ndim == 2:
+      b = b[:, None, :]
+    if b.ndim != 3 or b.shape[0] != N or b.shape[2] != h * w:
+      raise MvError("cell_bias: shape %s is neither [N=%d, K=%d] nor [N, Tm, K]"
+                    % (tuple(np.asarray(bias).shape), N, h * w))
+    b = f32(b)
+    check(self.lib.mv_set_cell_bias(self.handle, fptr(b), int(b.shape[1])), self.handle)
+    self._cell_bias_set = True
+
+  def _set_feed_cell_bias(self, bias):
+    """feed["cell_bias"], with the feed-scoped rule of feed["cell_mask"]."""
+    if bias is None:
+      if getattr(self, "_cell_bias_from_feed", False):
+        self.set_cell_bias(None)
+      return
+    self.set_cell_bias(bias)
+    self._cell_bias_from_feed = True
+
   def graph_captures(self):
     """Forwards captured into a hipGraph on this handle so far (a replay does not count)."""
     n = C.c_int64()
@@ -665,11 +716,12 @@ class Engine(object):
     self._sampling_limits = (int(top_k), float(top_p))
 
   def _truncated(self):
-    """Does the next / did the last beam forward sample under a top-k / nucleus limit or a cell
-    mask, i.e. from a proposal that is not the (tempered) model?"""
+    """Does the next / did the last beam forward sample under a top-k / nucleus limit, a cell
+    mask or a cell bias, i.e. from a proposal that is not the (tempered) model?"""
     top_k, top_p = getattr(self, "_sampling_limits", (0, 1.0))
     return getattr(self, "_sampling_on", False) and \
-        (top_k > 0 or top_p < 1.0 or getattr(self, "_cell_mask_set", False))
+        (top_k > 0 or top_p < 1.0 or getattr(self, "_cell_mask_set", False) or
+         getattr(self, "_cell_bias_set", False))
 
   def beam_proposal_logprobs(self):
     """float32 [N, B]: the log-probability of each future of the last SAMPLED forward under the
@@ -891,6 +943,7 @@ class Engine(object):
     self._set_pred_lengths(feed.get("pred_lengths"))
     self._set_obs_lengths(feed.get("obs_lengths"))
     self._set_feed_cell_mask(feed.get("cell_mask"))
+    self._set_feed_cell_bias(feed.get("cell_bias"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len
@@ -1384,15 +1437,28 @@ def _allowed_plane(allowed, samples, K):
   return a, a.ctypes.data_as(_u8p)
 
 
+def _bias_plane(bias, samples, K):
+  return f32(np.asarray(bias, dtype=np.float32).reshape(samples, K))
+
+
 def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device=0,
-                 allowed=None):
-  """allowed [N, K] (non-zero = the cell may be chosen): the masked step, mv_op_beam_step_masked."""
+                 allowed=None, bias=None):
+  """allowed [N, K] (non-zero = the cell may be chosen): the masked step, mv_op_beam_step_masked.
+  bias [N, K] float32 cell costs: the biased step, mv_op_beam_step_biased (allowed optional)."""
   lib = load()
   logits, prev_lp = f32(logits), f32(prev_lp)
   N, B, K = logits.shape
   new_lp = np.empty((N, B), dtype=np.float32)
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if bias is not None:
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K)
+    check(lib.mv_op_beam_step_biased(device, fptr(logits), fptr(prev_lp), ap, fptr(bz), N, B, K,
+                                     int(time), 1 if diverse else 0, float(gamma),
+                                     int(fix_num_timestep), fptr(new_lp), iptr(ids),
+                                     iptr(parents)))
+    return new_lp, ids, parents
   if allowed is not None:
     a, ap = _allowed_plane(allowed, N, K)
     check(lib.mv_op_beam_step_masked(device, fptr(logits), fptr(prev_lp), ap, N, B, K, int(time),
@@ -1406,16 +1472,25 @@ def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device
 
 
 def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0,
-                allowed=None):
+                allowed=None, bias=None):
   """One step of the sampling without replacement (mv_op_sbs_step): logits [N, B, K], prev_*
   [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B].  allowed [N, K]: the
-  masked step (mv_op_sbs_step_masked)."""
+  masked step (mv_op_sbs_step_masked).  bias [N, K]: the biased step (mv_op_sbs_step_biased;
+  allowed optional)."""
   lib = load()
   logits, prev_phi, prev_lp, prev_g = f32(logits), f32(prev_phi), f32(prev_lp), f32(prev_g)
   N, B, K = logits.shape
   phi, lp, g = (np.empty((N, B), dtype=np.float32) for _ in range(3))
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if bias is not None:
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K)
+    check(lib.mv_op_sbs_step_biased(device, fptr(logits), fptr(prev_phi), fptr(prev_lp),
+                                    fptr(prev_g), ap, fptr(bz), N, B, K, int(t),
+                                    float(temperature), int(seed) & 0xFFFFFFFF, fptr(phi),
+                                    fptr(lp), fptr(g), iptr(ids), iptr(parents)))
+    return phi, lp, g, ids, parents
   if allowed is not None:
     a, ap = _allowed_plane(allowed, N, K)
     check(lib.mv_op_sbs_step_masked(device, fptr(logits), fptr(prev_phi), fptr(prev_lp),
@@ -1449,17 +1524,26 @@ def enc_cone_build(labels, H, W, r0=1):
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,
-                   allowed=None):
+                   allowed=None, bias=None):
   """One step of the independent sampler under top-k / nucleus limits (mv_op_sample_step):
   logits [R, K], row r = future r % S of sample r // S -> (ids int32 [R], lp [R] the model's
   log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set).
-  allowed [R // S, K], one plane per sample: the masked step (mv_op_sample_step_masked)."""
+  allowed [R // S, K], one plane per sample: the masked step (mv_op_sample_step_masked).
+  bias [R // S, K]: the biased step (mv_op_sample_step_biased; allowed optional)."""
   lib = load()
   logits = f32(logits)
   R, K = logits.shape
   ids = np.empty(R, dtype=np.int32)
   lp, qlp = (np.empty(R, dtype=np.float32) for _ in range(2))
   keep = np.empty((R, K), dtype=np.uint8)
+  if bias is not None:
+    a, ap = _allowed_plane(allowed, R // int(S), K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, R // int(S), K)
+    check(lib.mv_op_sample_step_biased(device, fptr(logits), ap, fptr(bz), R, int(S), K, int(t),
+                                       float(temperature), int(seed) & 0xFFFFFFFF, int(top_k),
+                                       float(top_p), int(floor), iptr(ids), fptr(lp), fptr(qlp),
+                                       keep.ctypes.data_as(_u8p)))
+    return ids, lp, qlp, keep.astype(bool)
   if allowed is not None:
     a, ap = _allowed_plane(allowed, R // int(S), K)
     check(lib.mv_op_sample_step_masked(device, fptr(logits), ap, R, int(S), K, int(t),

@@ -240,6 +240,11 @@ _MF_FLAGS = [
     # these classes (multifuture.cell_mask_from_scene; the engine takes the mask per row:
     # mv_set_cell_mask).  A row with fewer than num_out such cells is decoded unconstrained.
     ("--allowed_classes", str, None), ("--allowed_min_share", float, 0.0),
+    # not in the reference: cell costs.  --class_costs "1:-2.0,4:0.5" (new class id : cost in
+    # nats): entering a grid cell costs the share-weighted sum of its pixels' class costs in the
+    # row's LAST observed frame (multifuture.cell_bias_from_scene; the engine adds the bias per
+    # row: mv_set_cell_bias).  Combines with --allowed_classes.
+    ("--class_costs", str, None),
 ]
 
 
@@ -276,6 +281,7 @@ def multifuture_inference_main(argv=None):
     raise SystemExit("--score_gt scores num_out futures per row; it does not combine with "
                      "--greedy")
   parse_allowed_classes(args)
+  parse_class_costs(args)
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)
@@ -335,6 +341,38 @@ def parse_allowed_classes(args):
     raise SystemExit("--allowed_min_share %s not in [0, 1]" % args.allowed_min_share)
   args.allowed_classes = classes
   args.unconstrained = []
+
+
+def parse_class_costs(args):
+  """--class_costs "1:-2.0,4:0.5" -> args.class_costs [(1, -2.0), (4, 0.5)] (None when not
+  given); refused with --greedy (the greedy decode chooses by argmax and reads no bias) and with
+  --score_gt (a given future's likelihood is the model's)."""
+  if args.class_costs is None:
+    return
+  if args.greedy:
+    raise SystemExit("--class_costs biases the beam search and the samplers; it does not "
+                     "combine with --greedy")
+  if args.score_gt is not None:
+    raise SystemExit("--class_costs biases a decode; --score_gt decodes nothing")
+  costs = []
+  try:
+    for one in str(args.class_costs).split(","):
+      if one.strip() == "":
+        continue
+      c, v = one.split(":")
+      costs.append((int(c), float(v)))
+  except ValueError:
+    raise SystemExit("--class_costs: a comma-separated list of id:cost pairs, not %r"
+                     % args.class_costs)
+  if not costs or any(c < 0 or c >= args.scene_class for c, _ in costs):
+    raise SystemExit("--class_costs %r: ids in [0, scene_class = %d)"
+                     % (args.class_costs, args.scene_class))
+  if len(set(c for c, _ in costs)) != len(costs):
+    raise SystemExit("--class_costs %r: a class id is given twice" % args.class_costs)
+  if any(not np.isfinite(v) for _, v in costs):
+    raise SystemExit("--class_costs %r: a cost is a finite number of nats (forbid a class with "
+                     "--allowed_classes)" % args.class_costs)
+  args.class_costs = costs
 
 
 def print_exact_nll(result):

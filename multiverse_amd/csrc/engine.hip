@@ -393,6 +393,40 @@ int mv_set_cell_mask(mv_handle h, const uint8_t* allowed, int32_t Tm) {
   });
 }
 
+int mv_set_cell_bias(mv_handle h, const float* bias, int32_t Tm) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_cell_bias: engine was created with beam_size 1 (the "
+               "greedy forward chooses by argmax and reads no bias: create a beam handle)");
+    // behind whatever forward or occupancy map still reads the previous bias on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!bias) {
+      h->cbias_tm = 0;
+      return;
+    }
+    MV_REQUIRE(Tm >= 1, "mv_set_cell_bias: Tm = %d must be >= 1 (1 = one plane for every step)",
+               (int)Tm);
+    const size_t N = (size_t)h->cfg.batch_size, K = (size_t)h->sc[beam_scale(h)].K;
+    const size_t Tcap = (size_t)h->cfg.max_pred_len;
+    // a cost is finite: a veto is the mask's job (a -inf here would reach the log-softmax of w)
+    for (size_t i = 0; i < N * Tm * K; ++i)
+      MV_REQUIRE(std::isfinite(bias[i]), "mv_set_cell_bias: bias[n = %d, tm = %d, k = %d] = %g is "
+                 "not finite (a cost is a finite float32; forbid a cell with mv_set_cell_mask)",
+                 (int)(i / ((size_t)Tm * K)), (int)(i / K % Tm), (int)(i % K), (double)bias[i]);
+    // one allocation for both layouts: the address a captured forward holds never changes
+    h->cbias_dev.alloc(N * Tcap * K);
+    if (Tm == 1) {
+      HIP_CHECK(hipMemcpy(h->cbias_dev.p, bias, N * K * sizeof(float), hipMemcpyHostToDevice));
+    } else {
+      const size_t planes = std::min((size_t)Tm, Tcap);   // a forward reads planes < pred_len
+      HIP_CHECK(hipMemcpy2D(h->cbias_dev.p, Tcap * K * sizeof(float), bias,
+                            (size_t)Tm * K * sizeof(float), planes * K * sizeof(float), N,
+                            hipMemcpyHostToDevice));
+    }
+    h->cbias_tm = Tm;
+  });
+}
+
 int mv_graph_captures(mv_handle h, int64_t* captures) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -533,6 +567,8 @@ int mv_submit_greedy(mv_handle h, const mv_inputs* in) {
     MV_REQUIRE(in, "mv_submit_greedy: NULL argument");
     MV_REQUIRE(!h->cmask_set(), "mv_submit_greedy: a cell mask is set (mv_set_cell_mask); the "
                "greedy forward chooses by argmax and reads no mask -- clear it first");
+    MV_REQUIRE(!h->cbias_set(), "mv_submit_greedy: a cell bias is set (mv_set_cell_bias); the "
+               "greedy forward chooses by argmax and reads no bias -- clear it first");
     pipeline_submit(h, in);
   });
 }
@@ -572,6 +608,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_init");
     MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_init");
+    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
@@ -623,6 +661,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_forward_backward");
+    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
@@ -691,6 +731,8 @@ int mv_train_apply(mv_handle h, float grad_scale) {
                "clear it first", "mv_train_apply");
     MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
                "cells -- clear it first", "mv_train_apply");
+    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
+               "cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -706,6 +748,8 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_step");
     MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
+               "cells -- clear it first", "mv_train_step");
+    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");

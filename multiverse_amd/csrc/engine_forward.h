@@ -1101,11 +1101,17 @@ __global__ void ragged_ids_tail_kernel(int32_t* __restrict__ ids, const int32_t*
 
 // The allowed cells of decode step t (mv_set_cell_mask): plane t of every row, or the one plane.
 // No mask set: the empty StepMask, and the step launches exactly what it launched before.
+// The cell costs of the step (mv_set_cell_bias) likewise: plane t of every row, or the one plane.
 StepMask step_mask(const mv_engine* e, int K, int t) {
   StepMask m;
-  if (!e->cmask_set()) return m;
-  m.p = e->cmask_dev.p + (size_t)t * e->cmask_step(K);
-  m.stride = e->cmask_stride(K);
+  if (e->cmask_set()) {
+    m.p = e->cmask_dev.p + (size_t)t * e->cmask_step(K);
+    m.stride = e->cmask_stride(K);
+  }
+  if (e->cbias_set()) {
+    m.bias = e->cbias_dev.p + (size_t)t * e->cbias_step(K);
+    m.bias_stride = e->cbias_stride(K);
+  }
   return m;
 }
 
@@ -1502,7 +1508,12 @@ void plan_scored(mv_engine* e) {
 // (after plan_ragged): every row that decodes needs an allowed cell at every step below its
 // length, and beam_size of them at step 0 where only the root's K children are candidates.
 void plan_cell_mask(mv_engine* e, ForwardKind kind) {
-  if (!e->cmask_set() || kind == ForwardKind::Scored || kind == ForwardKind::Greedy) return;
+  if (kind == ForwardKind::Scored || kind == ForwardKind::Greedy) return;
+  if (e->cbias_set())
+    MV_REQUIRE(e->cbias_tm == 1 || e->cbias_tm >= e->pred_len, "mv_set_cell_bias: the bias has "
+               "Tm = %d planes, the forward pred_len = %d steps (Tm must be 1 or at least "
+               "pred_len)", e->cbias_tm, e->pred_len);
+  if (!e->cmask_set()) return;
   const mv_config& c = e->cfg;
   const int N = c.batch_size, Tp = e->pred_len, Tm = e->cmask_tm, B = c.beam_size;
   MV_REQUIRE(Tm == 1 || Tm >= Tp, "mv_set_cell_mask: the mask has Tm = %d planes, the forward "
@@ -1559,6 +1570,8 @@ void run_forward(mv_engine* e, ForwardKind kind) {
   // a masked step holds a row in one wave: refused before anything is launched
   if (beam && kind != ForwardKind::Scored && e->cmask_set())
     require_row_fits_wave("mv_set_cell_mask: a masked step", e->sc[beam_scale(e)].K);
+  if (beam && kind != ForwardKind::Scored && e->cbias_set())
+    require_row_fits_wave("mv_set_cell_bias: a biased step", e->sc[beam_scale(e)].K);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
@@ -1574,9 +1587,10 @@ void run_forward(mv_engine* e, ForwardKind kind) {
     e->last = kind;
     return;
   }
-  // (a scoring forward reads no mask: one graph whatever is set)
-  const int mask_key = (kind == ForwardKind::Scored || kind == ForwardKind::Greedy ||
-                        !e->cmask_set()) ? 0 : (e->cmask_tm > 1 ? 2 : 1);
+  // (a scoring forward reads no mask and no bias: one graph whatever is set)
+  const bool constrainable = kind != ForwardKind::Scored && kind != ForwardKind::Greedy;
+  const int mask_key = (!constrainable || !e->cmask_set() ? 0 : (e->cmask_tm > 1 ? 2 : 1)) +
+                       3 * (!constrainable || !e->cbias_set() ? 0 : (e->cbias_tm > 1 ? 2 : 1));
   const auto key = std::make_tuple(kind, e->pred_len, e->num_frames, mask_key);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {

@@ -464,18 +464,23 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
 
 // K <= CPT * 256 cells: a thread's cells in registers (CPT 1 or 3); any K beyond
 // MASKED (mv_set_cell_mask): each future's step map is the softmax over the allowed cells
-template <bool RAGGED, bool MASKED>
+// BIASED (mv_set_cell_bias; the kernels' MASKED form with the mask plane optional): of l + b
+template <bool RAGGED, bool MASKED, bool BIASED = false>
 void launch_beam_occupancy(mv_engine* e, const float* lp, int N, int B, int Tp, int K) {
+  const bool mask = MASKED && e->cmask_set();
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(N * Tp), dim3(mv::kMfBlock), 0, e->stream, e->bm_out_logits.p,
                        lp, e->mf_occ.p, B, Tp, K, RAGGED ? e->lens_dev.p : nullptr,
-                       MASKED ? e->cmask_dev.p : (const uint8_t*)nullptr,
-                       MASKED ? e->cmask_stride(K) : (int64_t)0,
-                       MASKED ? e->cmask_step(K) : (int64_t)0);
+                       mask ? e->cmask_dev.p : (const uint8_t*)nullptr,
+                       mask ? e->cmask_stride(K) : (int64_t)0,
+                       mask ? e->cmask_step(K) : (int64_t)0,
+                       BIASED ? e->cbias_dev.p : (const float*)nullptr,
+                       BIASED ? e->cbias_stride(K) : (int64_t)0,
+                       BIASED ? e->cbias_step(K) : (int64_t)0);
   };
-  if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED, MASKED>);
-  else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED, MASKED>);
-  else go(mv::beam_occupancy_anyk_kernel<RAGGED, MASKED>);
+  if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED, MASKED, BIASED>);
+  else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED, MASKED, BIASED>);
+  else go(mv::beam_occupancy_anyk_kernel<RAGGED, MASKED, BIASED>);
 }
 
 void beam_occupancy(mv_engine* e, float* out) {
@@ -504,6 +509,11 @@ void beam_occupancy(mv_engine* e, float* out) {
                    "under the cell mask that is set now (mv_set_cell_mask)", n, cnt, t);
       }
   }
+  // the bias that is set now, as the mask
+  const RowForm form = step_row_form(masked, e->cbias_set());
+  if (form == RowForm::Biased)
+    MV_REQUIRE(e->cbias_tm == 1 || e->cbias_tm >= Tp, "mv_beam_occupancy: the cell bias has "
+               "Tm = %d planes, the last forward pred_len = %d steps", e->cbias_tm, Tp);
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
   // HBM-bound: every beam's logits row read once, the map written once
   // independently sampled futures are draws, not scored hypotheses: uniform weights, which the
@@ -517,7 +527,10 @@ void beam_occupancy(mv_engine* e, float* out) {
   }
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
     // the last forward ran with per-row lengths: 0 past a row's end
-    if (masked && e->len.ragged) launch_beam_occupancy<true, true>(e, lp, N, B, Tp, K);
+    if (form == RowForm::Biased && e->len.ragged)
+      launch_beam_occupancy<true, true, true>(e, lp, N, B, Tp, K);
+    else if (form == RowForm::Biased) launch_beam_occupancy<false, true, true>(e, lp, N, B, Tp, K);
+    else if (masked && e->len.ragged) launch_beam_occupancy<true, true>(e, lp, N, B, Tp, K);
     else if (masked) launch_beam_occupancy<false, true>(e, lp, N, B, Tp, K);
     else if (e->len.ragged) launch_beam_occupancy<true, false>(e, lp, N, B, Tp, K);
     else launch_beam_occupancy<false, false>(e, lp, N, B, Tp, K);

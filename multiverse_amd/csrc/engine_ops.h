@@ -255,15 +255,33 @@ static StepMask op_mask_up(OpCtx& ctx, DevBuf<uint8_t>& dm, const uint8_t* allow
   return m;
 }
 
+// the biased forms: `bias` [samples, K] floats goes up as well; `allowed` may be NULL there
+static void op_bias_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, StepMask& m,
+                       const uint8_t* allowed, const float* bias, size_t samples, int K,
+                       const char* who) {
+  MV_REQUIRE(bias, "%s: NULL bias", who);
+  require_row_fits_wave(who, K);
+  for (size_t i = 0; i < samples * K; ++i)
+    MV_REQUIRE(std::isfinite(bias[i]), "%s: bias[%d, %d] = %g is not finite", who, (int)(i / K),
+               (int)(i % K), (double)bias[i]);
+  if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
+  ctx.up(db, bias, samples * K);
+  m.bias = db.p;
+  m.bias_stride = K;
+}
+
 static int op_beam_step(int device, const float* logits, const float* prev_logprob,
                         int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
                         float gamma, int32_t fix_num_timestep, float* new_logprob,
-                        int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked) {
+                        int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked,
+                        const float* bias = nullptr, bool biased = false) {
   return guarded(nullptr, [&] {
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
+    DevBuf<float> db;
     StepMask mask;
-    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
+    if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_beam_step_biased");
+    else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     DevBuf<float> dl, dp, dn;
     DevBuf<int32_t> di, dpa;
@@ -296,19 +314,32 @@ int mv_op_beam_step_masked(int device, const float* logits, const float* prev_lo
                       fix_num_timestep, new_logprob, ids, parents, allowed, true);
 }
 
+int mv_op_beam_step_biased(int device, const float* logits, const float* prev_logprob,
+                           const uint8_t* allowed, const float* bias, int32_t N, int32_t B,
+                           int32_t K, int32_t time, int32_t diverse, float gamma,
+                           int32_t fix_num_timestep, float* new_logprob, int32_t* ids,
+                           int32_t* parents) {
+  return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
+                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
+                      bias, true);
+}
+
 static int op_sbs_step(int device, const float* logits, const float* prev_phi,
                        const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
                        int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                        float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents,
-                       const uint8_t* allowed, bool masked) {
+                       const uint8_t* allowed, bool masked, const float* bias = nullptr,
+                       bool biased = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
     MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
                (double)temperature);
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
+    DevBuf<float> db;
     StepMask mask;
-    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
+    if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_sbs_step_biased");
+    else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     const size_t R = (size_t)N * B;
     DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
@@ -345,10 +376,21 @@ int mv_op_sbs_step_masked(int device, const float* logits, const float* prev_phi
                      seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed, true);
 }
 
+int mv_op_sbs_step_biased(int device, const float* logits, const float* prev_phi,
+                          const float* prev_logprob, const float* prev_gumbel,
+                          const uint8_t* allowed, const float* bias, int32_t N, int32_t B,
+                          int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
+                          float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
+  return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
+                     allowed != nullptr, bias, true);
+}
+
 static int op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K,
                           int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
                           int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep,
-                          const uint8_t* allowed, bool masked) {
+                          const uint8_t* allowed, bool masked, const float* bias = nullptr,
+                          bool biased = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
@@ -362,8 +404,12 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     MV_REQUIRE(floor >= 1, "mv_op_sample_step: floor %d must be >= 1", (int)floor);
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
+    DevBuf<float> db;
     StepMask mask;
-    if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)(R / S), K, "mv_op_sample_step_masked");
+    if (biased)
+      op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)(R / S), K, "mv_op_sample_step_biased");
+    else if (masked)
+      mask = op_mask_up(ctx, dm, allowed, (size_t)(R / S), K, "mv_op_sample_step_masked");
     DevBuf<float> dl, dlp, dq;
     DevBuf<int32_t> di;
     DevBuf<uint8_t> dk;
@@ -396,6 +442,14 @@ int mv_op_sample_step_masked(int device, const float* logits, const uint8_t* all
                              float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
                         qlp, keep, allowed, true);
+}
+
+int mv_op_sample_step_biased(int device, const float* logits, const uint8_t* allowed,
+                             const float* bias, int32_t R, int32_t S, int32_t K, int32_t t,
+                             float temperature, uint32_t seed, int32_t top_k, float top_p,
+                             int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
+  return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
+                        qlp, keep, allowed, allowed != nullptr, bias, true);
 }
 
 int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,

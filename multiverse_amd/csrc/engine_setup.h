@@ -38,9 +38,16 @@ void with_rank_j(int K, F&& fn) {
 
 // The allowed cells of one decode step (mv_set_cell_mask): sample n's plane [K] is p + n * stride.
 // p == nullptr: no mask, and every launch is the unmasked one.
+// The cell costs of the step (mv_set_cell_bias) ride along: sample n's plane [K] floats is
+// bias + n * bias_stride; bias == nullptr: none.  With a bias the launch is the BIASED one, whether
+// or not p is set.
 struct StepMask {
   const uint8_t* p = nullptr;
   int64_t stride = 0;
+  const float* bias = nullptr;
+  int64_t bias_stride = 0;
+  RowForm form() const { return step_row_form(p != nullptr, bias != nullptr); }
+  bool constrained() const { return form() != RowForm::Plain; }
 };
 
 // One beam step (log-softmax + diversity penalty + top-B) in the form step_plan.h's
@@ -50,11 +57,12 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
                       float log_gamma, int fix_num_timestep, float* new_lp, int32_t* ids,
                       int32_t* parents, int32_t* src_row, int rows_per_sample,
                       int32_t* row_ref = nullptr, StepMask mask = StepMask{}) {
-  if (mask.p) {
-    require_row_fits_wave("beam step under a cell mask", K);
-    MV_REQUIRE(cand, "internal: beam step under a cell mask without the candidate scratch");
+  if (mask.constrained()) {
+    require_row_fits_wave(mask.bias ? "beam step under a cell bias" : "beam step under a cell mask",
+                          K);
+    MV_REQUIRE(cand, "internal: beam step under a cell mask or bias without the candidate scratch");
   }
-  if (beam_step_form(K, cand != nullptr, mask.p != nullptr) == BeamStepForm::Single) {
+  if (beam_step_form(K, cand != nullptr, mask.constrained()) == BeamStepForm::Single) {
     hipLaunchKernelGGL(mv::beam_step_kernel, dim3(N), dim3(512), beam_step_lds_bytes(B, K),
                        stream, logits, prev_lp, B, K, time, diverse, log_gamma,
                        fix_num_timestep, new_lp, ids, parents, src_row, rows_per_sample, row_ref);
@@ -65,13 +73,18 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.p)
+    if (mask.form() == RowForm::Biased)
+      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true>), grid, block, 0, stream, logits,
+                         prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
+                         mask.bias, mask.bias_stride);
+    else if (mask.p)
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, true>), grid, block, 0, stream, logits, prev_lp,
-                         R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride);
+                         R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
+                         (const float*)nullptr, (int64_t)0);
     else
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, false>), grid, block, 0, stream, logits,
                          prev_lp, R, B, K, time, diverse, log_gamma, cand,
-                         (const uint8_t*)nullptr, (int64_t)0);
+                         (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0);
   });
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
@@ -97,19 +110,24 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.p)
+    if (mask.form() == RowForm::Biased)
+      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true>), grid, block, 0, stream, logits,
+                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
+                         q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride);
+    else if (mask.p)
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true>), grid, block, 0, stream, logits,
                          prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                         q_plane, mask.p, mask.stride);
+                         q_plane, mask.p, mask.stride, (const float*)nullptr, (int64_t)0);
     else
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, false>), grid, block, 0, stream, logits,
                          prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                         q_plane, (const uint8_t*)nullptr, (int64_t)0);
+                         q_plane, (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr,
+                         (int64_t)0);
   });
   hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
                      prev_phi, prev_lp, B, K, t, new_phi, new_lp, new_g, ids, parents, src_row,
-                     rows_per_sample, row_ref, mask.p ? 1 : 0);
+                     rows_per_sample, row_ref, mask.constrained() ? 1 : 0);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -122,14 +140,21 @@ void launch_sample_step(hipStream_t stream, float* logits, int64_t row_stride, i
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.p)
+    if (mask.form() == RowForm::Biased)
+      hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true>), grid, block, 0, stream, logits,
+                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
+                         ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
+                         mask.bias_stride);
+    else if (mask.p)
       hipLaunchKernelGGL((mv::sample_step_kernel<J, true>), grid, block, 0, stream, logits,
                          row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
-                         ids_stride, src_row, keep_out, mask.p, mask.stride);
+                         ids_stride, src_row, keep_out, mask.p, mask.stride, (const float*)nullptr,
+                         (int64_t)0);
     else
       hipLaunchKernelGGL((mv::sample_step_kernel<J, false>), grid, block, 0, stream, logits,
                          row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
-                         ids_stride, src_row, keep_out, (const uint8_t*)nullptr, (int64_t)0);
+                         ids_stride, src_row, keep_out, (const uint8_t*)nullptr, (int64_t)0,
+                         (const float*)nullptr, (int64_t)0);
   });
 }
 

@@ -354,6 +354,13 @@ struct mv_engine {
   bool cmask_set() const { return cmask_tm > 0; }
   int64_t cmask_stride(int K) const { return cmask_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
   int64_t cmask_step(int K) const { return cmask_tm > 1 ? K : 0; }
+  // caller-given cell costs (mv_set_cell_bias; sticky until cleared): float32
+  // log-potentials in the mask's two layouts at ONE address, for the same reason.
+  DevBuf<float> cbias_dev;
+  int cbias_tm = 0;                // 0 = no bias
+  bool cbias_set() const { return cbias_tm > 0; }
+  int64_t cbias_stride(int K) const { return cbias_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
+  int64_t cbias_step(int K) const { return cbias_tm > 1 ? K : 0; }
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps
@@ -410,7 +417,7 @@ struct mv_engine {
     if (it != planes.end()) it->second.valid = false;
   }
   // hipGraph replay of the forward (one graph per (kind, T_pred, U, cell mask: 0 none, 1 one
-  // plane, 2 a plane per step))
+  // plane, 2 a plane per step -- plus 3 times the same code for the cell bias))
   bool graph_mode = false;
   std::map<std::tuple<ForwardKind, int, int, int>, hipGraphExec_t> graphs;
   int64_t graph_captures = 0;        // forwards captured so far (mv_graph_captures)

@@ -1347,21 +1347,53 @@ __device__ __forceinline__ bool step_cell_in(uint32_t am, int lane, int j, int K
   else return lane + 64 * j < K;
 }
 
+// Caller-given cell costs (include/multiverse_hip.h mv_set_cell_bias): a third, BIASED form of
+// the same kernels, instantiated as <J, true, true>.  It serves "bias only" and "bias + mask"
+// alike: it always works on the `am` bits, which are the in-row bits when no mask plane is given.
+// The row's bias plane [K] floats is read once per wave into b[J] exactly as the logits are
+// (lane l owns k = l + 64 j; 0 past the row).
+template <int J>
+__device__ __forceinline__ uint32_t step_row_biased_bits(const uint8_t* __restrict__ plane,
+                                                         int K, int lane) {
+  if (plane) return step_row_allowed_bits<J>(plane, K, lane);   // uniform
+  uint32_t am = 0u;
+#pragma unroll
+  for (int j = 0; j < J; ++j)
+    if (lane + 64 * j < K) am |= 1u << j;
+  return am;
+}
+
+template <int J>
+__device__ __forceinline__ void step_row_bias(const float* __restrict__ plane, int K, int lane,
+                                              float (&b)[J]) {
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    b[j] = k < K ? plane[k] : 0.f;
+  }
+}
+
 // MASKED: amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A cell
 // outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
 // nothing, so an allowed cell's rank counts allowed cells only.
-template <int J, bool MASKED = false>
+// BIASED (implies MASKED; amask may be NULL): the candidate is (prev_lp + lp) + b, with
+// b = bias + (r / B) * bias_stride, formed before the mask's -inf and before the ranks.
+template <int J, bool MASKED = false, bool BIASED = false>
 __global__ __launch_bounds__(256)
 void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict__ prev_lp,
                       int R, int B, int K, int time, int diverse, float log_gamma,
                       float* __restrict__ cand, const uint8_t* __restrict__ amask = nullptr,
-                      int64_t mask_stride = 0) {
+                      int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
+                      int64_t bias_stride = 0) {
+  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   if (time <= 1 && (r % B) != 0) return;   // only beam 0 is a candidate at the first step
   uint32_t am = 0u;
-  if constexpr (MASKED)
+  if constexpr (BIASED)
+    am = step_row_biased_bits<J>(amask ? amask + (size_t)(r / B) * mask_stride : nullptr, K, lane);
+  else if constexpr (MASKED)
     am = step_row_allowed_bits<J>(amask + (size_t)(r / B) * mask_stride, K, lane);
   const float* row = logits + (size_t)r * K;
   float v[J];
@@ -1383,6 +1415,12 @@ void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict_
   const float pl = prev_lp[r];
 #pragma unroll
   for (int j = 0; j < J; ++j) v[j] = pl + ((v[j] - mx) - lse);
+  if constexpr (BIASED) {
+    float b[J];
+    step_row_bias<J>(bias + (size_t)(r / B) * bias_stride, K, lane, b);
+#pragma unroll
+    for (int j = 0; j < J; ++j) v[j] = v[j] + b[j];
+  }
   if constexpr (MASKED) {
 #pragma unroll
     for (int j = 0; j < J; ++j)
@@ -1567,7 +1605,9 @@ __device__ __forceinline__ uint32_t float_order_key(float x) {
 // cells' sum of e, taken in the same order.
 // MASKED (mv_set_cell_mask): a cell outside the allowed set `am` is absent, as a cell past K is:
 // e, sum_e, c(k), m(k) and the floor run over the allowed cells, and mxq is their maximum.
-template <int J, bool MASKED = false>
+// BIASED (mv_set_cell_bias): w carries the bias, and the order of the limits is the order of w,
+// not of the logits: the key is taken of w, and keep(k) <=> float_order_key(w[k]) >= threshold.
+template <int J, bool MASKED = false, bool BIASED = false>
 __device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
                                                             const float (&w)[J], float mxq, int K,
                                                             int lane, int top_k, float top_p,
@@ -1579,7 +1619,8 @@ __device__ __forceinline__ uint32_t step_row_keep_threshold(const float (&v)[J],
 #pragma unroll
   for (int j = 0; j < J; ++j) {
     const bool in = step_cell_in<MASKED>(am, lane, j, K);
-    key[j] = in ? float_order_key(v[j]) : 0u;     // (a pad never counts: masked by e and `in`)
+    // (a pad never counts: masked by e and `in`)
+    key[j] = in ? float_order_key(BIASED ? w[j] : v[j]) : 0u;
     e[j] = in ? expf(w[j] - mxq) : 0.f;
     if (in) sum_e += e[j];
   }
@@ -1641,14 +1682,18 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // the log-softmax over ALL cells; the proposal treats a cell outside the plane as absent: w is
 // -inf there, mxq and the sums run over the allowed cells (also at temperature 1 with no limit:
 // the proposal differs from the model), and keep(k) = allowed and the limits' predicate.
-template <int J, bool MASKED = false>
+// BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): b = bias + n * bias_stride,
+// w = l / temperature + b, the limits order by w, and the score is (lp / temperature + b) + g.
+template <int J, bool MASKED = false, bool BIASED = false>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
                         int t, int shared, const uint32_t* __restrict__ params, int floor,
                         const int32_t* __restrict__ lens, float* __restrict__ lp_acc,
                         float* __restrict__ lq_acc, int32_t* __restrict__ ids, int ids_stride,
                         int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out,
-                        const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0) {
+                        const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0,
+                        const float* __restrict__ bias = nullptr, int64_t bias_stride = 0) {
+  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1668,15 +1713,24 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   uint32_t am = 0u;
-  if constexpr (MASKED) {
+  float b[BIASED ? J : 1];
+  if constexpr (BIASED) {
+    step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
+#pragma unroll
+    for (int j = 0; j < J; ++j) w[j] = w[j] + b[j];
+    am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
+  } else if constexpr (MASKED) {
     am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
+  }
+  if constexpr (MASKED) {
 #pragma unroll
     for (int j = 0; j < J; ++j)
       if (!step_cell_in<true>(am, lane, j, K)) w[j] = -INFINITY;
   }
   if (tempered || MASKED) step_regs_log_softmax<J, MASKED>(w, K, lane, mxq, lseq, am);
   if (limited)
-    thr = step_row_keep_threshold<J, MASKED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq, am);
+    thr = step_row_keep_threshold<J, MASKED, BIASED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq,
+                                                     am);
   float best = -INFINITY, blp = 0.f, blq = 0.f;
   int bi = 0x7fffffff;
 #pragma unroll
@@ -1684,12 +1738,14 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
     const int k = lane + 64 * j;
     if (k < K) {
       const bool kept = step_cell_in<MASKED>(am, lane, j, K) &&
-                        (!limited || float_order_key(v[j]) >= thr);
+                        (!limited || float_order_key(BIASED ? w[j] : v[j]) >= thr);
       if (keep_out) keep_out[(size_t)r * K + k] = kept ? 1 : 0;
       if (kept) {
         const float lp = (v[j] - mx) - lse;
         const float u = sample_uniform((uint32_t)s * (uint32_t)K + (uint32_t)k, seed, (uint32_t)t);
-        const float sc = lp / temperature + (-logf(-logf(u)));
+        float sc;
+        if constexpr (BIASED) sc = (lp / temperature + b[j]) + (-logf(-logf(u)));
+        else sc = lp / temperature + (-logf(-logf(u)));
         // strict: the lane's lowest index stays
         if (sc > best) { best = sc; bi = k; blp = lp; blq = (w[j] - mxq) - lseq; }
       }
@@ -1783,14 +1839,19 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 // MASKED (mv_set_cell_mask; amask + n * mask_stride = the sample's plane at this step): a cell
 // outside the plane is absent from the proposal as in sample_step_kernel -- q = cand = -inf -- and
 // the q plane is always written (sbs_select_kernel's force_q).
-template <int J, bool MASKED = false>
+// BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): w = l / temperature + b with
+// b = bias + n * bias_stride; q, the limits' order and the q plane follow w as in
+// sample_step_kernel.
+template <int J, bool MASKED = false, bool BIASED = false>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
                         const uint32_t* __restrict__ params, int floor,
                         float* __restrict__ cand, float* __restrict__ lp_plane,
                         float* __restrict__ q_plane, const uint8_t* __restrict__ amask = nullptr,
-                        int64_t mask_stride = 0) {
+                        int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
+                        int64_t bias_stride = 0) {
+  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1806,8 +1867,16 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   uint32_t am = 0u;
-  if constexpr (MASKED) {
+  if constexpr (BIASED) {
+    float b[J];
+    step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
+#pragma unroll
+    for (int j = 0; j < J; ++j) w[j] = w[j] + b[j];
+    am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
+  } else if constexpr (MASKED) {
     am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
+  }
+  if constexpr (MASKED) {
 #pragma unroll
     for (int j = 0; j < J; ++j)
       if (!step_cell_in<true>(am, lane, j, K)) w[j] = -INFINITY;
@@ -1820,7 +1889,8 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
   const bool limited = top_k > 0 || top_p < 1.f;   // uniform
   uint32_t thr = 0u;
   if (limited)
-    thr = step_row_keep_threshold<J, MASKED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq, am);
+    thr = step_row_keep_threshold<J, MASKED, BIASED>(v, w, mxq, K, lane, top_k, top_p, floor, lseq,
+                                                     am);
   const float phi = prev_phi[r], G = prev_g[r];
   float* lp_out = lp_plane + (size_t)r * K;
   float* q_out = q_plane + (size_t)r * K;
@@ -1831,7 +1901,7 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
     if (k < K) {
       const float lp = (v[j] - mx) - lse;
       const bool kept = step_cell_in<MASKED>(am, lane, j, K) &&
-                        (!limited || float_order_key(v[j]) >= thr);
+                        (!limited || float_order_key(BIASED ? w[j] : v[j]) >= thr);
       // == lp bit for bit at temperature 1 with the limits off
       const float q = kept ? (w[j] - mxq) - lseq : -INFINITY;
       lp_out[k] = lp;
@@ -1906,7 +1976,7 @@ void sbs_select_kernel(const float* __restrict__ cand, const float* __restrict__
       const size_t o = (size_t)n * B + sel, pr = (size_t)n * B + par;
       const size_t cell = (size_t)n * B * K + flat;
       // the q plane exists when the proposal differs from the model: tempered, truncated or
-      // (force_q) under a cell mask
+      // (force_q) under a cell mask or a cell bias
       const bool has_q = force_q != 0 ||
                          __builtin_bit_cast(float, params[1]) != 1.f || (int)params[2] > 0 ||
                          __builtin_bit_cast(float, params[3]) < 1.f;

@@ -140,21 +140,33 @@ __device__ __forceinline__ void occ_beam_weight_norm(const float* __restrict__ l
 // MASKED (mv_set_cell_mask): every future's step map is the softmax over the allowed cells of
 // (n, t) -- maximum and sum over them, a cell outside exactly 0.0f; the plane is
 // amask + n * mask_stride + t * mask_step, read once into one bit per owned cell.
-template <int CPT, bool RAGGED, bool MASKED = false>
+// BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL = every cell of the row): the step
+// map is the softmax of l + b over the allowed cells, b = bias + n * bias_stride + t * bias_step,
+// read once into a register per owned cell.
+template <int CPT, bool RAGGED, bool MASKED = false, bool BIASED = false>
 __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
     int B, int T, int K, const int32_t* __restrict__ lens,
-    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0) {
+    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0,
+    const float* __restrict__ bias = nullptr, int64_t bias_stride = 0, int64_t bias_step = 0) {
+  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
   uint32_t am = 0u;                                // MASKED: bit c = cell tid + c * 256 is allowed
   if constexpr (MASKED) {
     const uint8_t* plane = amask + (size_t)n * mask_stride + (size_t)t * mask_step;
+    const bool all = BIASED && !amask;             // block-uniform
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
       const int k = tid + c * kMfBlock;
-      if (k < K && plane[k] != 0) am |= 1u << c;
+      if (k < K && (all || plane[k] != 0)) am |= 1u << c;
     }
+  }
+  float bz[BIASED ? CPT : 1];
+  if constexpr (BIASED) {
+    const float* plane = bias + (size_t)n * bias_stride + (size_t)t * bias_step;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) bz[c] = plane[min(tid + c * kMfBlock, K - 1)];
   }
   // cell c of this thread takes part in the softmax (the unmasked form does not read `am`)
   auto in = [&](int c) {
@@ -185,7 +197,8 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
       for (int c = 0; c < CPT; ++c) {
         const int k = tid + c * kMfBlock;
         // a cell past the row reads the row's last one (no divergent load) and is masked
-        const float xv = live ? x[min(k, K - 1)] : 0.f;
+        float xv = live ? x[min(k, K - 1)] : 0.f;
+        if constexpr (BIASED) xv = xv + bz[c];
         v[j][c] = (live && in(c)) ? xv : -INFINITY;
         mx[j] = fmaxf(mx[j], v[j][c]);
       }
@@ -220,12 +233,14 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_kernel(
 // k = tid, tid + 256, ...  The row is read three times (maximum, sum, accumulation), the second
 // and third time from cache; the running map lives in the output row, which only this
 // workgroup -- and each cell only its own thread -- touches.
-// MASKED as above; the plane is read beside the row in every pass.
-template <bool RAGGED, bool MASKED = false>
+// MASKED and BIASED as above; the planes are read beside the row in every pass.
+template <bool RAGGED, bool MASKED = false, bool BIASED = false>
 __global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
     const float* __restrict__ logits, const float* __restrict__ lp, float* __restrict__ out,
     int B, int T, int K, const int32_t* __restrict__ lens,
-    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0) {
+    const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0, int64_t mask_step = 0,
+    const float* __restrict__ bias = nullptr, int64_t bias_stride = 0, int64_t bias_step = 0) {
+  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   __shared__ float red[kOccBeamChunk * kMfWaves];
   const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
   if constexpr (RAGGED) {
@@ -238,19 +253,28 @@ __global__ __launch_bounds__(kMfBlock) void beam_occupancy_anyk_kernel(
   occ_beam_weight_norm(lp + (size_t)n * B, B, &wm, &ws);
   float* o = out + (size_t)blockIdx.x * K;
   const uint8_t* am = nullptr;
-  if constexpr (MASKED) am = amask + (size_t)n * mask_stride + (size_t)t * mask_step;
-  auto in = [&](int k) { if constexpr (MASKED) return am[k] != 0; else return true; };
+  if constexpr (MASKED)
+    if (!BIASED || amask) am = amask + (size_t)n * mask_stride + (size_t)t * mask_step;
+  const float* bz = nullptr;
+  if constexpr (BIASED) bz = bias + (size_t)n * bias_stride + (size_t)t * bias_step;
+  auto in = [&](int k) {
+    if constexpr (BIASED) return !am || am[k] != 0;
+    else if constexpr (MASKED) return am[k] != 0;
+    else return true;
+  };
   for (int b = 0; b < B; ++b) {
     const float* x = logits + (((size_t)n * B + b) * T + t) * K;
+    // the cell's logit, plus its cost in the BIASED form
+    auto xb = [&](int k) { if constexpr (BIASED) return x[k] + bz[k]; else return x[k]; };
     float mx[1] = {-INFINITY};
-    for (int k = tid; k < K; k += kMfBlock) if (in(k)) mx[0] = fmaxf(mx[0], x[k]);
+    for (int k = tid; k < K; k += kMfBlock) if (in(k)) mx[0] = fmaxf(mx[0], xb(k));
     occ_block_reduce<true>(mx, red);
     float sm[1] = {0.f};
-    for (int k = tid; k < K; k += kMfBlock) if (in(k)) sm[0] += expf(x[k] - mx[0]);
+    for (int k = tid; k < K; k += kMfBlock) if (in(k)) sm[0] += expf(xb(k) - mx[0]);
     occ_block_reduce<false>(sm, red);
     const float w = expf(lp[(size_t)n * B + b] - wm) / ws;
     for (int k = tid; k < K; k += kMfBlock) {
-      const float p = in(k) ? (expf(x[k] - mx[0]) / sm[0]) * w : 0.f;
+      const float p = in(k) ? (expf(xb(k) - mx[0]) / sm[0]) * w : 0.f;
       o[k] = b == 0 ? p : o[k] + p;
     }
   }

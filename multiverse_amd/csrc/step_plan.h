@@ -78,6 +78,18 @@ inline BeamStepForm beam_step_form(int K, bool have_cand, bool masked) {
              ? BeamStepForm::Single : BeamStepForm::RankSelect;
 }
 
+// ------------------------------------------------------------------ constrained rows
+// The kernels that hold a row in one wave (beam_rank / sbs_perturb / sample_step) and the two
+// occupancy kernels come in three forms.  Plain: neither a cell mask nor a cell bias.  Masked:
+// mv_set_cell_mask alone, today's MASKED instantiation.  Biased: mv_set_cell_bias, with or without
+// a mask -- ONE instantiation, which takes the allowed bits as the in-row bits when no mask plane
+// is given.  A Masked or Biased beam step is a `masked` one to beam_step_form above: it exists in
+// the two-launch form only.
+enum class RowForm { Plain, Masked, Biased };
+inline RowForm step_row_form(bool masked, bool biased) {
+  return biased ? RowForm::Biased : (masked ? RowForm::Masked : RowForm::Plain);
+}
+
 // ------------------------------------------------------------------ graph attention (forward)
 // PerCell: gnn_attend_kernel, one wave per cell, any shape.  Tiled: gnn_attend_v2_kernel, LDS
 // tiles of 32 cells; its tiling wants W <= 32 and C == 256, and it stages ONE 64-channel scene

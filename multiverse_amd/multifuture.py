@@ -294,6 +294,30 @@ def cell_mask_from_scene(args, scene_onehot_last_frame, allowed_classes, min_sha
   return (count >= need).reshape(h, w)
 
 
+def cell_bias_from_scene(args, scene_onehot_last_frame, class_costs):
+  """The cost of entering each cell of the used grid, from one frame of scene semantics (not in
+  the reference; include/multiverse_hip.h mv_set_cell_bias): scene_onehot_last_frame
+  [scene_h, scene_w, scene_class] one-hot over the NEW class ids, class_costs {class id: cost in
+  nats} (or a list of pairs) -> float32 [h, w],
+    b[cell] = sum over c of cost[c] * share(cell, c)
+  with share(cell, c) the fraction of the cell's pixels of class c, under the pixel-to-cell map
+  of `cell_mask_from_scene` (pixel row i belongs to grid row floor(i * h / H), columns
+  likewise).  A cell that no pixel maps to costs 0."""
+  h, w = args.scene_grids[list(args.use_grids).index(True)]
+  sf = np.asarray(scene_onehot_last_frame)
+  H, W = sf.shape[:2]
+  rows = (np.arange(H) * h) // H
+  cols = (np.arange(W) * w) // W
+  cell = (rows[:, None] * w + cols[None, :]).reshape(-1)
+  total = np.bincount(cell, minlength=h * w).astype(np.float64)
+  b = np.zeros(h * w, dtype=np.float64)
+  for c, cost in (class_costs.items() if hasattr(class_costs, "items") else class_costs):
+    count = np.bincount(cell, weights=(sf[..., int(c)] != 0).reshape(-1).astype(np.float64),
+                        minlength=h * w)
+    b += float(cost) * (count / np.maximum(total, 1.0))
+  return b.reshape(h, w).astype(np.float32)
+
+
 def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_length=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
@@ -312,7 +336,10 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   "cell_mask" [N, K] for the used grid, row n built by `cell_mask_from_scene` from the row's
   LAST observed frame with args.allowed_min_share.  A row with fewer than num_out allowed cells
   gets the all-ones row (a beam of num_out needs that many first cells) and is listed in
-  "cell_mask_fallback" (positions in `idxs`); padding rows get all ones."""
+  "cell_mask_fallback" (positions in `idxs`); padding rows get all ones.
+  args.class_costs (a list of (new scene class id, cost in nats); not in the reference): the feed
+  carries "cell_bias" float32 [N, K], row n built by `cell_bias_from_scene` from the same frame;
+  padding rows get zeros."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
@@ -384,6 +411,14 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
         mask[r] = m
     feed["cell_mask"] = mask
     feed["cell_mask_fallback"] = fallback
+  class_costs = getattr(args, "class_costs", None)
+  if class_costs:
+    h, w = args.scene_grids[list(args.use_grids).index(True)]
+    bias = np.zeros((N, h * w), dtype="float32")
+    for r in range(n_real):
+      last = inputs["scene_feats"][int(np.asarray(inputs["obs_scene"][idxs[r]])[-1][0])]
+      bias[r] = cell_bias_from_scene(args, last, class_costs).reshape(-1)
+    feed["cell_bias"] = bias
   return feed, n_real
 
 

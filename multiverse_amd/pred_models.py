@@ -333,9 +333,9 @@ class Model(object):
   # -- one sess.run ----------------------------------------------------------
   def run_forward(self, feed):
     """-> (grid_pred_class list_s, grid_pred_reg list_s, beam_outputs).  The feed goes to the
-    engine as it is: "pred_lengths", "obs_lengths" and "cell_mask" ([N, K] or [N, Tm, K] allowed
-    cells of a multi-future decode, Engine.set_cell_mask) are set when present, cleared when
-    absent."""
+    engine as it is: "pred_lengths", "obs_lengths", "cell_mask" ([N, K] or [N, Tm, K] allowed
+    cells of a multi-future decode, Engine.set_cell_mask) and "cell_bias" (float32 cell costs of
+    the same shapes, Engine.set_cell_bias) are set when present, cleared when absent."""
     cfg = self.config
     compact = bool(feed.get("compact", False))
     if getattr(cfg, "use_beam_search", False):
@@ -371,7 +371,7 @@ class Model(object):
     {"trajs": float64 [N, B, T, 2]} (B = 1 for a greedy model) and, for a beam-search model,
     "ids" [N, B, T], "logprobs" [N, B], "gumbels" [N, B] when the model samples without
     replacement, "proposal_logprobs" [N, B] when it samples under a top-k / nucleus limit
-    (config.sample_top_k / sample_top_p) or under feed["cell_mask"], and -- with occupancy -- "occupancy" float32 [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
+    (config.sample_top_k / sample_top_p) or under feed["cell_mask"] / feed["cell_bias"], and -- with occupancy -- "occupancy" float32 [N, T, K].  The per-beam logits and the offset maps stay in HBM (logits=True: "logits"
     [N, B, T, K] is fetched as well, for a caller that stores them).  grid_centers: list over
     scales of [H, W, 2] cell centres (default: the feed's, else those already resident)."""
     cfg = self.config
