@@ -850,6 +850,17 @@ int  mv_op_sample_step_biased(int device, const float* logits /* [R, K] */,
 int  mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,
                        int32_t r0, int32_t* lists, int64_t* cells);
 
+/* One level of the scene stack (conv k x k, stride 2, SAME, + b, activation) in either of its
+ * forms: in [U, Hi, Wi, Ci], w [k, k, Ci, Co], b [Co] -> out [U, ceil(Hi/2), ceil(Wi/2), Co].
+ * form 0: the kernel the engine launches for this shape; 1: one thread per output element, the
+ * form every shape can take.  The two give the same bits.  mv_scene_conv_form (host only): the
+ * engine's choice for a shape, 0 = one thread per output, 1 = the 1x1 MFMA projection, 2 = the
+ * tiled k = 3 kernel. */
+int  mv_scene_conv_form(int32_t k, int32_t Ci, int32_t Co);
+int  mv_op_scene_conv(int device, int32_t form, const float* in, const float* w, const float* b,
+                      int32_t U, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t k,
+                      int32_t act, float* out);
+
 /* Backward of one ConvLSTMCell step (tf.gradients through the cell): inputs as
  * mv_op_convlstm_step (c == h == NULL: zero state) plus d h', d c' [M,H,W,C];
  * outputs d x [M,H,W,Cx], d h, d c [M,H,W,C], d kernel [3,3,Cx+C,4C], d biases [4C]. */

@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_train_lengths", "mv_last_train_gate_rows",
     "mv_set_cell_bias", "mv_op_beam_step_biased", "mv_op_sbs_step_biased",
     "mv_op_sample_step_biased",
+    "mv_scene_conv_form", "mv_op_scene_conv",
 ]
 
 
@@ -264,6 +265,9 @@ def load():
                                     _ip, _fp, _fp, _u8p]
   if hasattr(lib, "mv_enc_cone_build"):     # (an A/B build through MV_LIB_PATH may predate it)
     lib.mv_enc_cone_build.argtypes = [_ip] + [C.c_int32] * 5 + [_ip, C.POINTER(C.c_int64)]
+  if hasattr(lib, "mv_op_scene_conv"):      # (as above)
+    lib.mv_scene_conv_form.argtypes = [C.c_int32] * 3
+    lib.mv_op_scene_conv.argtypes = [C.c_int, C.c_int32, _fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]
   lib.mv_op_sbs_step.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, C.c_uint32, _fp, _fp, _fp, _ip, _ip]
   lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
@@ -1521,6 +1525,28 @@ def enc_cone_build(labels, H, W, r0=1):
                            cells.ctypes.data_as(C.POINTER(C.c_int64))) < 0:
     raise MvError("mv_enc_cone_build: a label is not a cell of the %d x %d grid" % (H, W))
   return lists, cells, int(ntile)
+
+
+SCENE_CONV_FORMS = ("per_output", "proj1x1", "tiled")    # SceneConvForm, csrc/step_plan.h
+
+
+def scene_conv_form(k, Ci, Co):
+  """The kernel the engine launches for a level of the scene stack (host only)."""
+  return SCENE_CONV_FORMS[load().mv_scene_conv_form(int(k), int(Ci), int(Co))]
+
+
+def op_scene_conv(x, w, b, act=0, per_output=False, device=0):
+  """One scene-stack level (mv_op_scene_conv): x [U, Hi, Wi, Ci], w [k, k, Ci, Co], b [Co] ->
+  [U, ceil(Hi/2), ceil(Wi/2), Co].  per_output: the one-thread-per-output kernel whatever the
+  shape; otherwise the engine's choice."""
+  lib = load()
+  x, w, b = f32(x), f32(w), f32(b)
+  U, Hi, Wi, Ci = x.shape
+  k, Co = int(w.shape[0]), int(w.shape[3])
+  out = np.empty((U, (Hi + 1) // 2, (Wi + 1) // 2, Co), dtype=np.float32)
+  check(lib.mv_op_scene_conv(device, 1 if per_output else 0, fptr(x), fptr(w), fptr(b), U, Hi,
+                             Wi, Ci, Co, k, int(act), fptr(out)))
+  return out
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,

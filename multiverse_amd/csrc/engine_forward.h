@@ -381,6 +381,31 @@ void run_conv_pairs(mv_engine* e, const std::vector<ConvLstmArgs>& a,
   { IssueOn on(e, 1); issue_gate_group(e, gb, pl); }
 }
 
+// One level of the scene stack in the form scene_conv_form (step_plan.h) chose; the forward, the
+// training forward and mv_op_scene_conv launch through here.
+static_assert(mv::kSceneTileCo == 64 && mv::kSceneTileCiMax == 64,
+              "scene_conv_form states the tiled kernel's channel bounds");
+void launch_scene_conv(hipStream_t stream, SceneConvForm form, const float* in, const float* w,
+                       const float* b, float* out, int U, int Hi, int Wi, int Ci, int Ho, int Wo,
+                       int Co, int k, int pad_t, int pad_l, int act) {
+  const size_t M = (size_t)U * Ho * Wo;
+  switch (form) {
+    case SceneConvForm::Proj1x1:
+      hipLaunchKernelGGL(mv::scene_proj1x1_mfma_kernel, dim3(cdiv(M, 128)), dim3(256), 0, stream,
+                         in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, act);
+      break;
+    case SceneConvForm::Tiled:
+      hipLaunchKernelGGL(mv::scene_conv3_s2_tiled_kernel, dim3(cdiv(M, mv::kSceneTilePix)),
+                         dim3(256), 0, stream, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, pad_t, pad_l,
+                         act);
+      break;
+    case SceneConvForm::PerOutput:
+      hipLaunchKernelGGL(mv::scene_conv_s2_tanh_kernel, dim3(cdiv(M * Co, 256)), dim3(256), 0,
+                         stream, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, k, pad_t, pad_l, act);
+      break;
+  }
+}
+
 // mean_lens (the training step's per-row observation lengths, engine_train.h): the window of
 // the scene mean when the forward's own obs plan is not in force
 void run_scene(mv_engine* e, const int32_t* mean_lens = nullptr) {
@@ -396,19 +421,19 @@ void run_scene(mv_engine* e, const int32_t* mean_lens = nullptr) {
     const size_t total = (size_t)U * Ho * Wo * Co;
     float* out = e->scene_conv[i].p;
     const float *w = e->scene_W[i]->dev.p, *b = e->scene_b[i]->dev.p;
-    if (k == 1 && Co <= 64) {     // --scene_conv_kernel 1: the dense 1x1 projection, on MFMA
+    const SceneConvForm form = scene_conv_form(k, Ci, Co);
+    if (form == SceneConvForm::Proj1x1) {     // --scene_conv_kernel 1: the dense 1x1 projection, on MFMA
       const size_t M = (size_t)U * Ho * Wo;
       launch(e, "scene_proj1x1_mfma", 2.0 * M * Ci * Co,
              4.0 * (total + (double)M * Ci), [&] {
-        hipLaunchKernelGGL(mv::scene_proj1x1_mfma_kernel, dim3(cdiv(M, 128)), dim3(256), 0,
-                           e->issue, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, c.activation);
+        launch_scene_conv(e->issue, form, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, k, 0, 0,
+                          c.activation);
       });
     } else {
     launch(e, "scene_conv_s2_tanh", 2.0 * total * k * k * Ci,
            4.0 * (total + (double)U * Hi * Wi * Ci), [&] {
-      hipLaunchKernelGGL(mv::scene_conv_s2_tanh_kernel, dim3(cdiv(total, 256)),
-                         dim3(256), 0, e->issue, in, w, b, out, U, Hi, Wi, Ci,
-                         Ho, Wo, Co, k, pad_h / 2, pad_w / 2, c.activation);
+      launch_scene_conv(e->issue, form, in, w, b, out, U, Hi, Wi, Ci, Ho, Wo, Co, k, pad_h / 2,
+                        pad_w / 2, c.activation);
     });
     }
     in = out; Hi = Ho; Wi = Wo; Ci = Co;

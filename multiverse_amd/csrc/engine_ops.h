@@ -464,6 +464,39 @@ int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, in
   return enc_cone_tiles(N + 1, H, W);
 }
 
+// ---- the scene stack's convolution in either of its forms (tests/test_gpu_helper_forms.py)
+
+int mv_scene_conv_form(int32_t k, int32_t Ci, int32_t Co) {
+  return (int)scene_conv_form(k, Ci, Co);
+}
+
+int mv_op_scene_conv(int device, int32_t form, const float* in, const float* w, const float* b,
+                     int32_t U, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t k,
+                     int32_t act, float* out) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(in && w && b && out, "mv_op_scene_conv: NULL argument");
+    MV_REQUIRE(U >= 1 && Hi >= 1 && Wi >= 1 && Ci >= 1 && Co >= 1 && k >= 1,
+               "mv_op_scene_conv: bad shape");
+    MV_REQUIRE(act >= 0 && act <= 2, "mv_op_scene_conv: activation %d", (int)act);
+    MV_REQUIRE(form == 0 || form == 1, "mv_op_scene_conv: form %d (0 = the plan's, 1 = one thread "
+               "per output)", (int)form);
+    const SceneConvForm f = form == 1 ? SceneConvForm::PerOutput : scene_conv_form(k, Ci, Co);
+    OpCtx ctx(device);
+    const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;      // SAME, stride 2
+    const int pad_h = std::max((Ho - 1) * 2 + k - Hi, 0), pad_w = std::max((Wo - 1) * 2 + k - Wi, 0);
+    DevBuf<float> di, dw, db, dout;
+    ctx.up(di, in, (size_t)U * Hi * Wi * Ci);
+    ctx.up(dw, w, (size_t)k * k * Ci * Co);
+    ctx.up(db, b, (size_t)Co);
+    const size_t total = (size_t)U * Ho * Wo * Co;
+    dout.alloc(total);
+    launch_scene_conv(ctx.stream, f, di.p, dw.p, db.p, dout.p, U, Hi, Wi, Ci, Ho, Wo, Co, k,
+                      pad_h / 2, pad_w / 2, act);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(out, dout, total);
+  });
+}
+
 int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* h,
                        const float* kernel, const float* biases, const float* dh_new,
                        const float* dc_new, int32_t M, int32_t H, int32_t W, int32_t Cx,

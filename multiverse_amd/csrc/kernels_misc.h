@@ -89,6 +89,108 @@ __global__ void scene_conv_s2_tanh_kernel(const float* __restrict__ in,
   out[idx] = act_apply(act, acc + b[co]);
 }
 
+// The same convolution for k = 3, tiled (step_plan.h scene_conv_form decides).
+// The kernel above walks one dependent fmaf chain per thread with a global input load and a
+// strided global weight load in every link: its time is chain length x load latency.  Here a
+// workgroup owns kSceneTilePix consecutive output pixels (flat over u, oy, ox) x all 64 output
+// channels; thread = (pixel ps = tid / 16, channel quad cq = tid % 16), four adjacent co, so four
+// independent chains per thread.  Per tap (ky, kx) the workgroup stages the tap's weights
+// [Ci][64] and the 16 pixels' input vectors [Ci] in LDS -- the next tap's loads are issued into
+// registers before the current tap is computed -- and every thread whose pixel has the tap in
+// the image walks ci: one LDS broadcast read of the input, one 16-byte LDS read of the weights,
+// four fmaf.  Each output's chain is the one of the kernel above: from 0.f, taps in ky, kx
+// order, ci ascending, taps outside the image skipped, + b[co], act_apply: the same bits.
+constexpr int kSceneTilePix = 16;      // output pixels per workgroup
+constexpr int kSceneTileCo = 64;       // output channels: 16 threads x 4
+constexpr int kSceneTileCiMax = 64;    // LDS: weights Ci x 64 floats (<= 16 KB) + inputs 16 x (Ci + 1)
+__global__ __launch_bounds__(256)
+void scene_conv3_s2_tiled_kernel(const float* __restrict__ in, const float* __restrict__ w,
+                                 const float* __restrict__ b, float* __restrict__ out, int U,
+                                 int Hi, int Wi, int Ci, int Ho, int Wo, int pad_t, int pad_l,
+                                 int act) {
+  constexpr int TP = kSceneTilePix, CO = kSceneTileCo, CIM = kSceneTileCiMax;
+  constexpr int NX = TP * CIM / 256;             // staged input floats per thread, at most
+  constexpr int NW = CIM * CO / 4 / 256;         // staged weight quads per thread, at most
+  __shared__ __attribute__((aligned(16))) float wl[CIM * CO];
+  __shared__ float xl[TP * (CIM + 1)];
+  const int tid = threadIdx.x, cq = tid & 15, ps = tid >> 4;
+  const int M = U * Ho * Wo;
+  const int m0 = blockIdx.x * TP;
+  // the thread's own pixel
+  const int m = m0 + ps;
+  int oy2 = 0, ox2 = 0;
+  if (m < M) {
+    const int ox = m % Wo, oy = (m / Wo) % Ho;
+    oy2 = oy * 2 - pad_t; ox2 = ox * 2 - pad_l;
+  }
+  // the input elements this thread stages: element i = tid + 256 j is (pixel i / Ci, ci i % Ci)
+  int sy2[NX], sx2[NX], sdst[NX];
+  size_t sbase[NX];
+  bool son[NX];
+#pragma unroll
+  for (int j = 0; j < NX; ++j) {
+    const int i = tid + 256 * j;
+    const int sp = i / Ci, sc = i - sp * Ci;
+    const int sm = m0 + sp;
+    son[j] = i < TP * Ci && sm < M;
+    sy2[j] = sx2[j] = 0; sbase[j] = 0; sdst[j] = 0;
+    if (son[j]) {
+      const int ox = sm % Wo, r = sm / Wo, oy = r % Ho, u = r / Ho;
+      sy2[j] = oy * 2 - pad_t; sx2[j] = ox * 2 - pad_l;
+      sbase[j] = (size_t)u * Hi * Wi * Ci + sc;
+      sdst[j] = sp * (Ci + 1) + sc;
+    }
+  }
+  const int nwq = Ci * (CO / 4);                 // weight quads of one tap
+  float xr[NX];
+  f32x4_t wr[NW];
+  auto fetch = [&](int tap) {
+    const int ky = tap / 3, kx = tap - ky * 3;
+#pragma unroll
+    for (int j = 0; j < NX; ++j) {
+      const int iy = sy2[j] + ky, ix = sx2[j] + kx;
+      xr[j] = (son[j] && iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
+                  ? in[sbase[j] + ((size_t)iy * Wi + ix) * Ci] : 0.f;
+    }
+    const f32x4_t* wg = reinterpret_cast<const f32x4_t*>(w + (size_t)tap * Ci * CO);
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+      if (tid + 256 * j < nwq) wr[j] = wg[tid + 256 * j];
+  };
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  fetch(0);
+  for (int tap = 0; tap < 9; ++tap) {
+    if (tap) __syncthreads();                    // the previous tap's reads of LDS are done
+#pragma unroll
+    for (int j = 0; j < NX; ++j)
+      if (son[j]) xl[sdst[j]] = xr[j];
+#pragma unroll
+    for (int j = 0; j < NW; ++j)
+      if (tid + 256 * j < nwq) reinterpret_cast<f32x4_t*>(wl)[tid + 256 * j] = wr[j];
+    __syncthreads();
+    if (tap + 1 < 9) fetch(tap + 1);
+    const int ky = tap / 3, kx = tap - ky * 3;
+    const int iy = oy2 + ky, ix = ox2 + kx;
+    if (m < M && iy >= 0 && iy < Hi && ix >= 0 && ix < Wi) {
+      const float* xp = xl + ps * (Ci + 1);
+      const f32x4_t* wp = reinterpret_cast<const f32x4_t*>(wl) + cq;
+#pragma unroll 8
+      for (int ci = 0; ci < Ci; ++ci) {
+        const float xv = xp[ci];
+        const f32x4_t wv = wp[ci * (CO / 4)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = fmaf(xv, wv[j], acc[j]);
+      }
+    }
+  }
+  if (m >= M) return;
+  const f32x4_t bv = reinterpret_cast<const f32x4_t*>(b)[cq];
+  f32x4_t o;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o[j] = act_apply(act, acc[j] + bv[j]);
+  reinterpret_cast<f32x4_t*>(out + (size_t)m * CO)[cq] = o;
+}
+
 // --scene_conv_kernel 1 (code/train.py:65, conv2d code/pred_models.py:155-165): the scene
 // stack degenerates to a strided 1x1 projection, a true dense GEMM
 //   out[(u, oy, ox)][co] = tanh(sum_ci in[u, 2 oy, 2 ox, ci] W[ci][co] + b[co])

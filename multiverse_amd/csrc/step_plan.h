@@ -149,6 +149,19 @@ inline TailForm tail_form(bool training, int E, int Kmax) {
   return TailForm::Grouped;
 }
 
+// ------------------------------------------------------------------ scene stack
+// Proj1x1: scene_proj1x1_mfma_kernel, --scene_conv_kernel 1 with at most 64 output channels.
+// Tiled: scene_conv3_s2_tiled_kernel -- k = 3 with exactly the 64 output channels its 16 x 4
+// thread map covers, and Ci <= 64: a tap's weights Ci x 64 floats (16 KB) and the 16 pixels'
+// inputs stay inside its static LDS.  PerOutput: scene_conv_s2_tanh_kernel, every other shape.
+// All three compute the same bits where they overlap.
+enum class SceneConvForm { PerOutput, Proj1x1, Tiled };
+inline SceneConvForm scene_conv_form(int k, int Ci, int Co) {
+  if (k == 1 && Co <= 64) return SceneConvForm::Proj1x1;
+  if (k == 3 && Co == 64 && Ci >= 1 && Ci <= 64) return SceneConvForm::Tiled;
+  return SceneConvForm::PerOutput;
+}
+
 // ------------------------------------------------------------------ chain pairs of the greedy forward
 // The four chains of a greedy forward (class / regression x two scales) exchange nothing between
 // the scene stage and the end of the decode, and want different things from the chip: a gate
