@@ -861,6 +861,40 @@ int  mv_op_scene_conv(int device, int32_t form, const float* in, const float* w,
                       int32_t U, int32_t Hi, int32_t Wi, int32_t Ci, int32_t Co, int32_t k,
                       int32_t act, float* out);
 
+/* The decoder tail of one step (hidden2grid, argmax, the next step's input embedding and its
+ * operand planes) for 1 to 4 chains in one call, in either of its forms.  The chains share C
+ * (128, 256 or 512), E (a multiple of 16) and the activation (0 tanh, 1 relu, 2 lrelu); each has
+ * its own rows, H, W and kind.
+ *   form   0: the grouped tail -- the weights packed, ONE h2g_q launch and ONE decode_tail launch
+ *             for all chains, as a decode step issues them; a grid of more than 1024 cells or an
+ *             E above 512 is refused and nothing is launched.
+ *          1: the separate tail, per chain hidden2grid_kernel, argmax_rows_kernel,
+ *             grid_emb_onehot_kernel (class) / grid_emb_dense_kernel (regression);
+ *          2: as 1 with grid_emb_onehot8_kernel for the class embedding;
+ *          3: as 1 with grid_emb_dense_kernel on the literal one-hot map for the class embedding.
+ *   next   0: no next step (output rows only); 1: ids only (class chains); 2: ids and embedding.
+ *   planes 0: none; 1: two fp16 planes (f16x3); 2: one bf16 plane -- of x, with next == 2.
+ * Every device buffer behind ids, x and planes is filled with the byte 0xA5 before the launches
+ * and copied back whole, so a caller sees what was not written.  `planes` receives the plane
+ * buffer as an engine allocates it: planes_elems = 2 * (rows*K*E + 32768 + 16) halves, plane 0
+ * at half 16, plane 1 (f16x3) at half 16 + planes_elems / 2; the layout inside a plane is
+ * csrc/plane_layout.h. */
+typedef struct mv_tail_chain {
+  int32_t rows, H, W;
+  int32_t kind;              /* 0: class chain (P = 1, one-hot); 1: regression chain (P = 2, dense) */
+  const float* h;            /* [rows, H, W, C] */
+  const float* w_out;        /* hidden2grid [3, 3, C, P] */
+  const float* emb_w;        /* [3, 3, P, E]; may be NULL unless next == 2 */
+  const float* emb_b;        /* [E]; likewise */
+  float* out;                /* [rows, K, P] */
+  int32_t* ids;              /* [rows]; may be NULL (always for a regression chain) */
+  float* x;                  /* [rows * K, E]; may be NULL */
+  uint16_t* planes;          /* [planes_elems]; may be NULL */
+  int64_t planes_elems;
+} mv_tail_chain;
+int  mv_op_decode_tail(int device, int32_t form, int32_t next, int32_t planes, int32_t C,
+                       int32_t E, int32_t act, const mv_tail_chain* chains, int32_t n);
+
 /* Backward of one ConvLSTMCell step (tf.gradients through the cell): inputs as
  * mv_op_convlstm_step (c == h == NULL: zero state) plus d h', d c' [M,H,W,C];
  * outputs d x [M,H,W,Cx], d h, d c [M,H,W,C], d kernel [3,3,Cx+C,4C], d biases [4C]. */

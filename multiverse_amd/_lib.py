@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = [
     "mv_set_cell_bias", "mv_op_beam_step_biased", "mv_op_sbs_step_biased",
     "mv_op_sample_step_biased",
     "mv_scene_conv_form", "mv_op_scene_conv",
+    "mv_op_decode_tail",
 ]
 
 
@@ -150,6 +151,15 @@ class mv_score_futures_in(C.Structure):
 
 class mv_score_outputs(C.Structure):
   _fields_ = [("step_logprobs", _fp), ("logprobs", _fp), ("ranks", _ip)]
+
+
+class mv_tail_chain(C.Structure):
+  _fields_ = [
+      ("rows", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("kind", C.c_int32),
+      ("h", _fp), ("w_out", _fp), ("emb_w", _fp), ("emb_b", _fp),
+      ("out", _fp), ("ids", _ip), ("x", _fp), ("planes", C.POINTER(C.c_uint16)),
+      ("planes_elems", C.c_int64),
+  ]
 
 
 class mv_train_config(C.Structure):
@@ -268,6 +278,9 @@ def load():
   if hasattr(lib, "mv_op_scene_conv"):      # (as above)
     lib.mv_scene_conv_form.argtypes = [C.c_int32] * 3
     lib.mv_op_scene_conv.argtypes = [C.c_int, C.c_int32, _fp, _fp, _fp] + [C.c_int32] * 7 + [_fp]
+  if hasattr(lib, "mv_op_decode_tail"):     # (as above)
+    lib.mv_op_decode_tail.argtypes = [C.c_int] + [C.c_int32] * 6 + [C.POINTER(mv_tail_chain),
+                                                                    C.c_int32]
   lib.mv_op_sbs_step.argtypes = [C.c_int, _fp, _fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32,
                                  C.c_int32, C.c_float, C.c_uint32, _fp, _fp, _fp, _ip, _ip]
   lib.mv_score_futures.argtypes = [h, C.POINTER(mv_inputs), C.POINTER(mv_score_futures_in),
@@ -1547,6 +1560,71 @@ def op_scene_conv(x, w, b, act=0, per_output=False, device=0):
   check(lib.mv_op_scene_conv(device, 1 if per_output else 0, fptr(x), fptr(w), fptr(b), U, Hi,
                              Wi, Ci, Co, k, int(act), fptr(out)))
   return out
+
+
+# mv_op_decode_tail: the plane buffer of an [M, E] operand as an engine allocates it
+# (csrc/plane_layout.h kPlaneSlack, csrc/convlstm_f16x3.h kPlanePad; the call refuses any other
+# size) and the byte every output buffer holds before the launches
+PLANE_SLACK, PLANE_PAD = 32 * 1024, 16
+OP_SENTINEL_BYTE = 0xA5
+TAIL_NEXT = {"none": 0, "ids": 1, "embed": 2}
+TAIL_PLANES = {None: 0, "f16x3": 1, "bf16": 2}
+TAIL_FORMS = {False: 0, True: 1, "onehot8": 2, "dense": 3}
+
+
+def plane_buffer_elems(M, E):
+  return 2 * (int(M) * int(E) + PLANE_SLACK + PLANE_PAD)
+
+
+def op_decode_tail(chains, act=0, next="embed", planes=None, separate=False, device=0):
+  """The decoder tail of one step for 1 to 4 chains in one call (mv_op_decode_tail).  chains:
+  dicts with kind ("cls": P = 1, one-hot; "reg": P = 2, dense), h [rows, H, W, C], w_out
+  [3, 3, C, P], emb_w [3, 3, P, E], emb_b [E].  next: "none" (output rows only), "ids" (argmax
+  without embedding) or "embed".  planes: None, "f16x3" (two fp16 planes) or "bf16" (one).
+  separate: False = the grouped tail (h2g_q + decode_tail, one launch each for all chains); True =
+  the separate tail's kernels per chain; "onehot8" / "dense" = the separate tail with the class
+  embedding by grid_emb_onehot8_kernel / by grid_emb_dense_kernel on the literal one-hot map.
+  Returns per chain a dict: out [rows, K, P]; ids [rows] (class chains); x [rows * K, E]; planes,
+  the whole raw uint16 plane buffer (plane_buffer_elems; plane 0 at PLANE_PAD, plane 1 half the
+  buffer further), when planes is not None.  Whatever the call did not write holds
+  OP_SENTINEL_BYTE in every byte."""
+  lib = load()
+  n = len(chains)
+  arr = (mv_tail_chain * max(n, 1))()
+  keep, res = [], []
+  C_, E = None, None
+  for i, ch in enumerate(chains):
+    cls = {"cls": True, "reg": False}[ch["kind"]]
+    P = 1 if cls else 2
+    h, w = f32(ch["h"]), f32(ch["w_out"])
+    ew, eb = f32(ch["emb_w"]), f32(ch["emb_b"])
+    rows, H, W, Ch = h.shape
+    if w.shape != (3, 3, Ch, P) or ew.shape[:3] != (3, 3, P) or eb.shape != (ew.shape[3],):
+      raise MvError("op_decode_tail: chain %d: weight shapes %r %r %r" % (i, w.shape, ew.shape,
+                                                                         eb.shape))
+    if (C_, E) not in ((None, None), (Ch, ew.shape[3])):
+      raise MvError("op_decode_tail: the chains of a call share C and E")
+    C_, E = Ch, int(ew.shape[3])
+    K = H * W
+    out = np.empty((rows, K, P), dtype=np.float32)
+    x = np.empty((rows * K, E), dtype=np.float32)
+    r = {"out": out, "x": x}
+    a = arr[i]
+    a.rows, a.H, a.W, a.kind = rows, H, W, 0 if cls else 1
+    a.h, a.w_out, a.emb_w, a.emb_b = fptr(h), fptr(w), fptr(ew), fptr(eb)
+    a.out, a.x = fptr(out), fptr(x)
+    if cls:
+      r["ids"] = np.empty(rows, dtype=np.int32)
+      a.ids = iptr(r["ids"])
+    if planes is not None:
+      r["planes"] = np.empty(plane_buffer_elems(rows * K, E), dtype=np.uint16)
+      a.planes = r["planes"].ctypes.data_as(C.POINTER(C.c_uint16))
+      a.planes_elems = r["planes"].size
+    keep.append((h, w, ew, eb))
+    res.append(r)
+  check(lib.mv_op_decode_tail(device, TAIL_FORMS[separate], TAIL_NEXT[next], TAIL_PLANES[planes],
+                              int(C_ or 0), int(E or 0), int(act), arr, n))
+  return res
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,

@@ -808,6 +808,27 @@ struct TailPlan {
   bool do_cls = true, do_reg = true;
 };
 
+// What every filler of a grouped tail launch (run_tail, mv_op_decode_tail) sets: the refusal of a
+// shape the tail does not fit, a chain's problem without a next step, and the next step's
+// embedding with its operand planes (x16 null: none; pst 0 with x16: the single bf16 plane).
+void require_tail_fits(int E, int K) {
+  MV_REQUIRE(tail_grouped_fits(E, K), "decode tail: K %d / emb_size %d", K, E);
+}
+mv::TailProblem tail_problem(const float* q, float* out, int64_t out_row_stride, int rows, int H,
+                             int W, bool cls, int E, int act) {
+  mv::TailProblem a{};
+  a.q = q; a.out = out; a.out_row_stride = out_row_stride;
+  a.rows = rows; a.H = H; a.W = W; a.P = cls ? 1 : 2; a.E = E; a.onehot = cls ? 1 : 0;
+  a.act = act;
+  return a;
+}
+void tail_embed(mv::TailProblem& a, const float* emb_w, const float* emb_b, float* x_out,
+                _Float16* x16 = nullptr, size_t pst = 0) {
+  a.emb_w = emb_w; a.emb_b = emb_b;
+  a.x_out = x_out;
+  a.x16 = x16; a.x16_stride = (int64_t)pst;
+}
+
 void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
   const mv_config& c = e->cfg;
   const int C = c.hidden_size, E = c.emb_size, N = c.batch_size;
@@ -816,7 +837,7 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
   double qbytes = 0, qflops = 0, tbytes = 0;
   for (const TailPlan& pl : plans) {
     ScaleState& S = e->sc[pl.s];
-    MV_REQUIRE(tail_grouped_fits(E, S.K), "decode tail: K %d / emb_size %d", S.K, E);
+    require_tail_fits(E, S.K);
     const int reg_rows = pl.reg_rows ? pl.reg_rows : N;
     const size_t cc = (size_t)pl.cls_rows * S.K, cr = (size_t)reg_rows * S.K;
     if (pl.do_cls) {
@@ -830,45 +851,38 @@ void run_tail(mv_engine* e, const std::vector<TailPlan>& plans) {
       qflops += 2.0 * 9 * C * 2.0 * cr;
     }
     if (pl.do_cls) {
-    mv::TailProblem a{};
-    a.q = S.q_cls.p; a.out = pl.cls_out; a.out_row_stride = pl.cls_stride;
-    a.rows = pl.cls_rows; a.H = S.H; a.W = S.W; a.P = 1; a.E = E; a.onehot = 1;
-    a.act = c.activation;
-    tbytes += 4.0 * cc * (9 + 1);
-    if (pl.cls_next) {
-      a.ids_out = pl.cls_ids_out ? pl.cls_ids_out : S.ids.p;
-      if (pl.cls_x_out) {           // training: fp32 embedding into the time-major x buffer
-        if (pl.cls_embed) {
-          a.emb_w = S.emb_cls_W->dev.p; a.emb_b = S.emb_cls_b->dev.p;
-          a.x_out = pl.cls_x_out;
-          tbytes += 4.0 * cc * E;
+      mv::TailProblem a = tail_problem(S.q_cls.p, pl.cls_out, pl.cls_stride, pl.cls_rows, S.H, S.W,
+                                       true, E, c.activation);
+      tbytes += 4.0 * cc * (9 + 1);
+      if (pl.cls_next) {
+        a.ids_out = pl.cls_ids_out ? pl.cls_ids_out : S.ids.p;
+        if (pl.cls_x_out) {           // training: fp32 embedding into the time-major x buffer
+          if (pl.cls_embed) {
+            tail_embed(a, S.emb_cls_W->dev.p, S.emb_cls_b->dev.p, pl.cls_x_out);
+            tbytes += 4.0 * cc * E;
+          }
+        } else if (!sparse_x_on(e, S)) {     // sparse x: the next step needs the id, not the embedding
+          size_t pst = 0;
+          _Float16* x16 = e->plane_out(S.xbuf_cls.p, &pst);
+          tail_embed(a, S.emb_cls_W->dev.p, S.emb_cls_b->dev.p, S.xbuf_cls.p, x16, pst);
+          tbytes += 4.0 * cc * E * (a.x16 ? 2 : 1);
         }
-      } else if (!sparse_x_on(e, S)) {     // sparse x: the next step needs the id, not the embedding
-        size_t pst = 0;
-        a.emb_w = S.emb_cls_W->dev.p; a.emb_b = S.emb_cls_b->dev.p;
-        a.x_out = S.xbuf_cls.p;
-        a.x16 = e->plane_out(S.xbuf_cls.p, &pst); a.x16_stride = (int64_t)pst;
-        tbytes += 4.0 * cc * E * (a.x16 ? 2 : 1);
       }
-    }
-    tp.push_back(a);
+      tp.push_back(a);
     }
     if (!pl.do_reg) continue;
-    mv::TailProblem b{};
-    b.q = S.q_reg.p; b.out = pl.reg_out; b.out_row_stride = pl.reg_stride;
-    b.rows = reg_rows; b.H = S.H; b.W = S.W; b.P = 2; b.E = E; b.onehot = 0;
-    b.act = c.activation;
+    mv::TailProblem b = tail_problem(S.q_reg.p, pl.reg_out, pl.reg_stride, reg_rows, S.H, S.W,
+                                     false, E, c.activation);
     tbytes += 4.0 * cr * (18 + 2);
     if (pl.reg_next) {
-      size_t pst = 0;
-      b.emb_w = S.emb_reg_W->dev.p; b.emb_b = S.emb_reg_b->dev.p;
       if (pl.reg_x_out) {
-        b.x_out = pl.reg_x_out;
+        tail_embed(b, S.emb_reg_W->dev.p, S.emb_reg_b->dev.p, pl.reg_x_out);
         tbytes += 4.0 * cr * E;
       } else {
-      b.x_out = S.xbuf_reg.p;
-      b.x16 = e->plane_out(S.xbuf_reg.p, &pst); b.x16_stride = (int64_t)pst;
-      tbytes += 4.0 * cr * E * (b.x16 ? 2 : 1);
+        size_t pst = 0;
+        _Float16* x16 = e->plane_out(S.xbuf_reg.p, &pst);
+        tail_embed(b, S.emb_reg_W->dev.p, S.emb_reg_b->dev.p, S.xbuf_reg.p, x16, pst);
+        tbytes += 4.0 * cr * E * (b.x16 ? 2 : 1);
       }
     }
     tp.push_back(b);

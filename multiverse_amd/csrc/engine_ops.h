@@ -497,6 +497,161 @@ int mv_op_scene_conv(int device, int32_t form, const float* in, const float* w, 
   });
 }
 
+// ---- the decoder tail of one step in either of its forms (tests/test_gpu_decode_tail.py):
+// grouped through the engine's own pack_h2g_kernel, launch_h2g_q and launch_decode_tail on
+// problems filled by run_tail's helpers, or the separate tail's kernels chain by chain
+
+namespace {
+struct TailChainDev {
+  DevBuf<float> h, w, wq, q, ew, eb, out, x, hot;
+  DevBuf<int32_t> ids;
+  DevBuf<_Float16> pl;
+  _Float16* p0 = nullptr;       // plane 0 (null: no planes) and the stride the kernels are given
+  size_t pst = 0;
+};
+constexpr int kOpSentinel = 0xA5;     // the byte every output buffer holds before the launches
+}  // namespace
+
+int mv_op_decode_tail(int device, int32_t form, int32_t next, int32_t planes, int32_t C,
+                      int32_t E, int32_t act, const mv_tail_chain* chains, int32_t n) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(chains && n >= 1 && n <= mv::kTailMax, "mv_op_decode_tail: 1 to %d chains, not %d",
+               mv::kTailMax, (int)n);
+    MV_REQUIRE(C == 128 || C == 256 || C == 512, "mv_op_decode_tail: C %d not 128, 256 or 512",
+               (int)C);
+    MV_REQUIRE(E >= 16 && E % 16 == 0, "mv_op_decode_tail: E %d must be a multiple of 16", (int)E);
+    MV_REQUIRE(act >= 0 && act <= 2, "mv_op_decode_tail: activation %d", (int)act);
+    MV_REQUIRE(form >= 0 && form <= 3, "mv_op_decode_tail: form %d (0 grouped, 1 separate, 2 "
+               "separate with the 8-channel one-hot embedding, 3 separate with the dense embedding "
+               "of the one-hot map)", (int)form);
+    MV_REQUIRE(next >= 0 && next <= 2, "mv_op_decode_tail: next %d (0 none, 1 ids only, 2 ids and "
+               "embedding)", (int)next);
+    MV_REQUIRE(planes >= 0 && planes <= 2, "mv_op_decode_tail: planes %d (0 none, 1 f16x3, 2 bf16)",
+               (int)planes);
+    // every refusal comes before the first launch
+    for (int i = 0; i < n; ++i) {
+      const mv_tail_chain& ch = chains[i];
+      MV_REQUIRE(ch.rows >= 1 && ch.H >= 1 && ch.W >= 1 && (ch.kind == 0 || ch.kind == 1),
+                 "mv_op_decode_tail: chain %d: bad shape or kind", i);
+      MV_REQUIRE((int64_t)ch.rows * ch.H * ch.W * std::max(C, E) < ((int64_t)1 << 31),
+                 "mv_op_decode_tail: chain %d: too large for an op call", i);
+      MV_REQUIRE(ch.h && ch.w_out && ch.out, "mv_op_decode_tail: chain %d: NULL h, w_out or out", i);
+      MV_REQUIRE(next < 2 || (ch.emb_w && ch.emb_b), "mv_op_decode_tail: chain %d: next == 2 "
+                 "needs emb_w and emb_b", i);
+      if (form == 0) require_tail_fits(E, ch.H * ch.W);
+      if (ch.planes) {
+        const int64_t want = 2 * ((int64_t)ch.rows * ch.H * ch.W * E + (int64_t)mv::kPlaneSlack +
+                                  mv::kPlanePad);
+        MV_REQUIRE(ch.planes_elems == want, "mv_op_decode_tail: chain %d: planes_elems %lld, the "
+                   "engine allocates %lld", i, (long long)ch.planes_elems, (long long)want);
+      }
+    }
+    OpCtx ctx(device);
+    TailChainDev dv[mv::kTailMax];
+    for (int i = 0; i < n; ++i) {
+      const mv_tail_chain& ch = chains[i];
+      TailChainDev& d = dv[i];
+      const int P = ch.kind == 0 ? 1 : 2;
+      const size_t cells = (size_t)ch.rows * ch.H * ch.W;
+      ctx.up(d.h, ch.h, cells * C);
+      ctx.up(d.w, ch.w_out, (size_t)9 * C * P);
+      if (ch.emb_w) ctx.up(d.ew, ch.emb_w, (size_t)9 * P * E);
+      if (ch.emb_b) ctx.up(d.eb, ch.emb_b, (size_t)E);
+      d.out.alloc(cells * P); d.x.alloc(cells * E); d.ids.alloc(ch.rows);
+      HIP_CHECK(hipMemsetAsync(d.out.p, kOpSentinel, cells * P * sizeof(float), ctx.stream));
+      HIP_CHECK(hipMemsetAsync(d.x.p, kOpSentinel, cells * E * sizeof(float), ctx.stream));
+      HIP_CHECK(hipMemsetAsync(d.ids.p, kOpSentinel, ch.rows * sizeof(int32_t), ctx.stream));
+      if (ch.planes) {     // [pad | plane 0 | slack][pad | plane 1 | slack], as mv_create lays it out
+        const size_t pst = cells * E + mv::kPlaneSlack + mv::kPlanePad;
+        d.pl.alloc(2 * pst);
+        HIP_CHECK(hipMemsetAsync(d.pl.p, kOpSentinel, 2 * pst * sizeof(_Float16), ctx.stream));
+        if (planes != 0 && next == 2) {
+          d.p0 = d.pl.p + mv::kPlanePad;
+          d.pst = planes == 2 ? 0 : pst;        // bf16: the single plane (stride 0)
+        }
+      }
+    }
+    if (form == 0) {
+      std::vector<mv::H2gQProblem> qp;
+      std::vector<mv::TailProblem> tp;
+      for (int i = 0; i < n; ++i) {
+        const mv_tail_chain& ch = chains[i];
+        TailChainDev& d = dv[i];
+        const bool cls = ch.kind == 0;
+        const int P = cls ? 1 : 2, K = ch.H * ch.W;
+        d.wq.alloc((size_t)C * 32); d.q.alloc((size_t)ch.rows * K * 9 * P);
+        hipLaunchKernelGGL(mv::pack_h2g_kernel, dim3(cdiv((size_t)C * 32, 256)), dim3(256), 0,
+                           ctx.stream, d.w.p, d.wq.p, C, P);
+        qp.push_back(mv::H2gQProblem{d.h.p, d.wq.p, d.q.p, (int32_t)(ch.rows * K), P});
+        mv::TailProblem a = tail_problem(d.q.p, d.out.p, (int64_t)K * P, ch.rows, ch.H, ch.W, cls,
+                                         E, act);
+        if (cls && next >= 1) a.ids_out = d.ids.p;
+        if (next == 2) tail_embed(a, d.ew.p, d.eb.p, d.x.p, d.p0, d.pst);
+        tp.push_back(a);
+      }
+      mv::launch_h2g_q(qp.data(), n, C, ctx.stream);
+      mv::launch_decode_tail(tp.data(), n, ctx.stream);
+      HIP_CHECK(hipGetLastError());
+    } else {
+      for (int i = 0; i < n; ++i) {
+        const mv_tail_chain& ch = chains[i];
+        TailChainDev& d = dv[i];
+        const bool cls = ch.kind == 0;
+        const int K = ch.H * ch.W;
+        const size_t cells = (size_t)ch.rows * K, total = cells * E;
+        if (cls)
+          hipLaunchKernelGGL(mv::hidden2grid_kernel<1>, dim3(cdiv(cells, 4)), dim3(256), 0,
+                             ctx.stream, d.h.p, d.w.p, d.out.p, (size_t)K, ch.rows, ch.H, ch.W, C);
+        else
+          hipLaunchKernelGGL(mv::hidden2grid_kernel<2>, dim3(cdiv(cells, 4)), dim3(256), 0,
+                             ctx.stream, d.h.p, d.w.p, d.out.p, (size_t)K * 2, ch.rows, ch.H, ch.W,
+                             C);
+        if (cls && next >= 1)
+          hipLaunchKernelGGL(mv::argmax_rows_kernel, dim3(ch.rows), dim3(64), 0, ctx.stream,
+                             d.out.p, (size_t)K, d.ids.p, ch.rows, K);
+        HIP_CHECK(hipGetLastError());
+        if (next < 2) continue;
+        if (!cls) {
+          hipLaunchKernelGGL(mv::grid_emb_dense_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
+                             ctx.stream, d.out.p, (size_t)K * 2, d.ew.p, d.eb.p, d.x.p, ch.rows,
+                             ch.H, ch.W, 2, E, d.p0, d.pst, act);
+        } else if (form == 1) {
+          hipLaunchKernelGGL(mv::grid_emb_onehot_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
+                             ctx.stream, d.ids.p, 1, 1, d.ew.p, d.eb.p, d.x.p, ch.rows, ch.H, ch.W,
+                             E, d.p0, d.pst, act);
+        } else if (form == 2) {
+          hipLaunchKernelGGL(mv::grid_emb_onehot8_kernel, dim3(cdiv(total / 8, 256)), dim3(256), 0,
+                             ctx.stream, d.ids.p, 1, 1, d.ew.p, d.eb.p, d.x.p, ch.rows, ch.H, ch.W,
+                             E, d.p0, d.pst, act);
+        } else {           // the literal one-hot map of the ids through the dense kernel, P = 1
+          std::vector<int32_t> hid(ch.rows);
+          ctx.down(hid.data(), d.ids, (size_t)ch.rows);
+          std::vector<float> hot(cells, 0.f);
+          for (int r = 0; r < ch.rows; ++r) {
+            MV_REQUIRE(hid[r] >= 0 && hid[r] < K, "mv_op_decode_tail: argmax %d of row %d is "
+                       "outside the grid", (int)hid[r], r);
+            hot[(size_t)r * K + hid[r]] = 1.f;
+          }
+          ctx.up(d.hot, hot.data(), cells);
+          hipLaunchKernelGGL(mv::grid_emb_dense_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
+                             ctx.stream, d.hot.p, (size_t)K, d.ew.p, d.eb.p, d.x.p, ch.rows, ch.H,
+                             ch.W, 1, E, d.p0, d.pst, act);
+        }
+        HIP_CHECK(hipGetLastError());
+      }
+    }
+    for (int i = 0; i < n; ++i) {
+      const mv_tail_chain& ch = chains[i];
+      const size_t cells = (size_t)ch.rows * ch.H * ch.W;
+      ctx.down(ch.out, dv[i].out, cells * (ch.kind == 0 ? 1 : 2));
+      if (ch.ids) ctx.down(ch.ids, dv[i].ids, (size_t)ch.rows);
+      if (ch.x) ctx.down(ch.x, dv[i].x, cells * E);
+      if (ch.planes)
+        ctx.down(reinterpret_cast<_Float16*>(ch.planes), dv[i].pl, (size_t)ch.planes_elems);
+    }
+  });
+}
+
 int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* h,
                        const float* kernel, const float* biases, const float* dh_new,
                        const float* dc_new, int32_t M, int32_t H, int32_t W, int32_t Cx,

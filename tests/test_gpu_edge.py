@@ -277,6 +277,144 @@ def test_sparse_x_table_terms_equal_the_dense_x_operand(built_lib, tmp_path):
           % (mode, worst, flipped))
 
 
+_SEPARATE_TAIL = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+from multiverse_amd import _lib, synth
+cfg = synth.default_config(batch_size=3, use_grids=(1, 1))
+params = synth.make_params(cfg, recurrent_gain=3.0, bias_scale=0.1)
+feed = synth.make_feed(cfg, seed=synth.SEED_BASE + 73)
+eng = _lib.Engine(cfg, device=0)
+eng.set_params(params)
+eng.set_compute_mode("f32")
+eng.set_profiling(True)
+cls, reg = eng.forward_greedy(feed)
+stats = eng.kernel_stats()
+eng.close()
+out = {"names": np.array(sorted(stats)), "launches": np.array([stats[k]["launches"] for k in sorted(stats)])}
+for s in range(2):
+  out["cls%%d" %% s] = cls[s]
+  out["reg%%d" %% s] = reg[s]
+np.savez(%(out)r, **out)
+"""
+
+
+def test_separate_decoder_tail_equals_the_grouped_one_in_a_whole_forward(built_lib, tmp_path):
+  """MV_TAIL=v1 (read once per process -> a subprocess): hidden2grid_kernel + argmax_rows_kernel +
+  grid_emb_* after every decode step instead of h2g_q + decode_tail, against the same engine in
+  the default form.  The argmax of every step equal, class logits and regression maps within
+  2e-5 * max(1, max|ref|) -- the bar of the sparse-x A/B above.  The profiles name the launches:
+  the v1 run embeds every step through grid_emb_onehot / grid_emb_dense and has no decode_tail;
+  the default run has decode_tail, no argmax_rows, and those two only for the first step's
+  inputs (one launch per scale)."""
+  import os
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  out = str(tmp_path / "separate_tail.npz")
+  subprocess.check_call([sys.executable, "-c", _SEPARATE_TAIL % dict(root=root, out=out)],
+                        env=dict(os.environ, MV_TAIL="v1"))
+  v1 = np.load(out)
+  v1_launches = dict(zip([str(n) for n in v1["names"]], [int(n) for n in v1["launches"]]))
+  cfg = synth.default_config(batch_size=3, use_grids=(1, 1))
+  params = synth.make_params(cfg, recurrent_gain=3.0, bias_scale=0.1)
+  feed = synth.make_feed(cfg, seed=synth.SEED_BASE + 73)
+  eng = built_lib.Engine(cfg, device=0)
+  eng.set_params(params)
+  eng.set_compute_mode("f32")
+  eng.set_profiling(True)
+  cls, reg = eng.forward_greedy(feed)
+  stats = eng.kernel_stats()
+  eng.close()
+  Tp = cfg.pred_len
+  assert "decode_tail" not in v1_launches and "argmax_rows" in v1_launches
+  assert v1_launches["grid_emb_onehot"] == 2 * Tp and v1_launches["grid_emb_dense"] == 2 * Tp
+  assert "decode_tail" in stats and "argmax_rows" not in stats
+  assert stats["grid_emb_onehot"]["launches"] == 2 and stats["grid_emb_dense"]["launches"] == 2
+  for s in range(2):
+    rc, rr = cls[s], reg[s]
+    assert (v1["cls%d" % s].reshape(3, Tp, -1).argmax(-1) == rc.reshape(3, Tp, -1).argmax(-1)).all()
+    dc = float(np.abs(v1["cls%d" % s] - rc).max())
+    dr = float(np.abs(v1["reg%d" % s] - rr).max())
+    print("scale %d: separate vs grouped tail, max|dcls| %.3g (max|cls| %.3g) max|dreg| %.3g "
+          "(max|reg| %.3g)" % (s, dc, np.abs(rc).max(), dr, np.abs(rr).max()))
+    assert dc <= 2e-5 * max(1.0, float(np.abs(rc).max()))
+    assert dr <= 2e-5 * max(1.0, float(np.abs(rr).max()))
+
+
+_SEPARATE_TRAIN_TAIL = r"""
+import sys
+import numpy as np
+sys.path.insert(0, %(root)r)
+from multiverse_amd import _lib, synth
+cfg = synth.default_config(batch_size=2, use_grids=(1, 1), is_train=True)
+params = synth.make_params(cfg, recurrent_gain=2.0, bias_scale=0.1)
+feed = synth.make_feed(cfg, seed=synth.SEED_BASE + 74)
+out = {}
+for mode in ("f32",):
+  eng = _lib.Engine(cfg, device=0)
+  eng.set_params(params)
+  eng.set_compute_mode(mode)
+  eng.train_init()
+  eng.set_profiling(True)
+  loss, wd, pgl = eng.train_forward_backward(feed)
+  out[mode + "/names"] = np.array(sorted(eng.kernel_stats()))
+  out[mode + "/loss"] = np.array([loss, wd], dtype=np.float64)
+  out[mode + "/pgl"] = np.asarray(pgl)
+  for name, _ in eng.param_specs():
+    out[mode + "/grad/" + name] = eng.get_grad(name)
+  eng.close()
+np.savez(%(out)r, **out)
+"""
+
+
+def test_separate_decoder_tail_in_a_training_step(built_lib, tmp_path):
+  """MV_TRAIN_TAIL=v1 (read once per process -> a subprocess), the tail training falls back to on
+  any grid above 1024 cells: one f32 training step at batch 2 on both scales, the loss against the
+  oracle and the worst gradient against the fp64 oracle at the bars of
+  test_emb_size_other_than_32 (1e-4 relative loss, 2e-3 of max|g|); no decode_tail launch in
+  its profile, while the default step has them."""
+  import os
+  import subprocess
+  import sys
+  import torch
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  out = str(tmp_path / "separate_train_tail.npz")
+  subprocess.check_call([sys.executable, "-c", _SEPARATE_TRAIN_TAIL % dict(root=root, out=out)],
+                        env=dict(os.environ, MV_TRAIN_TAIL="v1"))
+  v1 = np.load(out)
+  cfg = synth.default_config(batch_size=2, use_grids=(1, 1), is_train=True)
+  params = synth.make_params(cfg, recurrent_gain=2.0, bias_scale=0.1)
+  feed = synth.make_feed(cfg, seed=synth.SEED_BASE + 74)
+  oloss, owd, opgl, og64 = oracle.loss_and_grads(params, cfg, feed, dtype=torch.float64)
+  for mode in ("f32",):
+    names = [str(n) for n in v1[mode + "/names"]]
+    assert "decode_tail" not in names and "hidden2grid" in names and "argmax_rows" in names
+    loss = float(v1[mode + "/loss"][0])
+    assert abs(loss - oloss) < 1e-4 * max(1.0, abs(oloss)), (mode, loss, oloss)
+    assert np.allclose(v1[mode + "/pgl"], opgl, rtol=1e-4, atol=1e-5)
+    worst = 0.0
+    grads = [k for k in v1.files if k.startswith(mode + "/grad/")]
+    assert len(grads) > 20
+    for key in grads:
+      g, g64 = v1[key].astype("float64"), og64[key[len(mode + "/grad/"):]]
+      worst = max(worst, float(np.abs(g - g64).max() / max(np.abs(g64).max(), 1e-30)))
+    print("MV_TRAIN_TAIL=v1 %-5s training step: loss %.6f (oracle %.6f), worst gradient error "
+          "%.2e of max|g|" % (mode, loss, oloss, worst))
+    assert worst < 2e-3
+  # the default step of this process runs the grouped tail
+  eng = built_lib.Engine(cfg, device=0)
+  eng.set_params(params)
+  eng.set_compute_mode("f32")
+  eng.train_init()
+  eng.set_profiling(True)
+  eng.train_forward_backward(feed)
+  stats = eng.kernel_stats()
+  eng.close()
+  assert "decode_tail" in stats and "argmax_rows" not in stats
+
+
 @pytest.mark.parametrize("mode", ["f32", "f16x3"])
 def test_literal_baseline_grids_36x18_and_18x9(built_lib, mode):
   """BASELINE.json words the grids as 36x18 / 18x9 (648 / 162 cells over 72x36 scene maps);

@@ -251,7 +251,7 @@ def test_ctypes_structs_match_the_c_header(tmp_path, built_lib):
     pytest.skip("no gcc")
   root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
   names = ["mv_config", "mv_inputs", "mv_outputs", "mv_beam_outputs", "mv_train_config",
-           "mv_targets", "mv_losses", "mv_inputs_compact", "mv_targets_compact"]
+           "mv_targets", "mv_losses", "mv_inputs_compact", "mv_targets_compact", "mv_tail_chain"]
   lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "multiverse_hip.h"',
            'int main(void) {']
   for n in names:
