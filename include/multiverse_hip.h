@@ -512,6 +512,62 @@ int  mv_graph_captures(mv_handle h, int64_t* captures);
  * call). */
 int  mv_set_cell_bias(mv_handle h, const float* bias /* [N, Tm, K]; NULL clears */, int32_t Tm);
 
+/* ---- motion costs: per-row speed and turn priors (not in the reference; defined here) ---------
+ * A cell bias whose plane depends on the path so far: what a step costs depends on how far it
+ * moves from the path's last cell (a speed prior or limit) and on how much that move differs from
+ * the move before it (a turn prior).  The grid is the handle's one used scale, H x W,
+ * K = H * W <= 1024; cell k is (y, x) = (k / W, k % W), as multifuture.xy_to_grid_class numbers
+ * them.  For the row or slot (n, s) at decode step t:
+ *   p1 = the cell the row's path holds at step t - 1; at t == 0 the row's last observed label,
+ *        labels[n, obs_len - 1].
+ *   p0 = the cell before p1 on the same path: at t == 1 labels[n, obs_len - 1], at t == 0
+ *        labels[n, obs_len - 2]; ABSENT at t == 0 for a row whose observation length
+ *        (mv_set_obs_lengths; obs_len without it) is 1.
+ *   Beam search and sampling without replacement: a slot's path is its parent's path, the order
+ *        of the back-trace: p1 = ids[t-1][n, slot], p0 = ids[t-2][n, parents[t-1][n, slot]].
+ *   d(k) = cell(k) - cell(p1),  u = cell(p1) - cell(p0),  a(k) = d(k) - u, each a pair of ints
+ *        (rows, columns).
+ * With radius R (1 .. MV_MOTION_MAX_RADIUS) and D = 2 R + 1:
+ *   vterm(k) = vel[n, d.y + R, d.x + R] if max(|d.y|, |d.x|) <= R, else vel_far[n]
+ *   aterm(k) = acc[n, a.y + R, a.x + R] if max(|a.y|, |a.x|) <= R, else acc_far[n];
+ *              exactly 0.0f when no acc table is set or p0 is absent
+ *   b_eff[k] = (b[k] + vterm(k)) + aterm(k)   in float32, in this order; b is the row's cell-bias
+ *              plane of the step (mv_set_cell_bias), or 0.0f when no bias is set.
+ * Everything mv_set_cell_bias defines then holds with b_eff in place of b: the beam candidate
+ * (prev_lp + lp) + b_eff, formed before the mask's -inf and before the diversity ranks; the
+ * samplers' w = l / tau + b_eff and the limits ordered by w; qlogprobs and the without-replacement
+ * q plane, written whenever a motion cost is set; the two-launch beam step; lp, logits and
+ * logprobs stay the model's; mv_score_futures neither reads nor changes it, so scoring the
+ * returned ids reproduces logprobs bit for bit.  The carried and returned beam score includes
+ * every step's vterm + aterm (multifuture.path_motion_cost recomputes them on the host).
+ * Every table value is finite.  A speed LIMIT is the cost -1e30: exp(w - mxq) of such a cell is
+ * exactly 0, so the samplers never draw it while a cheaper cell is allowed.  The beam search and
+ * the sampling without replacement SELECT beam_size candidates: a slot that cannot be filled from
+ * inside the windows takes an outside cell and carries the -1e30 in its score (for example at
+ * step 0, where only the root's K children are candidates, with fewer in-window cells than
+ * beam_size).  That is defined and deterministic (ties by index); the caller filters on the score.
+ * Stickiness, the forwards it applies to, and how it combines with mv_set_cell_mask,
+ * mv_set_cell_bias, mv_set_pred_lengths and mv_set_obs_lengths are the bias's: row n equals its
+ * own uniform forward under its own tables.  The tables live in one engine-owned device
+ * allocation; this call synchronises the stream and rewrites it.  The graph key carries whether a
+ * motion cost is set, its radius and whether acc is present, so a replay follows new table VALUES
+ * without re-capture.
+ * Identity, eager and graph: with none set no launch differs (the same kernels, the same graph
+ * keys, mv_graph_captures unchanged).  With all-zero tables and zero far values every output that
+ * both handles define is bit-identical to the same handle without a motion cost.  (b + 0.0f turns
+ * a bias of -0.0f into +0.0f; the two differ in no comparison and in no sum with a non-zero term.)
+ * Errors, each message naming its cause: a greedy handle; radius outside 1 .. 4; a NaN or +-inf
+ * (the message names the table, n and the entry); acc / acc_far not both or neither; a grid of
+ * more than 1024 cells (at the forward); mv_train_*, mv_submit_greedy and mv_beam_occupancy while
+ * one is set (the message names the call: the occupancy map under a path-dependent plane is not
+ * defined here). */
+#define MV_MOTION_MAX_RADIUS 4
+int  mv_set_motion_cost(mv_handle h, int32_t radius,
+                        const float* vel     /* [N, D, D]; NULL clears */,
+                        const float* vel_far /* [N] */,
+                        const float* acc     /* [N, D, D] or NULL: no turn term */,
+                        const float* acc_far /* [N]; NULL exactly when acc is */);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -837,6 +893,40 @@ int  mv_op_sample_step_biased(int device, const float* logits /* [R, K] */,
                               int32_t K, int32_t t, float temperature, uint32_t seed,
                               int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
                               float* qlp, uint8_t* keep /* [R, K] */);
+
+/* The motion forms of the three step ops (mv_set_motion_cost above): the biased prototype with
+ * `motion` directly behind `bias`; `allowed` and `bias` may both be NULL.  The tables are per
+ * SAMPLE as `bias` is ([samples, D, D] and [samples]); prev1 / prev0 hold p1 / p0 of every ROW
+ * ([N * B] or [R]), prev0[r] = -1: absent.  W divides K; prev1 in [0, K), prev0 in [-1, K). */
+typedef struct mv_step_motion {
+  int32_t W, radius;
+  const float* vel;
+  const float* vel_far;
+  const float* acc;       /* NULL: no turn term */
+  const float* acc_far;   /* NULL exactly when acc is */
+  const int32_t* prev1;
+  const int32_t* prev0;
+} mv_step_motion;
+int  mv_op_beam_step_motion(int device, const float* logits, const float* prev_logprob,
+                            const uint8_t* allowed /* [N, K] or NULL */,
+                            const float* bias /* [N, K] or NULL */, const mv_step_motion* motion,
+                            int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
+                            float gamma, int32_t fix_num_timestep, float* new_logprob,
+                            int32_t* ids, int32_t* parents);
+int  mv_op_sbs_step_motion(int device, const float* logits, const float* prev_phi,
+                           const float* prev_logprob, const float* prev_gumbel,
+                           const uint8_t* allowed /* [N, K] or NULL */,
+                           const float* bias /* [N, K] or NULL */, const mv_step_motion* motion,
+                           int32_t N, int32_t B, int32_t K, int32_t t, float temperature,
+                           uint32_t seed, float* new_phi, float* new_logprob, float* new_gumbel,
+                           int32_t* ids, int32_t* parents);
+int  mv_op_sample_step_motion(int device, const float* logits /* [R, K] */,
+                              const uint8_t* allowed /* [R / S, K] or NULL */,
+                              const float* bias /* [R / S, K] or NULL */,
+                              const mv_step_motion* motion, int32_t R, int32_t S, int32_t K,
+                              int32_t t, float temperature, uint32_t seed, int32_t top_k,
+                              float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
+                              uint8_t* keep /* [R, K] */);
 
 /* Light cone of the class encoder (MV_ENC_CONE): the wave tiles of the F(3,3) gate
  * kernel each encoder step computes, as every upload builds them from the labels.  Host only: no

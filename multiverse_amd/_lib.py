@@ -58,6 +58,8 @@ EXPORTED_SYMBOLS = [
     "mv_op_sample_step_biased",
     "mv_scene_conv_form", "mv_op_scene_conv",
     "mv_op_decode_tail",
+    "mv_set_motion_cost", "mv_op_beam_step_motion", "mv_op_sbs_step_motion",
+    "mv_op_sample_step_motion",
 ]
 
 
@@ -109,6 +111,18 @@ class mv_inputs(C.Structure):
 
 _dp = C.POINTER(C.c_double)
 _u8p = C.POINTER(C.c_uint8)
+
+
+class mv_step_motion(C.Structure):
+  """The motion argument of the three `_motion` step ops (include/multiverse_hip.h)."""
+  _fields_ = [
+      ("W", C.c_int32), ("radius", C.c_int32),
+      ("vel", _fp), ("vel_far", _fp), ("acc", _fp), ("acc_far", _fp),
+      ("prev1", _ip), ("prev0", _ip),
+  ]
+
+
+MV_MOTION_MAX_RADIUS = 4
 
 
 class mv_inputs_compact(C.Structure):
@@ -262,6 +276,18 @@ def load():
                                           C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
                                           _fp, _fp, _fp, _ip, _ip]
     lib.mv_op_sample_step_biased.argtypes = [C.c_int, _fp, _u8p, _fp, C.c_int32, C.c_int32,
+                                             C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                             C.c_int32, C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
+  if hasattr(lib, "mv_set_motion_cost"):    # (as above)
+    _mp = C.POINTER(mv_step_motion)
+    lib.mv_set_motion_cost.argtypes = [h, C.c_int32, _fp, _fp, _fp, _fp]
+    lib.mv_op_beam_step_motion.argtypes = [C.c_int, _fp, _fp, _u8p, _fp, _mp, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                           C.c_int32, _fp, _ip, _ip]
+    lib.mv_op_sbs_step_motion.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _u8p, _fp, _mp, C.c_int32,
+                                          C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                          _fp, _fp, _fp, _ip, _ip]
+    lib.mv_op_sample_step_motion.argtypes = [C.c_int, _fp, _u8p, _fp, _mp, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_float, C.c_uint32,
                                              C.c_int32, C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
@@ -586,6 +612,7 @@ class Engine(object):
     self._set_obs_lengths(feed.get("obs_lengths"))
     self._set_feed_cell_mask(feed.get("cell_mask"))
     self._set_feed_cell_bias(feed.get("cell_bias"))
+    self._set_feed_motion_cost(feed.get("motion_cost"))
     return inp
 
   def _set_pred_lengths(self, lengths):
@@ -694,6 +721,63 @@ class Engine(object):
     self.set_cell_bias(bias)
     self._cell_bias_from_feed = True
 
+  def set_motion_cost(self, radius, vel=None, vel_far=None, acc=None, acc_far=None):
+    """Per-row speed and turn priors of a multi-future decode (include/multiverse_hip.h
+    mv_set_motion_cost): what a step costs by how far it moves from the path's last cell
+    (vel [N, D, D], vel_far [N]; D = 2 * radius + 1) and by how much that move differs from the
+    move before it (acc [N, D, D], acc_far [N]; both or neither).  Tables of one row ([D, D] and a
+    scalar) are taken for every row; `multifuture.motion_tables` builds them.  Every value finite;
+    a limit is the cost -1e30.  vel None (or radius None) clears.  Sticky, with the rule of
+    set_cell_bias: a cost set here stays through every later feed that has no "motion_cost" key;
+    one that a feed brought is cleared by the next feed without the key.  The beam search and both
+    samplers read it; score_futures does not, and beam_occupancy refuses while one is set."""
+    self._motion_cost_from_feed = False
+    if vel is None or radius is None:
+      check(self.lib.mv_set_motion_cost(self.handle, 0, None, None, None, None), self.handle)
+      self._motion_cost_set = False
+      return
+    if (acc is None) != (acc_far is None):
+      raise MvError("motion_cost: acc and acc_far are given both or neither")
+    N, D = self.cfg.batch_size, 2 * int(radius) + 1
+
+    def table(a, name):
+      a = np.asarray(a, dtype=np.float32)
+      if a.shape == (D, D):
+        a = np.broadcast_to(a, (N, D, D))
+      if a.shape != (N, D, D):
+        raise MvError("motion_cost: %s has shape %s, not [N=%d, D=%d, D] (radius %d)"
+                      % (name, tuple(a.shape), N, D, int(radius)))
+      return f32(a)
+
+    def far(a, name):
+      a = np.asarray(a, dtype=np.float32)
+      if a.ndim == 0:
+        a = np.broadcast_to(a, (N,))
+      if a.shape != (N,):
+        raise MvError("motion_cost: %s has shape %s, not [N=%d]" % (name, tuple(a.shape), N))
+      return f32(a)
+
+    if not 1 <= int(radius) <= MV_MOTION_MAX_RADIUS:
+      raise MvError("motion_cost: radius = %d not in [1, %d]" % (int(radius), MV_MOTION_MAX_RADIUS))
+    v, vf = table(vel, "vel"), far(vel_far, "vel_far")
+    a = table(acc, "acc") if acc is not None else None
+    af = far(acc_far, "acc_far") if acc is not None else None
+    check(self.lib.mv_set_motion_cost(self.handle, int(radius), fptr(v), fptr(vf),
+                                      fptr(a) if a is not None else None,
+                                      fptr(af) if af is not None else None), self.handle)
+    self._motion_cost_set = True
+
+  def _set_feed_motion_cost(self, cost):
+    """feed["motion_cost"]: the dict of `multifuture.motion_tables` (radius, vel, vel_far and,
+    optionally, acc, acc_far), with the feed-scoped rule of feed["cell_bias"]."""
+    if cost is None:
+      if getattr(self, "_motion_cost_from_feed", False):
+        self.set_motion_cost(None)
+      return
+    self.set_motion_cost(cost["radius"], cost["vel"], cost["vel_far"], cost.get("acc"),
+                         cost.get("acc_far"))
+    self._motion_cost_from_feed = True
+
   def graph_captures(self):
     """Forwards captured into a hipGraph on this handle so far (a replay does not count)."""
     n = C.c_int64()
@@ -738,7 +822,7 @@ class Engine(object):
     top_k, top_p = getattr(self, "_sampling_limits", (0, 1.0))
     return getattr(self, "_sampling_on", False) and \
         (top_k > 0 or top_p < 1.0 or getattr(self, "_cell_mask_set", False) or
-         getattr(self, "_cell_bias_set", False))
+         getattr(self, "_cell_bias_set", False) or getattr(self, "_motion_cost_set", False))
 
   def beam_proposal_logprobs(self):
     """float32 [N, B]: the log-probability of each future of the last SAMPLED forward under the
@@ -961,6 +1045,7 @@ class Engine(object):
     self._set_obs_lengths(feed.get("obs_lengths"))
     self._set_feed_cell_mask(feed.get("cell_mask"))
     self._set_feed_cell_bias(feed.get("cell_bias"))
+    self._set_feed_motion_cost(feed.get("motion_cost"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len
@@ -1458,16 +1543,53 @@ def _bias_plane(bias, samples, K):
   return f32(np.asarray(bias, dtype=np.float32).reshape(samples, K))
 
 
+def _step_motion(motion, samples, rows):
+  """motion: a dict with W, radius, vel [samples, D, D], vel_far [samples], optionally acc /
+  acc_far, and prev1 / prev0 int32 [rows] (prev0 -1 = absent) -> (mv_step_motion, the arrays it
+  points into, to be kept alive over the call)."""
+  D = 2 * int(motion["radius"]) + 1
+  m = mv_step_motion()
+  m.W, m.radius = int(motion["W"]), int(motion["radius"])
+  keep = []
+  for name, count in (("vel", samples * D * D), ("vel_far", samples), ("acc", samples * D * D),
+                      ("acc_far", samples)):
+    if motion.get(name) is None:
+      continue                   # (the library names a missing table)
+    a = f32(np.asarray(motion[name], dtype=np.float32).reshape(-1))
+    if 1 <= m.radius <= MV_MOTION_MAX_RADIUS and a.size != count:
+      raise MvError("motion: %s has %d values, not %d (samples = %d, radius = %d)"
+                    % (name, a.size, count, samples, m.radius))
+    keep.append(a)
+    setattr(m, name, fptr(a))
+  p1 = np.ascontiguousarray(np.asarray(motion["prev1"], dtype=np.int32).reshape(rows))
+  p0 = np.ascontiguousarray(np.asarray(motion["prev0"], dtype=np.int32).reshape(rows))
+  keep += [p1, p0]
+  m.prev1, m.prev0 = iptr(p1), iptr(p0)
+  return m, keep
+
+
 def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device=0,
-                 allowed=None, bias=None):
+                 allowed=None, bias=None, motion=None):
   """allowed [N, K] (non-zero = the cell may be chosen): the masked step, mv_op_beam_step_masked.
-  bias [N, K] float32 cell costs: the biased step, mv_op_beam_step_biased (allowed optional)."""
+  bias [N, K] float32 cell costs: the biased step, mv_op_beam_step_biased (allowed optional).
+  motion (the dict of `_step_motion`, prev1 / prev0 [N, B]): the step under a motion cost,
+  mv_op_beam_step_motion (allowed and bias optional)."""
   lib = load()
   logits, prev_lp = f32(logits), f32(prev_lp)
   N, B, K = logits.shape
   new_lp = np.empty((N, B), dtype=np.float32)
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if motion is not None:
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K) if bias is not None else None
+    m, keep = _step_motion(motion, N, N * B)
+    check(lib.mv_op_beam_step_motion(device, fptr(logits), fptr(prev_lp), ap,
+                                     fptr(bz) if bz is not None else None, C.byref(m), N, B, K,
+                                     int(time), 1 if diverse else 0, float(gamma),
+                                     int(fix_num_timestep), fptr(new_lp), iptr(ids),
+                                     iptr(parents)))
+    return new_lp, ids, parents
   if bias is not None:
     a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, N, K)
@@ -1489,7 +1611,7 @@ def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device
 
 
 def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0,
-                allowed=None, bias=None):
+                allowed=None, bias=None, motion=None):
   """One step of the sampling without replacement (mv_op_sbs_step): logits [N, B, K], prev_*
   [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B].  allowed [N, K]: the
   masked step (mv_op_sbs_step_masked).  bias [N, K]: the biased step (mv_op_sbs_step_biased;
@@ -1500,6 +1622,16 @@ def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, d
   phi, lp, g = (np.empty((N, B), dtype=np.float32) for _ in range(3))
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if motion is not None:       # mv_op_sbs_step_motion: allowed and bias optional
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K) if bias is not None else None
+    m, keep = _step_motion(motion, N, N * B)
+    check(lib.mv_op_sbs_step_motion(device, fptr(logits), fptr(prev_phi), fptr(prev_lp),
+                                    fptr(prev_g), ap, fptr(bz) if bz is not None else None,
+                                    C.byref(m), N, B, K, int(t), float(temperature),
+                                    int(seed) & 0xFFFFFFFF, fptr(phi), fptr(lp), fptr(g),
+                                    iptr(ids), iptr(parents)))
+    return phi, lp, g, ids, parents
   if bias is not None:
     a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, N, K)
@@ -1628,7 +1760,7 @@ def op_decode_tail(chains, act=0, next="embed", planes=None, separate=False, dev
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,
-                   allowed=None, bias=None):
+                   allowed=None, bias=None, motion=None):
   """One step of the independent sampler under top-k / nucleus limits (mv_op_sample_step):
   logits [R, K], row r = future r % S of sample r // S -> (ids int32 [R], lp [R] the model's
   log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set).
@@ -1640,6 +1772,16 @@ def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, fl
   ids = np.empty(R, dtype=np.int32)
   lp, qlp = (np.empty(R, dtype=np.float32) for _ in range(2))
   keep = np.empty((R, K), dtype=np.uint8)
+  if motion is not None:       # mv_op_sample_step_motion (prev1 / prev0 [R]): the rest optional
+    a, ap = _allowed_plane(allowed, R // int(S), K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, R // int(S), K) if bias is not None else None
+    m, alive = _step_motion(motion, R // int(S), R)
+    check(lib.mv_op_sample_step_motion(device, fptr(logits), ap,
+                                       fptr(bz) if bz is not None else None, C.byref(m), R, int(S),
+                                       K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
+                                       int(top_k), float(top_p), int(floor), iptr(ids), fptr(lp),
+                                       fptr(qlp), keep.ctypes.data_as(_u8p)))
+    return ids, lp, qlp, keep.astype(bool)
   if bias is not None:
     a, ap = _allowed_plane(allowed, R // int(S), K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, R // int(S), K)

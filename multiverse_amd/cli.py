@@ -245,6 +245,13 @@ _MF_FLAGS = [
     # row's LAST observed frame (multifuture.cell_bias_from_scene; the engine adds the bias per
     # row: mv_set_cell_bias).  Combines with --allowed_classes.
     ("--class_costs", str, None),
+    # not in the reference: motion costs (multifuture.motion_tables; the engine derives each
+    # path's cost from its own last two cells: mv_set_motion_cost).  --max_step_cells M: a step
+    # moves at most M grid cells (Chebyshev); --speed_cost c / --accel_cost c: a step of d cells
+    # costs c |d|^2 nats, a change of velocity of a cells c |a|^2; --motion_radius R: the window of
+    # the tables, M <= R <= 4.  They combine with --allowed_classes and --class_costs.
+    ("--max_step_cells", int, None), ("--speed_cost", float, 0.0), ("--accel_cost", float, 0.0),
+    ("--motion_radius", int, 2),
 ]
 
 
@@ -282,6 +289,7 @@ def multifuture_inference_main(argv=None):
                      "--greedy")
   parse_allowed_classes(args)
   parse_class_costs(args)
+  parse_motion_cost(args)
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)
@@ -373,6 +381,37 @@ def parse_class_costs(args):
     raise SystemExit("--class_costs %r: a cost is a finite number of nats (forbid a class with "
                      "--allowed_classes)" % args.class_costs)
   args.class_costs = costs
+
+
+def parse_motion_cost(args):
+  """--max_step_cells / --speed_cost / --accel_cost / --motion_radius -> args.motion_cost, the
+  dict of multifuture.motion_tables (None when none of the first three is given); refused with
+  --greedy (the greedy decode chooses by argmax and reads no cost) and with --score_gt."""
+  from multiverse_amd import multifuture as mf
+  args.motion_cost = None
+  given =[f for f, on in (("--max_step_cells", args.max_step_cells is not None),
+                           ("--speed_cost", args.speed_cost != 0),
+                           ("--accel_cost", args.accel_cost != 0)) if on]
+  if not given:
+    return
+  if args.greedy:
+    raise SystemExit("%s shapes the beam search and the samplers; it does not combine with "
+                     "--greedy" % given[0])
+  if args.score_gt is not None:
+    raise SystemExit("%s shapes a decode; --score_gt decodes nothing" % given[0])
+  R = args.motion_radius
+  if not 1 <= R <= 4:
+    raise SystemExit("--motion_radius %d: the window's radius is 1 .. 4 cells" % R)
+  M = args.max_step_cells
+  if M is not None and M < 1:
+    raise SystemExit("--max_step_cells %d: at least one cell per step" % M)
+  if M is not None and M > R:
+    raise SystemExit("--max_step_cells %d is larger than --motion_radius %d (the limit lies "
+                     "inside the window)" % (M, R))
+  for flag, c in (("--speed_cost", args.speed_cost), ("--accel_cost", args.accel_cost)):
+    if not np.isfinite(c) or c < 0:
+      raise SystemExit("%s %r: a cost is a finite number of nats >= 0" % (flag, c))
+  args.motion_cost = mf.motion_tables(R, M, args.speed_cost, args.accel_cost)
 
 
 def print_exact_nll(result):

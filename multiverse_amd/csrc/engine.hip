@@ -427,6 +427,52 @@ int mv_set_cell_bias(mv_handle h, const float* bias, int32_t Tm) {
   });
 }
 
+int mv_set_motion_cost(mv_handle h, int32_t radius, const float* vel, const float* vel_far,
+                       const float* acc, const float* acc_far) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_motion_cost: engine was created with beam_size 1 (the "
+               "greedy forward chooses by argmax and reads no cost: create a beam handle)");
+    // behind whatever forward still reads the previous tables on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!vel) {
+      h->motion_radius = 0;
+      h->motion_acc = false;
+      return;
+    }
+    MV_REQUIRE(radius >= 1 && radius <= MV_MOTION_MAX_RADIUS, "mv_set_motion_cost: radius = %d not "
+               "in [1, %d]", (int)radius, MV_MOTION_MAX_RADIUS);
+    MV_REQUIRE(vel_far, "mv_set_motion_cost: vel is given without vel_far");
+    MV_REQUIRE((acc != nullptr) == (acc_far != nullptr), "mv_set_motion_cost: acc and acc_far are "
+               "given both or neither (%s is NULL)", acc ? "acc_far" : "acc");
+    const size_t N = (size_t)h->cfg.batch_size, D = (size_t)(2 * radius + 1), DD = D * D;
+    // a cost is finite: a limit is the cost -1e30, a veto of a cell is the mask's job
+    auto finite = [&](const float* p, size_t per, const char* name) {
+      for (size_t i = 0; i < N * per; ++i)
+        MV_REQUIRE(std::isfinite(p[i]), "mv_set_motion_cost: %s[n = %d, entry %d] = %g is not "
+                   "finite (a cost is a finite float32; a limit is the cost -1e30)", name,
+                   (int)(i / per), (int)(i % per), (double)p[i]);
+    };
+    finite(vel, DD, "vel");
+    finite(vel_far, 1, "vel_far");
+    if (acc) { finite(acc, DD, "acc"); finite(acc_far, 1, "acc_far"); }
+    // one allocation for every radius: the addresses a captured forward holds never change
+    h->motion_dev.alloc(h->motion_floats());
+    float* d = h->motion_dev.p;
+    HIP_CHECK(hipMemcpy(d, vel, N * DD * sizeof(float), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d + h->motion_vel_far_at(), vel_far, N * sizeof(float),
+                        hipMemcpyHostToDevice));
+    if (acc) {
+      HIP_CHECK(hipMemcpy(d + h->motion_acc_at(), acc, N * DD * sizeof(float),
+                          hipMemcpyHostToDevice));
+      HIP_CHECK(hipMemcpy(d + h->motion_acc_far_at(), acc_far, N * sizeof(float),
+                          hipMemcpyHostToDevice));
+    }
+    h->motion_radius = radius;
+    h->motion_acc = acc != nullptr;
+  });
+}
+
 int mv_graph_captures(mv_handle h, int64_t* captures) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -569,6 +615,8 @@ int mv_submit_greedy(mv_handle h, const mv_inputs* in) {
                "greedy forward chooses by argmax and reads no mask -- clear it first");
     MV_REQUIRE(!h->cbias_set(), "mv_submit_greedy: a cell bias is set (mv_set_cell_bias); the "
                "greedy forward chooses by argmax and reads no bias -- clear it first");
+    MV_REQUIRE(!h->motion_set(), "mv_submit_greedy: a motion cost is set (mv_set_motion_cost); the "
+               "greedy forward chooses by argmax and reads no cost -- clear it first");
     pipeline_submit(h, in);
   });
 }
@@ -611,6 +659,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
                "cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_init");
+    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
+               "no cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -664,6 +714,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
                "cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_forward_backward");
+    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
+               "no cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -733,6 +785,8 @@ int mv_train_apply(mv_handle h, float grad_scale) {
                "cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_apply");
+    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
+               "no cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -751,6 +805,8 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
                "cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
                "cells -- clear it first", "mv_train_step");
+    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
+               "no cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "

@@ -1154,6 +1154,40 @@ StepMask step_mask(const mv_engine* e, int K, int t) {
   return m;
 }
 
+// The motion cost of decode step t (mv_set_motion_cost): the tables, and where the step kernels
+// find each row's p1 / p0 in what the forward already holds on the device -- the labels for the
+// observed cells, and the ids (and, for the beams, the parents) the earlier steps wrote.  No
+// launch and no buffer is added.  `ids` [.., R] x ids_stride: the chosen cell of row r at step u
+// is ids[u * step + r * ids_stride]; parents (beam, wor): [T, R], or NULL for rows that continue
+// themselves.  None set: m is left as it is.
+void step_motion(const mv_engine* e, const ScaleState& S, int t, const int32_t* ids,
+                 size_t ids_step, int ids_stride, const int32_t* parents, StepMask& m) {
+  if (!e->motion_set()) return;
+  const int T = e->cfg.obs_len, R = e->cfg.batch_size * e->cfg.beam_size;
+  mv::MotionRow& mo = m.mo;
+  mo.vel = e->motion_dev.p;
+  mo.vel_far = e->motion_dev.p + e->motion_vel_far_at();
+  mo.acc = e->motion_acc ? e->motion_dev.p + e->motion_acc_at() : nullptr;
+  mo.acc_far = e->motion_acc ? e->motion_dev.p + e->motion_acc_far_at() : nullptr;
+  mo.W = S.W;
+  mo.radius = e->motion_radius;
+  const int32_t* last = S.labels.p + (T - 1);      // labels[:, -1], one per sample
+  if (t == 0) {
+    mo.prev1 = last; mo.p1_stride = T; mo.p1_per_row = 0;
+    mo.prev0 = T >= 2 ? last - 1 : nullptr; mo.p0_stride = T; mo.p0_per_row = 0;
+    // a row observed for one frame has no cell before its last (right-aligned observations)
+    mo.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
+    return;
+  }
+  mo.prev1 = ids + (size_t)(t - 1) * ids_step; mo.p1_stride = ids_stride; mo.p1_per_row = 1;
+  if (t == 1) {
+    mo.prev0 = last; mo.p0_stride = T; mo.p0_per_row = 0;
+  } else {
+    mo.prev0 = ids + (size_t)(t - 2) * ids_step; mo.p0_stride = ids_stride; mo.p0_per_row = 1;
+    mo.prev0_via = parents ? parents + (size_t)(t - 1) * R : nullptr;
+  }
+}
+
 // Beam-search class decoder (grid_decoder_beam_search,
 // code/pred_models.py:474-806) with the un-beamed regression decoder advanced
 // in lockstep (its step t shares a launch with beam time t+1).
@@ -1272,7 +1306,8 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
         HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
-      const StepMask mask = step_mask(e, K, time - 1);
+      StepMask mask = step_mask(e, K, time - 1);
+      step_motion(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p, mask);
       if (wor) launch(e, "sbs_step", 0, 16.0 * n_now * B * K, [&] {
         launch_sbs_step(e->issue, logits, e->bm_phi[lpi].p, e->bm_lp[lpi].p, e->bm_g[lpi].p,
                         e->bm_cand.p, e->bm_sbs_lp.p, e->bm_sbs_q.p, e->samp_params.p, n_now, B,
@@ -1425,9 +1460,12 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
       });
       else launch(e, "sample_step", 0, step_bytes, [&] {
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
+        StepMask mask = step_mask(e, K, t);
+        // the sampler's rows continue themselves: their path is their own row of the [R, T] ids
+        step_motion(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr, mask);
         launch_sample_step(e->issue, logits, orow, rows, B, K, t, shared, e->samp_params.p, 1,
                            lens, e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr,
-                           step_mask(e, K, t));
+                           mask);
       });
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, Tp, S.xbuf_cls.p, n_next * B);
@@ -1611,6 +1649,9 @@ void run_forward(mv_engine* e, ForwardKind kind) {
     require_row_fits_wave("mv_set_cell_mask: a masked step", e->sc[beam_scale(e)].K);
   if (beam && kind != ForwardKind::Scored && e->cbias_set())
     require_row_fits_wave("mv_set_cell_bias: a biased step", e->sc[beam_scale(e)].K);
+  if (beam && kind != ForwardKind::Scored && e->motion_set())
+    require_row_fits_wave("mv_set_motion_cost: a step under a motion cost",
+                          e->sc[beam_scale(e)].K);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
@@ -1629,7 +1670,10 @@ void run_forward(mv_engine* e, ForwardKind kind) {
   // (a scoring forward reads no mask and no bias: one graph whatever is set)
   const bool constrainable = kind != ForwardKind::Scored && kind != ForwardKind::Greedy;
   const int mask_key = (!constrainable || !e->cmask_set() ? 0 : (e->cmask_tm > 1 ? 2 : 1)) +
-                       3 * (!constrainable || !e->cbias_set() ? 0 : (e->cbias_tm > 1 ? 2 : 1));
+                       3 * (!constrainable || !e->cbias_set() ? 0 : (e->cbias_tm > 1 ? 2 : 1)) +
+                       // a captured step bakes in the radius and whether acc is present
+                       9 * (!constrainable || !e->motion_set()
+                                ? 0 : 2 * e->motion_radius - 1 + (e->motion_acc ? 1 : 0));
   const auto key = std::make_tuple(kind, e->pred_len, e->num_frames, mask_key);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {

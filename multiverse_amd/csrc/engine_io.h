@@ -491,6 +491,9 @@ void beam_occupancy(mv_engine* e, float* out) {
   mf_require_forward(e, "mv_beam_occupancy");
   MV_REQUIRE(e->last != ForwardKind::Scored, "mv_beam_occupancy: the last forward scored given "
              "futures (mv_score_futures); a set of given futures is not a predictive mixture");
+  // (a plane that depends on each future's path has no per-step map of the mixture: left out)
+  MV_REQUIRE(!e->motion_set(), "mv_beam_occupancy: a motion cost is set (mv_set_motion_cost); the "
+             "occupancy map under a path-dependent cost is not defined -- clear it first");
   const ScaleState& S = e->sc[beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;

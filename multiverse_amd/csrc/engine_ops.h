@@ -270,17 +270,67 @@ static void op_bias_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, StepM
   m.bias_stride = K;
 }
 
+// the motion forms: the tables and every row's p1 / p0 go up; `allowed` and `bias` may be NULL
+struct OpMotionBufs {
+  DevBuf<float> vel, vel_far, acc, acc_far;
+  DevBuf<int32_t> prev1, prev0;
+};
+static void op_motion_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, OpMotionBufs& mb,
+                         StepMask& m, const uint8_t* allowed, const float* bias,
+                         const mv_step_motion* mo, size_t samples, size_t rows, int K,
+                         const char* who) {
+  MV_REQUIRE(mo && mo->vel && mo->vel_far && mo->prev1 && mo->prev0,
+             "%s: NULL motion, vel, vel_far, prev1 or prev0", who);
+  require_row_fits_wave(who, K);
+  MV_REQUIRE(mo->radius >= 1 && mo->radius <= MV_MOTION_MAX_RADIUS, "%s: radius %d not in [1, %d]",
+             who, (int)mo->radius, MV_MOTION_MAX_RADIUS);
+  MV_REQUIRE(mo->W >= 1 && K % mo->W == 0, "%s: W = %d does not divide K = %d", who, (int)mo->W, K);
+  MV_REQUIRE((mo->acc != nullptr) == (mo->acc_far != nullptr),
+             "%s: acc and acc_far are given both or neither", who);
+  const size_t DD = (size_t)(2 * mo->radius + 1) * (2 * mo->radius + 1);
+  auto finite = [&](const float* p, size_t per, const char* name) {
+    for (size_t i = 0; i < samples * per; ++i)
+      MV_REQUIRE(std::isfinite(p[i]), "%s: %s[n = %d, entry %d] = %g is not finite", who, name,
+                 (int)(i / per), (int)(i % per), (double)p[i]);
+  };
+  finite(mo->vel, DD, "vel");
+  finite(mo->vel_far, 1, "vel_far");
+  if (mo->acc) { finite(mo->acc, DD, "acc"); finite(mo->acc_far, 1, "acc_far"); }
+  for (size_t r = 0; r < rows; ++r) {
+    MV_REQUIRE(mo->prev1[r] >= 0 && mo->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)", who,
+               (int)r, (int)mo->prev1[r], K);
+    MV_REQUIRE(mo->prev0[r] >= -1 && mo->prev0[r] < K, "%s: prev0[%d] = %d not in [-1, K = %d)",
+               who, (int)r, (int)mo->prev0[r], K);
+  }
+  if (bias) op_bias_up(ctx, dm, db, m, allowed, bias, samples, K, who);
+  else if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
+  ctx.up(mb.vel, mo->vel, samples * DD);
+  ctx.up(mb.vel_far, mo->vel_far, samples);
+  if (mo->acc) { ctx.up(mb.acc, mo->acc, samples * DD); ctx.up(mb.acc_far, mo->acc_far, samples); }
+  ctx.up(mb.prev1, mo->prev1, rows);
+  ctx.up(mb.prev0, mo->prev0, rows);
+  m.mo.vel = mb.vel.p; m.mo.vel_far = mb.vel_far.p;
+  m.mo.acc = mo->acc ? mb.acc.p : nullptr; m.mo.acc_far = mo->acc ? mb.acc_far.p : nullptr;
+  m.mo.prev1 = mb.prev1.p; m.mo.prev0 = mb.prev0.p;
+  m.mo.W = mo->W; m.mo.radius = mo->radius;
+}
+
 static int op_beam_step(int device, const float* logits, const float* prev_logprob,
                         int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
                         float gamma, int32_t fix_num_timestep, float* new_logprob,
                         int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked,
-                        const float* bias = nullptr, bool biased = false) {
+                        const float* bias = nullptr, bool biased = false,
+                        const mv_step_motion* motion = nullptr, bool moving = false) {
   return guarded(nullptr, [&] {
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
+    OpMotionBufs mb;
     StepMask mask;
-    if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_beam_step_biased");
+    if (moving)
+      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
+                   "mv_op_beam_step_motion");
+    else if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_beam_step_biased");
     else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     DevBuf<float> dl, dp, dn;
@@ -324,12 +374,23 @@ int mv_op_beam_step_biased(int device, const float* logits, const float* prev_lo
                       bias, true);
 }
 
+int mv_op_beam_step_motion(int device, const float* logits, const float* prev_logprob,
+                           const uint8_t* allowed, const float* bias, const mv_step_motion* motion,
+                           int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
+                           float gamma, int32_t fix_num_timestep, float* new_logprob, int32_t* ids,
+                           int32_t* parents) {
+  return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
+                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
+                      bias, bias != nullptr, motion, true);
+}
+
 static int op_sbs_step(int device, const float* logits, const float* prev_phi,
                        const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
                        int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                        float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents,
                        const uint8_t* allowed, bool masked, const float* bias = nullptr,
-                       bool biased = false) {
+                       bool biased = false, const mv_step_motion* motion = nullptr,
+                       bool moving = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
     MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
@@ -337,8 +398,13 @@ static int op_sbs_step(int device, const float* logits, const float* prev_phi,
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
+    OpMotionBufs mb;
     StepMask mask;
-    if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_sbs_step_biased");
+    if (moving)
+      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
+                   "mv_op_sbs_step_motion");
+    else if (biased)
+      op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_sbs_step_biased");
     else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     const size_t R = (size_t)N * B;
@@ -386,16 +452,28 @@ int mv_op_sbs_step_biased(int device, const float* logits, const float* prev_phi
                      allowed != nullptr, bias, true);
 }
 
+int mv_op_sbs_step_motion(int device, const float* logits, const float* prev_phi,
+                          const float* prev_logprob, const float* prev_gumbel,
+                          const uint8_t* allowed, const float* bias, const mv_step_motion* motion,
+                          int32_t N, int32_t B, int32_t K, int32_t t, float temperature,
+                          uint32_t seed, float* new_phi, float* new_logprob, float* new_gumbel,
+                          int32_t* ids, int32_t* parents) {
+  return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
+                     allowed != nullptr, bias, bias != nullptr, motion, true);
+}
+
 static int op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K,
                           int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
                           int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep,
                           const uint8_t* allowed, bool masked, const float* bias = nullptr,
-                          bool biased = false) {
+                          bool biased = false, const mv_step_motion* motion = nullptr,
+                          bool moving = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
                (int)R, (int)S);
-    require_row_fits_wave("mv_op_sample_step", K);
+    require_row_fits_wave(moving ? "mv_op_sample_step_motion" : "mv_op_sample_step", K);
     MV_REQUIRE(temperature > 0.f, "mv_op_sample_step: temperature %g must be > 0",
                (double)temperature);
     MV_REQUIRE(top_k >= 0, "mv_op_sample_step: top_k %d must be >= 0 (0 = off)", (int)top_k);
@@ -405,8 +483,12 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
+    OpMotionBufs mb;
     StepMask mask;
-    if (biased)
+    if (moving)
+      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)(R / S), (size_t)R, K,
+                   "mv_op_sample_step_motion");
+    else if (biased)
       op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)(R / S), K, "mv_op_sample_step_biased");
     else if (masked)
       mask = op_mask_up(ctx, dm, allowed, (size_t)(R / S), K, "mv_op_sample_step_masked");
@@ -450,6 +532,15 @@ int mv_op_sample_step_biased(int device, const float* logits, const uint8_t* all
                              int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
                         qlp, keep, allowed, allowed != nullptr, bias, true);
+}
+
+int mv_op_sample_step_motion(int device, const float* logits, const uint8_t* allowed,
+                             const float* bias, const mv_step_motion* motion, int32_t R, int32_t S,
+                             int32_t K, int32_t t, float temperature, uint32_t seed, int32_t top_k,
+                             float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
+                             uint8_t* keep) {
+  return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
+                        qlp, keep, allowed, allowed != nullptr, bias, bias != nullptr, motion, true);
 }
 
 int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,

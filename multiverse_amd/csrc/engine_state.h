@@ -361,6 +361,18 @@ struct mv_engine {
   bool cbias_set() const { return cbias_tm > 0; }
   int64_t cbias_stride(int K) const { return cbias_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
   int64_t cbias_step(int K) const { return cbias_tm > 1 ? K : 0; }
+  // caller-given motion costs (mv_set_motion_cost; sticky until cleared): ONE
+  // allocation sized for the largest radius, so that the addresses a captured forward holds never
+  // change: vel [N, D, D] at 0, vel_far [N], acc [N, D, D], acc_far [N] at the offsets below.
+  DevBuf<float> motion_dev;
+  int motion_radius = 0;           // 0 = no motion cost
+  bool motion_acc = false;
+  bool motion_set() const { return motion_radius > 0; }
+  static constexpr size_t kMotionCells = (2 * MV_MOTION_MAX_RADIUS + 1) * (2 * MV_MOTION_MAX_RADIUS + 1);
+  size_t motion_vel_far_at() const { return (size_t)cfg.batch_size * kMotionCells; }
+  size_t motion_acc_at() const { return motion_vel_far_at() + (size_t)cfg.batch_size; }
+  size_t motion_acc_far_at() const { return motion_acc_at() + motion_vel_far_at(); }
+  size_t motion_floats() const { return motion_acc_far_at() + (size_t)cfg.batch_size; }
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps

@@ -1475,19 +1475,102 @@ __device__ __forceinline__ void step_row_bias(const float* __restrict__ plane, i
   }
 }
 
+// Caller-given motion costs (include/multiverse_hip.h mv_set_motion_cost): a fourth, MOTION form
+// of the same kernels, instantiated as <J, true, true, true>.  It is the BIASED form whose b[J]
+// is b_eff = (b + vterm) + aterm, with the two terms derived per wave from the row's own path:
+// one instantiation serves motion alone (no bias plane: b = 0.0f) and every combination with a
+// mask and a bias.  Where the row's path lies, per launch:
+//   p1 = prev1[(p1_per_row ? r : n) * p1_stride]
+//   p0 = prev0[(p0_per_row ? (prev0_via ? n * B + prev0_via[r] : r) : n) * p0_stride]
+//        (prev0 == NULL or a value < 0: absent; obs_lens: absent where obs_lens[n] < 2)
+// so that the engine points at the labels and at the ids / parents its steps already write, and
+// no launch and no [R, K] plane is added.  The tables [samples, D, D] hold at most 81 floats per
+// sample and are read through the cache, only by the lanes whose cell lies inside the window.
+struct MotionRow {
+  const float* vel = nullptr;         // [samples, D, D]; NULL: no motion cost
+  const float* vel_far = nullptr;     // [samples]
+  const float* acc = nullptr;         // [samples, D, D] or NULL: no turn term
+  const float* acc_far = nullptr;     // [samples]
+  const int32_t* prev1 = nullptr;
+  const int32_t* prev0 = nullptr;
+  const int32_t* prev0_via = nullptr; // the slot, within the sample, that holds the row's p0
+  const int32_t* obs_lens = nullptr;
+  int32_t p1_stride = 1, p0_stride = 1;
+  int32_t p1_per_row = 1, p0_per_row = 1;
+  int32_t W = 1, radius = 1;
+};
+
+// b[j] = (plane[k] + vterm(k)) + aterm(k) for the owned cells k = lane + 64 j of row r (sample n,
+// B rows per sample); plane == NULL: b = 0.0f.  0.0f past the row.  (y, x) of the owned cells
+// advance by 64 cells per j in (rows, columns) with one carry: no division per cell, and none
+// of a difference of cell indices (W is no power of two on the 9-, 10- and 18-column grids).
+template <int J>
+__device__ __forceinline__ void step_row_motion(const MotionRow& mo,
+                                                const float* __restrict__ plane, int n, int r,
+                                                int B, int K, int lane, float (&b)[J]) {
+  const int W = mo.W, rad = mo.radius, D = 2 * rad + 1;
+  int p1 = mo.prev1[(size_t)(mo.p1_per_row ? r : n) * mo.p1_stride];
+  int p0 = -1;
+  if (mo.prev0) {
+    const int row0 = mo.p0_per_row ? (mo.prev0_via ? n * B + mo.prev0_via[r] : r) : n;
+    p0 = mo.prev0[(size_t)row0 * mo.p0_stride];
+  }
+  if (mo.obs_lens && mo.obs_lens[n] < 2) p0 = -1;
+  p1 = __builtin_amdgcn_readfirstlane(p1);        // the wave's row: uniform
+  p0 = __builtin_amdgcn_readfirstlane(p0);
+  const int y1 = p1 / W, x1 = p1 - y1 * W;
+  const bool turn = mo.acc != nullptr && p0 >= 0;
+  int uy = 0, ux = 0;
+  if (turn) {
+    const int y0 = p0 / W, x0 = p0 - y0 * W;
+    uy = y1 - y0;
+    ux = x1 - x0;
+  }
+  const float* vel = mo.vel + (size_t)n * D * D;
+  const float* acc = turn ? mo.acc + (size_t)n * D * D : nullptr;
+  const float vfar = mo.vel_far[n];
+  const float afar = turn ? mo.acc_far[n] : 0.f;
+  const int qy = 64 / W, qx = 64 - qy * W;        // 64 cells on = qy rows and qx columns on
+  int y = lane / W, x = lane - y * W;
+#pragma unroll
+  for (int j = 0; j < J; ++j) {
+    const int k = lane + 64 * j;
+    float bj = 0.f;
+    if (k < K) {
+      if (plane) bj = plane[k];
+      const int dy = y - y1 + rad, dx = x - x1 + rad;          // inside the window: in [0, D)
+      const bool vin = (unsigned)dy < (unsigned)D && (unsigned)dx < (unsigned)D;
+      bj = bj + (vin ? vel[dy * D + dx] : vfar);
+      float at = 0.f;
+      if (turn) {
+        const int ay = dy - uy, ax = dx - ux;
+        const bool ain = (unsigned)ay < (unsigned)D && (unsigned)ax < (unsigned)D;
+        at = ain ? acc[ay * D + ax] : afar;
+      }
+      bj = bj + at;
+    }
+    b[j] = bj;
+    x += qx;
+    y += qy;
+    if (x >= W) { x -= W; y += 1; }
+  }
+}
+
 // MASKED: amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A cell
 // outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
 // nothing, so an allowed cell's rank counts allowed cells only.
 // BIASED (implies MASKED; amask may be NULL): the candidate is (prev_lp + lp) + b, with
 // b = bias + (r / B) * bias_stride, formed before the mask's -inf and before the ranks.
-template <int J, bool MASKED = false, bool BIASED = false>
+// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of the row.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
 __global__ __launch_bounds__(256)
 void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict__ prev_lp,
                       int R, int B, int K, int time, int diverse, float log_gamma,
                       float* __restrict__ cand, const uint8_t* __restrict__ amask = nullptr,
                       int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                      int64_t bias_stride = 0) {
+                      int64_t bias_stride = 0, MotionRow mo = MotionRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
+  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1519,7 +1602,11 @@ void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict_
   for (int j = 0; j < J; ++j) v[j] = pl + ((v[j] - mx) - lse);
   if constexpr (BIASED) {
     float b[J];
-    step_row_bias<J>(bias + (size_t)(r / B) * bias_stride, K, lane, b);
+    if constexpr (MOTION)
+      step_row_motion<J>(mo, bias ? bias + (size_t)(r / B) * bias_stride : nullptr, r / B, r, B, K,
+                         lane, b);
+    else
+      step_row_bias<J>(bias + (size_t)(r / B) * bias_stride, K, lane, b);
 #pragma unroll
     for (int j = 0; j < J; ++j) v[j] = v[j] + b[j];
   }
@@ -1786,7 +1873,8 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // the proposal differs from the model), and keep(k) = allowed and the limits' predicate.
 // BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): b = bias + n * bias_stride,
 // w = l / temperature + b, the limits order by w, and the score is (lp / temperature + b) + g.
-template <int J, bool MASKED = false, bool BIASED = false>
+// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of row r.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
                         int t, int shared, const uint32_t* __restrict__ params, int floor,
@@ -1794,8 +1882,10 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
                         float* __restrict__ lq_acc, int32_t* __restrict__ ids, int ids_stride,
                         int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out,
                         const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0,
-                        const float* __restrict__ bias = nullptr, int64_t bias_stride = 0) {
+                        const float* __restrict__ bias = nullptr, int64_t bias_stride = 0,
+                        MotionRow mo = MotionRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
+  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1817,7 +1907,10 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   uint32_t am = 0u;
   float b[BIASED ? J : 1];
   if constexpr (BIASED) {
-    step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
+    if constexpr (MOTION)
+      step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, S, K, lane, b);
+    else
+      step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
 #pragma unroll
     for (int j = 0; j < J; ++j) w[j] = w[j] + b[j];
     am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
@@ -1944,7 +2037,8 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 // BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): w = l / temperature + b with
 // b = bias + n * bias_stride; q, the limits' order and the q plane follow w as in
 // sample_step_kernel.
-template <int J, bool MASKED = false, bool BIASED = false>
+// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of parent row r.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
@@ -1952,8 +2046,9 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
                         float* __restrict__ cand, float* __restrict__ lp_plane,
                         float* __restrict__ q_plane, const uint8_t* __restrict__ amask = nullptr,
                         int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                        int64_t bias_stride = 0) {
+                        int64_t bias_stride = 0, MotionRow mo = MotionRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
+  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1970,10 +2065,13 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   uint32_t am = 0u;
   if constexpr (BIASED) {
-    float b[J];
-    step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
+    float bz[J];
+    if constexpr (MOTION)
+      step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, B, K, lane, bz);
+    else
+      step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, bz);
 #pragma unroll
-    for (int j = 0; j < J; ++j) w[j] = w[j] + b[j];
+    for (int j = 0; j < J; ++j) w[j] = w[j] + bz[j];
     am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
   } else if constexpr (MASKED) {
     am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);

@@ -85,9 +85,16 @@ inline BeamStepForm beam_step_form(int K, bool have_cand, bool masked) {
 // a mask -- ONE instantiation, which takes the allowed bits as the in-row bits when no mask plane
 // is given.  A Masked or Biased beam step is a `masked` one to beam_step_form above: it exists in
 // the two-launch form only.
-enum class RowForm { Plain, Masked, Biased };
+enum class RowForm { Plain, Masked, Biased, Motion };
 inline RowForm step_row_form(bool masked, bool biased) {
   return biased ? RowForm::Biased : (masked ? RowForm::Masked : RowForm::Plain);
+}
+// Motion: mv_set_motion_cost, with or without a mask and a bias -- the Biased instantiation plus
+// the terms each wave derives from its row's path, so ONE more instantiation serves every
+// combination (no bias plane: b = 0.0f).  The step kernels only: the occupancy kernels have no
+// such form (mv_beam_occupancy refuses while a motion cost is set).
+inline RowForm step_row_form_motion(bool masked, bool biased, bool motion) {
+  return motion ? RowForm::Motion : step_row_form(masked, biased);
 }
 
 // ------------------------------------------------------------------ graph attention (forward)

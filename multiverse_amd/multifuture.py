@@ -318,6 +318,84 @@ def cell_bias_from_scene(args, scene_onehot_last_frame, class_costs):
   return b.reshape(h, w).astype(np.float32)
 
 
+MOTION_LIMIT = np.float32(-1e30)   # the cost that stands for "never": exp of it is exactly 0
+
+
+def motion_tables(radius, max_step=None, speed_cost=0.0, accel_cost=0.0):
+  """The tables of a motion cost (not in the reference; include/multiverse_hip.h
+  mv_set_motion_cost) for one row, as the dict that feed["motion_cost"] and
+  Engine.set_motion_cost(**tables) take.  With R = radius, D = 2 R + 1 and offsets d, a in
+  [-R, R]^2 (rows, columns), |.|^2 the squared Euclidean length in cells:
+    vel[d] = -speed_cost * |d|^2 where max(|d.y|, |d.x|) <= max_step (everywhere inside the
+             window when max_step is None), else -1e30: at most max_step cells per step
+    vel_far = -1e30 when max_step is given, else -speed_cost * 2 (R + 1)^2
+    acc[a] = -accel_cost * |a|^2, acc_far = -accel_cost * 2 (R + 1)^2: prefer constant velocity
+  acc / acc_far are None when accel_cost is 0 (no turn term)."""
+  R = int(radius)
+  if not 1 <= R <= 4:
+    raise ValueError("motion_tables: radius = %d not in [1, 4]" % R)
+  if max_step is not None and not 1 <= int(max_step) <= R:
+    raise ValueError("motion_tables: max_step = %s not in [1, radius = %d]" % (max_step, R))
+  for name, c in (("speed_cost", speed_cost), ("accel_cost", accel_cost)):
+    if not np.isfinite(c) or c < 0:
+      raise ValueError("motion_tables: %s = %r is not a finite cost >= 0" % (name, c))
+  off = np.arange(-R, R + 1)
+  dy, dx = np.meshgrid(off, off, indexing="ij")
+  sq = (dy * dy + dx * dx).astype(np.float32)
+  far2 = np.float32(2 * (R + 1) ** 2)
+  vel = (-np.float32(speed_cost) * sq).astype(np.float32)
+  vel_far = -np.float32(speed_cost) * far2
+  if max_step is not None:
+    vel[np.maximum(np.abs(dy), np.abs(dx)) > int(max_step)] = MOTION_LIMIT
+    vel_far = MOTION_LIMIT
+  out = {"radius": R, "vel": vel, "vel_far": np.float32(vel_far), "acc": None, "acc_far": None}
+  if accel_cost != 0:
+    out["acc"] = (-np.float32(accel_cost) * sq).astype(np.float32)
+    out["acc_far"] = np.float32(-np.float32(accel_cost) * far2)
+  return out
+
+
+def path_motion_cost(ids, labels, W, tables, obs_lengths=None):
+  """The motion cost each returned path paid: ids int [N, B, T] (the engine's "ids"; -1 past a
+  row's length), labels int [N, T_o] the observed cells, W the grid's columns, tables the dict of
+  `motion_tables` (vel / acc [D, D] or [N, D, D], the far values scalars or [N]) ->
+  float32 [N, B, T], vterm + aterm of every step as mv_set_motion_cost defines them (0 where the
+  id is -1).  obs_lengths [N]: a row observed for one frame pays no turn term at step 0.  Plain
+  numpy on the host: a beam score minus the sum of this over T (and minus the cell bias along the
+  path) is the model's log-probability of the path."""
+  ids = np.asarray(ids)
+  labels = np.asarray(labels)
+  N, B, T = ids.shape
+  R = int(tables["radius"])
+  D = 2 * R + 1
+  vel = np.broadcast_to(np.asarray(tables["vel"], dtype=np.float32), (N, D, D))
+  vel_far = np.broadcast_to(np.asarray(tables["vel_far"], dtype=np.float32), (N,))
+  acc = acc_far = None
+  if tables.get("acc") is not None:
+    acc = np.broadcast_to(np.asarray(tables["acc"], dtype=np.float32), (N, D, D))
+    acc_far = np.broadcast_to(np.asarray(tables["acc_far"], dtype=np.float32), (N,))
+  To = labels.shape[1]
+  out = np.zeros((N, B, T), dtype=np.float32)
+  for n in range(N):
+    lo = To if obs_lengths is None else int(obs_lengths[n])
+    for b in range(B):
+      p1 = int(labels[n, To - 1])
+      p0 = int(labels[n, To - 2]) if lo >= 2 else -1
+      for t in range(T):
+        k = int(ids[n, b, t])
+        if k < 0:
+          break
+        dy, dx = k // W - p1 // W, k % W - p1 % W
+        v = vel[n, dy + R, dx + R] if max(abs(dy), abs(dx)) <= R else vel_far[n]
+        a = np.float32(0.0)
+        if acc is not None and p0 >= 0:
+          ay, ax = dy - (p1 // W - p0 // W), dx - (p1 % W - p0 % W)
+          a = acc[n, ay + R, ax + R] if max(abs(ay), abs(ax)) <= R else acc_far[n]
+        out[n, b, t] = np.float32(v) + np.float32(a)
+        p0, p1 = p1, k
+  return out
+
+
 def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_length=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
@@ -339,7 +417,9 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   "cell_mask_fallback" (positions in `idxs`); padding rows get all ones.
   args.class_costs (a list of (new scene class id, cost in nats); not in the reference): the feed
   carries "cell_bias" float32 [N, K], row n built by `cell_bias_from_scene` from the same frame;
-  padding rows get zeros."""
+  padding rows get zeros.
+  args.motion_cost (the dict of `motion_tables`; not in the reference): the feed carries
+  "motion_cost", the same tables for every real row and zero tables for the padding rows."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
@@ -419,6 +499,22 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
       last = inputs["scene_feats"][int(np.asarray(inputs["obs_scene"][idxs[r]])[-1][0])]
       bias[r] = cell_bias_from_scene(args, last, class_costs).reshape(-1)
     feed["cell_bias"] = bias
+  motion = getattr(args, "motion_cost", None)
+  if motion:
+    # one row's tables for every real row; a padding row pays nothing
+    D = 2 * int(motion["radius"]) + 1
+    pad = np.arange(N) >= n_real
+    cost = {"radius": int(motion["radius"])}
+    for key, shape in (("vel", (N, D, D)), ("vel_far", (N,)), ("acc", (N, D, D)),
+                       ("acc_far", (N,))):
+      one = motion.get(key)
+      if one is None:
+        cost[key] = None
+        continue
+      full = np.broadcast_to(np.asarray(one, dtype="float32"), shape).copy()
+      full[pad] = 0
+      cost[key] = full
+    feed["motion_cost"] = cost
   return feed, n_real
 
 

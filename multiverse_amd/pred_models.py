@@ -335,7 +335,8 @@ class Model(object):
     """-> (grid_pred_class list_s, grid_pred_reg list_s, beam_outputs).  The feed goes to the
     engine as it is: "pred_lengths", "obs_lengths", "cell_mask" ([N, K] or [N, Tm, K] allowed
     cells of a multi-future decode, Engine.set_cell_mask) and "cell_bias" (float32 cell costs of
-    the same shapes, Engine.set_cell_bias) are set when present, cleared when absent."""
+    the same shapes, Engine.set_cell_bias) are set when present, cleared when absent; so is
+    "motion_cost" (the dict of multifuture.motion_tables, Engine.set_motion_cost)."""
     cfg = self.config
     compact = bool(feed.get("compact", False))
     if getattr(cfg, "use_beam_search", False):
