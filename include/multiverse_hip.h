@@ -568,6 +568,51 @@ int  mv_set_motion_cost(mv_handle h, int32_t radius,
                         const float* acc     /* [N, D, D] or NULL: no turn term */,
                         const float* acc_far /* [N]; NULL exactly when acc is */);
 
+/* ---- revisit cost: a per-row penalty for paths that return to a cell they left (not in the
+ * reference; defined here) ------------------------------------------------------------------
+ * The first constraint on a WHOLE path: what a step costs depends on every cell the path has held,
+ * not on its last two.  The grid, the cell numbering, p1, the parent order of a slot's path and
+ * the condition K <= 1024 are those of mv_set_motion_cost.  For the row or slot (n, s) at decode
+ * step t the visited set V is
+ *   with seed_observed != 0: the row's own observed cells labels[n, obs_len - Lo[n] .. obs_len - 1]
+ *        (Lo[n] from mv_set_obs_lengths, obs_len without it; the columns in front of a short track
+ *        are not read),
+ *   plus the cells its path holds at steps 0 .. t - 1: the back-traced ids through the parents for
+ *        the beam search and the sampling without replacement, the row's own ids for the
+ *        independent sampler.
+ *   rterm(k) = cost[n] if k is in V and k != p1, else exactly 0.0f.  Staying in the current cell is
+ *        never a revisit (a cell is about 60 px wide and a pedestrian often stays); the path
+ *        A, A, B, A pays once, at its last step.
+ *   b_eff[k] = b_m[k] + rterm(k)   in float32; b_m is the motion b_eff of mv_set_motion_cost when a
+ *        motion cost is set, otherwise the step's bias plane, or 0.0f without one.
+ * Everything mv_set_cell_bias and mv_set_motion_cost define then holds with this b_eff: the beam
+ * candidate (prev_lp + lp) + b_eff, formed before the mask's -inf and before the diversity ranks;
+ * the samplers' w = l / tau + b_eff and the limits ordered by w; qlogprobs and the
+ * without-replacement q plane, written whenever a revisit cost is set; the two-launch beam step;
+ * lp, logits and logprobs stay the model's; the carried and returned beam score includes every
+ * step's rterm (multifuture.path_revisit_cost recomputes them on the host).  mv_score_futures
+ * neither reads nor changes the cost.
+ * cost[n] is any finite float.  0 is the identity.  -1e30 means "never", with the semantics of the
+ * motion LIMIT: the samplers never draw such a cell while another is allowed, and a beam or
+ * without-replacement slot that cannot be filled otherwise takes one, deterministically (ties by
+ * index), and carries the -1e30 in its score.
+ * Sticky as the motion cost is, and combined with mv_set_cell_mask, mv_set_cell_bias,
+ * mv_set_motion_cost, mv_set_pred_lengths and mv_set_obs_lengths in the same way: row n equals its
+ * own uniform forward under its own cost.  The call synchronises the stream and rewrites one
+ * engine-owned allocation; the visited sets live in a second one (256 B per row and step parity),
+ * maintained by the step kernels themselves: no launch is added.  The graph key carries whether a
+ * cost is set and seed_observed, not the values, so a replay follows new values without
+ * re-capture.
+ * Identity, eager and graph: with none set no launch differs (the same kernels, the same graph
+ * keys, mv_graph_captures unchanged).  With all-zero costs every output that both handles define
+ * is bit-identical to the handle without one (b + 0.0f turns a bias of -0.0f into +0.0f, as under
+ * a motion cost).
+ * Errors, each message naming its cause: a greedy handle; a NaN or +-inf (the message names n); a
+ * grid of more than 1024 cells (at the forward); mv_train_*, mv_submit_greedy and
+ * mv_beam_occupancy while one is set. */
+int  mv_set_revisit_cost(mv_handle h, const float* cost /* [N]; NULL clears */,
+                         int32_t seed_observed);
+
 /* ---- scoring given futures (not in the reference) ------------------------------------------
  * The teacher-forced log-likelihood of F = beam_size GIVEN futures per batch row under the class
  * decoder: the forward of mv_set_sampling with every id given instead of drawn.  Decode step t
@@ -927,6 +972,43 @@ int  mv_op_sample_step_motion(int device, const float* logits /* [R, K] */,
                               int32_t t, float temperature, uint32_t seed, int32_t top_k,
                               float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
                               uint8_t* keep /* [R, K] */);
+
+/* The path forms of the three step ops (mv_set_revisit_cost above): the motion prototype with
+ * `revisit` directly behind `motion`; `allowed`, `bias` and `motion` may all be NULL.  The op has
+ * no parent indirection and takes byte planes: visited[r, k] != 0 means cell k is in row r's set
+ * going INTO the step; the kernel ORs prev1[r] in, charges cost[sample] on the set without
+ * prev1[r], and visited_out (if given) receives the set it stored.  A row the step does not run
+ * (slots > 0 of the first beam / without-replacement step) stores nothing: its visited_out is its
+ * visited. */
+typedef struct mv_step_revisit {
+  const float* cost;        /* [samples] */
+  const int32_t* prev1;     /* [rows], in [0, K) */
+  const uint8_t* visited;   /* [rows, K] bytes, non-zero = in the row's set; NULL = empty */
+  uint8_t* visited_out;     /* [rows, K] or NULL: the set the kernel stored, visited | {prev1} */
+} mv_step_revisit;
+int  mv_op_beam_step_path(int device, const float* logits, const float* prev_logprob,
+                          const uint8_t* allowed /* [N, K] or NULL */,
+                          const float* bias /* [N, K] or NULL */,
+                          const mv_step_motion* motion /* or NULL */,
+                          const mv_step_revisit* revisit, int32_t N, int32_t B, int32_t K,
+                          int32_t time, int32_t diverse, float gamma, int32_t fix_num_timestep,
+                          float* new_logprob, int32_t* ids, int32_t* parents);
+int  mv_op_sbs_step_path(int device, const float* logits, const float* prev_phi,
+                         const float* prev_logprob, const float* prev_gumbel,
+                         const uint8_t* allowed /* [N, K] or NULL */,
+                         const float* bias /* [N, K] or NULL */,
+                         const mv_step_motion* motion /* or NULL */,
+                         const mv_step_revisit* revisit, int32_t N, int32_t B, int32_t K,
+                         int32_t t, float temperature, uint32_t seed, float* new_phi,
+                         float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents);
+int  mv_op_sample_step_path(int device, const float* logits /* [R, K] */,
+                            const uint8_t* allowed /* [R / S, K] or NULL */,
+                            const float* bias /* [R / S, K] or NULL */,
+                            const mv_step_motion* motion /* or NULL */,
+                            const mv_step_revisit* revisit, int32_t R, int32_t S, int32_t K,
+                            int32_t t, float temperature, uint32_t seed, int32_t top_k,
+                            float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
+                            uint8_t* keep /* [R, K] */);
 
 /* Light cone of the class encoder (MV_ENC_CONE): the wave tiles of the F(3,3) gate
  * kernel each encoder step computes, as every upload builds them from the labels.  Host only: no

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = [
     "mv_op_decode_tail",
     "mv_set_motion_cost", "mv_op_beam_step_motion", "mv_op_sbs_step_motion",
     "mv_op_sample_step_motion",
+    "mv_set_revisit_cost", "mv_op_beam_step_path", "mv_op_sbs_step_path",
+    "mv_op_sample_step_path",
 ]
 
 
@@ -123,6 +125,11 @@ class mv_step_motion(C.Structure):
 
 
 MV_MOTION_MAX_RADIUS = 4
+
+
+class mv_step_revisit(C.Structure):
+  """The revisit argument of the three `_path` step ops (include/multiverse_hip.h)."""
+  _fields_ = [("cost", _fp), ("prev1", _ip), ("visited", _u8p), ("visited_out", _u8p)]
 
 
 class mv_inputs_compact(C.Structure):
@@ -290,6 +297,19 @@ def load():
     lib.mv_op_sample_step_motion.argtypes = [C.c_int, _fp, _u8p, _fp, _mp, C.c_int32, C.c_int32,
                                              C.c_int32, C.c_int32, C.c_float, C.c_uint32,
                                              C.c_int32, C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
+  if hasattr(lib, "mv_set_revisit_cost"):   # (as above)
+    _mp = C.POINTER(mv_step_motion)
+    _rp = C.POINTER(mv_step_revisit)
+    lib.mv_set_revisit_cost.argtypes = [h, _fp, C.c_int32]
+    lib.mv_op_beam_step_path.argtypes = [C.c_int, _fp, _fp, _u8p, _fp, _mp, _rp, C.c_int32,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                         C.c_int32, _fp, _ip, _ip]
+    lib.mv_op_sbs_step_path.argtypes = [C.c_int, _fp, _fp, _fp, _fp, _u8p, _fp, _mp, _rp,
+                                        C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                        C.c_uint32, _fp, _fp, _fp, _ip, _ip]
+    lib.mv_op_sample_step_path.argtypes = [C.c_int, _fp, _u8p, _fp, _mp, _rp, C.c_int32,
+                                           C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_uint32,
+                                           C.c_int32, C.c_float, C.c_int32, _ip, _fp, _fp, _u8p]
   lib.mv_last_forward_gate_rows.argtypes = [h, C.POINTER(C.c_int64)]
   lib.mv_set_sampling.argtypes = [h, C.c_int32, C.c_float, C.c_uint32]
   lib.mv_set_sampling_mode.argtypes = [h, C.c_int32]
@@ -613,6 +633,7 @@ class Engine(object):
     self._set_feed_cell_mask(feed.get("cell_mask"))
     self._set_feed_cell_bias(feed.get("cell_bias"))
     self._set_feed_motion_cost(feed.get("motion_cost"))
+    self._set_feed_revisit_cost(feed.get("revisit_cost"))
     return inp
 
   def _set_pred_lengths(self, lengths):
@@ -778,6 +799,41 @@ class Engine(object):
                          cost.get("acc_far"))
     self._motion_cost_from_feed = True
 
+  def set_revisit_cost(self, cost, seed_observed=True):
+    """A per-row penalty for paths that return to a cell they left (include/multiverse_hip.h
+    mv_set_revisit_cost): a step into a cell the row's path (and, with seed_observed, its observed
+    track) has held before, other than the one it is in, pays cost[n].  cost float32 [N], or a
+    scalar taken for every row; every value finite, "never" is the cost -1e30
+    (multifuture.MOTION_LIMIT); None clears.  Sticky, with the rule of set_motion_cost: a cost set
+    here stays through every later feed that has no "revisit_cost" key; one that a feed brought is
+    cleared by the next feed without the key.  The beam search and both samplers read it;
+    score_futures does not, and beam_occupancy refuses while one is set."""
+    self._revisit_cost_from_feed = False
+    if cost is None:
+      check(self.lib.mv_set_revisit_cost(self.handle, None, 0), self.handle)
+      self._revisit_cost_set = False
+      return
+    N = self.cfg.batch_size
+    c = np.asarray(cost, dtype=np.float32)
+    if c.ndim == 0:
+      c = np.broadcast_to(c, (N,))
+    if c.shape != (N,):
+      raise MvError("revisit_cost: cost has shape %s, not [N=%d]" % (tuple(c.shape), N))
+    c = f32(c)
+    check(self.lib.mv_set_revisit_cost(self.handle, fptr(c), 1 if seed_observed else 0),
+          self.handle)
+    self._revisit_cost_set = True
+
+  def _set_feed_revisit_cost(self, cost):
+    """feed["revisit_cost"]: {"cost": [N] or a scalar, "seed_observed": bool (default True)},
+    with the feed-scoped rule of feed["motion_cost"]."""
+    if cost is None:
+      if getattr(self, "_revisit_cost_from_feed", False):
+        self.set_revisit_cost(None)
+      return
+    self.set_revisit_cost(cost["cost"], cost.get("seed_observed", True))
+    self._revisit_cost_from_feed = True
+
   def graph_captures(self):
     """Forwards captured into a hipGraph on this handle so far (a replay does not count)."""
     n = C.c_int64()
@@ -822,7 +878,8 @@ class Engine(object):
     top_k, top_p = getattr(self, "_sampling_limits", (0, 1.0))
     return getattr(self, "_sampling_on", False) and \
         (top_k > 0 or top_p < 1.0 or getattr(self, "_cell_mask_set", False) or
-         getattr(self, "_cell_bias_set", False) or getattr(self, "_motion_cost_set", False))
+         getattr(self, "_cell_bias_set", False) or getattr(self, "_motion_cost_set", False) or
+         getattr(self, "_revisit_cost_set", False))
 
   def beam_proposal_logprobs(self):
     """float32 [N, B]: the log-probability of each future of the last SAMPLED forward under the
@@ -1046,6 +1103,7 @@ class Engine(object):
     self._set_feed_cell_mask(feed.get("cell_mask"))
     self._set_feed_cell_bias(feed.get("cell_bias"))
     self._set_feed_motion_cost(feed.get("motion_cost"))
+    self._set_feed_revisit_cost(feed.get("revisit_cost"))
     check(self.lib.mv_upload_inputs_compact(self.handle, C.byref(inp)), self.handle)
     if feed.get("pred_xy") is not None and getattr(self, "_tc", None) is not None:
       Tp = inp.pred_len
@@ -1568,8 +1626,27 @@ def _step_motion(motion, samples, rows):
   return m, keep
 
 
+def _step_revisit(revisit, samples, rows, K):
+  """revisit: a dict with cost [samples], prev1 int32 [rows] and, optionally, visited [rows, K]
+  (non-zero = in the row's set going into the step; absent = empty) -> (mv_step_revisit, the
+  arrays it points into, visited_out uint8 [rows, K] that the op fills with the stored sets)."""
+  m = mv_step_revisit()
+  cost = f32(np.asarray(revisit["cost"], dtype=np.float32).reshape(samples))
+  p1 = np.ascontiguousarray(np.asarray(revisit["prev1"], dtype=np.int32).reshape(rows))
+  out = np.zeros((rows, K), dtype=np.uint8)
+  keep = [cost, p1, out]
+  m.cost, m.prev1 = fptr(cost), iptr(p1)
+  if revisit.get("visited") is not None:
+    v = np.ascontiguousarray((np.asarray(revisit["visited"]).reshape(rows, K) != 0)
+                             .astype(np.uint8))
+    keep.append(v)
+    m.visited = v.ctypes.data_as(_u8p)
+  m.visited_out = out.ctypes.data_as(_u8p)
+  return m, keep, out
+
+
 def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device=0,
-                 allowed=None, bias=None, motion=None):
+                 allowed=None, bias=None, motion=None, revisit=None):
   """allowed [N, K] (non-zero = the cell may be chosen): the masked step, mv_op_beam_step_masked.
   bias [N, K] float32 cell costs: the biased step, mv_op_beam_step_biased (allowed optional).
   motion (the dict of `_step_motion`, prev1 / prev0 [N, B]): the step under a motion cost,
@@ -1580,6 +1657,19 @@ def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device
   new_lp = np.empty((N, B), dtype=np.float32)
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if revisit is not None:
+    # mv_op_beam_step_path (the dict of `_step_revisit`, prev1 / visited per row [N, B]; allowed,
+    # bias and motion optional) -> (new_lp, ids, parents, visited_out bool [N, B, K])
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K) if bias is not None else None
+    m, keep = _step_motion(motion, N, N * B) if motion is not None else (None, None)
+    rv, alive, vout = _step_revisit(revisit, N, N * B, K)
+    check(lib.mv_op_beam_step_path(device, fptr(logits), fptr(prev_lp), ap,
+                                   fptr(bz) if bz is not None else None,
+                                   C.byref(m) if m is not None else None, C.byref(rv), N, B, K,
+                                   int(time), 1 if diverse else 0, float(gamma),
+                                   int(fix_num_timestep), fptr(new_lp), iptr(ids), iptr(parents)))
+    return new_lp, ids, parents, vout.reshape(N, B, K).astype(bool)
   if motion is not None:
     a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, N, K) if bias is not None else None
@@ -1611,7 +1701,7 @@ def op_beam_step(logits, prev_lp, time, diverse, gamma, fix_num_timestep, device
 
 
 def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, device=0,
-                allowed=None, bias=None, motion=None):
+                allowed=None, bias=None, motion=None, revisit=None):
   """One step of the sampling without replacement (mv_op_sbs_step): logits [N, B, K], prev_*
   [N, B] -> (new_phi, new_logprob, new_gumbel, ids, parents), each [N, B].  allowed [N, K]: the
   masked step (mv_op_sbs_step_masked).  bias [N, K]: the biased step (mv_op_sbs_step_biased;
@@ -1622,6 +1712,17 @@ def op_sbs_step(logits, prev_phi, prev_lp, prev_g, t, temperature=1.0, seed=0, d
   phi, lp, g = (np.empty((N, B), dtype=np.float32) for _ in range(3))
   ids = np.empty((N, B), dtype=np.int32)
   parents = np.empty((N, B), dtype=np.int32)
+  if revisit is not None:      # mv_op_sbs_step_path: the rest optional; + visited_out [N, B, K]
+    a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, N, K) if bias is not None else None
+    m, keep = _step_motion(motion, N, N * B) if motion is not None else (None, None)
+    rv, alive, vout = _step_revisit(revisit, N, N * B, K)
+    check(lib.mv_op_sbs_step_path(device, fptr(logits), fptr(prev_phi), fptr(prev_lp),
+                                  fptr(prev_g), ap, fptr(bz) if bz is not None else None,
+                                  C.byref(m) if m is not None else None, C.byref(rv), N, B, K,
+                                  int(t), float(temperature), int(seed) & 0xFFFFFFFF, fptr(phi),
+                                  fptr(lp), fptr(g), iptr(ids), iptr(parents)))
+    return phi, lp, g, ids, parents, vout.reshape(N, B, K).astype(bool)
   if motion is not None:       # mv_op_sbs_step_motion: allowed and bias optional
     a, ap = _allowed_plane(allowed, N, K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, N, K) if bias is not None else None
@@ -1760,7 +1861,7 @@ def op_decode_tail(chains, act=0, next="embed", planes=None, separate=False, dev
 
 
 def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, floor=1, device=0,
-                   allowed=None, bias=None, motion=None):
+                   allowed=None, bias=None, motion=None, revisit=None):
   """One step of the independent sampler under top-k / nucleus limits (mv_op_sample_step):
   logits [R, K], row r = future r % S of sample r // S -> (ids int32 [R], lp [R] the model's
   log-probability of the drawn cell, qlp [R] the proposal's, keep bool [R, K] the kept set).
@@ -1772,6 +1873,18 @@ def op_sample_step(logits, S, t, temperature=1.0, seed=0, top_k=0, top_p=1.0, fl
   ids = np.empty(R, dtype=np.int32)
   lp, qlp = (np.empty(R, dtype=np.float32) for _ in range(2))
   keep = np.empty((R, K), dtype=np.uint8)
+  if revisit is not None:      # mv_op_sample_step_path: the rest optional; + visited_out [R, K]
+    a, ap = _allowed_plane(allowed, R // int(S), K) if allowed is not None else (None, None)
+    bz = _bias_plane(bias, R // int(S), K) if bias is not None else None
+    m, alive = _step_motion(motion, R // int(S), R) if motion is not None else (None, None)
+    rv, alive2, vout = _step_revisit(revisit, R // int(S), R, K)
+    check(lib.mv_op_sample_step_path(device, fptr(logits), ap,
+                                     fptr(bz) if bz is not None else None,
+                                     C.byref(m) if m is not None else None, C.byref(rv), R, int(S),
+                                     K, int(t), float(temperature), int(seed) & 0xFFFFFFFF,
+                                     int(top_k), float(top_p), int(floor), iptr(ids), fptr(lp),
+                                     fptr(qlp), keep.ctypes.data_as(_u8p)))
+    return ids, lp, qlp, keep.astype(bool), vout.astype(bool)
   if motion is not None:       # mv_op_sample_step_motion (prev1 / prev0 [R]): the rest optional
     a, ap = _allowed_plane(allowed, R // int(S), K) if allowed is not None else (None, None)
     bz = _bias_plane(bias, R // int(S), K) if bias is not None else None

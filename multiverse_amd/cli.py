@@ -252,6 +252,13 @@ _MF_FLAGS = [
     # the tables, M <= R <= 4.  They combine with --allowed_classes and --class_costs.
     ("--max_step_cells", int, None), ("--speed_cost", float, 0.0), ("--accel_cost", float, 0.0),
     ("--motion_radius", int, 2),
+    # not in the reference: the revisit cost (the engine keeps every path's visited cells beside
+    # its slot: mv_set_revisit_cost).  --revisit_cost c: a step back into a cell the path (or the
+    # observed track) has left costs c nats; --no_revisit: never, while another cell is allowed;
+    # --revisit_ignore_observed: only the predicted cells count.  They combine with the three
+    # features above.
+    ("--revisit_cost", float, None), ("--no_revisit", B, None),
+    ("--revisit_ignore_observed", B, None),
 ]
 
 
@@ -290,6 +297,7 @@ def multifuture_inference_main(argv=None):
   parse_allowed_classes(args)
   parse_class_costs(args)
   parse_motion_cost(args)
+  parse_revisit_cost(args)
   traj_files = glob(os.path.join(args.traj_path, "*.txt"))
   traj_ids = [os.path.splitext(os.path.basename(one))[0] for one in traj_files]
   gt_trajs = mf.load_gt(args.multifuture_path, traj_ids)
@@ -412,6 +420,36 @@ def parse_motion_cost(args):
     if not np.isfinite(c) or c < 0:
       raise SystemExit("%s %r: a cost is a finite number of nats >= 0" % (flag, c))
   args.motion_cost = mf.motion_tables(R, M, args.speed_cost, args.accel_cost)
+
+
+def parse_revisit_cost(args):
+  """--revisit_cost / --no_revisit / --revisit_ignore_observed -> args.revisit_cost, the dict
+  {"cost", "seed_observed"} of multifuture.inference_feed (None when neither of the first two is
+  given); refused with --greedy (the greedy decode chooses by argmax and reads no cost), with
+  --score_gt, and with each other where they contradict."""
+  from multiverse_amd import multifuture as mf
+  cost = getattr(args, "revisit_cost", None)
+  never = bool(getattr(args, "no_revisit", False))
+  ignore = bool(getattr(args, "revisit_ignore_observed", False))
+  args.revisit_cost = None
+  given = [f for f, on in (("--revisit_cost", cost is not None), ("--no_revisit", never)) if on]
+  if not given:
+    if ignore:
+      raise SystemExit("--revisit_ignore_observed says what a revisit cost counts; give "
+                       "--revisit_cost or --no_revisit with it")
+    return
+  if len(given) == 2:
+    raise SystemExit("--revisit_cost and --no_revisit contradict each other: a cost in nats, or "
+                     "never")
+  if args.greedy:
+    raise SystemExit("%s shapes the beam search and the samplers; it does not combine with "
+                     "--greedy" % given[0])
+  if args.score_gt is not None:
+    raise SystemExit("%s shapes a decode; --score_gt decodes nothing" % given[0])
+  if not never and (not np.isfinite(cost) or cost < 0):
+    raise SystemExit("--revisit_cost %r: a cost is a finite number of nats >= 0" % (cost,))
+  args.revisit_cost = {"cost": float(mf.MOTION_LIMIT) if never else -float(cost),
+                       "seed_observed": not ignore}
 
 
 def print_exact_nll(result):

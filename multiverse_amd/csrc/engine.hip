@@ -473,6 +473,33 @@ int mv_set_motion_cost(mv_handle h, int32_t radius, const float* vel, const floa
   });
 }
 
+int mv_set_revisit_cost(mv_handle h, const float* cost, int32_t seed_observed) {
+  if (!h) return 1;
+  return guarded(h, [&] {
+    MV_REQUIRE(h->cfg.beam_size > 1, "mv_set_revisit_cost: engine was created with beam_size 1 (the "
+               "greedy forward chooses by argmax and reads no cost: create a beam handle)");
+    // behind whatever forward still reads the previous cost on the device
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (!cost) {
+      h->revisit_on = false;
+      h->revisit_seed = false;
+      return;
+    }
+    const size_t N = (size_t)h->cfg.batch_size;
+    // a cost is finite: "never" is the cost -1e30, a veto of a cell is the mask's job
+    for (size_t n = 0; n < N; ++n)
+      MV_REQUIRE(std::isfinite(cost[n]), "mv_set_revisit_cost: cost[n = %d] = %g is not finite (a "
+                 "cost is a finite float32; \"never\" is the cost -1e30)", (int)n, (double)cost[n]);
+    // allocated once: the addresses a captured forward holds never change
+    h->revisit_dev.alloc(N);
+    h->revisit_sets.alloc(2 * h->revisit_set_words());
+    HIP_CHECK(hipMemset(h->revisit_sets.p, 0, 2 * h->revisit_set_words() * sizeof(uint32_t)));
+    HIP_CHECK(hipMemcpy(h->revisit_dev.p, cost, N * sizeof(float), hipMemcpyHostToDevice));
+    h->revisit_on = true;
+    h->revisit_seed = seed_observed != 0;
+  });
+}
+
 int mv_graph_captures(mv_handle h, int64_t* captures) {
   if (!h) return 1;
   return guarded(h, [&] {
@@ -617,6 +644,8 @@ int mv_submit_greedy(mv_handle h, const mv_inputs* in) {
                "greedy forward chooses by argmax and reads no bias -- clear it first");
     MV_REQUIRE(!h->motion_set(), "mv_submit_greedy: a motion cost is set (mv_set_motion_cost); the "
                "greedy forward chooses by argmax and reads no cost -- clear it first");
+    MV_REQUIRE(!h->revisit_set(), "mv_submit_greedy: a revisit cost is set (mv_set_revisit_cost); "
+               "the greedy forward chooses by argmax and reads no cost -- clear it first");
     pipeline_submit(h, in);
   });
 }
@@ -661,6 +690,8 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
                "cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
                "no cells -- clear it first", "mv_train_init");
+    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
+               "chooses no cells -- clear it first", "mv_train_init");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -716,6 +747,8 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
                "cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
                "no cells -- clear it first", "mv_train_forward_backward");
+    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
+               "chooses no cells -- clear it first", "mv_train_forward_backward");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -787,6 +820,8 @@ int mv_train_apply(mv_handle h, float grad_scale) {
                "cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
                "no cells -- clear it first", "mv_train_apply");
+    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
+               "chooses no cells -- clear it first", "mv_train_apply");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -807,6 +842,8 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
                "cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
                "no cells -- clear it first", "mv_train_step");
+    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
+               "chooses no cells -- clear it first", "mv_train_step");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "

@@ -1188,6 +1188,35 @@ void step_motion(const mv_engine* e, const ScaleState& S, int t, const int32_t* 
   }
 }
 
+// The revisit cost of decode step t (mv_set_revisit_cost): the cost, the half of the engine's set
+// buffer that holds every row's visited set of step t - 1 and the half step t stores into, and
+// where the row's p1 lies (as step_motion finds it).  At t == 0 there is no set yet: the kernel
+// starts from the row's observed cells (seed_observed) or from nothing, and p1 -- the last
+// observed cell -- joins the set only as one of those.  parents (beam, wor): [T, R], or NULL for
+// rows that continue themselves.  No launch is added.  None set: m is left as it is.
+void step_revisit(const mv_engine* e, const ScaleState& S, int t, const int32_t* ids,
+                  size_t ids_step, int ids_stride, const int32_t* parents, StepMask& m) {
+  if (!e->revisit_set()) return;
+  const int T = e->cfg.obs_len, R = e->cfg.batch_size * e->cfg.beam_size;
+  mv::RevisitRow& rv = m.rv;
+  rv.cost = e->revisit_dev.p;
+  rv.set_out = e->revisit_sets.p + (size_t)(t & 1) * e->revisit_set_words();
+  if (t == 0) {
+    rv.prev1 = S.labels.p + (T - 1); rv.p1_stride = T; rv.p1_per_row = 0;
+    rv.or_p1 = 0;
+    if (e->revisit_seed) {
+      rv.seed = S.labels.p;
+      rv.seed_T = T;
+      // the columns in front of a short track are not read (right-aligned observations)
+      rv.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
+    }
+    return;
+  }
+  rv.set_in = e->revisit_sets.p + (size_t)((t - 1) & 1) * e->revisit_set_words();
+  rv.via = parents ? parents + (size_t)(t - 1) * R : nullptr;
+  rv.prev1 = ids + (size_t)(t - 1) * ids_step; rv.p1_stride = ids_stride; rv.p1_per_row = 1;
+}
+
 // Beam-search class decoder (grid_decoder_beam_search,
 // code/pred_models.py:474-806) with the un-beamed regression decoder advanced
 // in lockstep (its step t shares a launch with beam time t+1).
@@ -1308,6 +1337,7 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
         HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
       StepMask mask = step_mask(e, K, time - 1);
       step_motion(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p, mask);
+      step_revisit(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p, mask);
       if (wor) launch(e, "sbs_step", 0, 16.0 * n_now * B * K, [&] {
         launch_sbs_step(e->issue, logits, e->bm_phi[lpi].p, e->bm_lp[lpi].p, e->bm_g[lpi].p,
                         e->bm_cand.p, e->bm_sbs_lp.p, e->bm_sbs_q.p, e->samp_params.p, n_now, B,
@@ -1463,6 +1493,7 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
         StepMask mask = step_mask(e, K, t);
         // the sampler's rows continue themselves: their path is their own row of the [R, T] ids
         step_motion(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr, mask);
+        step_revisit(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr, mask);
         launch_sample_step(e->issue, logits, orow, rows, B, K, t, shared, e->samp_params.p, 1,
                            lens, e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr,
                            mask);
@@ -1652,6 +1683,9 @@ void run_forward(mv_engine* e, ForwardKind kind) {
   if (beam && kind != ForwardKind::Scored && e->motion_set())
     require_row_fits_wave("mv_set_motion_cost: a step under a motion cost",
                           e->sc[beam_scale(e)].K);
+  if (beam && kind != ForwardKind::Scored && e->revisit_set())
+    require_row_fits_wave("mv_set_revisit_cost: a step under a revisit cost",
+                          e->sc[beam_scale(e)].K);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
@@ -1673,7 +1707,10 @@ void run_forward(mv_engine* e, ForwardKind kind) {
                        3 * (!constrainable || !e->cbias_set() ? 0 : (e->cbias_tm > 1 ? 2 : 1)) +
                        // a captured step bakes in the radius and whether acc is present
                        9 * (!constrainable || !e->motion_set()
-                                ? 0 : 2 * e->motion_radius - 1 + (e->motion_acc ? 1 : 0));
+                                ? 0 : 2 * e->motion_radius - 1 + (e->motion_acc ? 1 : 0)) +
+                       // (the motion member is at most 8) a captured step bakes in whether a
+                       // revisit cost is set and whether it starts from the observed cells
+                       81 * (!constrainable || !e->revisit_set() ? 0 : (e->revisit_seed ? 2 : 1));
   const auto key = std::make_tuple(kind, e->pred_len, e->num_frames, mask_key);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {

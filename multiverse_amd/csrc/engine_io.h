@@ -494,6 +494,8 @@ void beam_occupancy(mv_engine* e, float* out) {
   // (a plane that depends on each future's path has no per-step map of the mixture: left out)
   MV_REQUIRE(!e->motion_set(), "mv_beam_occupancy: a motion cost is set (mv_set_motion_cost); the "
              "occupancy map under a path-dependent cost is not defined -- clear it first");
+  MV_REQUIRE(!e->revisit_set(), "mv_beam_occupancy: a revisit cost is set (mv_set_revisit_cost); "
+             "the occupancy map under a path-dependent cost is not defined -- clear it first");
   const ScaleState& S = e->sc[beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;

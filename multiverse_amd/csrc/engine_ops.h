@@ -315,19 +315,72 @@ static void op_motion_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, OpM
   m.mo.W = mo->W; m.mo.radius = mo->radius;
 }
 
+// the path forms: the cost, every row's p1 and the rows' visited sets go up, packed from the op's
+// byte planes into the device's lane-major words (kernels_misc.h RevisitRow: bit j of word l =
+// cell l + 64 j); `allowed`, `bias` and `motion` may be NULL.  The stored sets start as the given
+// ones, so that a row the step does not run reports its set as given.
+struct OpRevisitBufs {
+  DevBuf<float> cost;
+  DevBuf<int32_t> prev1;
+  DevBuf<uint32_t> in, out;
+  std::vector<uint32_t> words;
+};
+static void op_path_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, OpMotionBufs& mb,
+                       OpRevisitBufs& rb, StepMask& m, const uint8_t* allowed, const float* bias,
+                       const mv_step_motion* mo, const mv_step_revisit* rv, size_t samples,
+                       size_t rows, int K, const char* who) {
+  MV_REQUIRE(rv && rv->cost && rv->prev1, "%s: NULL revisit, cost or prev1", who);
+  require_row_fits_wave(who, K);
+  for (size_t n = 0; n < samples; ++n)
+    MV_REQUIRE(std::isfinite(rv->cost[n]), "%s: cost[n = %d] = %g is not finite", who, (int)n,
+               (double)rv->cost[n]);
+  for (size_t r = 0; r < rows; ++r)
+    MV_REQUIRE(rv->prev1[r] >= 0 && rv->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)", who,
+               (int)r, (int)rv->prev1[r], K);
+  if (mo) op_motion_up(ctx, dm, db, mb, m, allowed, bias, mo, samples, rows, K, who);
+  else if (bias) op_bias_up(ctx, dm, db, m, allowed, bias, samples, K, who);
+  else if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
+  rb.words.assign(rows * 64, 0u);
+  if (rv->visited)
+    for (size_t r = 0; r < rows; ++r)
+      for (int k = 0; k < K; ++k)
+        if (rv->visited[r * K + k]) rb.words[r * 64 + (k & 63)] |= 1u << (k >> 6);
+  ctx.up(rb.cost, rv->cost, samples);
+  ctx.up(rb.prev1, rv->prev1, rows);
+  ctx.up(rb.in, rb.words.data(), rows * 64);
+  ctx.up(rb.out, rb.words.data(), rows * 64);
+  m.rv.cost = rb.cost.p;
+  m.rv.prev1 = rb.prev1.p;
+  m.rv.set_in = rb.in.p;
+  m.rv.set_out = rb.out.p;
+}
+static void op_path_down(OpCtx& ctx, OpRevisitBufs& rb, const mv_step_revisit* rv, size_t rows,
+                         int K) {
+  if (!rv->visited_out) return;
+  ctx.down(rb.words.data(), rb.out, rows * 64);
+  for (size_t r = 0; r < rows; ++r)
+    for (int k = 0; k < K; ++k)
+      rv->visited_out[r * K + k] = (rb.words[r * 64 + (k & 63)] >> (k >> 6)) & 1u;
+}
+
 static int op_beam_step(int device, const float* logits, const float* prev_logprob,
                         int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
                         float gamma, int32_t fix_num_timestep, float* new_logprob,
                         int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked,
                         const float* bias = nullptr, bool biased = false,
-                        const mv_step_motion* motion = nullptr, bool moving = false) {
+                        const mv_step_motion* motion = nullptr, bool moving = false,
+                        const mv_step_revisit* revisit = nullptr, bool path = false) {
   return guarded(nullptr, [&] {
     OpCtx ctx(device);
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
     OpMotionBufs mb;
+    OpRevisitBufs rb;
     StepMask mask;
-    if (moving)
+    if (path)
+      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)N,
+                 (size_t)N * B, K, "mv_op_beam_step_path");
+    else if (moving)
       op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
                    "mv_op_beam_step_motion");
     else if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_beam_step_biased");
@@ -345,6 +398,7 @@ static int op_beam_step(int device, const float* logits, const float* prev_logpr
     ctx.down(new_logprob, dn, (size_t)N * B);
     ctx.down(ids, di, (size_t)N * B);
     ctx.down(parents, dpa, (size_t)N * B);
+    if (path) op_path_down(ctx, rb, revisit, (size_t)N * B, K);
   });
 }
 
@@ -384,13 +438,24 @@ int mv_op_beam_step_motion(int device, const float* logits, const float* prev_lo
                       bias, bias != nullptr, motion, true);
 }
 
+int mv_op_beam_step_path(int device, const float* logits, const float* prev_logprob,
+                         const uint8_t* allowed, const float* bias, const mv_step_motion* motion,
+                         const mv_step_revisit* revisit, int32_t N, int32_t B, int32_t K,
+                         int32_t time, int32_t diverse, float gamma, int32_t fix_num_timestep,
+                         float* new_logprob, int32_t* ids, int32_t* parents) {
+  return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
+                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
+                      bias, bias != nullptr, motion, motion != nullptr, revisit, true);
+}
+
 static int op_sbs_step(int device, const float* logits, const float* prev_phi,
                        const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
                        int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                        float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents,
                        const uint8_t* allowed, bool masked, const float* bias = nullptr,
                        bool biased = false, const mv_step_motion* motion = nullptr,
-                       bool moving = false) {
+                       bool moving = false, const mv_step_revisit* revisit = nullptr,
+                       bool path = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
     MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
@@ -399,8 +464,12 @@ static int op_sbs_step(int device, const float* logits, const float* prev_phi,
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
     OpMotionBufs mb;
+    OpRevisitBufs rb;
     StepMask mask;
-    if (moving)
+    if (path)
+      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)N,
+                 (size_t)N * B, K, "mv_op_sbs_step_path");
+    else if (moving)
       op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
                    "mv_op_sbs_step_motion");
     else if (biased)
@@ -422,6 +491,7 @@ static int op_sbs_step(int device, const float* logits, const float* prev_phi,
                     t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, mask);
     ctx.down(new_phi, nphi, R); ctx.down(new_logprob, nlp, R); ctx.down(new_gumbel, ng, R);
     ctx.down(ids, di, R); ctx.down(parents, dpa, R);
+    if (path) op_path_down(ctx, rb, revisit, R, K);
   });
 }
 
@@ -463,17 +533,31 @@ int mv_op_sbs_step_motion(int device, const float* logits, const float* prev_phi
                      allowed != nullptr, bias, bias != nullptr, motion, true);
 }
 
+int mv_op_sbs_step_path(int device, const float* logits, const float* prev_phi,
+                        const float* prev_logprob, const float* prev_gumbel,
+                        const uint8_t* allowed, const float* bias, const mv_step_motion* motion,
+                        const mv_step_revisit* revisit, int32_t N, int32_t B, int32_t K, int32_t t,
+                        float temperature, uint32_t seed, float* new_phi, float* new_logprob,
+                        float* new_gumbel, int32_t* ids, int32_t* parents) {
+  return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
+                     allowed != nullptr, bias, bias != nullptr, motion, motion != nullptr, revisit,
+                     true);
+}
+
 static int op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K,
                           int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
                           int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep,
                           const uint8_t* allowed, bool masked, const float* bias = nullptr,
                           bool biased = false, const mv_step_motion* motion = nullptr,
-                          bool moving = false) {
+                          bool moving = false, const mv_step_revisit* revisit = nullptr,
+                          bool path = false) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
                (int)R, (int)S);
-    require_row_fits_wave(moving ? "mv_op_sample_step_motion" : "mv_op_sample_step", K);
+    require_row_fits_wave(path ? "mv_op_sample_step_path"
+                          : moving ? "mv_op_sample_step_motion" : "mv_op_sample_step", K);
     MV_REQUIRE(temperature > 0.f, "mv_op_sample_step: temperature %g must be > 0",
                (double)temperature);
     MV_REQUIRE(top_k >= 0, "mv_op_sample_step: top_k %d must be >= 0 (0 = off)", (int)top_k);
@@ -484,8 +568,12 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     DevBuf<uint8_t> dm;
     DevBuf<float> db;
     OpMotionBufs mb;
+    OpRevisitBufs rb;
     StepMask mask;
-    if (moving)
+    if (path)
+      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)(R / S),
+                 (size_t)R, K, "mv_op_sample_step_path");
+    else if (moving)
       op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)(R / S), (size_t)R, K,
                    "mv_op_sample_step_motion");
     else if (biased)
@@ -508,6 +596,7 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     HIP_CHECK(hipGetLastError());
     ctx.down(ids, di, R); ctx.down(lp, dlp, R); ctx.down(qlp, dq, R);
     ctx.down(keep, dk, (size_t)R * K);
+    if (path) op_path_down(ctx, rb, revisit, (size_t)R, K);
   });
 }
 
@@ -541,6 +630,16 @@ int mv_op_sample_step_motion(int device, const float* logits, const uint8_t* all
                              uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
                         qlp, keep, allowed, allowed != nullptr, bias, bias != nullptr, motion, true);
+}
+
+int mv_op_sample_step_path(int device, const float* logits, const uint8_t* allowed,
+                           const float* bias, const mv_step_motion* motion,
+                           const mv_step_revisit* revisit, int32_t R, int32_t S, int32_t K,
+                           int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
+                           int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
+  return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
+                        qlp, keep, allowed, allowed != nullptr, bias, bias != nullptr, motion,
+                        motion != nullptr, revisit, true);
 }
 
 int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,

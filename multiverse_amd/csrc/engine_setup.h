@@ -49,8 +49,13 @@ struct StepMask {
   // the motion cost of the step (mv_set_motion_cost): the tables and where each row's p1 / p0
   // lie at this step; mo.vel == nullptr: none.  With one the launch is the MOTION one.
   mv::MotionRow mo;
+  // the revisit cost of the step (mv_set_revisit_cost): the cost, the rows' visited sets of the
+  // step before and where this step stores its own; rv.cost == nullptr: none.  With one the launch
+  // is the PATH one.
+  mv::RevisitRow rv;
   RowForm form() const {
-    return step_row_form_motion(p != nullptr, bias != nullptr, mo.vel != nullptr);
+    return step_row_form_path(p != nullptr, bias != nullptr, mo.vel != nullptr,
+                              rv.cost != nullptr);
   }
   bool constrained() const { return form() != RowForm::Plain; }
 };
@@ -63,7 +68,8 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
                       int32_t* parents, int32_t* src_row, int rows_per_sample,
                       int32_t* row_ref = nullptr, StepMask mask = StepMask{}) {
   if (mask.constrained()) {
-    require_row_fits_wave(mask.mo.vel ? "beam step under a motion cost"
+    require_row_fits_wave(mask.rv.cost ? "beam step under a revisit cost"
+                          : mask.mo.vel ? "beam step under a motion cost"
                           : mask.bias ? "beam step under a cell bias"
                                       : "beam step under a cell mask", K);
     MV_REQUIRE(cand, "internal: beam step under a cell mask, bias or motion cost without the "
@@ -80,23 +86,27 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Motion)
+    if (mask.form() == RowForm::Path)
+      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true, true, true>), grid, block, 0, stream,
+                         logits, prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p,
+                         mask.stride, mask.bias, mask.bias_stride, mask.mo, mask.rv);
+    else if (mask.form() == RowForm::Motion)
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true, true>), grid, block, 0, stream,
                          logits, prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p,
-                         mask.stride, mask.bias, mask.bias_stride, mask.mo);
+                         mask.stride, mask.bias, mask.bias_stride, mask.mo, mv::RevisitRow{});
     else if (mask.form() == RowForm::Biased)
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true>), grid, block, 0, stream, logits,
                          prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
-                         mask.bias, mask.bias_stride, mv::MotionRow{});
+                         mask.bias, mask.bias_stride, mv::MotionRow{}, mv::RevisitRow{});
     else if (mask.p)
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, true>), grid, block, 0, stream, logits, prev_lp,
                          R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
-                         (const float*)nullptr, (int64_t)0, mv::MotionRow{});
+                         (const float*)nullptr, (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
     else
       hipLaunchKernelGGL((mv::beam_rank_kernel<J, false>), grid, block, 0, stream, logits,
                          prev_lp, R, B, K, time, diverse, log_gamma, cand,
                          (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0,
-                         mv::MotionRow{});
+                         mv::MotionRow{}, mv::RevisitRow{});
   });
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
@@ -122,26 +132,31 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Motion)
+    if (mask.form() == RowForm::Path)
+      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true, true, true>), grid, block, 0,
+                         stream, logits, prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand,
+                         lp_plane, q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
+                         mask.mo, mask.rv);
+    else if (mask.form() == RowForm::Motion)
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true, true>), grid, block, 0, stream,
                          logits, prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand,
                          lp_plane, q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
-                         mask.mo);
+                         mask.mo, mv::RevisitRow{});
     else if (mask.form() == RowForm::Biased)
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true>), grid, block, 0, stream, logits,
                          prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
                          q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
-                         mv::MotionRow{});
+                         mv::MotionRow{}, mv::RevisitRow{});
     else if (mask.p)
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true>), grid, block, 0, stream, logits,
                          prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
                          q_plane, mask.p, mask.stride, (const float*)nullptr, (int64_t)0,
-                         mv::MotionRow{});
+                         mv::MotionRow{}, mv::RevisitRow{});
     else
       hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, false>), grid, block, 0, stream, logits,
                          prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
                          q_plane, (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr,
-                         (int64_t)0, mv::MotionRow{});
+                         (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
   });
   hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
@@ -159,26 +174,31 @@ void launch_sample_step(hipStream_t stream, float* logits, int64_t row_stride, i
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Motion)
+    if (mask.form() == RowForm::Path)
+      hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true, true, true>), grid, block, 0,
+                         stream, logits, row_stride, R, S, K, t, shared, params, floor, lens, lp_acc,
+                         lq_acc, ids, ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
+                         mask.bias_stride, mask.mo, mask.rv);
+    else if (mask.form() == RowForm::Motion)
       hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true, true>), grid, block, 0, stream,
                          logits, row_stride, R, S, K, t, shared, params, floor, lens, lp_acc,
                          lq_acc, ids, ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
-                         mask.bias_stride, mask.mo);
+                         mask.bias_stride, mask.mo, mv::RevisitRow{});
     else if (mask.form() == RowForm::Biased)
       hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true>), grid, block, 0, stream, logits,
                          row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
                          ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
-                         mask.bias_stride, mv::MotionRow{});
+                         mask.bias_stride, mv::MotionRow{}, mv::RevisitRow{});
     else if (mask.p)
       hipLaunchKernelGGL((mv::sample_step_kernel<J, true>), grid, block, 0, stream, logits,
                          row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
                          ids_stride, src_row, keep_out, mask.p, mask.stride, (const float*)nullptr,
-                         (int64_t)0, mv::MotionRow{});
+                         (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
     else
       hipLaunchKernelGGL((mv::sample_step_kernel<J, false>), grid, block, 0, stream, logits,
                          row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
                          ids_stride, src_row, keep_out, (const uint8_t*)nullptr, (int64_t)0,
-                         (const float*)nullptr, (int64_t)0, mv::MotionRow{});
+                         (const float*)nullptr, (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
   });
 }
 

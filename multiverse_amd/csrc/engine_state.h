@@ -373,6 +373,16 @@ struct mv_engine {
   size_t motion_acc_at() const { return motion_vel_far_at() + (size_t)cfg.batch_size; }
   size_t motion_acc_far_at() const { return motion_acc_at() + motion_vel_far_at(); }
   size_t motion_floats() const { return motion_acc_far_at() + (size_t)cfg.batch_size; }
+  // caller-given revisit cost (mv_set_revisit_cost; sticky until cleared): the
+  // cost [N], and the visited sets of every row, [2][N * B][64] words (kernels_misc.h RevisitRow;
+  // step t reads half (t - 1) & 1 and stores half t & 1).  Both allocated once at their largest
+  // size, so that the addresses a captured forward holds never change.
+  DevBuf<float> revisit_dev;
+  DevBuf<uint32_t> revisit_sets;
+  bool revisit_on = false;
+  bool revisit_seed = false;       // seed_observed
+  bool revisit_set() const { return revisit_on; }
+  size_t revisit_set_words() const { return (size_t)cfg.batch_size * cfg.beam_size * 64; }
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps

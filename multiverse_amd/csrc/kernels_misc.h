@@ -1556,21 +1556,92 @@ __device__ __forceinline__ void step_row_motion(const MotionRow& mo,
   }
 }
 
+// Caller-given revisit cost (include/multiverse_hip.h mv_set_revisit_cost): a fifth, PATH form of
+// the same kernels, instantiated as <J, true, true, true, true>.  It is the MOTION form with
+// rterm added to b[J]; the motion part runs only when mo.vel is set (a wave-uniform branch), so
+// ONE instantiation serves the revisit cost alone and every combination with a mask, a bias and
+// a motion cost.  The visited set of a row is 64 words, lane-major as the `am` bits are: bit j of
+// word l = cell l + 64 j, so a lane loads one word, ORs one bit and stores one word -- 256 B a row
+// for any K <= 1024, no LDS, no indexed arrays.  The step kernel maintains the sets itself:
+//   set = set_in[(via ? n * B + via[r] : r)]   (set_in == NULL: empty)
+//       | the row's observed cells seed[n, seed_T - Lo[n] .. seed_T - 1]   (seed == NULL: none)
+//       | (or_p1 ? {p1} : {})
+//   set_out[r] = set;   rterm(k) = cost[n] where k is in set and k != p1, else 0.0f
+// with p1 = prev1[(p1_per_row ? r : n) * p1_stride].  set_in and set_out differ (slots read other
+// slots' rows of the step before), so the engine keeps two and alternates.  No bit index is
+// formed from a value outside [0, K).
+struct RevisitRow {
+  const float* cost = nullptr;        // [samples]; NULL: no revisit cost
+  const uint32_t* set_in = nullptr;   // [rows, 64] the sets of the step before, or NULL: empty
+  uint32_t* set_out = nullptr;        // [rows, 64]
+  const int32_t* via = nullptr;       // the slot, within the sample, whose set the row continues
+  const int32_t* prev1 = nullptr;
+  const int32_t* seed = nullptr;      // labels [samples, seed_T], or NULL
+  const int32_t* obs_lens = nullptr;  // Lo [samples], or NULL: seed_T
+  int32_t p1_stride = 1, p1_per_row = 1;
+  int32_t seed_T = 0, or_p1 = 1;
+};
+
+// b[j] = b_m[k] + rterm(k) for the owned cells k = lane + 64 j of row r (sample n, B rows per
+// sample): b_m is step_row_motion's b_eff when a motion cost is set, else the bias plane or 0.0f.
+template <int J>
+__device__ __forceinline__ void step_row_path(const MotionRow& mo, const RevisitRow& rv,
+                                              const float* __restrict__ plane, int n, int r,
+                                              int B, int K, int lane, float (&b)[J]) {
+  static_assert(J <= 32, "one bit per owned cell");
+  if (mo.vel != nullptr) {                       // uniform
+    step_row_motion<J>(mo, plane, n, r, B, K, lane, b);
+  } else {
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+      const int k = lane + 64 * j;
+      b[j] = (plane != nullptr && k < K) ? plane[k] : 0.f;
+    }
+  }
+  int p1 = rv.prev1[(size_t)(rv.p1_per_row ? r : n) * rv.p1_stride];
+  p1 = __builtin_amdgcn_readfirstlane(p1);       // the wave's row: uniform
+  uint32_t set = 0u;
+  if (rv.set_in) {
+    int row = r;
+    if (rv.via) row = n * B + min(max(rv.via[r], 0), B - 1);
+    set = rv.set_in[(size_t)row * 64 + lane];
+  }
+  if (rv.seed) {
+    const int T = rv.seed_T;
+    int lo = rv.obs_lens ? min(max(rv.obs_lens[n], 0), T) : T;
+    lo = __builtin_amdgcn_readfirstlane(lo);
+    for (int i = T - lo; i < T; ++i) {           // uniform: at most obs_len cells
+      const int c = __builtin_amdgcn_readfirstlane(rv.seed[(size_t)n * T + i]);
+      if (c >= 0 && c < K && (c & 63) == lane) set |= 1u << (c >> 6);
+    }
+  }
+  const uint32_t p1bit = (p1 >= 0 && p1 < K && (p1 & 63) == lane) ? 1u << (p1 >> 6) : 0u;
+  if (rv.or_p1) set |= p1bit;
+  rv.set_out[(size_t)r * 64 + lane] = set;
+  const uint32_t pay = set & ~p1bit;             // staying in the current cell is no revisit
+  const float c = rv.cost[n];
+#pragma unroll
+  for (int j = 0; j < J; ++j) b[j] = b[j] + (((pay >> j) & 1u) ? c : 0.f);
+}
+
 // MASKED: amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A cell
 // outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
 // nothing, so an allowed cell's rank counts allowed cells only.
 // BIASED (implies MASKED; amask may be NULL): the candidate is (prev_lp + lp) + b, with
 // b = bias + (r / B) * bias_stride, formed before the mask's -inf and before the ranks.
 // MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of the row.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
+// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
 __global__ __launch_bounds__(256)
 void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict__ prev_lp,
                       int R, int B, int K, int time, int diverse, float log_gamma,
                       float* __restrict__ cand, const uint8_t* __restrict__ amask = nullptr,
                       int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                      int64_t bias_stride = 0, MotionRow mo = MotionRow{}) {
+                      int64_t bias_stride = 0, MotionRow mo = MotionRow{},
+                      RevisitRow rv = RevisitRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
+  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1602,7 +1673,10 @@ void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict_
   for (int j = 0; j < J; ++j) v[j] = pl + ((v[j] - mx) - lse);
   if constexpr (BIASED) {
     float b[J];
-    if constexpr (MOTION)
+    if constexpr (PATH)
+      step_row_path<J>(mo, rv, bias ? bias + (size_t)(r / B) * bias_stride : nullptr, r / B, r, B,
+                       K, lane, b);
+    else if constexpr (MOTION)
       step_row_motion<J>(mo, bias ? bias + (size_t)(r / B) * bias_stride : nullptr, r / B, r, B, K,
                          lane, b);
     else
@@ -1874,7 +1948,8 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): b = bias + n * bias_stride,
 // w = l / temperature + b, the limits order by w, and the score is (lp / temperature + b) + g.
 // MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of row r.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
+// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
                         int t, int shared, const uint32_t* __restrict__ params, int floor,
@@ -1883,9 +1958,10 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
                         int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out,
                         const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0,
                         const float* __restrict__ bias = nullptr, int64_t bias_stride = 0,
-                        MotionRow mo = MotionRow{}) {
+                        MotionRow mo = MotionRow{}, RevisitRow rv = RevisitRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
+  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1907,7 +1983,10 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
   uint32_t am = 0u;
   float b[BIASED ? J : 1];
   if constexpr (BIASED) {
-    if constexpr (MOTION)
+    if constexpr (PATH)
+      step_row_path<J>(mo, rv, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, S, K, lane,
+                       b);
+    else if constexpr (MOTION)
       step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, S, K, lane, b);
     else
       step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
@@ -2038,7 +2117,8 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 // b = bias + n * bias_stride; q, the limits' order and the q plane follow w as in
 // sample_step_kernel.
 // MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of parent row r.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false>
+// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
@@ -2046,9 +2126,11 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
                         float* __restrict__ cand, float* __restrict__ lp_plane,
                         float* __restrict__ q_plane, const uint8_t* __restrict__ amask = nullptr,
                         int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                        int64_t bias_stride = 0, MotionRow mo = MotionRow{}) {
+                        int64_t bias_stride = 0, MotionRow mo = MotionRow{},
+                      RevisitRow rv = RevisitRow{}) {
   static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
   static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
+  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -2066,7 +2148,10 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
   uint32_t am = 0u;
   if constexpr (BIASED) {
     float bz[J];
-    if constexpr (MOTION)
+    if constexpr (PATH)
+      step_row_path<J>(mo, rv, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, B, K, lane,
+                       bz);
+    else if constexpr (MOTION)
       step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, B, K, lane, bz);
     else
       step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, bz);

@@ -85,7 +85,7 @@ inline BeamStepForm beam_step_form(int K, bool have_cand, bool masked) {
 // a mask -- ONE instantiation, which takes the allowed bits as the in-row bits when no mask plane
 // is given.  A Masked or Biased beam step is a `masked` one to beam_step_form above: it exists in
 // the two-launch form only.
-enum class RowForm { Plain, Masked, Biased, Motion };
+enum class RowForm { Plain, Masked, Biased, Motion, Path };
 inline RowForm step_row_form(bool masked, bool biased) {
   return biased ? RowForm::Biased : (masked ? RowForm::Masked : RowForm::Plain);
 }
@@ -95,6 +95,13 @@ inline RowForm step_row_form(bool masked, bool biased) {
 // such form (mv_beam_occupancy refuses while a motion cost is set).
 inline RowForm step_row_form_motion(bool masked, bool biased, bool motion) {
   return motion ? RowForm::Motion : step_row_form(masked, biased);
+}
+// Path: mv_set_revisit_cost, with or without a mask, a bias and a motion cost -- the Motion
+// instantiation plus the row's visited set, whose motion part runs only when a motion cost is set:
+// again ONE more instantiation for every combination.  A Path beam step is a `masked` one to
+// beam_step_form above, as every constrained form is.
+inline RowForm step_row_form_path(bool masked, bool biased, bool motion, bool revisit) {
+  return revisit ? RowForm::Path : step_row_form_motion(masked, biased, motion);
 }
 
 // ------------------------------------------------------------------ graph attention (forward)

@@ -396,6 +396,37 @@ def path_motion_cost(ids, labels, W, tables, obs_lengths=None):
   return out
 
 
+def path_revisit_cost(ids, labels, cost, obs_lengths=None, seed_observed=True):
+  """The revisit cost each returned path paid (not in the reference; include/multiverse_hip.h
+  mv_set_revisit_cost): ids int [N, B, T] (the engine's "ids"; -1 past a row's length), labels int
+  [N, T_o] the observed cells, cost [N] or a scalar -> float32 [N, B, T]: cost[n] where the step
+  enters a cell the path held before (with seed_observed: or one of the row's observed cells,
+  the last obs_lengths[n] of them) other than the cell it is in, 0 elsewhere and where the id is
+  -1.  Staying is free; the path A, A, B, A pays once, at its last step.  Plain numpy on the host:
+  under cost 1 the result is all zero exactly when no path returns to a cell it left."""
+  ids = np.asarray(ids)
+  labels = np.asarray(labels)
+  N, B, T = ids.shape
+  cost = np.broadcast_to(np.asarray(cost, dtype=np.float32), (N,))
+  To = labels.shape[1]
+  out = np.zeros((N, B, T), dtype=np.float32)
+  for n in range(N):
+    lo = To if obs_lengths is None else int(obs_lengths[n])
+    seen0 = set(int(c) for c in labels[n, To - lo:]) if seed_observed else set()
+    for b in range(B):
+      seen = set(seen0)
+      p1 = int(labels[n, To - 1])
+      for t in range(T):
+        k = int(ids[n, b, t])
+        if k < 0:
+          break
+        if k in seen and k != p1:
+          out[n, b, t] = cost[n]
+        seen.add(k)
+        p1 = k
+  return out
+
+
 def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_length=None):
   """Engine feed for the samples `idxs` (all with the same T_pred), padded to
   `batch_size` by repeating the last one.  For one sample this is the feed of
@@ -419,7 +450,9 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
   carries "cell_bias" float32 [N, K], row n built by `cell_bias_from_scene` from the same frame;
   padding rows get zeros.
   args.motion_cost (the dict of `motion_tables`; not in the reference): the feed carries
-  "motion_cost", the same tables for every real row and zero tables for the padding rows."""
+  "motion_cost", the same tables for every real row and zero tables for the padding rows.
+  args.revisit_cost (a dict {"cost": nats <= 0, "seed_observed": bool}; not in the reference):
+  the feed carries "revisit_cost" with that cost for every real row and 0 for the padding rows."""
   idxs = list(idxs)
   n_real = len(idxs)
   N = batch_size or n_real
@@ -515,6 +548,12 @@ def inference_feed(inputs, args, idxs, batch_size=None, lengths=None, pred_lengt
       full[pad] = 0
       cost[key] = full
     feed["motion_cost"] = cost
+  revisit = getattr(args, "revisit_cost", None)
+  if revisit:
+    per_row = np.full(N, revisit["cost"], dtype="float32")
+    per_row[n_real:] = 0                    # a padding row pays nothing
+    feed["revisit_cost"] = {"cost": per_row,
+                            "seed_observed": bool(revisit.get("seed_observed", True))}
   return feed, n_real
 
 

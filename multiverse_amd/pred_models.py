@@ -336,7 +336,8 @@ class Model(object):
     engine as it is: "pred_lengths", "obs_lengths", "cell_mask" ([N, K] or [N, Tm, K] allowed
     cells of a multi-future decode, Engine.set_cell_mask) and "cell_bias" (float32 cell costs of
     the same shapes, Engine.set_cell_bias) are set when present, cleared when absent; so is
-    "motion_cost" (the dict of multifuture.motion_tables, Engine.set_motion_cost)."""
+    "motion_cost" (the dict of multifuture.motion_tables, Engine.set_motion_cost) and
+    "revisit_cost" ({"cost", "seed_observed"}, Engine.set_revisit_cost)."""
     cfg = self.config
     compact = bool(feed.get("compact", False))
     if getattr(cfg, "use_beam_search", False):
