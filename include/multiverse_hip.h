@@ -856,7 +856,10 @@ int  mv_op_convlstm_step(int device, const float* x, const float* c,
  * 3 = Winograd F(3,3) over image rows (any W -- widths that do not divide 32 take the halo
  * tiling, operands below 2 GiB --, H >= 3; csrc/convlstm_wino3.h), 4 = REDUCED precision: one
  * bf16 plane per operand on the same row-triple tile (compute mode 2's gate kernel; h16_out is
- * then that one plane decoded).
+ * then that one plane decoded), 5 = the same precision on the 32-cell body (what compute mode 2
+ * takes where the tile cannot run: H < 3, MV_BF16T=0; 16-channel x groups in pairs), 6 = that
+ * body with three x passes: x as two fp16 planes under its own exponent against the x rows of
+ * the kernel as an fp16 pair, h one bf16 plane (models with unbounded activations; dense x only).
  * h16_out (optional) [M,H,W,C]: the h' OPERAND PLANES the kernel emitted for the next
  * step, decoded back to fp32 ((hi + lo) / 256), so that a test sees the plane layout. */
 int  mv_op_convlstm_step16(int device, int32_t variant, const float* x, const float* c,

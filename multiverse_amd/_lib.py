@@ -1550,7 +1550,9 @@ def op_convlstm_step(x, c, h, kernel, biases, device=0):
 
 def op_convlstm_step16(x, c, h, kernel, biases, variant, device=0):
   """The step on the fp16 matrix pipe (f16x3 planes): variant 1 = direct form, 2 = Winograd
-  F(2,3) over image rows.  Returns c', h' and the h' operand planes decoded to fp32."""
+  F(2,3) over image rows, 3 = Winograd F(3,3), 4 = bf16 on the row-triple tile, 5 = bf16 on the
+  32-cell body, 6 = that body with three x passes (include/multiverse_hip.h).  Returns c', h' and
+  the h' operand planes decoded to fp32."""
   lib = load()
   x = f32(x)
   M, H, W, Cx = x.shape

@@ -69,19 +69,33 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
                           int32_t M, int32_t H, int32_t W, int32_t Cx, int32_t C,
                           float* c_out, float* h_out, float* h16_out) {
   return guarded(nullptr, [&] {
-    MV_REQUIRE(variant >= 1 && variant <= 4, "variant %d: 1 = direct f16x3, 2 = Winograd F(2,3), "
-               "3 = Winograd F(3,3), 4 = bf16 on the row-triple tile", variant);
-    const bool bf = variant == 4;
+    MV_REQUIRE(variant >= 1 && variant <= 6, "variant %d: 1 = direct f16x3, 2 = Winograd F(2,3), "
+               "3 = Winograd F(3,3), 4 = bf16 on the row-triple tile, 5 = bf16 on the 32-cell body, "
+               "6 = the same with three x passes", variant);
+    const bool bf = variant >= 4;
+    // variant 6: the x operand of an unbounded-activation model -- two fp16 planes of 2^e x under
+    // the tensor's own exponent; h stays one bf16 plane
+    const bool xf16 = variant == 6;
     MV_REQUIRE(C % mv::kChBlock == 0 && C % mv::kBK == 0, "C %d must be a multiple of 32", C);
     MV_REQUIRE(mv::f16x3_cx_supported(Cx), "Cx %d unsupported (multiple of 16, or <= 3)", Cx);
     MV_REQUIRE(H * W >= 32, "grids of at least 32 cells");
+    const bool small = x_is_small(Cx);
+    const int xpass = xf16 ? 3 : 1;
+    if (variant >= 5) {       // the 32-cell body's own refusals, as prepare_gate_operands states them
+      MV_REQUIRE(!(xf16 && small), "variant 6: the three x passes are of a dense x operand "
+                 "(Cx %d travels as the fp32 chunk)", Cx);
+      const int nxk = small ? 0 : xpass * mv::f16x3_xksteps(Cx), nhk = 9 * (C / 16);
+      MV_REQUIRE((nxk / 3) % MV_BF16_UNITS == 0 && (nhk / 3) % MV_BF16_UNITS == 0,
+                 "bf16 mode: %d x / %d h k-steps do not fill whole LDS stages (emb_size and "
+                 "scene_conv_dim must be multiples of 32)", nxk, nhk);
+    }
     OpCtx ctx(device);
     const size_t cells = (size_t)M * H * W;
-    const bool small = x_is_small(Cx);
     const int Cx16 = x_chunk16(Cx);
     const int Cin = Cx + C, N4 = 4 * C;
     DevBuf<float> dx, dc, dh, dw, db, dco, dho, dk, dwx, dplanes;
     DevBuf<_Float16> px, ph, pho, wp, v3x, v3h;
+    DevBuf<int32_t> xexp;
     ctx.up(dx, x, cells * Cx);
     ctx.up(db, biases, (size_t)4 * C);
     ctx.up(dk, kernel, (size_t)9 * Cin * N4);
@@ -95,13 +109,24 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
       ctx.up(dh, h, cells * C);
     }
     dco.alloc(cells * C); dho.alloc(cells * C);
+    mv::ConvLstm16Args q{};
+    mv::ConvLstmArgs& a = q.f;
     // operand planes: [pad | plane 0 | slack][pad | plane 1 | slack], zero-filled
     auto make_planes = [&](DevBuf<_Float16>& buf, const float* src, int Cc, size_t* stride) {
       const size_t pst = cells * Cc + mv::kPlaneSlack + mv::kPlanePad;
       buf.alloc(2 * pst + mv::kPlanePad);
       HIP_CHECK(hipMemsetAsync(buf.p, 0, (2 * pst + mv::kPlanePad) * sizeof(_Float16), ctx.stream));
       _Float16* p0 = buf.p + mv::kPlanePad;
-      if (src && bf)        // ONE unscaled bf16 plane (compute mode 2)
+      if (src && xf16 && src == dx.p) {       // as prepare_gate_operands splits an unbounded x
+        xexp.alloc(65);
+        HIP_CHECK(hipMemsetAsync(xexp.p, 0, 64 * sizeof(int32_t), ctx.stream));
+        hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, ctx.stream, src,
+                           cells * Cc, xexp.p);
+        hipLaunchKernelGGL(mv::split_planes_dyn_kernel, dim3(mv::split_planes_blocks(cells, Cc)),
+                           dim3(256), 0, ctx.stream, src, p0, p0 + pst, (int)cells, Cc, xexp.p,
+                           xexp.p + 64);
+        q.x_exp = xexp.p + 64;
+      } else if (src && bf)        // ONE unscaled bf16 plane (compute mode 2)
         hipLaunchKernelGGL(mv::split_plane_bf16_kernel, dim3(mv::split_planes_blocks(cells, Cc)),
                            dim3(256), 0, ctx.stream, src, p0, (int)cells, Cc);
       else if (src)
@@ -110,8 +135,6 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
       *stride = pst;
       return p0;
     };
-    mv::ConvLstm16Args q{};
-    mv::ConvLstmArgs& a = q.f;
     a.x = dx.p; a.h = dh.p; a.c = dc.p; a.wpack = dw.p; a.bias = db.p;
     a.h_out = dho.p; a.c_out = dco.p;
     a.rows = M; a.H = H; a.W = W; a.Cx = Cx; a.C = C;
@@ -121,9 +144,9 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
     if (!zero) { q.h16 = make_planes(ph, dh.p, C, &hst); q.h_plane_stride = (int64_t)hst; }
     q.h16_out = make_planes(pho, nullptr, C, &ost);
     q.h16_out_stride = (int64_t)ost;
-    q.n_xk = small ? 0 : mv::f16x3_xksteps(Cx);
+    q.n_xk = small ? 0 : xpass * mv::f16x3_xksteps(Cx);
     q.n_hk = zero ? 0 : 9 * (C / 16);
-    q.w_ksteps = small ? 9 * (C / 16) : mv::f16x3_xksteps(Cx) + 9 * (C / 16);
+    q.w_ksteps = (small ? 0 : xpass * mv::f16x3_xksteps(Cx)) + 9 * (C / 16);
     // the variant forces its form: the engine's packs and launcher, under an explicit plan
     // (block maps and shift as the engine would choose them)
     ForwardPlan pl;
@@ -141,6 +164,29 @@ int mv_op_convlstm_step16(int device, int32_t variant, const float* x, const flo
       }
       upload(wp, p16);
       q.wp16 = wp.p;
+    } else if (variant >= 5) {
+      // the 32-cell body of compute mode 2 (GateForm::Bf16), packed as ensure_packed_bf16 packs
+      std::vector<_Float16> pb(mv::bf16_wpack_elems(Cx16, C, xf16));
+      if (small) {
+        mv::pack_bf16_weights(kernel_h_rows(kernel, Cx, C).data(), 0, C, pb.data());
+        upload(dwx, small_x_chunk(kernel, Cx, C, 1.0f));
+        q.wx32 = dwx.p;
+      } else {
+        if (xf16) {       // the x rows travel as fp16 of 256 w: the engine's range bound
+          float mx = 0.f;
+          for (int t = 0; t < 9; ++t)
+            for (int ci = 0; ci < Cx; ++ci)
+              for (int n = 0; n < N4; ++n)
+                mx = std::max(mx, std::fabs(kernel[((size_t)t * Cin + ci) * N4 + n]));
+          MV_REQUIRE(mx * mv::kF16Scale < 60000.f, "variant 6: the x rows of the kernel reach %g, "
+                     "outside the scaled fp16 range", mx);
+        }
+        mv::pack_bf16_weights(kernel, Cx, C, pb.data(), xf16);
+      }
+      upload(wp, pb);
+      q.wp16 = wp.p;
+      pl.form = GateForm::Bf16;
+      pl.x_passes = xpass;
     } else if (variant == 4) {
       MV_REQUIRE(mv::bf16t_geometry_ok(a, q), "bf16 row-triple tile: H %d >= 3", H);
       pack_bf16t(ctx.stream, dk.p, Cx, C, wp);

@@ -81,7 +81,7 @@ def conv_layer(x, W, b=None, stride=1, act=None):
 
 # -------------------------------------------------------------- ConvLSTM
 
-def convlstm_cell(x, c, h, kernel, biases):
+def convlstm_cell(x, c, h, kernel, biases, rounding=None, role=None):
   """tf.contrib.rnn.ConvLSTMCell.call (TF 1.15
   tensorflow/contrib/rnn/python/ops/rnn_cell.py), constructed at reference
   code/pred_models.py:189-193,196-200,236-240,243-247:
@@ -90,13 +90,233 @@ def convlstm_cell(x, c, h, kernel, biases):
     i, j, f, o = split(g, 4, ch)
     c' = sigmoid(f + forget_bias) * c + sigmoid(i) * tanh(j)
     h' = tanh(c') * sigmoid(o)
+
+  rounding (an OperandRounding, default off): the gate convolution on operands rounded as the
+  bf16 compute mode holds them; role names the chain ("enc_class", "enc_reg", "dec_class",
+  "dec_reg"), which decides whether the x part is rounded.
   """
-  g = conv2d_same(torch.cat([x, h], dim=-1), kernel) + biases
+  if rounding is None:
+    g = conv2d_same(torch.cat([x, h], dim=-1), kernel) + biases
+  else:
+    g = rounding.gate_conv(x, h, kernel, role) + biases
   i, j, f, o = torch.chunk(g, 4, dim=-1)
   new_c = torch.sigmoid(f + FORGET_BIAS) * c
   new_c = new_c + torch.sigmoid(i) * torch.tanh(j)
   new_h = torch.tanh(new_c) * torch.sigmoid(o)
   return new_c, new_h
+
+
+# ---------------------------------------- operands as the bf16 compute mode holds them
+
+def _pow2(q):
+  """2^q as float64, exact (q an integer tensor within the normal range)."""
+  return ((q.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
+def _round_sig(t, bits, min_exp, max_finite):
+  """Round-to-nearest-even of finite t to `bits` significand bits with gradual underflow below
+  2^min_exp (the quantum stays 2^(min_exp - bits + 1)) and overflow to +-inf above max_finite;
+  any float dtype in, the same dtype out (computed in float64: every step is exact)."""
+  v = t.detach().to(torch.float64)
+  _, e = torch.frexp(v)                               # |v| in [2^(e-1), 2^e)
+  q = torch.clamp(e.to(torch.int64) - 1, min=min_exp, max=1000) - (bits - 1)
+  quantum = _pow2(q)
+  r = torch.round(v / quantum) * quantum             # torch.round: half to even
+  r = torch.where(r.abs() > max_finite, torch.sign(r) * float("inf"), r)
+  return r.to(t.dtype)
+
+
+def round_bf16(t):
+  """t rounded to bfloat16 (8 significand bits, fp32's exponent range), round-to-nearest-even:
+  csrc/convlstm_f16x3.h bf16_as_half, i.e. a torch.bfloat16 cast of float32 values."""
+  return _round_sig(t, 8, -126, 3.3895313892515355e38)
+
+
+def round_f16(t):
+  """t rounded to IEEE half (11 significand bits, subnormals below 2^-14 at a quantum of 2^-24,
+  +-inf above 65504), round-to-nearest-even: a numpy.float16 cast."""
+  return _round_sig(t, 11, -14, 65504.0)
+
+
+def _scale_exp(t, top):
+  """csrc/convlstm_wgrad_f16x3.h chain_exp_kernel: e = top - ilogb(max |t|), clamped to +-100;
+  0 for an all-zero tensor."""
+  mx = float(t.detach().abs().max())
+  if not mx > 0.0:
+    return 0
+  return int(min(100, max(-100, top - (math.frexp(mx)[1] - 1))))
+
+
+def _wgrad_plain(a, g, kh=3, kw=3):
+  """dW[ky, kx, ci, n] = sum_m a[m + (ky - kh//2, kx - kw//2)][ci] g[m][n] (SAME, zero outside the
+  image): the gradient of conv2d_same(a, K) in K under the upstream gradient g."""
+  K0 = torch.zeros(kh, kw, a.shape[-1], g.shape[-1], dtype=a.dtype, requires_grad=True)
+  with torch.enable_grad():
+    y = conv2d_same(a.detach(), K0)
+  return torch.autograd.grad(y, K0, g.detach())[0]
+
+
+class _RoundedGateConv(torch.autograd.Function):
+  """conv2d_same(concat([x, h]), kernel) of a ConvLSTM gate with the operands of each pass
+  rounded as the bf16 compute mode rounds them (OperandRounding).  The kernel gets no gradient
+  here: its wgrad runs once per chain over all steps (OperandRounding.chain_wgrads)."""
+
+  @staticmethod
+  def forward(ctx, x, h, kernel, rnd, x_exact, key):
+    Cx = x.shape[-1]
+    ctx.rnd, ctx.key, ctx.Cx = rnd, key, Cx
+    ctx.save_for_backward(x, h, kernel)
+    kr = rnd.bf16(kernel)
+    xr = x
+    if x_exact:
+      kr = torch.cat([kernel[:, :, :Cx], kr[:, :, Cx:]], dim=2)
+    else:
+      xr = rnd.bf16(x)
+    return conv2d_same(torch.cat([xr, rnd.bf16(h)], dim=-1), kr)
+
+  @staticmethod
+  def backward(ctx, G):
+    x, h, kernel = ctx.saved_tensors
+    rnd = ctx.rnd
+    # dgrad: d[x | h](m) = sum_tap G(m - d_tap) K[tap]^T -- the SAME convolution of G with the
+    # tap-flipped, transposed kernel; ONE bf16 plane of G against ONE of the whole kernel
+    kt = rnd.bf16(kernel).flip(0, 1).permute(0, 1, 3, 2)
+    d_in = conv2d_same(rnd.bf16(G), kt)
+    rnd.record(ctx.key, x, h, G)
+    return d_in[..., :ctx.Cx], d_in[..., ctx.Cx:], None, None, None, None
+
+
+class OperandRounding(object):
+  """Which operands of the ConvLSTM gate convolutions the bf16 compute mode rounds, and how --
+  restated from csrc/ (NOT obtained from the library), for the default knobs.  It touches the
+  gate convolution only; everything else is the plain oracle in `dtype`.
+
+  forward   h and the kernel rows it meets: bf16, round-to-nearest-even.  x and its rows too,
+            EXCEPT (x_exact): a <= 3-channel x (the fp32 chunk of the regression encoder); every
+            x of a relu / lrelu model (bounded=False: the x part runs as an f16x3 split, fp32
+            class); and, in inference (train=False), the class encoder's and class decoder's x
+            on grids of at least 3 x 3, which csrc/sparse_x.h evaluates from fp64 tables of the
+            unrounded weights (one-hot feedback; teacher forcing is not modelled).
+  dgrad     bf16(G) against bf16 of the whole kernel (csrc/convlstm_f16x3.h
+            pack_bf16_dgrad_kernel, split_plane_bf16_kernel), whatever the forward did with x.
+  wgrad     per chain (one gate kernel, all its steps), by csrc/gate_plan.h plan_wgrad:
+            W % 16 != 0 or C % 128 != 0 -> the fp32 kernel: no rounding;
+            else each operand and G is ONE fp16 plane under a power-of-two scale: v ->
+            half(v 2^e) / 2^e with e = 8 for h, 13 - ilogb(max |x|) for x and
+            13 - ilogb(max |G|) for G, the maxima over the whole chain (chain_exp_kernel).  An
+            element that stays a normal half is rounded to 11 significand bits whatever e is.
+            Underflow: csrc/convlstm_wgrad_f16x3.h transpose_split_kernel, `const float s =
+            tile[..][ch] * sc2e; const _Float16 h0 = (_Float16)s;` (the same two statements in
+            transpose_split3_kernel, transpose_split_narrow_kernel and both wino3_transpose_*
+            kernels) -- an fp32 -> fp16 conversion of the SCALED value with gradual underflow:
+            below 2^(-14 - e) the quantum stays 2^(-24 - e), below 2^(-25 - e) the element is
+            zero.  Nothing overflows: the largest scaled element lies in [2^13, 2^14).
+            H % 3 == 0 (H >= 3): the row-triple form.  The planes hold the Winograd F(3,3)
+            components of each row triple -- V0..V4 of the five operand rows around it, U0..U4 of
+            its three G rows (wino3_transpose_a3_kernel, wino3_transpose_g_kernel), formed in
+            full precision and THEN rounded as above (x: e = 10 - ilogb(max |x|), |V| <= 6 |x|);
+            the 15 partial taps M_c = sum V_c U_c combine to the nine after the sum over cells.
+  biases    column sums of the unrounded G: plain autograd.
+
+  bf16 / f16 are the two rounding functions (instance attributes: a test replaces them by the
+  identity to check the algebra).  tests/test_bf16_oracle.py::test_restated_rules_are_the_ones_
+  in_csrc holds every rule above to the statement of csrc/ it restates.
+
+  What it is a reference FOR: a kernel handed the same, already rounded operands
+  (tests/test_gpu_bf16_kernels.py does that for the forward, with the numpy twin of the rule).
+  Against a whole forward or training step of the engine it is no sharper than the plain oracle:
+  the engine's fp32 pre-images and this oracle's fp64 ones round 0.1 - 0.4 % of the elements to
+  different neighbours, and those flips alone are a quarter to a half of the rounding's whole
+  effect on a gradient slice."""
+
+  def __init__(self, train=False, bounded=True, sparse_x=True):
+    self.train, self.bounded, self.sparse_x = bool(train), bool(bounded), bool(sparse_x)
+    self.bf16, self.f16 = round_bf16, round_f16
+    self.begin()
+
+  @classmethod
+  def of(cls, cfg):
+    """The rounding of a model of this config: training or inference, tanh or not; sparse_x as
+    csrc/engine_setup.h sparse_x_on states it (default knobs; the grid's H, W >= 3 in x_exact)."""
+    act = getattr(cfg, "activation_func", "tanh")
+    name = act if isinstance(act, str) else getattr(act, "__name__", "tanh")
+    E, D = int(cfg.emb_size), int(getattr(cfg, "scene_conv_dim", 64))
+    return cls(train=bool(cfg.is_train), bounded=name == "tanh",
+               sparse_x=E % 16 == 0 and D % 16 == 0 and D <= 64)
+
+  def begin(self):
+    self._chains, self._order = {}, []
+
+  def x_exact(self, role, H, W, Cx):
+    if Cx <= 3 or not self.bounded:
+      return True
+    return (not self.train and self.sparse_x and role in ("enc_class", "dec_class")
+            and H >= 3 and W >= 3)
+
+  @staticmethod
+  def wgrad_form(H, W, C):
+    """None (the fp32 kernel), "direct" or "triple": csrc/gate_plan.h plan_wgrad with
+    csrc/convlstm_wgrad_f16x3.h wgrad16_ok and wgrad16_wino3_ok, default knobs."""
+    if W % 16 != 0 or C % 128 != 0:
+      return None
+    return "triple" if (H >= 3 and H % 3 == 0) else "direct"
+
+  def gate_conv(self, x, h, kernel, role):
+    _, H, W, Cx = x.shape
+    return _RoundedGateConv.apply(x, h, kernel, self, self.x_exact(role, H, W, Cx), id(kernel))
+
+  def record(self, key, x, h, G):
+    if key not in self._chains:
+      self._chains[key] = []
+      self._order.append(key)
+    self._chains[key].append((x.detach(), h.detach(), G.detach()))
+
+  def f16_scaled(self, t, e):
+    """half(t 2^e) / 2^e"""
+    return torch.ldexp(self.f16(torch.ldexp(t, torch.tensor(e))), torch.tensor(-e))
+
+  def wgrad(self, x, h, G):
+    """The kernel gradient [3, 3, Cx + C, 4C] of one chain: x [R, H, W, Cx], h [R, H, W, C] (the
+    steps' INPUT states) and G [R, H, W, 4C] over all its steps."""
+    _, H, W, C4 = G.shape
+    form = self.wgrad_form(H, W, C4 // 4)
+    if form is None:
+      return _wgrad_plain(torch.cat([x, h], dim=-1), G)
+    eg, eh = _scale_exp(G, 13), 8
+    ex = _scale_exp(x, 10 if form == "triple" else 13)
+    if form == "direct":
+      a = torch.cat([self.f16_scaled(x, ex), self.f16_scaled(h, eh)], dim=-1)
+      return _wgrad_plain(a, self.f16_scaled(G, eg))
+
+    def rows5(t):        # image rows 3t - 1 .. 3t + 3 of every triple, zero outside the image
+      p = F.pad(t, (0, 0, 0, 0, 1, 1))
+      return [p[:, i:i + H - 2:3] for i in range(5)]
+
+    def comps_a(t, e):   # wino3_transpose_a3_kernel
+      d = rows5(t)
+      v3, d32 = d[3] - d[1], d[3] - d[2]
+      V = [2.0 * (d[0] - d[2]) + v3, d32 - 2.0 * d[1], 2.0 * (d[1] - d[2]) + d32, v3,
+           2.0 * v3 + (d[2] - d[4])]
+      return [self.f16_scaled(v, e) for v in V]
+
+    g0, g1, g2 = G[:, 0::3], G[:, 1::3], G[:, 2::3]
+    U = [0.5 * g0, -0.5 * ((g0 + g1) + g2), ((g1 - g0) - g2) * (1.0 / 6.0),
+         ((g0 + 2.0 * g1) + 4.0 * g2) * (1.0 / 6.0), -g2]       # wino3_transpose_g_kernel
+    U = [self.f16_scaled(u, eg) for u in U]
+    V = [torch.cat([vx, vh], dim=-1) for vx, vh in zip(comps_a(x, ex), comps_a(h, eh))]
+    M = [_wgrad_plain(V[c], U[c], 1, 3) for c in range(5)]       # [1, 3, Cx + C, 4C] each
+    return torch.cat([((M[0] + M[1]) + M[2]) + M[3], (M[1] - M[2]) + 2.0 * M[3],
+                      ((M[1] + M[2]) + 4.0 * M[3]) + M[4]], dim=0)   # wgrad_wino3_reduce_kernel
+
+  def chain_wgrads(self):
+    """id(kernel tensor) -> the conv part of its gradient, from the steps recorded since
+    begin()."""
+    out = {}
+    for key in self._order:
+      steps = self._chains[key]
+      out[key] = self.wgrad(*(torch.cat([s[i] for s in steps], dim=0) for i in range(3)))
+    self.begin()
+    return out
 
 
 # ------------------------------------------------------------------- GNN
@@ -181,7 +401,7 @@ def one_hot_grid(labels, H, W, dtype):
   return oh.reshape(tuple(lab.shape) + (H, W, 1))
 
 
-def run_encoder(x_seq, kernel, biases, C, drop=None):
+def run_encoder(x_seq, kernel, biases, C, drop=None, rounding=None, role=None):
   """tf.nn.dynamic_rnn over [N, T, H, W, Cx] from the zero state with
   sequence_length == T (code/pred_models.py:212-215, 232-234; lengths are
   all obs_len, :1057-1062).  Returns the last (c, h)."""
@@ -192,7 +412,7 @@ def run_encoder(x_seq, kernel, biases, C, drop=None):
     x = x_seq[:, t]
     if drop is not None:
       x = drop(x)                  # DropoutWrapper(cell, keep_prob): input dropout
-    c, h = convlstm_cell(x, c, h, kernel, biases)
+    c, h = convlstm_cell(x, c, h, kernel, biases, rounding, role)
   return c, h
 
 
@@ -278,7 +498,7 @@ def soft_grid_labels(labels, H, W, soft_grid):
 
 
 def greedy_decoder(P, cfg, s, kind, first_input, state, T_pred, scene_mean,
-                   trace=None, feedback=None, pred_gt=None, drop=None):
+                   trace=None, feedback=None, pred_gt=None, drop=None, rounding=None):
   """`Model.grid_decoder` under `tf.nn.raw_rnn` (code/pred_models.py:311-471)
   at test time (`input_onehot = not is_train or train_w_onehot`).
 
@@ -311,7 +531,7 @@ def greedy_decoder(P, cfg, s, kind, first_input, state, T_pred, scene_mean,
     x = conv_layer(x_in, embW, embb, act=activation_of(cfg))
     if drop is not None:
       x = drop(x)                  # DropoutWrapper: input dropout (:241-249)
-    c, h = convlstm_cell(x, c, h, kernel, biases)
+    c, h = convlstm_cell(x, c, h, kernel, biases, rounding, "dec_" + kind)
     out = conv2d_same(h, outW)  # hidden2grid: no bias, identity (:948-950)
     outs.append(out)
     hs.append(h)
@@ -363,7 +583,7 @@ def topk_stable(x, k):
 
 
 def beam_decoder(P, cfg, s, first_input, state, T_pred, scene_mean, trace=None,
-                 save_states=False):
+                 save_states=False, rounding=None):
   """`Model.grid_decoder_beam_search` (code/pred_models.py:474-806).
 
   Returns (best_beam_logits [N,T,H,W,1], logits [N,B,T,K], ids [N,B,T],
@@ -394,7 +614,7 @@ def beam_decoder(P, cfg, s, first_input, state, T_pred, scene_mean, trace=None,
   # raw_rnn: loop_fn(0) -> [cell -> loop_fn(time)] for time = 1..T_pred
   for time in range(0, T_pred + 1):
     if time > 0:
-      c, h = convlstm_cell(x, c, h, kernel, biases)
+      c, h = convlstm_cell(x, c, h, kernel, biases, rounding, "dec_class")
       if save_states:
         all_states.append(h.reshape(N, B, H, W, C))
       logits = conv2d_same(h, outW).reshape(N, B, K)        # :550-555
@@ -467,7 +687,7 @@ def beam_decoder(P, cfg, s, first_input, state, T_pred, scene_mean, trace=None,
   return best, out_logits, out_ids, prev_lp
 
 
-def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None):
+def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None, rounding=None):
   """`Model.build_forward` (code/pred_models.py:123-308) on torch tensors
   (autograd-capable: the training oracle differentiates through it).
   Returns (grid_pred_decoded list_s, grid_pred_reg_decoded list_s, beam)."""
@@ -506,10 +726,11 @@ def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None):
     x_cls = scene_convs[s] * obs_oh                      # :210
     enc_c = run_encoder(
         x_cls, P["encoder_grid_class_%d/enc_grid_%d/kernel" % (s, s)],
-        P["encoder_grid_class_%d/enc_grid_%d/biases" % (s, s)], C, drop)
+        P["encoder_grid_class_%d/enc_grid_%d/biases" % (s, s)], C, drop, rounding, "enc_class")
     enc_r = run_encoder(
         obs_reg, P["encoder_grid_reg_%d/enc_grid_regress_%d/kernel" % (s, s)],
-        P["encoder_grid_reg_%d/enc_grid_regress_%d/biases" % (s, s)], C, drop)
+        P["encoder_grid_reg_%d/enc_grid_regress_%d/biases" % (s, s)], C, drop, rounding,
+        "enc_reg")
     scene_mean = scene_convs[s].mean(dim=1)              # :828
     if trace is not None:
       trace["enc_class_c_%d" % s] = enc_c[0].detach().numpy()
@@ -523,7 +744,7 @@ def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None):
       reg_gt = None
       single = getattr(cfg, "use_single_decoder", False)
       res = beam_decoder(P, cfg, s, obs_oh[:, -1], enc_c, T_pred, scene_mean, trace,
-                         save_states=single)
+                         save_states=single, rounding=rounding)
       best, lg, ids, lps = res[:4]
       if single:       # [N, B, T, H, W, C] -> [N*B, T, H, W, C] (:291-294)
         dec_h = res[4].reshape((-1,) + tuple(res[4].shape[2:]))
@@ -539,7 +760,7 @@ def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None):
         reg_gt = _t(feed["grid_pred_regress"][s], dtype)
       dec_cls, dec_h = greedy_decoder(
           P, cfg, s, "class", obs_oh[:, -1], enc_c, T_pred, scene_mean, trace,
-          feedback=cls_fb, pred_gt=cls_gt, drop=drop)
+          feedback=cls_fb, pred_gt=cls_gt, drop=drop, rounding=rounding)
       if trace is not None:
         trace["dec_class_h_%d" % s] = dec_h.detach().numpy()
     if getattr(cfg, "use_single_decoder", False):
@@ -553,13 +774,14 @@ def forward_tensors(P, cfg, feed, dtype=torch.float32, trace=None):
     else:
       dec_reg, _ = greedy_decoder(
           P, cfg, s, "reg", obs_reg[:, -1], enc_r, T_pred, scene_mean, trace,
-          feedback=reg_fb, pred_gt=reg_gt if reg_fb == "teacher" else None, drop=drop)
+          feedback=reg_fb, pred_gt=reg_gt if reg_fb == "teacher" else None, drop=drop,
+          rounding=rounding)
     cls_out.append(dec_cls)
     reg_out.append(dec_reg)
   return cls_out, reg_out, beam_out
 
 
-def forward(params, cfg, feed, dtype=torch.float32, trace=None):
+def forward(params, cfg, feed, dtype=torch.float32, trace=None, rounding=None):
   """`Model.build_forward` + the fetch contract of `Tester.step`
   (code/pred_models.py:1761-1790).
 
@@ -567,10 +789,11 @@ def forward(params, cfg, feed, dtype=torch.float32, trace=None):
         grid_obs_labels list_s [N,T_o] int, grid_obs_regress list_s
         [N,T_o,H,W,2], pred_length int.
   Returns (grid_pred_class list_s, grid_pred_reg list_s, beam_outputs) as
-  numpy arrays; unused scales give []."""
+  numpy arrays; unused scales give [].  rounding: an OperandRounding (default off: the plain
+  oracle, bit for bit)."""
   P = Params(params, dtype)
   with torch.no_grad():
-    cls_out, reg_out, beam_out = forward_tensors(P, cfg, feed, dtype, trace)
+    cls_out, reg_out, beam_out = forward_tensors(P, cfg, feed, dtype, trace, rounding)
   cls_out = [c if isinstance(c, list) else c.numpy() for c in cls_out]
   reg_out = [r if isinstance(r, list) else r.numpy() for r in reg_out]
   if beam_out is not None:
@@ -681,16 +904,26 @@ def learning_rate(cfg, global_step):
   return lr * cfg.emb_lr
 
 
-def loss_and_grads(params, cfg, feed, dtype=torch.float32):
+def loss_and_grads(params, cfg, feed, dtype=torch.float32, rounding=None):
   """tf.gradients(loss, trainable_variables) (code/pred_models.py:1694-1698).
-  Returns (loss, wd_loss, pred_grid_loss, grads dict name -> numpy)."""
+  Returns (loss, wd_loss, pred_grid_loss, grads dict name -> numpy).  rounding: an
+  OperandRounding (default off: the plain oracle, bit for bit); with it the gate kernels'
+  gradients are the chains' rounded wgrads (OperandRounding.chain_wgrads)."""
   P = Params(params, dtype)
   for v in P.p.values():
     v.requires_grad_(True)
-  cls_out, reg_out, _ = forward_tensors(P, cfg, feed, dtype)
+  if rounding is not None:
+    rounding.begin()
+  cls_out, reg_out, _ = forward_tensors(P, cfg, feed, dtype, rounding=rounding)
   loss, wd, pgl = build_loss(P, cfg, cls_out, reg_out, feed, dtype)
   names = sorted(P.p)
-  gs = torch.autograd.grad(loss, [P.p[n] for n in names], allow_unused=True)
+  gs = list(torch.autograd.grad(loss, [P.p[n] for n in names], allow_unused=True))
+  if rounding is not None:       # the gate kernels' conv gradients, chain by chain
+    conv = rounding.chain_wgrads()
+    for i, n in enumerate(names):
+      dw = conv.get(id(P.p[n]))
+      if dw is not None:
+        gs[i] = dw if gs[i] is None else gs[i] + dw
   grads = {n: (None if g is None else g.numpy()) for n, g in zip(names, gs)}
   return (float(loss.detach()), float(wd.detach()) if wd is not None else 0.0,
           [float(l.detach()) for l in pgl], grads)
