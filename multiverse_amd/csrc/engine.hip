@@ -77,6 +77,21 @@ ForwardKind beam_kind(const mv_engine* e) {
   return e->sampling_mode == 1 ? ForwardKind::SampledWor : ForwardKind::Sampled;
 }
 
+// The entry points that choose no cells refuse a handle on which a constraint is set.  `why`:
+// "training chooses no cells", or (names_what) a clause that ends in what is not read.
+void require_unconstrained(const mv_engine* h, const char* who, const char* why,
+                           bool names_what = false) {
+  const StepConstraints& c = h->con;
+  const struct { bool set; const char* what; const char* setter; const char* noun; } rows[] = {
+      {c.mask.set(), "a cell mask", "mv_set_cell_mask", "mask"},
+      {c.bias.set(), "a cell bias", "mv_set_cell_bias", "bias"},
+      {c.motion_set(), "a motion cost", "mv_set_motion_cost", "cost"},
+      {c.revisit_set(), "a revisit cost", "mv_set_revisit_cost", "cost"}};
+  for (const auto& r : rows)
+    MV_REQUIRE(!r.set, "%s: %s is set (%s); %s%s -- clear it first", who, r.what, r.setter, why,
+               names_what ? r.noun : "");
+}
+
 }  // namespace
 
 // ===================================================================== C ABI
@@ -366,30 +381,20 @@ int mv_set_cell_mask(mv_handle h, const uint8_t* allowed, int32_t Tm) {
     // behind whatever forward or occupancy map still reads the previous mask on the device
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!allowed) {
-      h->cmask_tm = 0;
-      h->cmask_count.clear();
+      h->con.mask.tm = 0;
+      h->con.mask_count.clear();
       return;
     }
     MV_REQUIRE(Tm >= 1, "mv_set_cell_mask: Tm = %d must be >= 1 (1 = one mask for every step)",
                (int)Tm);
     const size_t N = (size_t)h->cfg.batch_size, K = (size_t)h->sc[beam_scale(h)].K;
-    const size_t Tcap = (size_t)h->cfg.max_pred_len;
-    h->cmask_count.assign(N * Tm, 0);
+    h->con.mask_count.assign(N * Tm, 0);
     for (size_t p = 0; p < N * Tm; ++p) {
       int32_t cnt = 0;
       for (size_t k = 0; k < K; ++k) cnt += allowed[p * K + k] != 0;
-      h->cmask_count[p] = cnt;
+      h->con.mask_count[p] = cnt;
     }
-    // one allocation for both layouts: the address a captured forward holds never changes
-    h->cmask_dev.alloc(N * Tcap * K);
-    if (Tm == 1) {
-      HIP_CHECK(hipMemcpy(h->cmask_dev.p, allowed, N * K, hipMemcpyHostToDevice));
-    } else {
-      const size_t planes = std::min((size_t)Tm, Tcap);   // a forward reads planes < pred_len
-      HIP_CHECK(hipMemcpy2D(h->cmask_dev.p, Tcap * K, allowed, (size_t)Tm * K, planes * K, N,
-                            hipMemcpyHostToDevice));
-    }
-    h->cmask_tm = Tm;
+    h->con.mask.upload(allowed, N, Tm, K, (size_t)h->cfg.max_pred_len);
   });
 }
 
@@ -401,29 +406,18 @@ int mv_set_cell_bias(mv_handle h, const float* bias, int32_t Tm) {
     // behind whatever forward or occupancy map still reads the previous bias on the device
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!bias) {
-      h->cbias_tm = 0;
+      h->con.bias.tm = 0;
       return;
     }
     MV_REQUIRE(Tm >= 1, "mv_set_cell_bias: Tm = %d must be >= 1 (1 = one plane for every step)",
                (int)Tm);
     const size_t N = (size_t)h->cfg.batch_size, K = (size_t)h->sc[beam_scale(h)].K;
-    const size_t Tcap = (size_t)h->cfg.max_pred_len;
     // a cost is finite: a veto is the mask's job (a -inf here would reach the log-softmax of w)
     for (size_t i = 0; i < N * Tm * K; ++i)
       MV_REQUIRE(std::isfinite(bias[i]), "mv_set_cell_bias: bias[n = %d, tm = %d, k = %d] = %g is "
                  "not finite (a cost is a finite float32; forbid a cell with mv_set_cell_mask)",
                  (int)(i / ((size_t)Tm * K)), (int)(i / K % Tm), (int)(i % K), (double)bias[i]);
-    // one allocation for both layouts: the address a captured forward holds never changes
-    h->cbias_dev.alloc(N * Tcap * K);
-    if (Tm == 1) {
-      HIP_CHECK(hipMemcpy(h->cbias_dev.p, bias, N * K * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-      const size_t planes = std::min((size_t)Tm, Tcap);   // a forward reads planes < pred_len
-      HIP_CHECK(hipMemcpy2D(h->cbias_dev.p, Tcap * K * sizeof(float), bias,
-                            (size_t)Tm * K * sizeof(float), planes * K * sizeof(float), N,
-                            hipMemcpyHostToDevice));
-    }
-    h->cbias_tm = Tm;
+    h->con.bias.upload(bias, N, Tm, K, (size_t)h->cfg.max_pred_len);
   });
 }
 
@@ -436,8 +430,8 @@ int mv_set_motion_cost(mv_handle h, int32_t radius, const float* vel, const floa
     // behind whatever forward still reads the previous tables on the device
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!vel) {
-      h->motion_radius = 0;
-      h->motion_acc = false;
+      h->con.motion_radius = 0;
+      h->con.motion_acc = false;
       return;
     }
     MV_REQUIRE(radius >= 1 && radius <= MV_MOTION_MAX_RADIUS, "mv_set_motion_cost: radius = %d not "
@@ -457,19 +451,19 @@ int mv_set_motion_cost(mv_handle h, int32_t radius, const float* vel, const floa
     finite(vel_far, 1, "vel_far");
     if (acc) { finite(acc, DD, "acc"); finite(acc_far, 1, "acc_far"); }
     // one allocation for every radius: the addresses a captured forward holds never change
-    h->motion_dev.alloc(h->motion_floats());
-    float* d = h->motion_dev.p;
+    h->con.motion_dev.alloc(StepConstraints::motion_floats(N));
+    float* d = h->con.motion_dev.p;
     HIP_CHECK(hipMemcpy(d, vel, N * DD * sizeof(float), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(d + h->motion_vel_far_at(), vel_far, N * sizeof(float),
+    HIP_CHECK(hipMemcpy(d + StepConstraints::motion_vel_far_at(N), vel_far, N * sizeof(float),
                         hipMemcpyHostToDevice));
     if (acc) {
-      HIP_CHECK(hipMemcpy(d + h->motion_acc_at(), acc, N * DD * sizeof(float),
+      HIP_CHECK(hipMemcpy(d + StepConstraints::motion_acc_at(N), acc, N * DD * sizeof(float),
                           hipMemcpyHostToDevice));
-      HIP_CHECK(hipMemcpy(d + h->motion_acc_far_at(), acc_far, N * sizeof(float),
+      HIP_CHECK(hipMemcpy(d + StepConstraints::motion_acc_far_at(N), acc_far, N * sizeof(float),
                           hipMemcpyHostToDevice));
     }
-    h->motion_radius = radius;
-    h->motion_acc = acc != nullptr;
+    h->con.motion_radius = radius;
+    h->con.motion_acc = acc != nullptr;
   });
 }
 
@@ -481,8 +475,8 @@ int mv_set_revisit_cost(mv_handle h, const float* cost, int32_t seed_observed) {
     // behind whatever forward still reads the previous cost on the device
     HIP_CHECK(hipStreamSynchronize(h->stream));
     if (!cost) {
-      h->revisit_on = false;
-      h->revisit_seed = false;
+      h->con.revisit_on = false;
+      h->con.revisit_seed = false;
       return;
     }
     const size_t N = (size_t)h->cfg.batch_size;
@@ -491,12 +485,13 @@ int mv_set_revisit_cost(mv_handle h, const float* cost, int32_t seed_observed) {
       MV_REQUIRE(std::isfinite(cost[n]), "mv_set_revisit_cost: cost[n = %d] = %g is not finite (a "
                  "cost is a finite float32; \"never\" is the cost -1e30)", (int)n, (double)cost[n]);
     // allocated once: the addresses a captured forward holds never change
-    h->revisit_dev.alloc(N);
-    h->revisit_sets.alloc(2 * h->revisit_set_words());
-    HIP_CHECK(hipMemset(h->revisit_sets.p, 0, 2 * h->revisit_set_words() * sizeof(uint32_t)));
-    HIP_CHECK(hipMemcpy(h->revisit_dev.p, cost, N * sizeof(float), hipMemcpyHostToDevice));
-    h->revisit_on = true;
-    h->revisit_seed = seed_observed != 0;
+    const size_t words = StepConstraints::revisit_set_words(N * h->cfg.beam_size);
+    h->con.revisit_dev.alloc(N);
+    h->con.revisit_sets.alloc(2 * words);
+    HIP_CHECK(hipMemset(h->con.revisit_sets.p, 0, 2 * words * sizeof(uint32_t)));
+    HIP_CHECK(hipMemcpy(h->con.revisit_dev.p, cost, N * sizeof(float), hipMemcpyHostToDevice));
+    h->con.revisit_on = true;
+    h->con.revisit_seed = seed_observed != 0;
   });
 }
 
@@ -638,14 +633,9 @@ int mv_submit_greedy(mv_handle h, const mv_inputs* in) {
   if (!h) return 1;
   return guarded(h, [&] {
     MV_REQUIRE(in, "mv_submit_greedy: NULL argument");
-    MV_REQUIRE(!h->cmask_set(), "mv_submit_greedy: a cell mask is set (mv_set_cell_mask); the "
-               "greedy forward chooses by argmax and reads no mask -- clear it first");
-    MV_REQUIRE(!h->cbias_set(), "mv_submit_greedy: a cell bias is set (mv_set_cell_bias); the "
-               "greedy forward chooses by argmax and reads no bias -- clear it first");
-    MV_REQUIRE(!h->motion_set(), "mv_submit_greedy: a motion cost is set (mv_set_motion_cost); the "
-               "greedy forward chooses by argmax and reads no cost -- clear it first");
-    MV_REQUIRE(!h->revisit_set(), "mv_submit_greedy: a revisit cost is set (mv_set_revisit_cost); "
-               "the greedy forward chooses by argmax and reads no cost -- clear it first");
+    require_unconstrained(h, "mv_submit_greedy",
+                          "the greedy forward chooses by argmax and reads no ",
+                          /*names_what=*/true);
     pipeline_submit(h, in);
   });
 }
@@ -684,14 +674,7 @@ int mv_train_init(mv_handle h, const mv_train_config* tc) {
     MV_REQUIRE(tc, "mv_train_init: NULL config");
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_init");
-    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
-               "cells -- clear it first", "mv_train_init");
-    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
-               "cells -- clear it first", "mv_train_init");
-    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
-               "no cells -- clear it first", "mv_train_init");
-    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
-               "chooses no cells -- clear it first", "mv_train_init");
+    require_unconstrained(h, "mv_train_init", "training chooses no cells");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_init");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -741,14 +724,7 @@ int mv_train_forward_backward(mv_handle h, const mv_inputs* in, const mv_targets
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_forward_backward");
-    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
-               "cells -- clear it first", "mv_train_forward_backward");
-    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
-               "cells -- clear it first", "mv_train_forward_backward");
-    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
-               "no cells -- clear it first", "mv_train_forward_backward");
-    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
-               "chooses no cells -- clear it first", "mv_train_forward_backward");
+    require_unconstrained(h, "mv_train_forward_backward", "training chooses no cells");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_forward_backward");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -814,14 +790,7 @@ int mv_train_apply(mv_handle h, float grad_scale) {
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_apply");
-    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
-               "cells -- clear it first", "mv_train_apply");
-    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
-               "cells -- clear it first", "mv_train_apply");
-    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
-               "no cells -- clear it first", "mv_train_apply");
-    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
-               "chooses no cells -- clear it first", "mv_train_apply");
+    require_unconstrained(h, "mv_train_apply", "training chooses no cells");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_apply");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "
@@ -836,14 +805,7 @@ int mv_train_step(mv_handle h, const mv_inputs* in, const mv_targets* tg, mv_los
   return guarded(h, [&] {
     MV_REQUIRE(!h->sampling, "%s: sampling is on (mv_set_sampling); training does not sample -- "
                "clear it first", "mv_train_step");
-    MV_REQUIRE(!h->cmask_set(), "%s: a cell mask is set (mv_set_cell_mask); training chooses no "
-               "cells -- clear it first", "mv_train_step");
-    MV_REQUIRE(!h->cbias_set(), "%s: a cell bias is set (mv_set_cell_bias); training chooses no "
-               "cells -- clear it first", "mv_train_step");
-    MV_REQUIRE(!h->motion_set(), "%s: a motion cost is set (mv_set_motion_cost); training chooses "
-               "no cells -- clear it first", "mv_train_step");
-    MV_REQUIRE(!h->revisit_set(), "%s: a revisit cost is set (mv_set_revisit_cost); training "
-               "chooses no cells -- clear it first", "mv_train_step");
+    require_unconstrained(h, "mv_train_step", "training chooses no cells");
     MV_REQUIRE(!h->lens_set, "%s: per-row prediction lengths are set (mv_set_pred_lengths); "
                "training runs every row to pred_len -- clear them first", "mv_train_step");
     MV_REQUIRE(!h->obs_lens_short(), "%s: per-row observation lengths are set "

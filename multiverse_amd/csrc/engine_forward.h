@@ -1138,83 +1138,80 @@ __global__ void ragged_ids_tail_kernel(int32_t* __restrict__ ids, const int32_t*
   if (idx % T >= lens[idx / T / S]) ids[idx] = -1;
 }
 
-// The allowed cells of decode step t (mv_set_cell_mask): plane t of every row, or the one plane.
-// No mask set: the empty StepMask, and the step launches exactly what it launched before.
-// The cell costs of the step (mv_set_cell_bias) likewise: plane t of every row, or the one plane.
-StepMask step_mask(const mv_engine* e, int K, int t) {
-  StepMask m;
-  if (e->cmask_set()) {
-    m.p = e->cmask_dev.p + (size_t)t * e->cmask_step(K);
-    m.stride = e->cmask_stride(K);
+// What constrains decode step t (StepTerms, engine_setup.h), from what is set on the engine;
+// nothing set: the empty StepTerms, and the step launches exactly what it launched before.
+//   mask, bias  plane t of every row, or the one plane.
+//   motion      the tables, and where the step kernels find each row's p1 / p0 in what the
+//               forward already holds on the device -- the labels for the observed cells, and the
+//               ids (and, for the beams, the parents) the earlier steps wrote.
+//   revisit     the cost, the half of the engine's set buffer that holds every row's visited set
+//               of step t - 1 and the half step t stores into, and where the row's p1 lies.  At
+//               t == 0 there is no set yet: the kernel starts from the row's observed cells
+//               (seed_observed) or from nothing, and p1 -- the last observed cell -- joins the
+//               set only as one of those.
+// No launch and no buffer is added.  `ids` [.., R] x ids_stride: the chosen cell of row r at step
+// u is ids[u * ids_step + r * ids_stride]; parents (beam, wor): [T, R], or NULL for rows that
+// continue themselves.
+StepTerms step_terms(const mv_engine* e, const ScaleState& S, int t, const int32_t* ids,
+                     size_t ids_step, int ids_stride, const int32_t* parents) {
+  const StepConstraints& con = e->con;
+  const int T = e->cfg.obs_len, K = S.K, Tcap = e->cfg.max_pred_len;
+  const size_t N = (size_t)e->cfg.batch_size, R = N * e->cfg.beam_size;
+  const int32_t* last = S.labels.p + (T - 1);      // labels[:, -1], one per sample
+  StepTerms m;
+  if (con.mask.set()) {
+    m.amask = con.mask.at(K, t);
+    m.mask_stride = con.mask.stride(K, Tcap);
   }
-  if (e->cbias_set()) {
-    m.bias = e->cbias_dev.p + (size_t)t * e->cbias_step(K);
-    m.bias_stride = e->cbias_stride(K);
+  if (con.bias.set()) {
+    m.bias = con.bias.at(K, t);
+    m.bias_stride = con.bias.stride(K, Tcap);
+  }
+  if (con.motion_set()) {
+    mv::MotionRow& mo = m.mo;
+    const float* d = con.motion_dev.p;
+    mo.vel = d;
+    mo.vel_far = d + StepConstraints::motion_vel_far_at(N);
+    mo.acc = con.motion_acc ? d + StepConstraints::motion_acc_at(N) : nullptr;
+    mo.acc_far = con.motion_acc ? d + StepConstraints::motion_acc_far_at(N) : nullptr;
+    mo.W = S.W;
+    mo.radius = con.motion_radius;
+    if (t == 0) {
+      mo.prev1 = last; mo.p1_stride = T; mo.p1_per_row = 0;
+      mo.prev0 = T >= 2 ? last - 1 : nullptr; mo.p0_stride = T; mo.p0_per_row = 0;
+      // a row observed for one frame has no cell before its last (right-aligned observations)
+      mo.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
+    } else {
+      mo.prev1 = ids + (size_t)(t - 1) * ids_step; mo.p1_stride = ids_stride; mo.p1_per_row = 1;
+      if (t == 1) {
+        mo.prev0 = last; mo.p0_stride = T; mo.p0_per_row = 0;
+      } else {
+        mo.prev0 = ids + (size_t)(t - 2) * ids_step; mo.p0_stride = ids_stride; mo.p0_per_row = 1;
+        mo.prev0_via = parents ? parents + (size_t)(t - 1) * R : nullptr;
+      }
+    }
+  }
+  if (con.revisit_set()) {
+    mv::RevisitRow& rv = m.rv;
+    const size_t words = StepConstraints::revisit_set_words(R);
+    rv.cost = con.revisit_dev.p;
+    rv.set_out = con.revisit_sets.p + (size_t)(t & 1) * words;
+    if (t == 0) {
+      rv.prev1 = last; rv.p1_stride = T; rv.p1_per_row = 0;
+      rv.or_p1 = 0;
+      if (con.revisit_seed) {
+        rv.seed = S.labels.p;
+        rv.seed_T = T;
+        // the columns in front of a short track are not read (right-aligned observations)
+        rv.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
+      }
+    } else {
+      rv.set_in = con.revisit_sets.p + (size_t)((t - 1) & 1) * words;
+      rv.via = parents ? parents + (size_t)(t - 1) * R : nullptr;
+      rv.prev1 = ids + (size_t)(t - 1) * ids_step; rv.p1_stride = ids_stride; rv.p1_per_row = 1;
+    }
   }
   return m;
-}
-
-// The motion cost of decode step t (mv_set_motion_cost): the tables, and where the step kernels
-// find each row's p1 / p0 in what the forward already holds on the device -- the labels for the
-// observed cells, and the ids (and, for the beams, the parents) the earlier steps wrote.  No
-// launch and no buffer is added.  `ids` [.., R] x ids_stride: the chosen cell of row r at step u
-// is ids[u * step + r * ids_stride]; parents (beam, wor): [T, R], or NULL for rows that continue
-// themselves.  None set: m is left as it is.
-void step_motion(const mv_engine* e, const ScaleState& S, int t, const int32_t* ids,
-                 size_t ids_step, int ids_stride, const int32_t* parents, StepMask& m) {
-  if (!e->motion_set()) return;
-  const int T = e->cfg.obs_len, R = e->cfg.batch_size * e->cfg.beam_size;
-  mv::MotionRow& mo = m.mo;
-  mo.vel = e->motion_dev.p;
-  mo.vel_far = e->motion_dev.p + e->motion_vel_far_at();
-  mo.acc = e->motion_acc ? e->motion_dev.p + e->motion_acc_at() : nullptr;
-  mo.acc_far = e->motion_acc ? e->motion_dev.p + e->motion_acc_far_at() : nullptr;
-  mo.W = S.W;
-  mo.radius = e->motion_radius;
-  const int32_t* last = S.labels.p + (T - 1);      // labels[:, -1], one per sample
-  if (t == 0) {
-    mo.prev1 = last; mo.p1_stride = T; mo.p1_per_row = 0;
-    mo.prev0 = T >= 2 ? last - 1 : nullptr; mo.p0_stride = T; mo.p0_per_row = 0;
-    // a row observed for one frame has no cell before its last (right-aligned observations)
-    mo.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
-    return;
-  }
-  mo.prev1 = ids + (size_t)(t - 1) * ids_step; mo.p1_stride = ids_stride; mo.p1_per_row = 1;
-  if (t == 1) {
-    mo.prev0 = last; mo.p0_stride = T; mo.p0_per_row = 0;
-  } else {
-    mo.prev0 = ids + (size_t)(t - 2) * ids_step; mo.p0_stride = ids_stride; mo.p0_per_row = 1;
-    mo.prev0_via = parents ? parents + (size_t)(t - 1) * R : nullptr;
-  }
-}
-
-// The revisit cost of decode step t (mv_set_revisit_cost): the cost, the half of the engine's set
-// buffer that holds every row's visited set of step t - 1 and the half step t stores into, and
-// where the row's p1 lies (as step_motion finds it).  At t == 0 there is no set yet: the kernel
-// starts from the row's observed cells (seed_observed) or from nothing, and p1 -- the last
-// observed cell -- joins the set only as one of those.  parents (beam, wor): [T, R], or NULL for
-// rows that continue themselves.  No launch is added.  None set: m is left as it is.
-void step_revisit(const mv_engine* e, const ScaleState& S, int t, const int32_t* ids,
-                  size_t ids_step, int ids_stride, const int32_t* parents, StepMask& m) {
-  if (!e->revisit_set()) return;
-  const int T = e->cfg.obs_len, R = e->cfg.batch_size * e->cfg.beam_size;
-  mv::RevisitRow& rv = m.rv;
-  rv.cost = e->revisit_dev.p;
-  rv.set_out = e->revisit_sets.p + (size_t)(t & 1) * e->revisit_set_words();
-  if (t == 0) {
-    rv.prev1 = S.labels.p + (T - 1); rv.p1_stride = T; rv.p1_per_row = 0;
-    rv.or_p1 = 0;
-    if (e->revisit_seed) {
-      rv.seed = S.labels.p;
-      rv.seed_T = T;
-      // the columns in front of a short track are not read (right-aligned observations)
-      rv.obs_lens = e->obs.ragged ? e->obs_lens_dev.p : nullptr;
-    }
-    return;
-  }
-  rv.set_in = e->revisit_sets.p + (size_t)((t - 1) & 1) * e->revisit_set_words();
-  rv.via = parents ? parents + (size_t)(t - 1) * R : nullptr;
-  rv.prev1 = ids + (size_t)(t - 1) * ids_step; rv.p1_stride = ids_stride; rv.p1_per_row = 1;
 }
 
 // Beam-search class decoder (grid_decoder_beam_search,
@@ -1335,21 +1332,20 @@ void run_decoders_beam(mv_engine* e, int s, Cursors& cur, int Tp, bool wor) {
       int32_t* parents = e->bm_parents.p + (size_t)(time - 1) * R;
       if (dedupe)
         HIP_CHECK(hipMemsetAsync(e->bm_ref.p, 0, (size_t)n_now * B * sizeof(int32_t), e->issue));
-      StepMask mask = step_mask(e, K, time - 1);
-      step_motion(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p, mask);
-      step_revisit(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p, mask);
+      const StepTerms terms =
+          step_terms(e, S, time - 1, e->bm_ids.p, (size_t)R, 1, e->bm_parents.p);
       if (wor) launch(e, "sbs_step", 0, 16.0 * n_now * B * K, [&] {
         launch_sbs_step(e->issue, logits, e->bm_phi[lpi].p, e->bm_lp[lpi].p, e->bm_g[lpi].p,
                         e->bm_cand.p, e->bm_sbs_lp.p, e->bm_sbs_q.p, e->samp_params.p, n_now, B,
                         K, time - 1, e->bm_phi[lpi ^ 1].p, e->bm_lp[lpi ^ 1].p,
                         e->bm_g[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
-                        one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, mask);
+                        one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, terms);
       });
       else launch(e, "beam_step", 0, 4.0 * n_now * B * K, [&] {
         launch_beam_step(e->issue, logits, e->bm_lp[lpi].p, e->bm_cand.p, n_now, B, K, time,
                          c.diverse_beam, logf(c.diverse_gamma), c.fix_num_timestep,
                          e->bm_lp[lpi ^ 1].p, ids, parents, e->bm_src_row.p,
-                         one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, mask);
+                         one_per_sample ? 1 : B, dedupe ? e->bm_ref.p : nullptr, terms);
       });
       lpi ^= 1;
       src = e->bm_src_row.p;
@@ -1490,13 +1486,10 @@ void run_decoders_selfcont(mv_engine* e, int s, Cursors& cur, int Tp, bool score
       });
       else launch(e, "sample_step", 0, step_bytes, [&] {
         const int32_t* lens = ragged ? e->lens_dev.p : nullptr;
-        StepMask mask = step_mask(e, K, t);
         // the sampler's rows continue themselves: their path is their own row of the [R, T] ids
-        step_motion(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr, mask);
-        step_revisit(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr, mask);
         launch_sample_step(e->issue, logits, orow, rows, B, K, t, shared, e->samp_params.p, 1,
                            lens, e->bm_lp[0].p, e->lq_acc.p, ids, Tp, srow, (uint8_t*)nullptr,
-                           mask);
+                           step_terms(e, S, t, e->bm_out_ids.p, 1, Tp, nullptr));
       });
       if (time == Tsteps) break;
       if (!sparse) run_emb_onehot(e, S, ids, Tp, S.xbuf_cls.p, n_next * B);
@@ -1617,20 +1610,21 @@ void plan_scored(mv_engine* e) {
 // length, and beam_size of them at step 0 where only the root's K children are candidates.
 void plan_cell_mask(mv_engine* e, ForwardKind kind) {
   if (kind == ForwardKind::Scored || kind == ForwardKind::Greedy) return;
-  if (e->cbias_set())
-    MV_REQUIRE(e->cbias_tm == 1 || e->cbias_tm >= e->pred_len, "mv_set_cell_bias: the bias has "
+  const StepConstraints& con = e->con;
+  if (con.bias.set())
+    MV_REQUIRE(con.bias.tm == 1 || con.bias.tm >= e->pred_len, "mv_set_cell_bias: the bias has "
                "Tm = %d planes, the forward pred_len = %d steps (Tm must be 1 or at least "
-               "pred_len)", e->cbias_tm, e->pred_len);
-  if (!e->cmask_set()) return;
+               "pred_len)", con.bias.tm, e->pred_len);
+  if (!con.mask.set()) return;
   const mv_config& c = e->cfg;
-  const int N = c.batch_size, Tp = e->pred_len, Tm = e->cmask_tm, B = c.beam_size;
+  const int N = c.batch_size, Tp = e->pred_len, Tm = con.mask.tm, B = c.beam_size;
   MV_REQUIRE(Tm == 1 || Tm >= Tp, "mv_set_cell_mask: the mask has Tm = %d planes, the forward "
              "pred_len = %d steps (Tm must be 1 or at least pred_len)", Tm, Tp);
   const bool top_b = kind == ForwardKind::Beam || kind == ForwardKind::SampledWor;
   for (int n = 0; n < N; ++n) {
     const int L = e->len.ragged ? e->lens_host[n] : Tp;
     for (int t = 0; t < L; ++t) {
-      const int cnt = e->cmask_count[(size_t)n * Tm + (Tm > 1 ? t : 0)];
+      const int cnt = con.mask_count[(size_t)n * Tm + (Tm > 1 ? t : 0)];
       MV_REQUIRE(cnt >= 1, "mv_set_cell_mask: row n = %d has %d allowed cells at step t = %d "
                  "(every step below the row's length needs at least one)", n, cnt, t);
       if (t == 0 && top_b)
@@ -1675,17 +1669,16 @@ void run_forward(mv_engine* e, ForwardKind kind) {
                "supported (the scoring forward keeps the un-beamed regression decoder)");
   }
   MV_REQUIRE(e->inputs_ready, "no inputs uploaded (mv_upload_inputs)");
-  // a masked step holds a row in one wave: refused before anything is launched
-  if (beam && kind != ForwardKind::Scored && e->cmask_set())
-    require_row_fits_wave("mv_set_cell_mask: a masked step", e->sc[beam_scale(e)].K);
-  if (beam && kind != ForwardKind::Scored && e->cbias_set())
-    require_row_fits_wave("mv_set_cell_bias: a biased step", e->sc[beam_scale(e)].K);
-  if (beam && kind != ForwardKind::Scored && e->motion_set())
-    require_row_fits_wave("mv_set_motion_cost: a step under a motion cost",
-                          e->sc[beam_scale(e)].K);
-  if (beam && kind != ForwardKind::Scored && e->revisit_set())
-    require_row_fits_wave("mv_set_revisit_cost: a step under a revisit cost",
-                          e->sc[beam_scale(e)].K);
+  // a constrained step holds a row in one wave: refused before anything is launched
+  const StepConstraints& con = e->con;
+  const bool constrainable = kind != ForwardKind::Scored && kind != ForwardKind::Greedy;
+  const struct { bool set; const char* who; } row_bound[] = {
+      {con.mask.set(), "mv_set_cell_mask: a masked step"},
+      {con.bias.set(), "mv_set_cell_bias: a biased step"},
+      {con.motion_set(), "mv_set_motion_cost: a step under a motion cost"},
+      {con.revisit_set(), "mv_set_revisit_cost: a step under a revisit cost"}};
+  for (const auto& b : row_bound)
+    if (constrainable && b.set) require_row_fits_wave(b.who, e->sc[beam_scale(e)].K);
   ensure_params(e);
   if (beam)
     MV_REQUIRE(c.beam_size > 1, "engine was created with beam_size 1");
@@ -1702,15 +1695,9 @@ void run_forward(mv_engine* e, ForwardKind kind) {
     return;
   }
   // (a scoring forward reads no mask and no bias: one graph whatever is set)
-  const bool constrainable = kind != ForwardKind::Scored && kind != ForwardKind::Greedy;
-  const int mask_key = (!constrainable || !e->cmask_set() ? 0 : (e->cmask_tm > 1 ? 2 : 1)) +
-                       3 * (!constrainable || !e->cbias_set() ? 0 : (e->cbias_tm > 1 ? 2 : 1)) +
-                       // a captured step bakes in the radius and whether acc is present
-                       9 * (!constrainable || !e->motion_set()
-                                ? 0 : 2 * e->motion_radius - 1 + (e->motion_acc ? 1 : 0)) +
-                       // (the motion member is at most 8) a captured step bakes in whether a
-                       // revisit cost is set and whether it starts from the observed cells
-                       81 * (!constrainable || !e->revisit_set() ? 0 : (e->revisit_seed ? 2 : 1));
+  const int mask_key = !constrainable ? 0
+      : constraint_graph_key(con.mask.layout(), con.bias.layout(), con.motion_radius,
+                             con.motion_acc, con.revisit_set(), con.revisit_seed);
   const auto key = std::make_tuple(kind, e->pred_len, e->num_frames, mask_key);
   auto it = e->graphs.find(key);
   if (it == e->graphs.end()) {

@@ -463,20 +463,25 @@ void decode_trajectories(mv_engine* e, int scale, int center_only, double* out) 
 }
 
 // K <= CPT * 256 cells: a thread's cells in registers (CPT 1 or 3); any K beyond
-// MASKED (mv_set_cell_mask): each future's step map is the softmax over the allowed cells
-// BIASED (mv_set_cell_bias; the kernels' MASKED form with the mask plane optional): of l + b
-template <bool RAGGED, bool MASKED, bool BIASED = false>
+// Masked (mv_set_cell_mask): each future's step map is the softmax over the allowed cells
+// Biased (mv_set_cell_bias; the kernels' MASKED form with the mask plane optional): of l + b
+// (the occupancy kernels have no Motion and no Path form: beam_occupancy refuses before it asks)
+template <bool RAGGED, RowForm F>
 void launch_beam_occupancy(mv_engine* e, const float* lp, int N, int B, int Tp, int K) {
-  const bool mask = MASKED && e->cmask_set();
+  static_assert(F <= RowForm::Biased, "the occupancy kernels come in the first three forms");
+  constexpr bool MASKED = mv::row_has_bits(F), BIASED = mv::row_has_bias(F);
+  const StepConstraints& con = e->con;
+  const int Tcap = e->cfg.max_pred_len;
+  const bool mask = MASKED && con.mask.set();
   auto go = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, dim3(N * Tp), dim3(mv::kMfBlock), 0, e->stream, e->bm_out_logits.p,
                        lp, e->mf_occ.p, B, Tp, K, RAGGED ? e->lens_dev.p : nullptr,
-                       mask ? e->cmask_dev.p : (const uint8_t*)nullptr,
-                       mask ? e->cmask_stride(K) : (int64_t)0,
-                       mask ? e->cmask_step(K) : (int64_t)0,
-                       BIASED ? e->cbias_dev.p : (const float*)nullptr,
-                       BIASED ? e->cbias_stride(K) : (int64_t)0,
-                       BIASED ? e->cbias_step(K) : (int64_t)0);
+                       mask ? con.mask.dev.p : (const uint8_t*)nullptr,
+                       mask ? con.mask.stride(K, Tcap) : (int64_t)0,
+                       mask ? con.mask.step(K) : (int64_t)0,
+                       BIASED ? con.bias.dev.p : (const float*)nullptr,
+                       BIASED ? con.bias.stride(K, Tcap) : (int64_t)0,
+                       BIASED ? con.bias.step(K) : (int64_t)0);
   };
   if (K <= mv::kMfBlock) go(mv::beam_occupancy_kernel<1, RAGGED, MASKED, BIASED>);
   else if (K <= 3 * mv::kMfBlock) go(mv::beam_occupancy_kernel<3, RAGGED, MASKED, BIASED>);
@@ -492,33 +497,34 @@ void beam_occupancy(mv_engine* e, float* out) {
   MV_REQUIRE(e->last != ForwardKind::Scored, "mv_beam_occupancy: the last forward scored given "
              "futures (mv_score_futures); a set of given futures is not a predictive mixture");
   // (a plane that depends on each future's path has no per-step map of the mixture: left out)
-  MV_REQUIRE(!e->motion_set(), "mv_beam_occupancy: a motion cost is set (mv_set_motion_cost); the "
+  const StepConstraints& con = e->con;
+  MV_REQUIRE(!con.motion_set(), "mv_beam_occupancy: a motion cost is set (mv_set_motion_cost); the "
              "occupancy map under a path-dependent cost is not defined -- clear it first");
-  MV_REQUIRE(!e->revisit_set(), "mv_beam_occupancy: a revisit cost is set (mv_set_revisit_cost); "
+  MV_REQUIRE(!con.revisit_set(), "mv_beam_occupancy: a revisit cost is set (mv_set_revisit_cost); "
              "the occupancy map under a path-dependent cost is not defined -- clear it first");
   const ScaleState& S = e->sc[beam_scale(e)];
   const int N = c.batch_size, B = c.beam_size, Tp = e->pred_len, K = S.K;
   const size_t cells = (size_t)N * Tp * K;
   // the mask the forward chose its cells under, if it is still set (the forward checked it)
-  const bool masked = e->cmask_set();
+  const bool masked = con.mask.set();
   if (masked) {
-    MV_REQUIRE(e->cmask_tm == 1 || e->cmask_tm >= Tp, "mv_beam_occupancy: the cell mask has "
-               "Tm = %d planes, the last forward pred_len = %d steps", e->cmask_tm, Tp);
+    MV_REQUIRE(con.mask.tm == 1 || con.mask.tm >= Tp, "mv_beam_occupancy: the cell mask has "
+               "Tm = %d planes, the last forward pred_len = %d steps", con.mask.tm, Tp);
     // the mask may have been set after the forward, which checked ITS mask: a step map over an
     // empty set would be 0 / 0
     const bool rag = e->len.ragged && e->lens_host.size() == (size_t)N;
     for (int n = 0; n < N; ++n)
       for (int t = 0; t < (rag ? e->lens_host[n] : Tp); ++t) {
-        const int cnt = e->cmask_count[(size_t)n * e->cmask_tm + (e->cmask_tm > 1 ? t : 0)];
+        const int cnt = con.mask_count[(size_t)n * con.mask.tm + (con.mask.tm > 1 ? t : 0)];
         MV_REQUIRE(cnt >= 1, "mv_beam_occupancy: row n = %d has %d allowed cells at step t = %d "
                    "under the cell mask that is set now (mv_set_cell_mask)", n, cnt, t);
       }
   }
   // the bias that is set now, as the mask
-  const RowForm form = step_row_form(masked, e->cbias_set());
+  const RowForm form = row_form(masked, con.bias.set(), false, false);
   if (form == RowForm::Biased)
-    MV_REQUIRE(e->cbias_tm == 1 || e->cbias_tm >= Tp, "mv_beam_occupancy: the cell bias has "
-               "Tm = %d planes, the last forward pred_len = %d steps", e->cbias_tm, Tp);
+    MV_REQUIRE(con.bias.tm == 1 || con.bias.tm >= Tp, "mv_beam_occupancy: the cell bias has "
+               "Tm = %d planes, the last forward pred_len = %d steps", con.bias.tm, Tp);
   e->mf_occ.alloc((size_t)N * c.max_pred_len * K);
   // HBM-bound: every beam's logits row read once, the map written once
   // independently sampled futures are draws, not scored hypotheses: uniform weights, which the
@@ -532,13 +538,13 @@ void beam_occupancy(mv_engine* e, float* out) {
   }
   launch(e, "beam_occupancy", 5.0 * cells * B, 4.0 * cells * (B + 1) + 4.0 * N * B, [&] {
     // the last forward ran with per-row lengths: 0 past a row's end
-    if (form == RowForm::Biased && e->len.ragged)
-      launch_beam_occupancy<true, true, true>(e, lp, N, B, Tp, K);
-    else if (form == RowForm::Biased) launch_beam_occupancy<false, true, true>(e, lp, N, B, Tp, K);
-    else if (masked && e->len.ragged) launch_beam_occupancy<true, true>(e, lp, N, B, Tp, K);
-    else if (masked) launch_beam_occupancy<false, true>(e, lp, N, B, Tp, K);
-    else if (e->len.ragged) launch_beam_occupancy<true, false>(e, lp, N, B, Tp, K);
-    else launch_beam_occupancy<false, false>(e, lp, N, B, Tp, K);
+    with_row_form(form, [&](auto f) {
+      constexpr RowForm F = decltype(f)::value;
+      if constexpr (F <= RowForm::Biased) {
+        if (e->len.ragged) launch_beam_occupancy<true, F>(e, lp, N, B, Tp, K);
+        else launch_beam_occupancy<false, F>(e, lp, N, B, Tp, K);
+      }
+    });
   });
   HIP_CHECK(hipGetLastError());
   HIP_CHECK(hipMemcpyAsync(out, e->mf_occ.p, cells * sizeof(float), hipMemcpyDeviceToHost,

@@ -289,148 +289,137 @@ int mv_op_hidden2grid(int device, const float* h, const float* w, int32_t M,
   });
 }
 
-// the masked forms of the three step ops: `allowed` [samples, K] goes up beside the logits
-static StepMask op_mask_up(OpCtx& ctx, DevBuf<uint8_t>& dm, const uint8_t* allowed, size_t samples,
-                           int K, const char* who) {
-  MV_REQUIRE(allowed, "%s: NULL allowed", who);
-  require_row_fits_wave(who, K);
-  ctx.up(dm, allowed, samples * K);
-  StepMask m;
-  m.p = dm.p;
-  m.stride = K;
-  return m;
-}
-
-// the biased forms: `bias` [samples, K] floats goes up as well; `allowed` may be NULL there
-static void op_bias_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, StepMask& m,
-                       const uint8_t* allowed, const float* bias, size_t samples, int K,
-                       const char* who) {
-  MV_REQUIRE(bias, "%s: NULL bias", who);
-  require_row_fits_wave(who, K);
-  for (size_t i = 0; i < samples * K; ++i)
-    MV_REQUIRE(std::isfinite(bias[i]), "%s: bias[%d, %d] = %g is not finite", who, (int)(i / K),
-               (int)(i % K), (double)bias[i]);
-  if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
-  ctx.up(db, bias, samples * K);
-  m.bias = db.p;
-  m.bias_stride = K;
-}
-
-// the motion forms: the tables and every row's p1 / p0 go up; `allowed` and `bias` may be NULL
-struct OpMotionBufs {
-  DevBuf<float> vel, vel_far, acc, acc_far;
-  DevBuf<int32_t> prev1, prev0;
-};
-static void op_motion_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, OpMotionBufs& mb,
-                         StepMask& m, const uint8_t* allowed, const float* bias,
-                         const mv_step_motion* mo, size_t samples, size_t rows, int K,
-                         const char* who) {
-  MV_REQUIRE(mo && mo->vel && mo->vel_far && mo->prev1 && mo->prev0,
-             "%s: NULL motion, vel, vel_far, prev1 or prev0", who);
-  require_row_fits_wave(who, K);
-  MV_REQUIRE(mo->radius >= 1 && mo->radius <= MV_MOTION_MAX_RADIUS, "%s: radius %d not in [1, %d]",
-             who, (int)mo->radius, MV_MOTION_MAX_RADIUS);
-  MV_REQUIRE(mo->W >= 1 && K % mo->W == 0, "%s: W = %d does not divide K = %d", who, (int)mo->W, K);
-  MV_REQUIRE((mo->acc != nullptr) == (mo->acc_far != nullptr),
-             "%s: acc and acc_far are given both or neither", who);
-  const size_t DD = (size_t)(2 * mo->radius + 1) * (2 * mo->radius + 1);
-  auto finite = [&](const float* p, size_t per, const char* name) {
-    for (size_t i = 0; i < samples * per; ++i)
-      MV_REQUIRE(std::isfinite(p[i]), "%s: %s[n = %d, entry %d] = %g is not finite", who, name,
-                 (int)(i / per), (int)(i % per), (double)p[i]);
-  };
-  finite(mo->vel, DD, "vel");
-  finite(mo->vel_far, 1, "vel_far");
-  if (mo->acc) { finite(mo->acc, DD, "acc"); finite(mo->acc_far, 1, "acc_far"); }
-  for (size_t r = 0; r < rows; ++r) {
-    MV_REQUIRE(mo->prev1[r] >= 0 && mo->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)", who,
-               (int)r, (int)mo->prev1[r], K);
-    MV_REQUIRE(mo->prev0[r] >= -1 && mo->prev0[r] < K, "%s: prev0[%d] = %d not in [-1, K = %d)",
-               who, (int)r, (int)mo->prev0[r], K);
-  }
-  if (bias) op_bias_up(ctx, dm, db, m, allowed, bias, samples, K, who);
-  else if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
-  ctx.up(mb.vel, mo->vel, samples * DD);
-  ctx.up(mb.vel_far, mo->vel_far, samples);
-  if (mo->acc) { ctx.up(mb.acc, mo->acc, samples * DD); ctx.up(mb.acc_far, mo->acc_far, samples); }
-  ctx.up(mb.prev1, mo->prev1, rows);
-  ctx.up(mb.prev0, mo->prev0, rows);
-  m.mo.vel = mb.vel.p; m.mo.vel_far = mb.vel_far.p;
-  m.mo.acc = mo->acc ? mb.acc.p : nullptr; m.mo.acc_far = mo->acc ? mb.acc_far.p : nullptr;
-  m.mo.prev1 = mb.prev1.p; m.mo.prev0 = mb.prev0.p;
-  m.mo.W = mo->W; m.mo.radius = mo->radius;
-}
-
-// the path forms: the cost, every row's p1 and the rows' visited sets go up, packed from the op's
-// byte planes into the device's lane-major words (kernels_misc.h RevisitRow: bit j of word l =
-// cell l + 64 j); `allowed`, `bias` and `motion` may be NULL.  The stored sets start as the given
-// ones, so that a row the step does not run reports its set as given.
-struct OpRevisitBufs {
-  DevBuf<float> cost;
-  DevBuf<int32_t> prev1;
-  DevBuf<uint32_t> in, out;
+// What constrains the step of a single-kernel step op: the device copies of the four optional
+// inputs and the StepTerms that point at them.  Every part that is given -- and the one the entry
+// point `who` needs, given or not -- validates and uploads itself.
+enum class OpNeeds { Nothing, Allowed, Bias, Motion, Revisit };
+struct OpStepTerms {
+  DevBuf<uint8_t> allowed;
+  DevBuf<float> bias, vel, vel_far, acc, acc_far, cost;
+  DevBuf<int32_t> motion_prev1, motion_prev0, revisit_prev1;
+  DevBuf<uint32_t> set_in, set_out;
   std::vector<uint32_t> words;
-};
-static void op_path_up(OpCtx& ctx, DevBuf<uint8_t>& dm, DevBuf<float>& db, OpMotionBufs& mb,
-                       OpRevisitBufs& rb, StepMask& m, const uint8_t* allowed, const float* bias,
-                       const mv_step_motion* mo, const mv_step_revisit* rv, size_t samples,
-                       size_t rows, int K, const char* who) {
-  MV_REQUIRE(rv && rv->cost && rv->prev1, "%s: NULL revisit, cost or prev1", who);
-  require_row_fits_wave(who, K);
-  for (size_t n = 0; n < samples; ++n)
-    MV_REQUIRE(std::isfinite(rv->cost[n]), "%s: cost[n = %d] = %g is not finite", who, (int)n,
-               (double)rv->cost[n]);
-  for (size_t r = 0; r < rows; ++r)
-    MV_REQUIRE(rv->prev1[r] >= 0 && rv->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)", who,
-               (int)r, (int)rv->prev1[r], K);
-  if (mo) op_motion_up(ctx, dm, db, mb, m, allowed, bias, mo, samples, rows, K, who);
-  else if (bias) op_bias_up(ctx, dm, db, m, allowed, bias, samples, K, who);
-  else if (allowed) m = op_mask_up(ctx, dm, allowed, samples, K, who);
-  rb.words.assign(rows * 64, 0u);
-  if (rv->visited)
+  const mv_step_revisit* revisit = nullptr;
+  size_t rows = 0;
+  int K = 0;
+  StepTerms terms;
+
+  // `allowed` [samples, K], `bias` [samples, K] floats, the motion tables with every row's
+  // p1 / p0, the revisit cost with every row's p1 and visited set
+  void up(OpCtx& ctx, const uint8_t* allowed_h, const float* bias_h, const mv_step_motion* mo,
+          const mv_step_revisit* rv, OpNeeds needs, size_t samples, size_t rows_, int K_,
+          const char* who) {
+    rows = rows_;
+    K = K_;
+    if (rv || needs == OpNeeds::Revisit) up_revisit(ctx, rv, samples, who);
+    if (mo || needs == OpNeeds::Motion) up_motion(ctx, mo, samples, who);
+    if (bias_h || needs == OpNeeds::Bias) up_bias(ctx, bias_h, samples, who);
+    if (allowed_h || needs == OpNeeds::Allowed) {
+      MV_REQUIRE(allowed_h, "%s: NULL allowed", who);
+      require_row_fits_wave(who, K);
+      ctx.up(allowed, allowed_h, samples * K);
+      terms.amask = allowed.p;
+      terms.mask_stride = K;
+    }
+  }
+
+  void up_bias(OpCtx& ctx, const float* bias_h, size_t samples, const char* who) {
+    MV_REQUIRE(bias_h, "%s: NULL bias", who);
+    require_row_fits_wave(who, K);
+    for (size_t i = 0; i < samples * K; ++i)
+      MV_REQUIRE(std::isfinite(bias_h[i]), "%s: bias[%d, %d] = %g is not finite", who,
+                 (int)(i / K), (int)(i % K), (double)bias_h[i]);
+    ctx.up(bias, bias_h, samples * K);
+    terms.bias = bias.p;
+    terms.bias_stride = K;
+  }
+
+  void up_motion(OpCtx& ctx, const mv_step_motion* mo, size_t samples, const char* who) {
+    MV_REQUIRE(mo && mo->vel && mo->vel_far && mo->prev1 && mo->prev0,
+               "%s: NULL motion, vel, vel_far, prev1 or prev0", who);
+    require_row_fits_wave(who, K);
+    MV_REQUIRE(mo->radius >= 1 && mo->radius <= MV_MOTION_MAX_RADIUS,
+               "%s: radius %d not in [1, %d]", who, (int)mo->radius, MV_MOTION_MAX_RADIUS);
+    MV_REQUIRE(mo->W >= 1 && K % mo->W == 0, "%s: W = %d does not divide K = %d", who, (int)mo->W,
+               K);
+    MV_REQUIRE((mo->acc != nullptr) == (mo->acc_far != nullptr),
+               "%s: acc and acc_far are given both or neither", who);
+    const size_t DD = (size_t)(2 * mo->radius + 1) * (2 * mo->radius + 1);
+    auto finite = [&](const float* p, size_t per, const char* name) {
+      for (size_t i = 0; i < samples * per; ++i)
+        MV_REQUIRE(std::isfinite(p[i]), "%s: %s[n = %d, entry %d] = %g is not finite", who, name,
+                   (int)(i / per), (int)(i % per), (double)p[i]);
+    };
+    finite(mo->vel, DD, "vel");
+    finite(mo->vel_far, 1, "vel_far");
+    if (mo->acc) { finite(mo->acc, DD, "acc"); finite(mo->acc_far, 1, "acc_far"); }
+    for (size_t r = 0; r < rows; ++r) {
+      MV_REQUIRE(mo->prev1[r] >= 0 && mo->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)",
+                 who, (int)r, (int)mo->prev1[r], K);
+      MV_REQUIRE(mo->prev0[r] >= -1 && mo->prev0[r] < K, "%s: prev0[%d] = %d not in [-1, K = %d)",
+                 who, (int)r, (int)mo->prev0[r], K);
+    }
+    ctx.up(vel, mo->vel, samples * DD);
+    ctx.up(vel_far, mo->vel_far, samples);
+    if (mo->acc) { ctx.up(acc, mo->acc, samples * DD); ctx.up(acc_far, mo->acc_far, samples); }
+    ctx.up(motion_prev1, mo->prev1, rows);
+    ctx.up(motion_prev0, mo->prev0, rows);
+    mv::MotionRow& m = terms.mo;
+    m.vel = vel.p; m.vel_far = vel_far.p;
+    m.acc = mo->acc ? acc.p : nullptr; m.acc_far = mo->acc ? acc_far.p : nullptr;
+    m.prev1 = motion_prev1.p; m.prev0 = motion_prev0.p;
+    m.W = mo->W; m.radius = mo->radius;
+  }
+
+  // the rows' visited sets go up packed from the op's byte planes into the device's lane-major
+  // words (kernels_misc.h RevisitRow: bit j of word l = cell l + 64 j).  The stored sets start as
+  // the given ones, so that a row the step does not run reports its set as given.
+  void up_revisit(OpCtx& ctx, const mv_step_revisit* rv, size_t samples, const char* who) {
+    MV_REQUIRE(rv && rv->cost && rv->prev1, "%s: NULL revisit, cost or prev1", who);
+    require_row_fits_wave(who, K);
+    for (size_t n = 0; n < samples; ++n)
+      MV_REQUIRE(std::isfinite(rv->cost[n]), "%s: cost[n = %d] = %g is not finite", who, (int)n,
+                 (double)rv->cost[n]);
+    for (size_t r = 0; r < rows; ++r)
+      MV_REQUIRE(rv->prev1[r] >= 0 && rv->prev1[r] < K, "%s: prev1[%d] = %d not in [0, K = %d)",
+                 who, (int)r, (int)rv->prev1[r], K);
+    revisit = rv;
+    words.assign(rows * 64, 0u);
+    if (rv->visited)
+      for (size_t r = 0; r < rows; ++r)
+        for (int k = 0; k < K; ++k)
+          if (rv->visited[r * K + k]) words[r * 64 + (k & 63)] |= 1u << (k >> 6);
+    ctx.up(cost, rv->cost, samples);
+    ctx.up(revisit_prev1, rv->prev1, rows);
+    ctx.up(set_in, words.data(), rows * 64);
+    ctx.up(set_out, words.data(), rows * 64);
+    terms.rv.cost = cost.p;
+    terms.rv.prev1 = revisit_prev1.p;
+    terms.rv.set_in = set_in.p;
+    terms.rv.set_out = set_out.p;
+  }
+
+  // the sets the step stored, unpacked into visited_out (where a revisit cost went up and asks)
+  void down(OpCtx& ctx) {
+    if (!revisit || !revisit->visited_out) return;
+    ctx.down(words.data(), set_out, rows * 64);
     for (size_t r = 0; r < rows; ++r)
       for (int k = 0; k < K; ++k)
-        if (rv->visited[r * K + k]) rb.words[r * 64 + (k & 63)] |= 1u << (k >> 6);
-  ctx.up(rb.cost, rv->cost, samples);
-  ctx.up(rb.prev1, rv->prev1, rows);
-  ctx.up(rb.in, rb.words.data(), rows * 64);
-  ctx.up(rb.out, rb.words.data(), rows * 64);
-  m.rv.cost = rb.cost.p;
-  m.rv.prev1 = rb.prev1.p;
-  m.rv.set_in = rb.in.p;
-  m.rv.set_out = rb.out.p;
-}
-static void op_path_down(OpCtx& ctx, OpRevisitBufs& rb, const mv_step_revisit* rv, size_t rows,
-                         int K) {
-  if (!rv->visited_out) return;
-  ctx.down(rb.words.data(), rb.out, rows * 64);
-  for (size_t r = 0; r < rows; ++r)
-    for (int k = 0; k < K; ++k)
-      rv->visited_out[r * K + k] = (rb.words[r * 64 + (k & 63)] >> (k >> 6)) & 1u;
-}
+        revisit->visited_out[r * K + k] = (words[r * 64 + (k & 63)] >> (k >> 6)) & 1u;
+  }
+};
 
 static int op_beam_step(int device, const float* logits, const float* prev_logprob,
                         int32_t N, int32_t B, int32_t K, int32_t time, int32_t diverse,
                         float gamma, int32_t fix_num_timestep, float* new_logprob,
-                        int32_t* ids, int32_t* parents, const uint8_t* allowed, bool masked,
-                        const float* bias = nullptr, bool biased = false,
-                        const mv_step_motion* motion = nullptr, bool moving = false,
-                        const mv_step_revisit* revisit = nullptr, bool path = false) {
+                        int32_t* ids, int32_t* parents, const char* who, OpNeeds needs,
+                        const uint8_t* allowed = nullptr, const float* bias = nullptr,
+                        const mv_step_motion* motion = nullptr,
+                        const mv_step_revisit* revisit = nullptr) {
   return guarded(nullptr, [&] {
     OpCtx ctx(device);
-    DevBuf<uint8_t> dm;
-    DevBuf<float> db;
-    OpMotionBufs mb;
-    OpRevisitBufs rb;
-    StepMask mask;
-    if (path)
-      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)N,
-                 (size_t)N * B, K, "mv_op_beam_step_path");
-    else if (moving)
-      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
-                   "mv_op_beam_step_motion");
-    else if (biased) op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_beam_step_biased");
-    else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_beam_step_masked");
+    OpStepTerms st;
+    st.up(ctx, allowed, bias, motion, revisit, needs, (size_t)N, (size_t)N * B, K, who);
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     DevBuf<float> dl, dp, dn;
     DevBuf<int32_t> di, dpa;
@@ -440,11 +429,11 @@ static int op_beam_step(int device, const float* logits, const float* prev_logpr
     DevBuf<float> dc;
     dc.alloc((size_t)N * B * K);
     launch_beam_step(ctx.stream, dl.p, dp.p, dc.p, N, B, K, time, diverse, logf(gamma),
-                     fix_num_timestep, dn.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, mask);
+                     fix_num_timestep, dn.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, st.terms);
     ctx.down(new_logprob, dn, (size_t)N * B);
     ctx.down(ids, di, (size_t)N * B);
     ctx.down(parents, dpa, (size_t)N * B);
-    if (path) op_path_down(ctx, rb, revisit, (size_t)N * B, K);
+    st.down(ctx);
   });
 }
 
@@ -453,7 +442,8 @@ int mv_op_beam_step(int device, const float* logits, const float* prev_logprob,
                     float gamma, int32_t fix_num_timestep, float* new_logprob,
                     int32_t* ids, int32_t* parents) {
   return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
-                      fix_num_timestep, new_logprob, ids, parents, nullptr, false);
+                      fix_num_timestep, new_logprob, ids, parents,
+                      "mv_op_beam_step", OpNeeds::Nothing);
 }
 
 int mv_op_beam_step_masked(int device, const float* logits, const float* prev_logprob,
@@ -461,7 +451,8 @@ int mv_op_beam_step_masked(int device, const float* logits, const float* prev_lo
                            int32_t diverse, float gamma, int32_t fix_num_timestep,
                            float* new_logprob, int32_t* ids, int32_t* parents) {
   return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
-                      fix_num_timestep, new_logprob, ids, parents, allowed, true);
+                      fix_num_timestep, new_logprob, ids, parents,
+                      "mv_op_beam_step_masked", OpNeeds::Allowed, allowed);
 }
 
 int mv_op_beam_step_biased(int device, const float* logits, const float* prev_logprob,
@@ -470,8 +461,8 @@ int mv_op_beam_step_biased(int device, const float* logits, const float* prev_lo
                            int32_t fix_num_timestep, float* new_logprob, int32_t* ids,
                            int32_t* parents) {
   return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
-                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
-                      bias, true);
+                      fix_num_timestep, new_logprob, ids, parents,
+                      "mv_op_beam_step_biased", OpNeeds::Bias, allowed, bias);
 }
 
 int mv_op_beam_step_motion(int device, const float* logits, const float* prev_logprob,
@@ -480,8 +471,8 @@ int mv_op_beam_step_motion(int device, const float* logits, const float* prev_lo
                            float gamma, int32_t fix_num_timestep, float* new_logprob, int32_t* ids,
                            int32_t* parents) {
   return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
-                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
-                      bias, bias != nullptr, motion, true);
+                      fix_num_timestep, new_logprob, ids, parents,
+                      "mv_op_beam_step_motion", OpNeeds::Motion, allowed, bias, motion);
 }
 
 int mv_op_beam_step_path(int device, const float* logits, const float* prev_logprob,
@@ -490,37 +481,24 @@ int mv_op_beam_step_path(int device, const float* logits, const float* prev_logp
                          int32_t time, int32_t diverse, float gamma, int32_t fix_num_timestep,
                          float* new_logprob, int32_t* ids, int32_t* parents) {
   return op_beam_step(device, logits, prev_logprob, N, B, K, time, diverse, gamma,
-                      fix_num_timestep, new_logprob, ids, parents, allowed, allowed != nullptr,
-                      bias, bias != nullptr, motion, motion != nullptr, revisit, true);
+                      fix_num_timestep, new_logprob, ids, parents,
+                      "mv_op_beam_step_path", OpNeeds::Revisit, allowed, bias, motion, revisit);
 }
 
 static int op_sbs_step(int device, const float* logits, const float* prev_phi,
                        const float* prev_logprob, const float* prev_gumbel, int32_t N, int32_t B,
                        int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                        float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents,
-                       const uint8_t* allowed, bool masked, const float* bias = nullptr,
-                       bool biased = false, const mv_step_motion* motion = nullptr,
-                       bool moving = false, const mv_step_revisit* revisit = nullptr,
-                       bool path = false) {
+                       const char* who, OpNeeds needs, const uint8_t* allowed = nullptr,
+                       const float* bias = nullptr, const mv_step_motion* motion = nullptr,
+                       const mv_step_revisit* revisit = nullptr) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(N > 0 && B > 0 && K > 0 && t >= 0, "mv_op_sbs_step: N, B, K > 0 and t >= 0");
     MV_REQUIRE(temperature > 0.f, "mv_op_sbs_step: temperature %g must be > 0",
                (double)temperature);
     OpCtx ctx(device);
-    DevBuf<uint8_t> dm;
-    DevBuf<float> db;
-    OpMotionBufs mb;
-    OpRevisitBufs rb;
-    StepMask mask;
-    if (path)
-      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)N,
-                 (size_t)N * B, K, "mv_op_sbs_step_path");
-    else if (moving)
-      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)N, (size_t)N * B, K,
-                   "mv_op_sbs_step_motion");
-    else if (biased)
-      op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)N, K, "mv_op_sbs_step_biased");
-    else if (masked) mask = op_mask_up(ctx, dm, allowed, (size_t)N, K, "mv_op_sbs_step_masked");
+    OpStepTerms st;
+    st.up(ctx, allowed, bias, motion, revisit, needs, (size_t)N, (size_t)N * B, K, who);
     ensure_beam_step_lds(device, beam_step_lds_bytes(B, K));
     const size_t R = (size_t)N * B;
     DevBuf<float> dl, dphi, dlp, dg, nphi, nlp, ng, cand, lpp, qp;
@@ -534,10 +512,10 @@ static int op_sbs_step(int device, const float* logits, const float* prev_phi,
     nphi.alloc(R); nlp.alloc(R); ng.alloc(R); di.alloc(R); dpa.alloc(R);
     cand.alloc(R * K); lpp.alloc(R * K); qp.alloc(R * K);
     launch_sbs_step(ctx.stream, dl.p, dphi.p, dlp.p, dg.p, cand.p, lpp.p, qp.p, dprm.p, N, B, K,
-                    t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, mask);
+                    t, nphi.p, nlp.p, ng.p, di.p, dpa.p, (int32_t*)nullptr, B, nullptr, st.terms);
     ctx.down(new_phi, nphi, R); ctx.down(new_logprob, nlp, R); ctx.down(new_gumbel, ng, R);
     ctx.down(ids, di, R); ctx.down(parents, dpa, R);
-    if (path) op_path_down(ctx, rb, revisit, R, K);
+    st.down(ctx);
   });
 }
 
@@ -546,7 +524,8 @@ int mv_op_sbs_step(int device, const float* logits, const float* prev_phi,
                    int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                    float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
   return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
-                     seed, new_phi, new_logprob, new_gumbel, ids, parents, nullptr, false);
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents,
+                     "mv_op_sbs_step", OpNeeds::Nothing);
 }
 
 int mv_op_sbs_step_masked(int device, const float* logits, const float* prev_phi,
@@ -555,7 +534,8 @@ int mv_op_sbs_step_masked(int device, const float* logits, const float* prev_phi
                           float temperature, uint32_t seed, float* new_phi, float* new_logprob,
                           float* new_gumbel, int32_t* ids, int32_t* parents) {
   return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
-                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed, true);
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents,
+                     "mv_op_sbs_step_masked", OpNeeds::Allowed, allowed);
 }
 
 int mv_op_sbs_step_biased(int device, const float* logits, const float* prev_phi,
@@ -564,8 +544,8 @@ int mv_op_sbs_step_biased(int device, const float* logits, const float* prev_phi
                           int32_t K, int32_t t, float temperature, uint32_t seed, float* new_phi,
                           float* new_logprob, float* new_gumbel, int32_t* ids, int32_t* parents) {
   return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
-                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
-                     allowed != nullptr, bias, true);
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents,
+                     "mv_op_sbs_step_biased", OpNeeds::Bias, allowed, bias);
 }
 
 int mv_op_sbs_step_motion(int device, const float* logits, const float* prev_phi,
@@ -575,8 +555,8 @@ int mv_op_sbs_step_motion(int device, const float* logits, const float* prev_phi
                           uint32_t seed, float* new_phi, float* new_logprob, float* new_gumbel,
                           int32_t* ids, int32_t* parents) {
   return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
-                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
-                     allowed != nullptr, bias, bias != nullptr, motion, true);
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents,
+                     "mv_op_sbs_step_motion", OpNeeds::Motion, allowed, bias, motion);
 }
 
 int mv_op_sbs_step_path(int device, const float* logits, const float* prev_phi,
@@ -586,24 +566,21 @@ int mv_op_sbs_step_path(int device, const float* logits, const float* prev_phi,
                         float temperature, uint32_t seed, float* new_phi, float* new_logprob,
                         float* new_gumbel, int32_t* ids, int32_t* parents) {
   return op_sbs_step(device, logits, prev_phi, prev_logprob, prev_gumbel, N, B, K, t, temperature,
-                     seed, new_phi, new_logprob, new_gumbel, ids, parents, allowed,
-                     allowed != nullptr, bias, bias != nullptr, motion, motion != nullptr, revisit,
-                     true);
+                     seed, new_phi, new_logprob, new_gumbel, ids, parents,
+                     "mv_op_sbs_step_path", OpNeeds::Revisit, allowed, bias, motion, revisit);
 }
 
 static int op_sample_step(int device, const float* logits, int32_t R, int32_t S, int32_t K,
                           int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
                           int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep,
-                          const uint8_t* allowed, bool masked, const float* bias = nullptr,
-                          bool biased = false, const mv_step_motion* motion = nullptr,
-                          bool moving = false, const mv_step_revisit* revisit = nullptr,
-                          bool path = false) {
+                          const char* who, OpNeeds needs, const uint8_t* allowed = nullptr,
+                          const float* bias = nullptr, const mv_step_motion* motion = nullptr,
+                          const mv_step_revisit* revisit = nullptr) {
   return guarded(nullptr, [&] {
     MV_REQUIRE(R > 0 && S > 0 && K > 0 && t >= 0, "mv_op_sample_step: R, S, K > 0 and t >= 0");
     MV_REQUIRE(R % S == 0, "mv_op_sample_step: R = %d rows are not S = %d futures per sample",
                (int)R, (int)S);
-    require_row_fits_wave(path ? "mv_op_sample_step_path"
-                          : moving ? "mv_op_sample_step_motion" : "mv_op_sample_step", K);
+    require_row_fits_wave(needs >= OpNeeds::Motion ? who : "mv_op_sample_step", K);
     MV_REQUIRE(temperature > 0.f, "mv_op_sample_step: temperature %g must be > 0",
                (double)temperature);
     MV_REQUIRE(top_k >= 0, "mv_op_sample_step: top_k %d must be >= 0 (0 = off)", (int)top_k);
@@ -611,21 +588,8 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
                (double)top_p);
     MV_REQUIRE(floor >= 1, "mv_op_sample_step: floor %d must be >= 1", (int)floor);
     OpCtx ctx(device);
-    DevBuf<uint8_t> dm;
-    DevBuf<float> db;
-    OpMotionBufs mb;
-    OpRevisitBufs rb;
-    StepMask mask;
-    if (path)
-      op_path_up(ctx, dm, db, mb, rb, mask, allowed, bias, motion, revisit, (size_t)(R / S),
-                 (size_t)R, K, "mv_op_sample_step_path");
-    else if (moving)
-      op_motion_up(ctx, dm, db, mb, mask, allowed, bias, motion, (size_t)(R / S), (size_t)R, K,
-                   "mv_op_sample_step_motion");
-    else if (biased)
-      op_bias_up(ctx, dm, db, mask, allowed, bias, (size_t)(R / S), K, "mv_op_sample_step_biased");
-    else if (masked)
-      mask = op_mask_up(ctx, dm, allowed, (size_t)(R / S), K, "mv_op_sample_step_masked");
+    OpStepTerms st;
+    st.up(ctx, allowed, bias, motion, revisit, needs, (size_t)(R / S), (size_t)R, K, who);
     DevBuf<float> dl, dlp, dq;
     DevBuf<int32_t> di;
     DevBuf<uint8_t> dk;
@@ -638,11 +602,12 @@ static int op_sample_step(int device, const float* logits, int32_t R, int32_t S,
     HIP_CHECK(hipMemsetAsync(dlp.p, 0, (size_t)R * sizeof(float), ctx.stream));
     HIP_CHECK(hipMemsetAsync(dq.p, 0, (size_t)R * sizeof(float), ctx.stream));
     launch_sample_step(ctx.stream, dl.p, (int64_t)K, R, S, K, t, 0, dprm.p, floor,
-                       (const int32_t*)nullptr, dlp.p, dq.p, di.p, 1, (int32_t*)nullptr, dk.p, mask);
+                       (const int32_t*)nullptr, dlp.p, dq.p, di.p, 1, (int32_t*)nullptr, dk.p,
+                       st.terms);
     HIP_CHECK(hipGetLastError());
     ctx.down(ids, di, R); ctx.down(lp, dlp, R); ctx.down(qlp, dq, R);
     ctx.down(keep, dk, (size_t)R * K);
-    if (path) op_path_down(ctx, rb, revisit, (size_t)R, K);
+    st.down(ctx);
   });
 }
 
@@ -650,7 +615,7 @@ int mv_op_sample_step(int device, const float* logits, int32_t R, int32_t S, int
                       float temperature, uint32_t seed, int32_t top_k, float top_p, int32_t floor,
                       int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
-                        qlp, keep, nullptr, false);
+                        qlp, keep, "mv_op_sample_step", OpNeeds::Nothing);
 }
 
 int mv_op_sample_step_masked(int device, const float* logits, const uint8_t* allowed, int32_t R,
@@ -658,7 +623,7 @@ int mv_op_sample_step_masked(int device, const float* logits, const uint8_t* all
                              int32_t top_k, float top_p, int32_t floor, int32_t* ids, float* lp,
                              float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
-                        qlp, keep, allowed, true);
+                        qlp, keep, "mv_op_sample_step_masked", OpNeeds::Allowed, allowed);
 }
 
 int mv_op_sample_step_biased(int device, const float* logits, const uint8_t* allowed,
@@ -666,7 +631,7 @@ int mv_op_sample_step_biased(int device, const float* logits, const uint8_t* all
                              float temperature, uint32_t seed, int32_t top_k, float top_p,
                              int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
-                        qlp, keep, allowed, allowed != nullptr, bias, true);
+                        qlp, keep, "mv_op_sample_step_biased", OpNeeds::Bias, allowed, bias);
 }
 
 int mv_op_sample_step_motion(int device, const float* logits, const uint8_t* allowed,
@@ -675,7 +640,8 @@ int mv_op_sample_step_motion(int device, const float* logits, const uint8_t* all
                              float top_p, int32_t floor, int32_t* ids, float* lp, float* qlp,
                              uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
-                        qlp, keep, allowed, allowed != nullptr, bias, bias != nullptr, motion, true);
+                        qlp, keep,
+                        "mv_op_sample_step_motion", OpNeeds::Motion, allowed, bias, motion);
 }
 
 int mv_op_sample_step_path(int device, const float* logits, const uint8_t* allowed,
@@ -684,8 +650,8 @@ int mv_op_sample_step_path(int device, const float* logits, const uint8_t* allow
                            int32_t t, float temperature, uint32_t seed, int32_t top_k, float top_p,
                            int32_t floor, int32_t* ids, float* lp, float* qlp, uint8_t* keep) {
   return op_sample_step(device, logits, R, S, K, t, temperature, seed, top_k, top_p, floor, ids, lp,
-                        qlp, keep, allowed, allowed != nullptr, bias, bias != nullptr, motion,
-                        motion != nullptr, revisit, true);
+                        qlp, keep,
+                        "mv_op_sample_step_path", OpNeeds::Revisit, allowed, bias, motion, revisit);
 }
 
 int mv_enc_cone_build(const int32_t* labels, int32_t N, int32_t T, int32_t H, int32_t W,

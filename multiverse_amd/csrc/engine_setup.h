@@ -36,29 +36,24 @@ void with_rank_j(int K, F&& fn) {
   else fn(std::integral_constant<int, mv::kBeamRankJ>{});
 }
 
-// The allowed cells of one decode step (mv_set_cell_mask): sample n's plane [K] is p + n * stride.
-// p == nullptr: no mask, and every launch is the unmasked one.
-// The cell costs of the step (mv_set_cell_bias) ride along: sample n's plane [K] floats is
-// bias + n * bias_stride; bias == nullptr: none.  With a bias the launch is the BIASED one, whether
-// or not p is set.
-struct StepMask {
-  const uint8_t* p = nullptr;
-  int64_t stride = 0;
-  const float* bias = nullptr;
-  int64_t bias_stride = 0;
-  // the motion cost of the step (mv_set_motion_cost): the tables and where each row's p1 / p0
-  // lie at this step; mo.vel == nullptr: none.  With one the launch is the MOTION one.
-  mv::MotionRow mo;
-  // the revisit cost of the step (mv_set_revisit_cost): the cost, the rows' visited sets of the
-  // step before and where this step stores its own; rv.cost == nullptr: none.  With one the launch
-  // is the PATH one.
-  mv::RevisitRow rv;
-  RowForm form() const {
-    return step_row_form_path(p != nullptr, bias != nullptr, mo.vel != nullptr,
-                              rv.cost != nullptr);
+// fn(std::integral_constant<RowForm, F>) for the form of a constrained step (row_form.h).
+template <typename Fn>
+void with_row_form(RowForm form, Fn&& fn) {
+  switch (form) {
+    case RowForm::Plain:  fn(std::integral_constant<RowForm, RowForm::Plain>{}); break;
+    case RowForm::Masked: fn(std::integral_constant<RowForm, RowForm::Masked>{}); break;
+    case RowForm::Biased: fn(std::integral_constant<RowForm, RowForm::Biased>{}); break;
+    case RowForm::Motion: fn(std::integral_constant<RowForm, RowForm::Motion>{}); break;
+    case RowForm::Path:   fn(std::integral_constant<RowForm, RowForm::Path>{}); break;
   }
-  bool constrained() const { return form() != RowForm::Plain; }
-};
+}
+
+// What constrains one decode step, as the step kernels take it (kernels_misc.h RowTerms): the
+// allowed cells (mv_set_cell_mask), the cell costs (mv_set_cell_bias), the motion cost of the step
+// (mv_set_motion_cost: the tables and where each row's p1 / p0 lie) and its revisit cost
+// (mv_set_revisit_cost: the cost and the rows' visited sets).  A part that is not set stays as
+// constructed; form() names the launch's instantiation, the empty one launches the plain step.
+using StepTerms = mv::RowTerms;
 
 // One beam step (log-softmax + diversity penalty + top-B) in the form step_plan.h's
 // beam_step_form chooses.  `cand` = [N*B, K] scratch of the two-launch form.
@@ -66,16 +61,16 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
                       float* cand, int N, int B, int K, int time, int diverse,
                       float log_gamma, int fix_num_timestep, float* new_lp, int32_t* ids,
                       int32_t* parents, int32_t* src_row, int rows_per_sample,
-                      int32_t* row_ref = nullptr, StepMask mask = StepMask{}) {
-  if (mask.constrained()) {
-    require_row_fits_wave(mask.rv.cost ? "beam step under a revisit cost"
-                          : mask.mo.vel ? "beam step under a motion cost"
-                          : mask.bias ? "beam step under a cell bias"
-                                      : "beam step under a cell mask", K);
+                      int32_t* row_ref = nullptr, StepTerms terms = StepTerms{}) {
+  if (terms.constrained()) {
+    require_row_fits_wave(terms.rv.cost ? "beam step under a revisit cost"
+                          : terms.mo.vel ? "beam step under a motion cost"
+                          : terms.bias ? "beam step under a cell bias"
+                                       : "beam step under a cell mask", K);
     MV_REQUIRE(cand, "internal: beam step under a cell mask, bias or motion cost without the "
                "candidate scratch");
   }
-  if (beam_step_form(K, cand != nullptr, mask.constrained()) == BeamStepForm::Single) {
+  if (beam_step_form(K, cand != nullptr, terms.constrained()) == BeamStepForm::Single) {
     hipLaunchKernelGGL(mv::beam_step_kernel, dim3(N), dim3(512), beam_step_lds_bytes(B, K),
                        stream, logits, prev_lp, B, K, time, diverse, log_gamma,
                        fix_num_timestep, new_lp, ids, parents, src_row, rows_per_sample, row_ref);
@@ -86,27 +81,10 @@ void launch_beam_step(hipStream_t stream, const float* logits, const float* prev
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Path)
-      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true, true, true>), grid, block, 0, stream,
-                         logits, prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p,
-                         mask.stride, mask.bias, mask.bias_stride, mask.mo, mask.rv);
-    else if (mask.form() == RowForm::Motion)
-      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true, true>), grid, block, 0, stream,
-                         logits, prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p,
-                         mask.stride, mask.bias, mask.bias_stride, mask.mo, mv::RevisitRow{});
-    else if (mask.form() == RowForm::Biased)
-      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true, true>), grid, block, 0, stream, logits,
-                         prev_lp, R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
-                         mask.bias, mask.bias_stride, mv::MotionRow{}, mv::RevisitRow{});
-    else if (mask.p)
-      hipLaunchKernelGGL((mv::beam_rank_kernel<J, true>), grid, block, 0, stream, logits, prev_lp,
-                         R, B, K, time, diverse, log_gamma, cand, mask.p, mask.stride,
-                         (const float*)nullptr, (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
-    else
-      hipLaunchKernelGGL((mv::beam_rank_kernel<J, false>), grid, block, 0, stream, logits,
-                         prev_lp, R, B, K, time, diverse, log_gamma, cand,
-                         (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0,
-                         mv::MotionRow{}, mv::RevisitRow{});
+    with_row_form(terms.form(), [&](auto f) {
+      hipLaunchKernelGGL((mv::beam_rank_kernel<J, decltype(f)::value>), grid, block, 0, stream,
+                         logits, prev_lp, R, B, K, time, diverse, log_gamma, cand, terms);
+    });
   });
   hipLaunchKernelGGL(mv::beam_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, B, K, time,
@@ -124,7 +102,7 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
                      float* q_plane, const uint32_t* params, int N, int B, int K, int t,
                      float* new_phi, float* new_lp, float* new_g, int32_t* ids, int32_t* parents,
                      int32_t* src_row, int rows_per_sample, int32_t* row_ref = nullptr,
-                     StepMask mask = StepMask{}) {
+                     StepTerms terms = StepTerms{}) {
   require_row_fits_wave("sampling without replacement", K);
   MV_REQUIRE(B <= K, "sampling without replacement: beam_size %d > K = %d cells (the first step "
              "has only K distinct candidates)", B, K);
@@ -132,36 +110,16 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Path)
-      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true, true, true>), grid, block, 0,
-                         stream, logits, prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand,
-                         lp_plane, q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
-                         mask.mo, mask.rv);
-    else if (mask.form() == RowForm::Motion)
-      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true, true>), grid, block, 0, stream,
+    with_row_form(terms.form(), [&](auto f) {
+      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, decltype(f)::value>), grid, block, 0, stream,
                          logits, prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand,
-                         lp_plane, q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
-                         mask.mo, mv::RevisitRow{});
-    else if (mask.form() == RowForm::Biased)
-      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true, true>), grid, block, 0, stream, logits,
-                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                         q_plane, mask.p, mask.stride, mask.bias, mask.bias_stride,
-                         mv::MotionRow{}, mv::RevisitRow{});
-    else if (mask.p)
-      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, true>), grid, block, 0, stream, logits,
-                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                         q_plane, mask.p, mask.stride, (const float*)nullptr, (int64_t)0,
-                         mv::MotionRow{}, mv::RevisitRow{});
-    else
-      hipLaunchKernelGGL((mv::sbs_perturb_kernel<J, false>), grid, block, 0, stream, logits,
-                         prev_phi, prev_g, R, B, K, t, params, t == 0 ? B : 1, cand, lp_plane,
-                         q_plane, (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr,
-                         (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
+                         lp_plane, q_plane, terms);
+    });
   });
   hipLaunchKernelGGL(mv::sbs_select_kernel, dim3(N), dim3(1024),
                      ((size_t)B * K + 64) * sizeof(float), stream, cand, lp_plane, q_plane, params,
                      prev_phi, prev_lp, B, K, t, new_phi, new_lp, new_g, ids, parents, src_row,
-                     rows_per_sample, row_ref, mask.constrained() ? 1 : 0);
+                     rows_per_sample, row_ref, terms.constrained() ? 1 : 0);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -170,35 +128,15 @@ void launch_sbs_step(hipStream_t stream, const float* logits, const float* prev_
 void launch_sample_step(hipStream_t stream, float* logits, int64_t row_stride, int R, int S,
                         int K, int t, int shared, const uint32_t* params, int floor,
                         const int32_t* lens, float* lp_acc, float* lq_acc, int32_t* ids,
-                        int ids_stride, int32_t* src_row, uint8_t* keep_out, StepMask mask) {
+                        int ids_stride, int32_t* src_row, uint8_t* keep_out, StepTerms terms) {
   const dim3 grid(cdiv((size_t)R, 4)), block(256);
   with_rank_j(K, [&](auto j) {
     constexpr int J = decltype(j)::value;
-    if (mask.form() == RowForm::Path)
-      hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true, true, true>), grid, block, 0,
-                         stream, logits, row_stride, R, S, K, t, shared, params, floor, lens, lp_acc,
-                         lq_acc, ids, ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
-                         mask.bias_stride, mask.mo, mask.rv);
-    else if (mask.form() == RowForm::Motion)
-      hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true, true>), grid, block, 0, stream,
+    with_row_form(terms.form(), [&](auto f) {
+      hipLaunchKernelGGL((mv::sample_step_kernel<J, decltype(f)::value>), grid, block, 0, stream,
                          logits, row_stride, R, S, K, t, shared, params, floor, lens, lp_acc,
-                         lq_acc, ids, ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
-                         mask.bias_stride, mask.mo, mv::RevisitRow{});
-    else if (mask.form() == RowForm::Biased)
-      hipLaunchKernelGGL((mv::sample_step_kernel<J, true, true>), grid, block, 0, stream, logits,
-                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
-                         ids_stride, src_row, keep_out, mask.p, mask.stride, mask.bias,
-                         mask.bias_stride, mv::MotionRow{}, mv::RevisitRow{});
-    else if (mask.p)
-      hipLaunchKernelGGL((mv::sample_step_kernel<J, true>), grid, block, 0, stream, logits,
-                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
-                         ids_stride, src_row, keep_out, mask.p, mask.stride, (const float*)nullptr,
-                         (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
-    else
-      hipLaunchKernelGGL((mv::sample_step_kernel<J, false>), grid, block, 0, stream, logits,
-                         row_stride, R, S, K, t, shared, params, floor, lens, lp_acc, lq_acc, ids,
-                         ids_stride, src_row, keep_out, (const uint8_t*)nullptr, (int64_t)0,
-                         (const float*)nullptr, (int64_t)0, mv::MotionRow{}, mv::RevisitRow{});
+                         lq_acc, ids, ids_stride, src_row, keep_out, terms);
+    });
   });
 }
 

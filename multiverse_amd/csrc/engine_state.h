@@ -243,6 +243,63 @@ struct ScaleState {
   bool cone_ready = false;
 };
 
+// Caller-given planes per (sample, step) of a beam handle: the allowed cells (uint8_t,
+// mv_set_cell_mask) and the cell costs (float32 log-potentials, mv_set_cell_bias,
+// DESIGN.md 8.12).  The device copy has ONE address and one of two layouts, so that a captured
+// forward follows a later upload: [N, 1, K] for Tm == 1, [N, Tcap, K] for Tm > 1 with
+// Tcap = max_pred_len (planes past it are never read and not kept).
+template <typename T>
+struct CellPlanes {
+  DevBuf<T> dev;
+  int tm = 0;                      // 0 = not set
+  bool set() const { return tm > 0; }
+  int layout() const { return tm > 1 ? 2 : tm; }    // step_plan.h constraint_graph_key's code
+  int64_t stride(int K, int Tcap) const { return tm > 1 ? (int64_t)Tcap * K : K; }
+  int64_t step(int K) const { return tm > 1 ? K : 0; }
+  const T* at(int K, int t) const { return dev.p + (size_t)t * step(K); }   // plane t of sample 0
+  // one allocation for both layouts: the address a captured forward holds never changes
+  void upload(const T* host, size_t N, int Tm, size_t K, size_t Tcap) {
+    dev.alloc(N * Tcap * K);
+    if (Tm == 1) {
+      HIP_CHECK(hipMemcpy(dev.p, host, N * K * sizeof(T), hipMemcpyHostToDevice));
+    } else {
+      const size_t planes = std::min((size_t)Tm, Tcap);   // a forward reads planes < pred_len
+      HIP_CHECK(hipMemcpy2D(dev.p, Tcap * K * sizeof(T), host, (size_t)Tm * K * sizeof(T),
+                            planes * K * sizeof(T), N, hipMemcpyHostToDevice));
+    }
+    tm = Tm;
+  }
+};
+
+struct StepConstraints {
+  CellPlanes<uint8_t> mask;
+  std::vector<int32_t> mask_count; // [N, Tm] allowed cells per plane, taken on the host when the
+                                   // mask is set and checked at the forward
+  CellPlanes<float> bias;
+  // motion costs: ONE allocation sized for the largest radius, so that the
+  // addresses a captured forward holds never change: vel [N, D, D] at 0, vel_far [N],
+  // acc [N, D, D], acc_far [N] at the offsets below (N = batch_size).
+  DevBuf<float> motion_dev;
+  int motion_radius = 0;           // 0 = no motion cost
+  bool motion_acc = false;
+  bool motion_set() const { return motion_radius > 0; }
+  static constexpr size_t kMotionCells = (2 * MV_MOTION_MAX_RADIUS + 1) * (2 * MV_MOTION_MAX_RADIUS + 1);
+  static size_t motion_vel_far_at(size_t N) { return N * kMotionCells; }
+  static size_t motion_acc_at(size_t N) { return motion_vel_far_at(N) + N; }
+  static size_t motion_acc_far_at(size_t N) { return motion_acc_at(N) + motion_vel_far_at(N); }
+  static size_t motion_floats(size_t N) { return motion_acc_far_at(N) + N; }
+  // revisit cost: the cost [N], and the visited sets of every row,
+  // [2][rows][64] words (kernels_misc.h RevisitRow; rows = batch_size * beam_size; step t reads
+  // half (t - 1) & 1 and stores half t & 1).  Both allocated once at their largest size, so that
+  // the addresses a captured forward holds never change.
+  DevBuf<float> revisit_dev;
+  DevBuf<uint32_t> revisit_sets;
+  bool revisit_on = false;
+  bool revisit_seed = false;       // seed_observed
+  bool revisit_set() const { return revisit_on; }
+  static size_t revisit_set_words(size_t rows) { return rows * 64; }
+};
+
 }  // namespace
 
 struct mv_engine {
@@ -343,46 +400,9 @@ struct mv_engine {
   // [N, B] log-probability of each future under the PROPOSAL (tempered, truncated):
   // the independent sampler accumulates it beside bm_lp[0]; without replacement it is the final phi
   DevBuf<float> lq_acc;
-  // caller-given allowed cells (mv_set_cell_mask; sticky until cleared).  The
-  // device copy has ONE address and one of two layouts, so that a captured forward follows a
-  // later mask: [N, 1, K] for Tm == 1, [N, max_pred_len, K] for Tm > 1 (planes past max_pred_len
-  // are never read and not kept).  cmask_count [N, Tm]: allowed cells per plane, taken on the
-  // host when the mask is set and checked at the forward.
-  DevBuf<uint8_t> cmask_dev;
-  std::vector<int32_t> cmask_count;
-  int cmask_tm = 0;                // 0 = no mask
-  bool cmask_set() const { return cmask_tm > 0; }
-  int64_t cmask_stride(int K) const { return cmask_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
-  int64_t cmask_step(int K) const { return cmask_tm > 1 ? K : 0; }
-  // caller-given cell costs (mv_set_cell_bias; sticky until cleared): float32
-  // log-potentials in the mask's two layouts at ONE address, for the same reason.
-  DevBuf<float> cbias_dev;
-  int cbias_tm = 0;                // 0 = no bias
-  bool cbias_set() const { return cbias_tm > 0; }
-  int64_t cbias_stride(int K) const { return cbias_tm > 1 ? (int64_t)cfg.max_pred_len * K : K; }
-  int64_t cbias_step(int K) const { return cbias_tm > 1 ? K : 0; }
-  // caller-given motion costs (mv_set_motion_cost; sticky until cleared): ONE
-  // allocation sized for the largest radius, so that the addresses a captured forward holds never
-  // change: vel [N, D, D] at 0, vel_far [N], acc [N, D, D], acc_far [N] at the offsets below.
-  DevBuf<float> motion_dev;
-  int motion_radius = 0;           // 0 = no motion cost
-  bool motion_acc = false;
-  bool motion_set() const { return motion_radius > 0; }
-  static constexpr size_t kMotionCells = (2 * MV_MOTION_MAX_RADIUS + 1) * (2 * MV_MOTION_MAX_RADIUS + 1);
-  size_t motion_vel_far_at() const { return (size_t)cfg.batch_size * kMotionCells; }
-  size_t motion_acc_at() const { return motion_vel_far_at() + (size_t)cfg.batch_size; }
-  size_t motion_acc_far_at() const { return motion_acc_at() + motion_vel_far_at(); }
-  size_t motion_floats() const { return motion_acc_far_at() + (size_t)cfg.batch_size; }
-  // caller-given revisit cost (mv_set_revisit_cost; sticky until cleared): the
-  // cost [N], and the visited sets of every row, [2][N * B][64] words (kernels_misc.h RevisitRow;
-  // step t reads half (t - 1) & 1 and stores half t & 1).  Both allocated once at their largest
-  // size, so that the addresses a captured forward holds never change.
-  DevBuf<float> revisit_dev;
-  DevBuf<uint32_t> revisit_sets;
-  bool revisit_on = false;
-  bool revisit_seed = false;       // seed_observed
-  bool revisit_set() const { return revisit_on; }
-  size_t revisit_set_words() const { return (size_t)cfg.batch_size * cfg.beam_size * 64; }
+  // what constrains the cells a beam / sampled forward chooses (mv_set_cell_mask, mv_set_cell_bias,
+  // mv_set_motion_cost, mv_set_revisit_cost; sticky until cleared)
+  StepConstraints con;
   // scoring of GIVEN futures (mv_score_futures): a teacher-forced forward of the
   // sampled driver, asked for per forward (ForwardKind::Scored): nothing about it is sticky.
   // The uploaded ids live in score_ids with a valid cell at every step (a finished future keeps

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "plane_layout.h"
+#include "row_form.h"
 #include <stdint.h>
 #include <math.h>
 
@@ -1425,10 +1426,10 @@ void beam_step_kernel(const float* __restrict__ logits,
 constexpr int kBeamRankJ = 16;   // K <= 1024
 
 // Caller-given allowed cells (include/multiverse_hip.h mv_set_cell_mask): the kernels that hold a
-// row in one wave's registers come in a MASKED form, instantiated beside the unmasked one, whose
-// in-row predicate `lane + 64 j < K` is "in row AND allowed".  The row's mask plane [K] (one
-// byte per cell, non-zero = allowed) is read once per wave into one bit per owned cell (bit j:
-// k = lane + 64 j); a cell past the row is not allowed.  No LDS, no scratch, no indexed arrays.
+// row in one wave's registers come in a Masked form (row_form.h), instantiated beside the plain
+// one, whose in-row predicate `lane + 64 j < K` is "in row AND allowed".  The row's mask plane [K]
+// (one byte per cell, non-zero = allowed) is read once per wave into one bit per owned cell (bit
+// j: k = lane + 64 j); a cell past the row is not allowed.  No LDS, no scratch, no indexed arrays.
 template <int J>
 __device__ __forceinline__ uint32_t step_row_allowed_bits(const uint8_t* __restrict__ plane,
                                                           int K, int lane) {
@@ -1449,8 +1450,8 @@ __device__ __forceinline__ bool step_cell_in(uint32_t am, int lane, int j, int K
   else return lane + 64 * j < K;
 }
 
-// Caller-given cell costs (include/multiverse_hip.h mv_set_cell_bias): a third, BIASED form of
-// the same kernels, instantiated as <J, true, true>.  It serves "bias only" and "bias + mask"
+// Caller-given cell costs (include/multiverse_hip.h mv_set_cell_bias): a third, Biased form of
+// the same kernels.  It serves "bias only" and "bias + mask"
 // alike: it always works on the `am` bits, which are the in-row bits when no mask plane is given.
 // The row's bias plane [K] floats is read once per wave into b[J] exactly as the logits are
 // (lane l owns k = l + 64 j; 0 past the row).
@@ -1475,8 +1476,8 @@ __device__ __forceinline__ void step_row_bias(const float* __restrict__ plane, i
   }
 }
 
-// Caller-given motion costs (include/multiverse_hip.h mv_set_motion_cost): a fourth, MOTION form
-// of the same kernels, instantiated as <J, true, true, true>.  It is the BIASED form whose b[J]
+// Caller-given motion costs (include/multiverse_hip.h mv_set_motion_cost): a fourth, Motion form
+// of the same kernels.  It is the Biased form whose b[J]
 // is b_eff = (b + vterm) + aterm, with the two terms derived per wave from the row's own path:
 // one instantiation serves motion alone (no bias plane: b = 0.0f) and every combination with a
 // mask and a bias.  Where the row's path lies, per launch:
@@ -1556,8 +1557,8 @@ __device__ __forceinline__ void step_row_motion(const MotionRow& mo,
   }
 }
 
-// Caller-given revisit cost (include/multiverse_hip.h mv_set_revisit_cost): a fifth, PATH form of
-// the same kernels, instantiated as <J, true, true, true, true>.  It is the MOTION form with
+// Caller-given revisit cost (include/multiverse_hip.h mv_set_revisit_cost): a fifth, Path form of
+// the same kernels.  It is the Motion form with
 // rterm added to b[J]; the motion part runs only when mo.vel is set (a wave-uniform branch), so
 // ONE instantiation serves the revisit cost alone and every combination with a mask, a bias and
 // a motion cost.  The visited set of a row is 64 words, lane-major as the `am` bits are: bit j of
@@ -1624,33 +1625,61 @@ __device__ __forceinline__ void step_row_path(const MotionRow& mo, const Revisit
   for (int j = 0; j < J; ++j) b[j] = b[j] + (((pay >> j) & 1u) ? c : 0.f);
 }
 
-// MASKED: amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A cell
-// outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
+// Everything a constrained step reads beyond its logits, as ONE kernel argument (the launchers'
+// StepTerms, engine_setup.h): sample n's mask plane [K] is amask + n * mask_stride, its bias plane
+// [K] floats bias + n * bias_stride; a NULL amask / bias / mo.vel / rv.cost: that part is not set.
+struct RowTerms {
+  const uint8_t* amask = nullptr;
+  int64_t mask_stride = 0;
+  const float* bias = nullptr;
+  int64_t bias_stride = 0;
+  MotionRow mo;
+  RevisitRow rv;
+  RowForm form() const {
+    return row_form(amask != nullptr, bias != nullptr, mo.vel != nullptr, rv.cost != nullptr);
+  }
+  bool constrained() const { return form() != RowForm::Plain; }
+};
+
+// The per-row block of the three step kernels: the allowed bits `am` and the additive terms b[J]
+// of row r (sample n, B rows per sample), as form F has them.  Plain reads nothing of `tm` and
+// leaves both alone; Masked forms `am` only (b is a one-element dummy below Biased).
+template <int J, RowForm F>
+__device__ __forceinline__ void step_row_terms(const RowTerms& tm, int n, int r, int B, int K,
+                                               int lane, uint32_t& am,
+                                               float (&b)[row_has_bias(F) ? J : 1]) {
+  if constexpr (row_has_bias(F)) {
+    if constexpr (row_has_motion(F)) {
+      const float* plane = tm.bias ? tm.bias + (size_t)n * tm.bias_stride : nullptr;
+      if constexpr (row_has_path(F)) step_row_path<J>(tm.mo, tm.rv, plane, n, r, B, K, lane, b);
+      else step_row_motion<J>(tm.mo, plane, n, r, B, K, lane, b);
+    } else {
+      step_row_bias<J>(tm.bias + (size_t)n * tm.bias_stride, K, lane, b);
+    }
+    am = step_row_biased_bits<J>(tm.amask ? tm.amask + (size_t)n * tm.mask_stride : nullptr, K,
+                                 lane);
+  } else if constexpr (row_has_bits(F)) {
+    am = step_row_allowed_bits<J>(tm.amask + (size_t)n * tm.mask_stride, K, lane);
+  }
+}
+
+// Masked: terms.amask + (r / B) * mask_stride is the plane of the row's sample at this step.  A
+// cell outside it becomes the candidate -inf after lp + prev_lp and BEFORE the ranks: it precedes
 // nothing, so an allowed cell's rank counts allowed cells only.
-// BIASED (implies MASKED; amask may be NULL): the candidate is (prev_lp + lp) + b, with
+// Biased (amask may be NULL): the candidate is (prev_lp + lp) + b, with
 // b = bias + (r / B) * bias_stride, formed before the mask's -inf and before the ranks.
-// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of the row.
-// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
+// Motion (bias may be NULL): b is step_row_motion's b_eff of the row.
+// Path (mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, RowForm F>
 __global__ __launch_bounds__(256)
 void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict__ prev_lp,
                       int R, int B, int K, int time, int diverse, float log_gamma,
-                      float* __restrict__ cand, const uint8_t* __restrict__ amask = nullptr,
-                      int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                      int64_t bias_stride = 0, MotionRow mo = MotionRow{},
-                      RevisitRow rv = RevisitRow{}) {
-  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
-  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
-  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
+                      float* __restrict__ cand, RowTerms terms) {
+  constexpr bool MASKED = row_has_bits(F), BIASED = row_has_bias(F);
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
   if (time <= 1 && (r % B) != 0) return;   // only beam 0 is a candidate at the first step
-  uint32_t am = 0u;
-  if constexpr (BIASED)
-    am = step_row_biased_bits<J>(amask ? amask + (size_t)(r / B) * mask_stride : nullptr, K, lane);
-  else if constexpr (MASKED)
-    am = step_row_allowed_bits<J>(amask + (size_t)(r / B) * mask_stride, K, lane);
   const float* row = logits + (size_t)r * K;
   float v[J];
   float mx = -INFINITY;
@@ -1671,20 +1700,14 @@ void beam_rank_kernel(const float* __restrict__ logits, const float* __restrict_
   const float pl = prev_lp[r];
 #pragma unroll
   for (int j = 0; j < J; ++j) v[j] = pl + ((v[j] - mx) - lse);
-  if constexpr (BIASED) {
-    float b[J];
-    if constexpr (PATH)
-      step_row_path<J>(mo, rv, bias ? bias + (size_t)(r / B) * bias_stride : nullptr, r / B, r, B,
-                       K, lane, b);
-    else if constexpr (MOTION)
-      step_row_motion<J>(mo, bias ? bias + (size_t)(r / B) * bias_stride : nullptr, r / B, r, B, K,
-                         lane, b);
-    else
-      step_row_bias<J>(bias + (size_t)(r / B) * bias_stride, K, lane, b);
-#pragma unroll
-    for (int j = 0; j < J; ++j) v[j] = v[j] + b[j];
-  }
   if constexpr (MASKED) {
+    uint32_t am = 0u;
+    float b[BIASED ? J : 1];
+    step_row_terms<J, F>(terms, r / B, r, B, K, lane, am, b);
+    if constexpr (BIASED) {
+#pragma unroll
+      for (int j = 0; j < J; ++j) v[j] = v[j] + b[j];
+    }
 #pragma unroll
     for (int j = 0; j < J; ++j)
       if (!step_cell_in<true>(am, lane, j, K)) v[j] = -INFINITY;
@@ -1941,27 +1964,23 @@ __device__ __forceinline__ void step_row_copy_out(float* __restrict__ out, int K
 // state row the S rows of sample n continue from.  params: {seed, temperature bits, top_k,
 // top_p bits}, read on the device so that a replayed graph follows mv_set_sampling and
 // mv_set_sampling_truncation.  keep_out (mv_op_sample_step only): the kept set [R, K].
-// MASKED (mv_set_cell_mask): amask + n * mask_stride is the sample's plane at this step.  lp stays
-// the log-softmax over ALL cells; the proposal treats a cell outside the plane as absent: w is
-// -inf there, mxq and the sums run over the allowed cells (also at temperature 1 with no limit:
+// Masked (mv_set_cell_mask): terms.amask + n * mask_stride is the sample's plane at this step.  lp
+// stays the log-softmax over ALL cells; the proposal treats a cell outside the plane as absent: w
+// is -inf there, mxq and the sums run over the allowed cells (also at temperature 1 with no limit:
 // the proposal differs from the model), and keep(k) = allowed and the limits' predicate.
-// BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): b = bias + n * bias_stride,
+// Biased (mv_set_cell_bias; amask may be NULL): b = bias + n * bias_stride,
 // w = l / temperature + b, the limits order by w, and the score is (lp / temperature + b) + g.
-// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of row r.
-// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
+// Motion (bias may be NULL): b is step_row_motion's b_eff of row r.
+// Path (mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, RowForm F>
 __global__ __launch_bounds__(256)
 void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, int S, int K,
                         int t, int shared, const uint32_t* __restrict__ params, int floor,
                         const int32_t* __restrict__ lens, float* __restrict__ lp_acc,
                         float* __restrict__ lq_acc, int32_t* __restrict__ ids, int ids_stride,
                         int32_t* __restrict__ src_row, uint8_t* __restrict__ keep_out,
-                        const uint8_t* __restrict__ amask = nullptr, int64_t mask_stride = 0,
-                        const float* __restrict__ bias = nullptr, int64_t bias_stride = 0,
-                        MotionRow mo = MotionRow{}, RevisitRow rv = RevisitRow{}) {
-  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
-  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
-  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
+                        RowTerms terms) {
+  constexpr bool MASKED = row_has_bits(F), BIASED = row_has_bias(F);
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -1981,20 +2000,11 @@ void sample_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, i
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   uint32_t am = 0u;
-  float b[BIASED ? J : 1];
+  float b[BIASED ? J : 1];     // live to the score below
+  step_row_terms<J, F>(terms, n, r, S, K, lane, am, b);
   if constexpr (BIASED) {
-    if constexpr (PATH)
-      step_row_path<J>(mo, rv, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, S, K, lane,
-                       b);
-    else if constexpr (MOTION)
-      step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, S, K, lane, b);
-    else
-      step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, b);
 #pragma unroll
     for (int j = 0; j < J; ++j) w[j] = w[j] + b[j];
-    am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
-  } else if constexpr (MASKED) {
-    am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
   }
   if constexpr (MASKED) {
 #pragma unroll
@@ -2110,27 +2120,22 @@ void score_step_kernel(float* __restrict__ logits, int64_t row_stride, int R, in
 // With a top-k / nucleus limit on (step_row_keep_threshold; floor = B at t == 0, else 1), q is
 // renormalised over the kept cells and a dropped cell is the candidate -inf, never selected.
 
-// MASKED (mv_set_cell_mask; amask + n * mask_stride = the sample's plane at this step): a cell
-// outside the plane is absent from the proposal as in sample_step_kernel -- q = cand = -inf -- and
-// the q plane is always written (sbs_select_kernel's force_q).
-// BIASED (mv_set_cell_bias; implies MASKED, amask may be NULL): w = l / temperature + b with
+// Masked (mv_set_cell_mask; terms.amask + n * mask_stride = the sample's plane at this step): a
+// cell outside the plane is absent from the proposal as in sample_step_kernel -- q = cand = -inf --
+// and the q plane is always written (sbs_select_kernel's force_q).
+// Biased (mv_set_cell_bias; amask may be NULL): w = l / temperature + b with
 // b = bias + n * bias_stride; q, the limits' order and the q plane follow w as in
 // sample_step_kernel.
-// MOTION (implies BIASED; bias may be NULL): b is step_row_motion's b_eff of parent row r.
-// PATH (implies MOTION; mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
-template <int J, bool MASKED = false, bool BIASED = false, bool MOTION = false, bool PATH = false>
+// Motion (bias may be NULL): b is step_row_motion's b_eff of parent row r.
+// Path (mo.vel may be NULL): b is step_row_path's, and the row's set is stored.
+template <int J, RowForm F>
 __global__ __launch_bounds__(256)
 void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restrict__ prev_phi,
                         const float* __restrict__ prev_g, int R, int B, int K, int t,
                         const uint32_t* __restrict__ params, int floor,
                         float* __restrict__ cand, float* __restrict__ lp_plane,
-                        float* __restrict__ q_plane, const uint8_t* __restrict__ amask = nullptr,
-                        int64_t mask_stride = 0, const float* __restrict__ bias = nullptr,
-                        int64_t bias_stride = 0, MotionRow mo = MotionRow{},
-                      RevisitRow rv = RevisitRow{}) {
-  static_assert(MASKED || !BIASED, "the BIASED form works on the allowed bits");
-  static_assert(BIASED || !MOTION, "the MOTION form is the BIASED one with b_eff for b");
-  static_assert(MOTION || !PATH, "the PATH form is the MOTION one with rterm added to b");
+                        float* __restrict__ q_plane, RowTerms terms) {
+  constexpr bool MASKED = row_has_bits(F), BIASED = row_has_bias(F);
   const int lane = threadIdx.x & 63;
   const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= R) return;
@@ -2146,22 +2151,13 @@ void sbs_perturb_kernel(const float* __restrict__ logits, const float* __restric
 #pragma unroll
   for (int j = 0; j < J; ++j) w[j] = tempered ? v[j] / temperature : v[j];
   uint32_t am = 0u;
-  if constexpr (BIASED) {
-    float bz[J];
-    if constexpr (PATH)
-      step_row_path<J>(mo, rv, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, B, K, lane,
-                       bz);
-    else if constexpr (MOTION)
-      step_row_motion<J>(mo, bias ? bias + (size_t)n * bias_stride : nullptr, n, r, B, K, lane, bz);
-    else
-      step_row_bias<J>(bias + (size_t)n * bias_stride, K, lane, bz);
-#pragma unroll
-    for (int j = 0; j < J; ++j) w[j] = w[j] + bz[j];
-    am = step_row_biased_bits<J>(amask ? amask + (size_t)n * mask_stride : nullptr, K, lane);
-  } else if constexpr (MASKED) {
-    am = step_row_allowed_bits<J>(amask + (size_t)n * mask_stride, K, lane);
-  }
   if constexpr (MASKED) {
+    float bz[BIASED ? J : 1];
+    step_row_terms<J, F>(terms, n, r, B, K, lane, am, bz);
+    if constexpr (BIASED) {
+#pragma unroll
+      for (int j = 0; j < J; ++j) w[j] = w[j] + bz[j];
+    }
 #pragma unroll
     for (int j = 0; j < J; ++j)
       if (!step_cell_in<true>(am, lane, j, K)) w[j] = -INFINITY;

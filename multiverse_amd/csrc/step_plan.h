@@ -10,6 +10,8 @@
 // against tables written out there.)
 #pragma once
 
+#include "row_form.h"
+
 namespace {
 
 // ------------------------------------------------------------------ the A/B switches
@@ -79,29 +81,24 @@ inline BeamStepForm beam_step_form(int K, bool have_cand, bool masked) {
 }
 
 // ------------------------------------------------------------------ constrained rows
-// The kernels that hold a row in one wave (beam_rank / sbs_perturb / sample_step) and the two
-// occupancy kernels come in three forms.  Plain: neither a cell mask nor a cell bias.  Masked:
-// mv_set_cell_mask alone, today's MASKED instantiation.  Biased: mv_set_cell_bias, with or without
-// a mask -- ONE instantiation, which takes the allowed bits as the in-row bits when no mask plane
-// is given.  A Masked or Biased beam step is a `masked` one to beam_step_form above: it exists in
-// the two-launch form only.
-enum class RowForm { Plain, Masked, Biased, Motion, Path };
-inline RowForm step_row_form(bool masked, bool biased) {
-  return biased ? RowForm::Biased : (masked ? RowForm::Masked : RowForm::Plain);
-}
-// Motion: mv_set_motion_cost, with or without a mask and a bias -- the Biased instantiation plus
-// the terms each wave derives from its row's path, so ONE more instantiation serves every
-// combination (no bias plane: b = 0.0f).  The step kernels only: the occupancy kernels have no
-// such form (mv_beam_occupancy refuses while a motion cost is set).
-inline RowForm step_row_form_motion(bool masked, bool biased, bool motion) {
-  return motion ? RowForm::Motion : step_row_form(masked, biased);
-}
-// Path: mv_set_revisit_cost, with or without a mask, a bias and a motion cost -- the Motion
-// instantiation plus the row's visited set, whose motion part runs only when a motion cost is set:
-// again ONE more instantiation for every combination.  A Path beam step is a `masked` one to
-// beam_step_form above, as every constrained form is.
-inline RowForm step_row_form_path(bool masked, bool biased, bool motion, bool revisit) {
-  return revisit ? RowForm::Path : step_row_form_motion(masked, biased, motion);
+// The form of a constrained step and the rule that picks it: row_form.h.
+using mv::RowForm;
+using mv::row_form;
+
+// The constraint member of a captured forward's graph key (engine_forward.h run_forward): what a
+// captured step bakes in of the four constraints.  Layout codes of the mask and of the bias: 0 not
+// set, 1 one plane for every step, 2 a plane per step.  The motion cost: its radius (0 = not set)
+// and whether the acc tables are present.  The revisit cost: set or not, and whether it starts from
+// the observed cells.  Two different states never share a value; the values themselves mean
+// nothing and are never stored.
+constexpr int kMotionKeys = 9;   // not set, or a radius with acc absent / present
+static_assert(2 * MV_MOTION_MAX_RADIUS < kMotionKeys,
+              "graph key: the motion member 2 * radius - 1 + acc must stay below its radix");
+inline int constraint_graph_key(int mask_layout, int bias_layout, int radius, bool acc,
+                                bool revisit, bool revisit_seed) {
+  const int motion = radius > 0 ? 2 * radius - 1 + (acc ? 1 : 0) : 0;
+  const int path = revisit ? (revisit_seed ? 2 : 1) : 0;
+  return mask_layout + 3 * (bias_layout + 3 * (motion + kMotionKeys * path));
 }
 
 // ------------------------------------------------------------------ graph attention (forward)

@@ -59,6 +59,15 @@ int main() {
   c.batch_size = 64;
   printf(" %%d %%d\n", (int)chain_pairs_planned(c, true, true, false, true, true),
          (int)chain_pairs_planned(c, true, true, false, false, false));
+  for (int f = 0; f < 16; ++f)
+    printf("row_form %%d %%d %%d %%d %%d\n", f & 1, (f >> 1) & 1, (f >> 2) & 1, (f >> 3) & 1,
+           (int)row_form((f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (f & 8) != 0));
+  for (int m = 0; m < 3; ++m) for (int b = 0; b < 3; ++b)
+    for (int radius = 0; radius <= MV_MOTION_MAX_RADIUS; ++radius) for (int acc = 0; acc < 2; ++acc)
+      for (int rv = 0; rv < 3; ++rv)
+        printf("key %%d %%d %%d %%d %%d %%d\n", m, b, radius, acc, rv,
+               constraint_graph_key(m, b, radius, acc != 0, rv != 0, rv == 2));
+  printf("max_radius %%d\n", MV_MOTION_MAX_RADIUS);
   return 0;
 }
 """
@@ -66,6 +75,7 @@ int main() {
 PER_CELL, TILED, BLOCKED = 0, 1, 2        # GnnForm, in its declared (weaker-first) order
 SINGLE, RANK_SELECT = 0, 1                # BeamStepForm
 GROUPED, SEPARATE = 0, 1                  # TailForm
+PLAIN, MASKED, BIASED, MOTION, PATH = range(5)   # RowForm (row_form.h), in its declared order
 
 _SWITCHES = ("MV_GNN", "MV_TAIL", "MV_TRAIN_TAIL", "MV_BEAM_STEP", "MV_BEAM_SHARED_FIRST",
              "MV_BEAM_GNN_DEDUPE", "MV_SPARSE_X", "MV_CHAIN_STREAMS", "MV_CHAIN_PRIORITY")
@@ -144,3 +154,33 @@ def test_switches_select_the_fallback_forms(plan_exe):
   assert [r for r in rows if r[0] == "dedupe"] == [["dedupe", "0", "0", "0"]]
   for switch in ({"MV_GNN": "v1"}, {"MV_BEAM_GNN_DEDUPE": "0"}):
     assert [r for r in _run(plan_exe, **switch) if r[0] == "dedupe"] == [["dedupe", "0", "0", "0"]]
+
+
+def test_row_form_table(plan_exe):
+  """One rule for the form of a constrained step: the last of mask / bias / motion / revisit that
+  is set names it, whatever is set below it."""
+  rows = [[int(x) for x in r[1:]] for r in _run(plan_exe) if r[0] == "row_form"]
+  assert len(rows) == 16
+  for masked, biased, motion, revisit, got in rows:
+    want = (PATH if revisit else MOTION if motion else BIASED if biased else MASKED if masked
+            else PLAIN)
+    assert got == want, (masked, biased, motion, revisit, got, want)
+
+
+def test_graph_key_members_are_distinct(plan_exe):
+  """The constraint member of the graph key: mask layout 0 - 2, bias layout 0 - 2, the motion
+  member (unset, or a radius from 1 to MV_MOTION_MAX_RADIUS with acc absent or present) and the
+  revisit member 0 - 2 -- two different states never share a key."""
+  out = _run(plan_exe)
+  max_radius = int([r for r in out if r[0] == "max_radius"][0][1])
+  assert max_radius == 4                  # motion member 0 - 8
+  keys = {}
+  for r in out:
+    if r[0] != "key":
+      continue
+    m, b, radius, acc, rv, key = (int(x) for x in r[1:])
+    motion = 0 if radius == 0 else 2 * radius - 1 + acc     # acc means nothing without a radius
+    keys.setdefault((m, b, motion, rv), set()).add(key)
+  assert len(keys) == 3 * 3 * (2 * max_radius + 1) * 3 == 243
+  assert all(len(v) == 1 for v in keys.values()), "a member combination with two keys"
+  assert len({next(iter(v)) for v in keys.values()}) == 243
