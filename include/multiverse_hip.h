@@ -1078,6 +1078,36 @@ int  mv_op_convlstm_bwd(int device, const float* x, const float* c, const float*
                         const float* dh_new, const float* dc_new, int32_t M,
                         int32_t H, int32_t W, int32_t Cx, int32_t C, float* dx,
                         float* dh, float* dc, float* dkernel, float* dbiases);
+/* The matrix-pipe backward of ONE gate convolution, kernel by kernel (the backward's counterpart
+ * of mv_op_convlstm_step16): x [M,H,W,Cx], h [M,H,W,C] (the step's INPUT state), G [M,H,W,4C] the
+ * pre-activation gate gradient -- an input, so that nothing upstream of the two GEMMs rounds --,
+ * kernel [3,3,Cx+C,4C] -> dx [M,H,W,Cx], dh [M,H,W,C], dkernel [3,3,Cx+C,4C].  The engine's own
+ * packs, plane splits, transposes, exponent kernels and launchers; the variant picks the form,
+ * everything else (split-K, DPP column shift, narrow or wide tile, split counts) is the
+ * planner's (csrc/gate_plan.h).  0 skips that half (its outputs and inputs may then be NULL).
+ *   variant_dgrad  1 f16x3 direct; 2 f16x3 Winograd F(2,3) (32 % W == 0, H >= 2); 3 ONE bf16
+ *                  plane per operand, whole-K
+ *   variant_wgrad  1 f16x3 direct; 2 f16x3 row-triple (H % 3 == 0); 3 ONE fp16 plane per operand,
+ *                  direct; 4 one plane, row-triple.  All four: W % 16 == 0, C % 128 == 0.
+ * A shape the planner would not give the form is refused before any launch, the message naming
+ * the planner's condition.  exps [3]: the power-of-two scale exponents the device computed for G,
+ * h and x (wgrad; with variant_wgrad 0 and an f16x3 dgrad exps[0] is the dgrad's G exponent, the
+ * rest 0).  forms [8]: wide, wide_x, nsplit, nsplit_x (wgrad); split-K slices of the d h and of
+ * the d x blocks, DPP column shift (dgrad); transpose3 (wgrad).  Every output and partial buffer
+ * holds the byte 0xA5 before the launches. */
+int  mv_op_convlstm_bwd16(int device, int32_t variant_dgrad, int32_t variant_wgrad,
+                          const float* x, const float* h, const float* G, const float* kernel,
+                          int32_t M, int32_t H, int32_t W, int32_t Cx, int32_t C, float* dx,
+                          float* dh, float* dkernel, int32_t* exps, int32_t* forms);
+/* The pointwise backward of one step in each of its kernels: form 0 scalar, 1 four channels per
+ * thread, 2 the same emitting G also as ONE bf16 plane.  gates [cells,4,C] the saved activations
+ * (si | tj | sf | so), c_prev (NULL: zero), c_new, dh, dc [cells,C] -> G [cells,4C], dc_out
+ * [cells,C], gmax_bits: the float bits of max |G| as the kernel tracked them; plane_out (form 2;
+ * else it may be NULL) [cells,4C]: the plane's values. */
+int  mv_op_lstm_gate_bwd(int device, int32_t form, const float* gates, const float* c_prev,
+                         const float* c_new, const float* dh, const float* dc, int32_t cells,
+                         int32_t C, float* G_out, float* dc_out, int32_t* gmax_bits,
+                         float* plane_out);
 /* Backward of h + GNN(h) given g = d out: d h [M,H,W,C], d scene_mean [M,H,W,D]. */
 int  mv_op_gnn_bwd(int device, const float* h, const float* scene_mean,
                    const float* g, int32_t M, int32_t H, int32_t W, int32_t C,

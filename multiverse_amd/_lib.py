@@ -40,7 +40,7 @@ EXPORTED_SYMBOLS = [
     "mv_attack_begin", "mv_attack_end", "mv_set_scene_feat", "mv_get_scene_feat",
     "mv_get_scene_grad", "mv_attack_step", "mv_scene_mix", "mv_get_sample_losses",
     "mv_set_label_mixup", "mv_clear_label_mixup",
-    "mv_op_convlstm_bwd", "mv_op_gnn_bwd",
+    "mv_op_convlstm_bwd", "mv_op_gnn_bwd", "mv_op_convlstm_bwd16", "mv_op_lstm_gate_bwd",
     "mv_set_grid_centers", "mv_upload_inputs_compact", "mv_upload_targets_compact",
     "mv_pipeline_create", "mv_submit_greedy", "mv_collect_greedy",
     "mv_decode_trajectories", "mv_beam_occupancy", "mv_download_beam_ids",
@@ -391,6 +391,11 @@ def load():
   lib.mv_set_opt_slot.argtypes = [h, C.c_char_p, C.c_int32, _fp, C.c_int64]
   lib.mv_op_convlstm_bwd.argtypes = [C.c_int] + [_fp] * 7 + [C.c_int32] * 5 + [_fp] * 5
   lib.mv_op_gnn_bwd.argtypes = [C.c_int, _fp, _fp, _fp] + [C.c_int32] * 5 + [_fp, _fp]
+  if hasattr(lib, "mv_op_convlstm_bwd16"):  # (an A/B build through MV_LIB_PATH may predate it)
+    lib.mv_op_convlstm_bwd16.argtypes = [C.c_int, C.c_int32, C.c_int32] + [_fp] * 4 + \
+        [C.c_int32] * 5 + [_fp] * 3 + [_ip, _ip]
+    lib.mv_op_lstm_gate_bwd.argtypes = [C.c_int, C.c_int32] + [_fp] * 5 + [C.c_int32] * 2 + \
+        [_fp, _fp, _ip, _fp]
   if lib.mv_abi_version() != MV_ABI_VERSION:
     raise MvError("ABI version mismatch: library %d, binding %d"
                   % (lib.mv_abi_version(), MV_ABI_VERSION))
@@ -1940,6 +1945,57 @@ def op_convlstm_bwd(x, c, h, kernel, biases, dh_new, dc_new, device=0):
                                fptr(dh_new), fptr(dc_new), M, H, W, Cx, Cc, fptr(dx),
                                fptr(dh), fptr(dc), fptr(dk), fptr(db)))
   return dx, dh, dc, dk, db
+
+
+BWD16_DGRAD = {None: 0, "f16x3": 1, "wino": 2, "bf16": 3}
+BWD16_WGRAD = {None: 0, "f16x3": 1, "f16x3_triple": 2, "one": 3, "one_triple": 4}
+
+
+def op_convlstm_bwd16(x, h, G, kernel, dgrad=None, wgrad=None, device=0):
+  """The matrix-pipe backward of one gate convolution by its single kernels
+  (mv_op_convlstm_bwd16): dgrad in BWD16_DGRAD, wgrad in BWD16_WGRAD, None skips that half.
+  -> dict(dx, dh, dkernel (None where skipped), exps=(G, h, x), wide, wide_x, nsplit, nsplit_x,
+  dgrad_slices=(d h, d x), shift, transpose3)."""
+  lib = load()
+  x, h, G, kernel = f32(x), f32(h), f32(G), f32(kernel)
+  M, H, W, Cx = x.shape
+  Cc = int(kernel.shape[3]) // 4
+  assert h.shape == (M, H, W, Cc) and G.shape == (M, H, W, 4 * Cc)
+  assert kernel.shape == (3, 3, Cx + Cc, 4 * Cc)
+  vd, vw = BWD16_DGRAD[dgrad], BWD16_WGRAD[wgrad]
+  dx = np.empty((M, H, W, Cx), dtype=np.float32) if vd else None
+  dh = np.empty((M, H, W, Cc), dtype=np.float32) if vd else None
+  dk = np.empty(kernel.shape, dtype=np.float32) if vw else None
+  exps = np.zeros(3, dtype=np.int32)
+  forms = np.zeros(8, dtype=np.int32)
+  opt = lambda a: fptr(a) if a is not None else _fp()
+  check(lib.mv_op_convlstm_bwd16(device, vd, vw, fptr(x), fptr(h), fptr(G), fptr(kernel), M, H,
+                                 W, Cx, Cc, opt(dx), opt(dh), opt(dk), iptr(exps), iptr(forms)))
+  return dict(dx=dx, dh=dh, dkernel=dk, exps=tuple(int(e) for e in exps), wide=bool(forms[0]),
+              wide_x=bool(forms[1]), nsplit=int(forms[2]), nsplit_x=int(forms[3]),
+              dgrad_slices=(int(forms[4]), int(forms[5])), shift=bool(forms[6]),
+              transpose3=bool(forms[7]))
+
+
+def op_lstm_gate_bwd(gates, c_prev, c_new, dh, dc, form, device=0):
+  """lstm_gate_bwd in its form 0 (scalar), 1 (four channels per thread) or 2 (the same with the
+  bf16 plane): gates [cells, 4, C] -> (G [cells, 4C], dc [cells, C], gmax bits, plane or None)."""
+  lib = load()
+  gates, c_new, dh, dc = f32(gates), f32(c_new), f32(dh), f32(dc)
+  cells, Cc = c_new.shape
+  assert gates.size == cells * 4 * Cc
+  cp = _fp()
+  if c_prev is not None:
+    c_prev = f32(c_prev)
+    cp = fptr(c_prev)
+  G = np.empty((cells, 4 * Cc), dtype=np.float32)
+  dco = np.empty((cells, Cc), dtype=np.float32)
+  plane = np.empty((cells, 4 * Cc), dtype=np.float32) if form == 2 else None
+  bits = np.zeros(1, dtype=np.int32)
+  check(lib.mv_op_lstm_gate_bwd(device, int(form), fptr(gates), cp, fptr(c_new), fptr(dh),
+                                fptr(dc), cells, Cc, fptr(G), fptr(dco), iptr(bits),
+                                fptr(plane) if plane is not None else _fp()))
+  return G, dco, int(bits[0]), plane
 
 
 def op_gnn_bwd(h, scene_mean, g, device=0):

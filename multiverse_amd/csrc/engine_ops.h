@@ -949,6 +949,317 @@ int mv_op_convlstm_bwd(int device, const float* x, const float* c, const float* 
   });
 }
 
+// ---- the matrix-pipe backward of one gate convolution, kernel by kernel
+// (tests/test_gpu_bwd_kernels.py): G is an INPUT, so nothing upstream of the two GEMMs rounds; the
+// engine's own packs, splits, transposes, exponent kernels and launchers (run_dgrad_group_f16x3 and
+// run_wgrad of engine_train.h, on one problem = one chain of one step), the form forced by the
+// variant, the rest of the plan from gate_plan.h.  Every output and partial buffer holds the byte
+// 0xA5 before the launches: what a kernel leaves unwritten is seen.
+int mv_op_convlstm_bwd16(int device, int32_t variant_dgrad, int32_t variant_wgrad, const float* x,
+                         const float* h, const float* G, const float* kernel, int32_t M,
+                         int32_t H, int32_t W, int32_t Cx, int32_t C, float* dx, float* dh,
+                         float* dkernel, int32_t* exps, int32_t* forms) {
+  return guarded(nullptr, [&] {
+    const int vd = variant_dgrad, vw = variant_wgrad;
+    MV_REQUIRE(vd >= 0 && vd <= 3, "convlstm_bwd16: dgrad variant %d (0 none, 1 f16x3 direct, 2 "
+               "f16x3 Winograd F(2,3), 3 bf16 one plane)", vd);
+    MV_REQUIRE(vw >= 0 && vw <= 4, "convlstm_bwd16: wgrad variant %d (0 none, 1 f16x3 direct, 2 "
+               "f16x3 row-triple, 3 one-plane direct, 4 one-plane row-triple)", vw);
+    MV_REQUIRE(vd != 0 || vw != 0, "convlstm_bwd16: nothing to run");
+    MV_REQUIRE(G && kernel && exps && forms, "convlstm_bwd16: NULL G, kernel, exps or forms");
+    MV_REQUIRE(M >= 1 && H >= 1 && W >= 1 && H * W >= 32, "convlstm_bwd16: grids of at least 32 "
+               "cells");
+    MV_REQUIRE(C % 128 == 0 && C <= 512, "convlstm_bwd16: C 128, 256, 384 or 512");
+    MV_REQUIRE(Cx >= 1 && (Cx % 16 == 0 || x_is_small(Cx)) && (Cx <= 64 || Cx % 64 == 0),
+               "convlstm_bwd16: Cx %d unsupported (<= 3, 16, 32, 48, 64 or a multiple of 64)", Cx);
+    MV_REQUIRE((int64_t)M * H * W * 4 * C < ((int64_t)1 << 31), "convlstm_bwd16: too large for an "
+               "op call");
+    MV_REQUIRE(vd == 0 || (dh && dx), "convlstm_bwd16: NULL dx or dh");
+    MV_REQUIRE(vw == 0 || (x && h && dkernel), "convlstm_bwd16: NULL x, h or dkernel");
+    const size_t cells = (size_t)M * H * W;
+    const int N4 = 4 * C, Cin = Cx + C;
+    // ---- every refusal before the first launch: the planner's conditions, by name
+    mv::ConvLstmArgs da{};
+    mv::convlstm_dgrad_args(da, nullptr, nullptr, nullptr, nullptr, M, H, W, Cx, C, true, true);
+    if (vd == 2)
+      MV_REQUIRE(wino_dgrad_geometry_ok(da), "convlstm_bwd16: wino_dgrad_geometry_ok: W %d must "
+                 "divide 32, H %d >= 2, C in whole 64-column blocks, 4C / 16 a multiple of 8", W, H);
+    if (vd == 3)
+      MV_REQUIRE((9 * (N4 / 16) / 3) % MV_BF16_UNITS == 0, "convlstm_bwd16: bf16 dgrad stage "
+                 "count %d does not fill whole LDS stages", 9 * (N4 / 16) / 3);
+    if (vw != 0)
+      MV_REQUIRE(mv::wgrad16_ok(W, C), "convlstm_bwd16: wgrad16_ok: W %d %% 16 == 0 and C %d %% "
+                 "128 == 0", W, C);
+    const bool wn = vw == 2 || vw == 4;
+    if (wn)
+      MV_REQUIRE(mv::wgrad16_wino3_ok(H), "convlstm_bwd16: wgrad16_wino3_ok: H %d >= 3 and a "
+                 "multiple of 3", H);
+    for (int i = 0; i < 3; ++i) exps[i] = 0;
+    for (int i = 0; i < 8; ++i) forms[i] = 0;
+
+    OpCtx ctx(device);
+    DevBuf<float> dG, dK;
+    DevBuf<int32_t> gmax, cexp;       // [64] max |G| bits; [0] G exp [1] 8 [2] x exp [64..127] max |x|
+    ctx.up(dG, G, cells * N4);
+    ctx.up(dK, kernel, (size_t)9 * Cin * N4);
+    gmax.alloc(64); cexp.alloc(128);
+    HIP_CHECK(hipMemsetAsync(gmax.p, 0, 64 * sizeof(int32_t), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(cexp.p, 0, 128 * sizeof(int32_t), ctx.stream));
+    hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, ctx.stream, dG.p,
+                       cells * N4, gmax.p);
+
+    // ------------------------------------------------------------------ dgrad
+    DevBuf<float> dxo, dho, part0, part1;
+    DevBuf<_Float16> g16, wd16, wdb, wdw;
+    DevBuf<int32_t> gexp;
+    if (vd != 0) {
+      dxo.alloc(cells * Cx); dho.alloc(cells * C);
+      HIP_CHECK(hipMemsetAsync(dxo.p, kOpSentinel, cells * Cx * sizeof(float), ctx.stream));
+      HIP_CHECK(hipMemsetAsync(dho.p, kOpSentinel, cells * C * sizeof(float), ctx.stream));
+      mv::ConvLstmArgs a{};
+      mv::convlstm_dgrad_args(a, dG.p, nullptr, dho.p, dxo.p, M, H, W, Cx, C, true, true);
+      const bool has_wdw = vd == 2;
+      const DgradPlan pl = plan_dgrad_group(vd == 3 ? 2 : 1, &a, &has_wdw, 1);
+      MV_REQUIRE(pl.bf16 == (vd == 3) && pl.wino == (vd == 2), "convlstm_bwd16: dgrad variant %d "
+                 "is switched off in this process (MV_BF16_BWD, MV_WINO, MV_WINO_DGRAD)", vd);
+      const bool bf = pl.bf16;
+      const size_t nel = cells * a.C;                 // a.C == 4C
+      const size_t pst = nel + mv::kPlaneSlack + mv::kPlanePad;
+      g16.alloc(2 * pst + mv::kPlanePad);
+      HIP_CHECK(hipMemsetAsync(g16.p, 0, (2 * pst + mv::kPlanePad) * sizeof(_Float16), ctx.stream));
+      _Float16* p0 = g16.p + mv::kPlanePad;
+      gexp.alloc(1);
+      HIP_CHECK(hipMemsetAsync(gexp.p, 0, sizeof(int32_t), ctx.stream));
+      if (bf) {
+        hipLaunchKernelGGL(mv::split_plane_bf16_kernel, dim3(mv::split_planes_blocks(cells, a.C)),
+                           dim3(256), 0, ctx.stream, a.h, p0, (int)cells, a.C);
+        const size_t db = mv::bf16_dgrad_wpack_elems(Cx, C);
+        wdb.alloc(db);
+        hipLaunchKernelGGL(mv::pack_bf16_dgrad_kernel, dim3(cdiv(db, 256)), dim3(256), 0,
+                           ctx.stream, dK.p, wdb.p, Cx, C, db);
+      } else {
+        hipLaunchKernelGGL(mv::split_planes_dyn_kernel, dim3(mv::split_planes_blocks(cells, a.C)),
+                           dim3(256), 0, ctx.stream, a.h, p0, p0 + pst, (int)cells, a.C, gmax.p,
+                           gexp.p);
+        const size_t dhv = mv::f16x3_dgrad_wpack_elems(Cx, C);
+        wd16.alloc(dhv);
+        hipLaunchKernelGGL(mv::pack_f16x3_dgrad_kernel, dim3(cdiv(dhv / 2, 256)), dim3(256), 0,
+                           ctx.stream, dK.p, wd16.p, Cx, C, dhv / 2);
+        if (pl.wino) {
+          const size_t dw = mv::wino_dgrad_wpack_elems(Cx, C);
+          wdw.alloc(dw);
+          hipLaunchKernelGGL(mv::pack_wino_dgrad_kernel, dim3(cdiv(dw / 2, 256)), dim3(256), 0,
+                             ctx.stream, dK.p, wdw.p, Cx, C, dw / 2);
+        }
+      }
+      mv::ConvLstm16Args q{};
+      q.f = a;
+      q.h16 = p0; q.h_plane_stride = (int64_t)pst;
+      q.x16 = nullptr; q.x_plane_stride = 0;
+      q.wp16 = bf ? wdb.p : wd16.p;
+      q.n_xk = 0; q.n_hk = 9 * (a.C / 16); q.w_ksteps = q.n_hk;
+      q.g_exp = bf ? nullptr : gexp.p;
+      const DgradPlan::Slices& ks = pl.s[0];
+      const int ns0 = pl.wino ? ks.nks_main : ks.n_kslice, ns1 = pl.wino ? ks.nks_x : ks.n_kslice;
+      const bool need_dx = pl.wino ? ns1 > 1 : a.out1_cols > 0;
+      q.n_kslice = ks.n_kslice;
+      if (ns0 > 1) {
+        part0.alloc((size_t)ns0 * cells * a.out0_cols);
+        HIP_CHECK(hipMemsetAsync(part0.p, kOpSentinel, part0.n * sizeof(float), ctx.stream));
+        q.part0 = part0.p;
+      }
+      if (ns1 > 1 && need_dx) {
+        part1.alloc((size_t)ns1 * cells * ((a.out1_cols + 3) / 4 * 4));
+        HIP_CHECK(hipMemsetAsync(part1.p, kOpSentinel, part1.n * sizeof(float), ctx.stream));
+        q.part1 = part1.p;
+      }
+      if (pl.wino) {
+        mv::ConvLstmWinoArgs w{};
+        w.nks_main = ks.nks_main; w.nks_x = ks.nks_x;
+        w.b = q;
+        w.b.f.n_colblocks = ns1 > 1 ? mv::wino_dgrad_colblocks(a.out1_cols, a.out0_cols)
+                                    : a.out0_cols / 64;
+        w.wpw = wdw.p;
+        w.n_xc = 0;
+        mv::launch_convlstm_wino_dgrads(&w, 1, ctx.stream);
+      } else {
+        mv::launch_convlstm16_dgrads(&q, 1, bf, pl.shift, ctx.stream);
+      }
+      HIP_CHECK(hipGetLastError());
+      mv::SumSlicesArgs sa{};
+      unsigned blocks = 0;
+      sa.nslice = 1;
+      for (int o = 0; o < 2; ++o) {
+        const int ns = o ? ns1 : ns0;
+        if (ns <= 1) continue;
+        float* out = o ? q.f.out1 : q.f.out0;
+        const size_t n = cells * (size_t)(o ? q.f.out1_cols : q.f.out0_cols);
+        if (!out || n == 0) continue;
+        MV_REQUIRE(n % 4 == 0, "convlstm_bwd16: the dgrad slice sum needs a multiple of 4 elements");
+        sa.part[sa.nseg] = o ? q.part1 : q.part0;
+        sa.out[sa.nseg] = out;
+        sa.n[sa.nseg] = n;
+        sa.nslice_seg[sa.nseg] = ns;
+        blocks += cdiv(n / 4, 256);
+        sa.block_end[sa.nseg] = blocks;
+        ++sa.nseg;
+      }
+      if (sa.nseg > 0)
+        hipLaunchKernelGGL(mv::sum_slices_kernel, dim3(blocks), dim3(256), 0, ctx.stream, sa);
+      HIP_CHECK(hipGetLastError());
+      forms[4] = ns0; forms[5] = ns1; forms[6] = (!pl.wino && pl.shift) ? 1 : 0;
+    }
+
+    // ------------------------------------------------------------------ wgrad
+    DevBuf<float> dX, dH, partial, bias_part, dW;
+    DevBuf<_Float16> gt16, at16[3], xt16[3];
+    const size_t ncols = (size_t)9 * Cin * N4;
+    if (vw != 0) {
+      ctx.up(dX, x, cells * Cx);
+      ctx.up(dH, h, cells * C);
+      const WgradPlan pl = plan_wgrad(vw >= 3 ? 2 : 1, 3, M, H, W, Cx, C, wn ? 1 : 0);
+      MV_REQUIRE(pl.f16 && pl.one == (vw >= 3) && pl.wino == wn && pl.nsplit_x <= pl.nsplit,
+                 "convlstm_bwd16: wgrad variant %d is switched off in this process (MV_BF16_BWD)",
+                 vw);
+      const int npl = pl.one ? 1 : 2;
+      const size_t pl_cells = pl.wino ? 5 * ((size_t)pl.Mrow3 + 64) : (size_t)pl.Mrow;
+      auto zalloc = [&](DevBuf<_Float16>& b, size_t n) {
+        b.alloc(n);
+        HIP_CHECK(hipMemsetAsync(b.p, 0, n * sizeof(_Float16), ctx.stream));
+      };
+      zalloc(gt16, (size_t)2 * N4 * pl_cells);
+      for (int d = 0; d < 3; ++d) zalloc(at16[d], (size_t)2 * C * pl_cells);
+      for (int d = 0; d < 3; ++d) zalloc(xt16[d], (size_t)2 * std::max(64, Cx) * pl_cells);
+      bias_part.alloc((size_t)(pl.Mrow / 64) * N4);
+      partial.alloc(pl.partial_elems);
+      HIP_CHECK(hipMemsetAsync(partial.p, kOpSentinel, pl.partial_elems * sizeof(float), ctx.stream));
+      dW.alloc(ncols);
+      HIP_CHECK(hipMemsetAsync(dW.p, kOpSentinel, ncols * sizeof(float), ctx.stream));
+      { const int32_t eight = 8;
+        HIP_CHECK(hipMemcpyAsync(cexp.p + 1, &eight, sizeof(eight), hipMemcpyHostToDevice,
+                                 ctx.stream));
+        HIP_CHECK(hipStreamSynchronize(ctx.stream)); }
+      wgrad16_set_attributes();
+      hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, ctx.stream, gmax.p, 1, 64,
+                         cexp.p);
+      if (pl.wino)
+        hipLaunchKernelGGL(mv::wino3_transpose_g_kernel, dim3((unsigned)(pl.Mrow3 / 64), N4 / 32),
+                           dim3(256), 0, ctx.stream, dG.p, gt16.p, pl.Mtot3, N4, pl.Mrow3, W,
+                           cexp.p, bias_part.p, (long long)2 * N4 * pl.Mrow3, npl);
+      else
+        hipLaunchKernelGGL(mv::transpose_split_kernel, dim3((unsigned)(pl.Mrow / 64), N4 / 64),
+                           dim3(256), 0, ctx.stream, dG.p, gt16.p, pl.Mtot, N4, pl.Mrow, W, 0,
+                           cexp.p, 0, bias_part.p, npl);
+      wgrad_transpose_operand(ctx.stream, pl, dH.p, at16, C, H, W, nullptr, 8, npl);
+      hipLaunchKernelGGL(mv::absmax_bits_kernel, dim3(256), dim3(256), 0, ctx.stream, dX.p,
+                         (size_t)pl.Mtot * Cx, cexp.p + 64);
+      hipLaunchKernelGGL(mv::chain_exp_kernel, dim3(1), dim3(64), 0, ctx.stream, cexp.p + 64, 1,
+                         64, cexp.p + 2, pl.wino ? 10 : 13);
+      wgrad_transpose_operand(ctx.stream, pl, dX.p, xt16, Cx, H, W, cexp.p + 2, 0, npl);
+      HIP_CHECK(hipGetLastError());
+      mv::Wgrad16Args q{};
+      for (int d = 0; d < 3; ++d) q.at[d] = at16[d].p;
+      q.gt = gt16.p; q.partial = partial.p; q.g_exp = cexp.p;
+      q.a_exp = cexp.p + 1;
+      q.Mrow = pl.Mrow; q.H = H; q.W = W; q.Cx = Cx; q.C = C; q.Ca = C;
+      if (pl.wino) {
+        q.ntaps = 15; q.Mrow = pl.Mrow3; q.H = H / 3;
+        q.a_comp_stride = (int64_t)2 * C * pl.Mrow3; q.g_comp_stride = (int64_t)2 * N4 * pl.Mrow3;
+      }
+      if (pl.wide) q.map_mode = pl.map_mode;
+      mv::wgrad16_plan(q, pl.Mgemm, pl.nsplit);
+      launch_wgrad16(ctx.stream, q, pl.wide, pl.one, false);
+      mv::Wgrad16Args qx = q;
+      for (int d = 0; d < 3; ++d) qx.at[d] = xt16[d].p;
+      qx.Ca = Cx; qx.a_exp = cexp.p + 2;
+      if (pl.wino) {
+        qx.a_comp_stride = (int64_t)2 * Cx * pl.Mrow3;
+        mv::wgrad16_plan(qx, pl.Mgemm, pl.nsplit_x);
+      }
+      launch_wgrad16(ctx.stream, qx, pl.wide_x, pl.one, true);
+      HIP_CHECK(hipGetLastError());
+      if (pl.wino)
+        hipLaunchKernelGGL(mv::wgrad_wino3_reduce_kernel, dim3(cdiv(ncols / 3, 256)), dim3(256), 0,
+                           ctx.stream, partial.p, pl.nsplit, pl.nsplit_x, (size_t)Cx * N4,
+                           ncols / 9, dW.p);
+      else
+        hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(ncols, 256)), dim3(256), 0, ctx.stream,
+                           partial.p, dW.p, (size_t)pl.nsplit, ncols, (size_t)pl.nsplit);
+      HIP_CHECK(hipGetLastError());
+      forms[0] = pl.wide; forms[1] = pl.wide_x; forms[2] = pl.nsplit; forms[3] = pl.nsplit_x;
+      forms[7] = pl.transpose3;
+    }
+    if (vd != 0) {
+      ctx.down(dx, dxo, cells * Cx);
+      ctx.down(dh, dho, cells * C);
+    }
+    if (vw != 0) ctx.down(dkernel, dW, ncols);
+    int32_t ce[3] = {0, 0, 0};
+    { DevBuf<int32_t>& src = cexp; HIP_CHECK(hipStreamSynchronize(ctx.stream));
+      HIP_CHECK(hipMemcpy(ce, src.p, sizeof(ce), hipMemcpyDeviceToHost)); }
+    if (vw != 0) { exps[0] = ce[0]; exps[1] = ce[1]; exps[2] = ce[2]; }
+    else if (vd == 1 || vd == 2) ctx.down(exps, gexp, 1);
+  });
+}
+
+// The pointwise backward of one step in each of its three kernels: form 0 lstm_gate_bwd_kernel,
+// 1 lstm_gate_bwd4_kernel, 2 lstm_gate_bwd4_plane_kernel (train_kernels.h).  gates [cells,4,C] the
+// saved activations, dc the incoming d c'; G_out [cells,4C], dc_out [cells,C], gmax_bits the
+// largest of the 64 spread maxima; plane_out (form 2) [cells,4C]: the bf16 plane decoded.
+int mv_op_lstm_gate_bwd(int device, int32_t form, const float* gates, const float* c_prev,
+                        const float* c_new, const float* dh, const float* dc, int32_t cells,
+                        int32_t C, float* G_out, float* dc_out, int32_t* gmax_bits,
+                        float* plane_out) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(form >= 0 && form <= 2, "lstm_gate_bwd: form %d (0 scalar, 1 four channels per "
+               "thread, 2 the same with the bf16 plane)", (int)form);
+    MV_REQUIRE(cells >= 1 && C >= 32 && C % 32 == 0 && C <= 512, "lstm_gate_bwd: C a multiple of "
+               "32 up to 512");
+    MV_REQUIRE(gates && c_new && dh && dc && G_out && dc_out && gmax_bits,
+               "lstm_gate_bwd: NULL argument");
+    MV_REQUIRE(form != 2 || plane_out, "lstm_gate_bwd: form 2 needs plane_out");
+    OpCtx ctx(device);
+    const size_t n = (size_t)cells, total = n * C;
+    DevBuf<float> g, cp, cn, d_h, d_c, dec;
+    DevBuf<int32_t> mb;
+    DevBuf<_Float16> plane;
+    ctx.up(g, gates, total * 4);
+    if (c_prev) ctx.up(cp, c_prev, total);
+    ctx.up(cn, c_new, total);
+    ctx.up(d_h, dh, total);
+    ctx.up(d_c, dc, total);
+    mb.alloc(64);
+    HIP_CHECK(hipMemsetAsync(mb.p, 0, 64 * sizeof(int32_t), ctx.stream));
+    if (form == 2) {
+      const size_t pn = 2 * (total * 4 + mv::kPlaneSlack + mv::kPlanePad);
+      plane.alloc(pn);
+      HIP_CHECK(hipMemsetAsync(plane.p, kOpSentinel, pn * sizeof(_Float16), ctx.stream));
+      hipLaunchKernelGGL(mv::lstm_gate_bwd4_plane_kernel,
+                         dim3((unsigned)(((n + 31) / 32) * (size_t)(C / 32))), dim3(256), 0,
+                         ctx.stream, g.p, cp.p, cn.p, d_h.p, d_c.p, (long long)cells, C,
+                         plane.p + mv::kPlanePad, mb.p);
+      dec.alloc(total * 4);
+      hipLaunchKernelGGL(decode_plane_bf16_kernel, dim3(cdiv(total * 4, 256)), dim3(256), 0,
+                         ctx.stream, plane.p + mv::kPlanePad, dec.p, n, 4 * C);
+    } else if (form == 1) {
+      hipLaunchKernelGGL(mv::lstm_gate_bwd4_kernel, dim3(cdiv(total / 4, 256)), dim3(256), 0,
+                         ctx.stream, g.p, cp.p, cn.p, d_h.p, d_c.p, total / 4, C, mb.p);
+    } else {
+      hipLaunchKernelGGL(mv::lstm_gate_bwd_kernel, dim3(cdiv(total, 256)), dim3(256), 0,
+                         ctx.stream, g.p, cp.p, cn.p, d_h.p, d_c.p, total, C, mb.p);
+    }
+    HIP_CHECK(hipGetLastError());
+    ctx.down(G_out, g, total * 4);
+    ctx.down(dc_out, d_c, total);
+    if (form == 2) ctx.down(plane_out, dec, total * 4);
+    int32_t hb[64];
+    ctx.down(hb, mb, (size_t)64);
+    int32_t best = 0;
+    for (int i = 0; i < 64; ++i) best = std::max(best, hb[i]);
+    *gmax_bits = best;
+  });
+}
+
 int mv_op_gnn_bwd(int device, const float* h, const float* scene_mean, const float* g,
                   int32_t M, int32_t H, int32_t W, int32_t C, int32_t D, float* dh,
                   float* dscene_mean) {

@@ -1182,50 +1182,60 @@ void comm_reduce_rest_and_join(mv_engine* e) {
 
 // f16x3 wgrad: one operand [Mtot][Cc] of a chain -> its transposed, column-shifted fp16 planes
 // dst[0..2] (row-triple form: the five components of each).  Scale 2^exp[0], or 2^fixed_exp.
-void wgrad_transpose_operand(mv_engine* e, const WgradPlan& pl, const float* src,
+void wgrad_transpose_operand(hipStream_t stream, const WgradPlan& pl, const float* src,
                              DevBuf<_Float16>* dst, int Cc, int H, int W, const int32_t* exp,
                              int fixed_exp, int npl) {
   if (pl.wino) {
     hipLaunchKernelGGL(mv::wino3_transpose_a3_kernel,
                        dim3((unsigned)(pl.Mrow3 / 64), (unsigned)((Cc + 31) / 32)), dim3(256), 0,
-                       e->stream, src, dst[0].p, dst[1].p, dst[2].p, pl.Mtot3, Cc, pl.Mrow3, H, W,
+                       stream, src, dst[0].p, dst[1].p, dst[2].p, pl.Mtot3, Cc, pl.Mrow3, H, W,
                        exp, fixed_exp, (long long)2 * Cc * pl.Mrow3, npl);
     return;
   }
   const dim3 grid((unsigned)(pl.Mrow / 64), Cc / 64);
   if (Cc % 64 == 0 && pl.transpose3) {     // the three column-shifted copies from one read
-    hipLaunchKernelGGL(mv::transpose_split3_kernel, grid, dim3(256), 0, e->stream, src, dst[0].p,
+    hipLaunchKernelGGL(mv::transpose_split3_kernel, grid, dim3(256), 0, stream, src, dst[0].p,
                        dst[1].p, dst[2].p, pl.Mtot, Cc, pl.Mrow, W, exp, fixed_exp, npl);
     return;
   }
   for (int d = 0; d < 3; ++d) {
     if (Cc % 64 == 0)
-      hipLaunchKernelGGL(mv::transpose_split_kernel, grid, dim3(256), 0, e->stream, src, dst[d].p,
+      hipLaunchKernelGGL(mv::transpose_split_kernel, grid, dim3(256), 0, stream, src, dst[d].p,
                          pl.Mtot, Cc, pl.Mrow, W, d - 1, exp, fixed_exp, (float*)nullptr, npl);
     else      // any width up to 64
       hipLaunchKernelGGL(mv::transpose_split_narrow_kernel, dim3((unsigned)(pl.Mrow / 64)),
-                         dim3(256), 0, e->stream, src, dst[d].p, pl.Mtot, Cc, pl.Mrow, W, d - 1, exp,
+                         dim3(256), 0, stream, src, dst[d].p, pl.Mtot, Cc, pl.Mrow, W, d - 1, exp,
                          npl);
   }
+}
+
+void wgrad_transpose_operand(mv_engine* e, const WgradPlan& pl, const float* src,
+                             DevBuf<_Float16>* dst, int Cc, int H, int W, const int32_t* exp,
+                             int fixed_exp, int npl) {
+  wgrad_transpose_operand(e->stream, pl, src, dst, Cc, H, W, exp, fixed_exp, npl);
 }
 
 // f16x3 wgrad GEMM of the h rows (xrows false) or the x rows of one chain: the kernel instance
 // for {narrow, wide tile} x {1, 3 planes}.  (The narrow three-plane tile needs its dynamic-LDS
 // limit raised, once per training state.)
-void wgrad16_init_attributes(TrainState& t) {
-  if (t.wgrad16_attr) return;
+void wgrad16_set_attributes() {
   HIP_CHECK(hipFuncSetAttribute(
       reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<false, 3>),
       hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
   HIP_CHECK(hipFuncSetAttribute(
       reinterpret_cast<const void*>(mv::convlstm_wgrad_f16x3_kernel<true, 3>),
       hipFuncAttributeMaxDynamicSharedMemorySize, (int)mv::kWg16LdsBytes));
+}
+void wgrad16_init_attributes(TrainState& t) {
+  if (t.wgrad16_attr) return;
+  wgrad16_set_attributes();
   t.wgrad16_attr = true;
 }
-void launch_wgrad16(mv_engine* e, const mv::Wgrad16Args& q, bool wide, bool one, bool xrows) {
+void launch_wgrad16(hipStream_t stream, const mv::Wgrad16Args& q, bool wide, bool one,
+                    bool xrows) {
   const dim3 grid(wide ? mv::wgrad16_wide_blocks(q, xrows) : mv::wgrad16_blocks(q, xrows));
   const size_t lds = wide ? 0 : (one ? mv::kWg16LdsBytes1 : mv::kWg16LdsBytes);
-  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, e->stream, q); };
+  auto go = [&](auto kernel) { hipLaunchKernelGGL(kernel, grid, dim3(256), lds, stream, q); };
   if (!xrows) {
     if (wide && one) go(mv::convlstm_wgrad_f16x3_wide_kernel<1>);
     else if (wide) go(mv::convlstm_wgrad_f16x3_wide_kernel<3>);
@@ -1237,6 +1247,9 @@ void launch_wgrad16(mv_engine* e, const mv::Wgrad16Args& q, bool wide, bool one,
     else if (one) go(mv::convlstm_wgrad_f16x3_kernel<true, 1>);
     else go(mv::convlstm_wgrad_f16x3_kernel<true, 3>);
   }
+}
+void launch_wgrad16(mv_engine* e, const mv::Wgrad16Args& q, bool wide, bool one, bool xrows) {
+  launch_wgrad16(e->stream, q, wide, one, xrows);
 }
 
 // gslot: first gmax slot of the chain's steps (f16x3 mode), see train_backward

@@ -314,7 +314,10 @@ struct WgradPlan {
   size_t partial_elems = 0;         // floats the chosen form writes to the partial buffer
   mv::WgradArgs fp32{};             // the fp32 kernel's plan (pointers unset)
 };
-inline WgradPlan plan_wgrad(int mode, int ksize, int R, int H, int W, int Cx, int C) {
+// force_wino: -1 the planner's choice; 0 / 1 the direct / the row-triple form whatever the switches
+// say (mv_op_convlstm_bwd16, which checks wgrad16_wino3_ok itself)
+inline WgradPlan plan_wgrad(int mode, int ksize, int R, int H, int W, int Cx, int C,
+                            int force_wino = -1) {
   const GateKnobs& k = gate_knobs();
   WgradPlan pl;
   pl.Mtot = (long long)R * H * W;
@@ -332,6 +335,7 @@ inline WgradPlan plan_wgrad(int mode, int ksize, int R, int H, int W, int Cx, in
   if (!pl.f16) return pl;
   pl.one = mode == 2 && k.bf16_bwd;
   pl.wino = k.wgrad_wino && (k.wgrad_wino_bf16 || !pl.one) && mv::wgrad16_wino3_ok(H);
+  if (force_wino >= 0) pl.wino = force_wino == 1;
   pl.transpose3 = k.transpose3;
   if (pl.wino) { pl.ntaps = 15; pl.Mgemm = pl.Mtot3; }
   // the wide tile balances on 7 / 14 / 21 splits; the x rows and the reduction follow its count

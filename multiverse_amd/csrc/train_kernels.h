@@ -28,23 +28,29 @@ __global__ void lstm_gate_bwd_kernel(float* __restrict__ gates,
                                      float* __restrict__ dc_io, size_t total, int C,
                                      int32_t* __restrict__ gmax_bits = nullptr) {
   const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;       // total is a multiple of the block size (C = 256)
-  const size_t m = idx / C;
-  const int ch = (int)(idx - m * C);
-  float* gp = gates + m * 4 * (size_t)C + ch;
-  const float si = gp[0], tj = gp[C], sf = gp[2 * C], so = gp[3 * C];
-  const float tc = tanhf(c_new[idx]);
-  const float dhv = dh[idx];
-  const float dcv = dc_io[idx] + dhv * so * (1.f - tc * tc);
-  const float cp = c_prev ? c_prev[idx] : 0.f;
-  const float gi = dcv * tj * (si * (1.f - si));
-  const float gj = dcv * si * (1.f - tj * tj);
-  const float gf = dcv * cp * (sf * (1.f - sf));
-  const float go = dhv * tc * (so * (1.f - so));
-  gp[0] = gi; gp[C] = gj; gp[2 * C] = gf; gp[3 * C] = go;
-  dc_io[idx] = dcv * sf;
+  // (no early return: with C = 128 and an odd cell count the last block is half full, and the
+  // max below is a reduction of the WHOLE block -- a wave that had left would leave its slot of
+  // wm unwritten)
+  float mx = 0.f;
+  if (idx < total) {
+    const size_t m = idx / C;
+    const int ch = (int)(idx - m * C);
+    float* gp = gates + m * 4 * (size_t)C + ch;
+    const float si = gp[0], tj = gp[C], sf = gp[2 * C], so = gp[3 * C];
+    const float tc = tanhf(c_new[idx]);
+    const float dhv = dh[idx];
+    const float dcv = dc_io[idx] + dhv * so * (1.f - tc * tc);
+    const float cp = c_prev ? c_prev[idx] : 0.f;
+    const float gi = dcv * tj * (si * (1.f - si));
+    const float gj = dcv * si * (1.f - tj * tj);
+    const float gf = dcv * cp * (sf * (1.f - sf));
+    const float go = dhv * tc * (so * (1.f - so));
+    gp[0] = gi; gp[C] = gj; gp[2 * C] = gf; gp[3 * C] = go;
+    dc_io[idx] = dcv * sf;
+    mx = fmaxf(fmaxf(fabsf(gi), fabsf(gj)), fmaxf(fabsf(gf), fabsf(go)));
+  }
   if (gmax_bits) {   // max |G| of the tensor (f16x3 dgrad scale); max is order-independent
-    float m = fmaxf(fmaxf(fabsf(gi), fabsf(gj)), fmaxf(fabsf(gf), fabsf(go)));
+    float m = mx;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off, 64));
     // one atomic per WORKGROUP, spread over 64 addresses per tensor (block id mod

@@ -35,13 +35,16 @@ behind the other eight).  Two guards on the inputs keep a degenerate feed from p
 CPU oracle's own per-slice error against fp64 < 2e-4, and every slice's max|fp64| > 1e-5.  f16x3
 against the f32 mode of the same engine: 5e-5 per tensor, kernels as x rows / h rows
 (test_f16x3_gradients_match_f32_mode).  bf16: finite, cosine against the fp32 oracle > 0.999 (a
-per-slice bar against an oracle on rounded operands does not exist at this level: DESIGN.md 3d).
+per-slice bar against an oracle on rounded operands does not exist at this level: DESIGN.md 3d --
+it exists one level down, kernel by kernel on operands exact in every plane:
+tests/test_gpu_bwd_kernels.py).
 """
 
 import numpy as np
 import pytest
 import torch
 
+from bwd_cases import kernel_slices
 from multiverse_amd import synth
 from oracle import multiverse_oracle as oracle
 
@@ -148,14 +151,7 @@ def slices(name, a, C):
   """(label, view) of a gradient: a gate kernel per tap and x rows / h rows, else whole."""
   if not is_gate_kernel(name, a, C):
     return [("all", a)]
-  Cx = a.shape[2] - C
-  out = []
-  for ky in range(3):
-    for kx in range(3):
-      if Cx > 0:
-        out.append(("tap %d,%d x rows" % (ky, kx), a[ky, kx, :Cx]))
-      out.append(("tap %d,%d h rows" % (ky, kx), a[ky, kx, Cx:]))
-  return out
+  return kernel_slices(a, C)
 
 
 def _err(a, b):
