@@ -1227,6 +1227,16 @@ void add_scaled_sumsq_kernel(float* __restrict__ g, const float* __restrict__ w,
   if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
 }
 
+// The element-wise clip of the four optimizer kernels below: clip_by_value
+// (code/pred_models.py:1700-1705) of the SCALED gradient, written as comparisons so that a NaN
+// gradient stays NaN (both comparisons are false) and reaches the variable and its slots, as
+// np.clip in oracle.train_step and TF's clip_by_value keep it.  fminf(fmaxf(g, -clip), clip)
+// would return -clip for a NaN: a diverged run would go on writing finite, wrong weights.
+// +-inf clip to +-clip.
+__device__ __forceinline__ float clip_value(float g, float clip) {
+  return g < -clip ? -clip : (g > clip ? clip : g);
+}
+
 // clip_by_value (code/pred_models.py:1700-1705) + TF ApplyAdadelta
 // (AdadeltaOptimizer(lr, rho=0.95, epsilon=1e-8), :1671-1672):
 //   accum = rho accum + (1-rho) g^2
@@ -1239,7 +1249,7 @@ __global__ void adadelta_kernel(float* __restrict__ var, float* __restrict__ acc
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float g = grad[i] * gscale;
-  if (do_clip) g = fminf(fmaxf(g, -clip), clip);
+  if (do_clip) g = clip_value(g, clip);
   const float a = accum[i] * rho + g * g * (1.f - rho);
   const float upd = sqrtf(accum_update[i] + eps) * (1.0f / sqrtf(a + eps)) * g;
   var[i] = var[i] - upd * lr;
@@ -1255,7 +1265,7 @@ __global__ void momentum_kernel(float* __restrict__ var, float* __restrict__ acc
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float g = grad[i] * gscale;
-  if (do_clip) g = fminf(fmaxf(g, -clip), clip);
+  if (do_clip) g = clip_value(g, clip);
   const float a = accum[i] * momentum + g;
   var[i] = var[i] - a * lr;
   accum[i] = a;
@@ -1271,7 +1281,7 @@ __global__ void adam_kernel(float* __restrict__ var, float* __restrict__ m,
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float g = grad[i] * gscale;
-  if (do_clip) g = fminf(fmaxf(g, -clip), clip);
+  if (do_clip) g = clip_value(g, clip);
   const float mm = m[i] + (g - m[i]) * omb1;
   const float vv = v[i] + (g * g - v[i]) * omb2;
   var[i] = var[i] - (mm * alpha) / (sqrtf(vv) + eps);
@@ -1288,7 +1298,7 @@ __global__ void rmsprop_kernel(float* __restrict__ var, float* __restrict__ ms,
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   float g = grad[i] * gscale;
-  if (do_clip) g = fminf(fmaxf(g, -clip), clip);
+  if (do_clip) g = clip_value(g, clip);
   const float s2 = ms[i] + (g * g - ms[i]) * omd;
   const float mo = mom[i] * momentum + (g * lr) * (1.0f / sqrtf(s2 + eps));
   var[i] = var[i] - mo;

@@ -953,33 +953,39 @@ def optimizer_init(cfg, params):
 
 def apply_optimizer(cfg, lr, v, g, slots, npd, powers=None):
   """One variable's update as the TF-1.15 training_ops kernels compute it
-  (code/pred_models.py:1667-1679 picks the optimizer).  -> (new value, new slots)."""
+  (code/pred_models.py:1667-1679 picks the optimizer).  -> (new value, new slots).
+
+  The hyper-parameters reach those kernels as float32 tensors (the optimizers cast lr, rho,
+  beta, epsilon to the variable's dtype), and the kernels form `T(1) - beta` in T = float32: the
+  constants below are those float32 VALUES in either precision, so npd = float64 is the same
+  operation on the same operands carried out exactly.  (1 - 0.999 taken in double and then
+  rounded is 1.3e-5 away from float32 1 - 0.999f, the factor ApplyAdam multiplies by.)"""
+  f = np.float32
   one = npd(1)
   if cfg.optimizer == "adadelta":     # ApplyAdadelta, rho 0.95, eps 1e-8
-    rho, eps = npd(0.95), npd(1e-8)
+    rho, eps = npd(f(0.95)), npd(f(1e-8))
     acc, acc_up = slots
     acc = acc.astype(npd) * rho + g * g * (one - rho)
     upd = np.sqrt(acc_up.astype(npd) + eps) * (one / np.sqrt(acc + eps)) * g
-    new = (v.astype(npd) - upd * npd(lr)).astype(npd)
+    new = (v.astype(npd) - upd * npd(f(lr))).astype(npd)
     acc_up = acc_up.astype(npd) * rho + upd * upd * (one - rho)
     return new, (acc, acc_up)
   if cfg.optimizer == "momentum":     # ApplyMomentum, momentum 0.9, no Nesterov
     (acc,) = slots
-    acc = acc.astype(npd) * npd(0.9) + g
-    return (v.astype(npd) - acc * npd(lr)).astype(npd), (acc,)
+    acc = acc.astype(npd) * npd(f(0.9)) + g
+    return (v.astype(npd) - acc * npd(f(lr))).astype(npd), (acc,)
   if cfg.optimizer == "adam":         # ApplyAdam, beta 0.9 / 0.999, eps 1e-8
     m, vv = slots
     b1p, b2p = powers
-    alpha = npd(np.float32(lr) * np.sqrt(np.float32(1) - np.float32(b2p)) /
-                (np.float32(1) - np.float32(b1p)))
-    m = m.astype(npd) + (g - m.astype(npd)) * npd(1.0 - 0.9)
-    vv = vv.astype(npd) + (g * g - vv.astype(npd)) * npd(1.0 - 0.999)
-    new = (v.astype(npd) - (m * alpha) / (np.sqrt(vv) + npd(1e-8))).astype(npd)
+    alpha = npd(f(lr) * np.sqrt(f(1) - f(b2p)) / (f(1) - f(b1p)))
+    m = m.astype(npd) + (g - m.astype(npd)) * npd(f(1) - f(0.9))
+    vv = vv.astype(npd) + (g * g - vv.astype(npd)) * npd(f(1) - f(0.999))
+    new = (v.astype(npd) - (m * alpha) / (np.sqrt(vv) + npd(f(1e-8)))).astype(npd)
     return new, (m, vv)
   if cfg.optimizer == "rmsprop":      # ApplyRMSProp, decay 0.9, momentum 0, eps 1e-10
     ms, mom = slots
-    ms = ms.astype(npd) + (g * g - ms.astype(npd)) * npd(1.0 - 0.9)
-    mom = mom.astype(npd) * npd(0.0) + (g * npd(lr)) * (one / np.sqrt(ms + npd(1e-10)))
+    ms = ms.astype(npd) + (g * g - ms.astype(npd)) * npd(f(1) - f(0.9))
+    mom = mom.astype(npd) * npd(0.0) + (g * npd(f(lr))) * (one / np.sqrt(ms + npd(f(1e-10))))
     return (v.astype(npd) - mom).astype(npd), (ms, mom)
   raise ValueError("Optimizer not implemented")
 

@@ -344,7 +344,18 @@ def test_two_rank_test_fails_when_an_event_wait_is_dropped(built_lib, tmp_path, 
   for attempt in range(1 if what == "done" else 3):
     sub = tmp_path / ("attempt%d" % attempt)
     sub.mkdir()
-    res = _two_ranks_vs_one_process(built_lib, sub, env)
+    try:
+      res = _two_ranks_vs_one_process(built_lib, sub, env)
+    except mp.ProcessRaisedException as err:
+      # The optimizer kernels keep a NaN gradient (train_kernels.h clip_value): the poison reaches
+      # the weights, and a rank in f16x3 refuses the step it would otherwise run on them.  A rank
+      # that raises fails the test above as well: detected, and loudly.
+      if "MvError" not in str(err) or "after optimizer step" not in str(err):
+        raise
+      print("dropped `%s` wait (attempt %d): a rank refused the poisoned step -> DETECTED\n%s" % (
+          what, attempt, str(err).strip().splitlines()[-1]))
+      broken = True
+      break
     broken = (not res["ranks_equal"]) or not (res["grad"] <= 2e-4) or \
         not (res["param_upd"] <= 2e-3)
     print("dropped `%s` wait (attempt %d): ranks_equal %s grad %.2e param_upd %.2e -> %s" % (
