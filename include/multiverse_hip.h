@@ -1113,6 +1113,63 @@ int  mv_op_gnn_bwd(int device, const float* h, const float* scene_mean,
                    const float* g, int32_t M, int32_t H, int32_t W, int32_t C,
                    int32_t D, float* dh, float* dscene_mean);
 
+/* ---- The helper kernels of a training step, one entry point each (kernel-level parity tests,
+ * tests/test_gpu_train_helpers.py).  Each runs the engine's own host-side choice of kernel and its
+ * launch on the operands given; a forced form the shape cannot take is refused by name before
+ * any launch.  Output buffers hold the byte 0xA5 before the launches.
+ *
+ * dgrad of a small 3x3 SAME conv (hidden2grid, grid_emb): dout [M][dout_rs] with the first
+ * H*W*Co floats of a row in use, w [9][Ci][Co], din [M][din_rs] IN and OUT (the whole buffer
+ * travels both ways, so what lies between the rows comes back as it went in).  form 0 the plan's,
+ * 1 scalar, 2 dgrad4<1>, 3 dgrad4<2>; form_ran: 1, 2 or 3. */
+int  mv_op_small_conv_dgrad(int device, int32_t form, const float* dout, int64_t dout_rs,
+                            const float* w, float* din, int64_t din_rs, int32_t M, int32_t H,
+                            int32_t W, int32_t Ci, int32_t Co, int32_t accumulate,
+                            int32_t* form_ran);
+/* wgrad of the same conv over R images: in [R,H,W,Ci], dout [R,H,W,Co] -> dw [9][Ci][Co] after
+ * the two-level fold.  form 0 the plan's, 1 small_wgrad<false> (walks the output cells), 2
+ * small_wgrad<true> (walks the input cells), 3 the hidden2grid kernel.  Ci*Co > 512 is refused
+ * outside the hidden2grid shape.  info [4]: form that ran, blocks, cells per block, cell groups
+ * G per workgroup. */
+int  mv_op_small_conv_wgrad(int device, int32_t form, const float* in, const float* dout,
+                            int32_t R, int32_t H, int32_t W, int32_t Ci, int32_t Co, float* dw,
+                            int32_t* info);
+/* The deterministic column sum of x [rows, ncols] -> out [ncols].  info [2]: slabs, and whether
+ * the narrow kernel summed them. */
+int  mv_op_colsum(int device, const float* x, int64_t rows, int64_t ncols, float* out,
+                  int32_t* info);
+/* out[0] = scale * sum of x [n]; chunked: whether the per-chunk stage ran. */
+int  mv_op_long_sum(int device, const float* x, int64_t n, float scale, float* out,
+                    int32_t* chunked);
+/* Backward of one level of the stride-2 SAME scene stack given its input, its forward output y
+ * and dy: dpre = dy * act'(y) [U,Ho,Wo,Co], din [U,Hi,Wi,Ci] (accumulate: onto din_init; else
+ * din_init may be NULL), dw [k,k,Ci,Co] (slab partials folded), db [Co].  info [4]: pad_t,
+ * pad_l, wgrad slabs, output rows per slab. */
+int  mv_op_scene_conv_bwd(int device, const float* in, const float* y, const float* dy,
+                          const float* w, int32_t U, int32_t Hi, int32_t Wi, int32_t Ci,
+                          int32_t Co, int32_t k, int32_t act, const float* din_init,
+                          int32_t accumulate, float* dpre, float* din, float* dw, float* db,
+                          int32_t* info);
+/* dW [9][E] of the class encoder's grid_emb from its one-hot input: dpre [T,N,H,W,E] time-major,
+ * labels [N][T] (each a cell of the grid, checked on the host); dw IN and OUT (accumulate adds
+ * onto it). */
+int  mv_op_grid_emb_onehot_wgrad(int device, const float* dpre, const int32_t* labels, int32_t N,
+                                 int32_t T, int32_t H, int32_t W, int32_t E, int32_t accumulate,
+                                 float* dw);
+/* One loss of a training step.  kind 0 ce (labels [N][T]), 1 ce_soft (soft [T*N,K]), 2 ce_len
+ * (pred_lens [N]; labels, or soft when given), 3 huber, 4 huber_len, 5 huber_masked (fg [T,N,K];
+ * with the foreground count in front and the masked mean behind).  pred time-major: logits
+ * [T,N,K], or [T,N,K,2] against target [N,T,K,2].  scale multiplies the gradient and the summed
+ * loss (kind 5: the loss weight).  sample_w [N] (kinds 0 and 1, or NULL) scales the rows.  Labels
+ * outside [0, K) and lengths outside [0, T] are refused before any launch.  loss: [T*N] rows, or
+ * [T,N,K,2] elements; grad as pred; loss_sum [1]; info [2]: the foreground count (kind 5),
+ * whether the long sum ran its chunk stage. */
+int  mv_op_train_loss(int device, int32_t kind, const float* pred, const int32_t* labels,
+                      const float* soft, const float* target, const float* fg,
+                      const float* sample_w, const int32_t* pred_lens, int32_t T, int32_t N,
+                      int32_t K, float scale, float* loss, float* grad, float* loss_sum,
+                      int32_t* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,8 @@ EXPORTED_SYMBOLS = [
     "mv_op_sample_step_motion",
     "mv_set_revisit_cost", "mv_op_beam_step_path", "mv_op_sbs_step_path",
     "mv_op_sample_step_path",
+    "mv_op_small_conv_dgrad", "mv_op_small_conv_wgrad", "mv_op_colsum", "mv_op_long_sum",
+    "mv_op_scene_conv_bwd", "mv_op_grid_emb_onehot_wgrad", "mv_op_train_loss",
 ]
 
 
@@ -396,6 +398,19 @@ def load():
         [C.c_int32] * 5 + [_fp] * 3 + [_ip, _ip]
     lib.mv_op_lstm_gate_bwd.argtypes = [C.c_int, C.c_int32] + [_fp] * 5 + [C.c_int32] * 2 + \
         [_fp, _fp, _ip, _fp]
+  if hasattr(lib, "mv_op_train_loss"):      # (an A/B build through MV_LIB_PATH may predate them)
+    i64 = C.c_int64
+    lib.mv_op_small_conv_dgrad.argtypes = [C.c_int, C.c_int32, _fp, i64, _fp, _fp, i64] + \
+        [C.c_int32] * 6 + [_ip]
+    lib.mv_op_small_conv_wgrad.argtypes = [C.c_int, C.c_int32, _fp, _fp] + [C.c_int32] * 5 + \
+        [_fp, _ip]
+    lib.mv_op_colsum.argtypes = [C.c_int, _fp, i64, i64, _fp, _ip]
+    lib.mv_op_long_sum.argtypes = [C.c_int, _fp, i64, C.c_float, _fp, _ip]
+    lib.mv_op_scene_conv_bwd.argtypes = [C.c_int, _fp, _fp, _fp, _fp] + [C.c_int32] * 7 + \
+        [_fp, C.c_int32, _fp, _fp, _fp, _fp, _ip]
+    lib.mv_op_grid_emb_onehot_wgrad.argtypes = [C.c_int, _fp, _ip] + [C.c_int32] * 6 + [_fp]
+    lib.mv_op_train_loss.argtypes = [C.c_int, C.c_int32, _fp, _ip, _fp, _fp, _fp, _fp, _ip] + \
+        [C.c_int32] * 3 + [C.c_float, _fp, _fp, _fp, _ip]
   if lib.mv_abi_version() != MV_ABI_VERSION:
     raise MvError("ABI version mismatch: library %d, binding %d"
                   % (lib.mv_abi_version(), MV_ABI_VERSION))
@@ -2007,3 +2022,129 @@ def op_gnn_bwd(h, scene_mean, g, device=0):
   check(lib.mv_op_gnn_bwd(device, fptr(h), fptr(scene_mean), fptr(g), M, H, W, Cc,
                           scene_mean.shape[-1], fptr(dh), fptr(ds)))
   return dh, ds
+
+
+# ---- the helper kernels of a training step, one door each (include/multiverse_hip.h)
+SMALL_DGRAD_FORMS = {None: 0, "scalar": 1, "dgrad4<1>": 2, "dgrad4<2>": 3}
+SMALL_WGRAD_FORMS = {None: 0, "small_wgrad<false>": 1, "small_wgrad<true>": 2, "h2g": 3}
+TRAIN_LOSS_KINDS = {"ce": 0, "ce_soft": 1, "ce_len": 2, "huber": 3, "huber_len": 4,
+                    "huber_masked": 5}
+
+
+def _name_of(table, code):
+  return [k for k, v in table.items() if v == code][0]
+
+
+def op_small_conv_dgrad(dout, w, din, H, W, accumulate=False, form=None, device=0):
+  """mv_op_small_conv_dgrad: dout [M, dout_rs] and din [M, din_rs] are whole strided buffers (the
+  first H*W*C floats of a row in use); w [3, 3, Ci, Co].  Returns (din after the launch, the name
+  of the form that ran)."""
+  lib = load()
+  dout, w = f32(dout), f32(w)
+  din = f32(din).copy()
+  M = int(dout.shape[0])
+  Ci, Co = int(w.shape[2]), int(w.shape[3])
+  assert dout.ndim == 2 and din.ndim == 2 and din.shape[0] == M and w.shape[:2] == (3, 3)
+  ran = np.zeros(1, dtype=np.int32)
+  check(lib.mv_op_small_conv_dgrad(device, SMALL_DGRAD_FORMS[form], fptr(dout),
+                                   int(dout.shape[1]), fptr(w), fptr(din), int(din.shape[1]), M,
+                                   int(H), int(W), Ci, Co, 1 if accumulate else 0, iptr(ran)))
+  return din, _name_of(SMALL_DGRAD_FORMS, int(ran[0]))
+
+
+def op_small_conv_wgrad(x, dout, form=None, device=0):
+  """mv_op_small_conv_wgrad: x [R, H, W, Ci], dout [R, H, W, Co] -> (dw [3, 3, Ci, Co], dict of
+  form, blocks, cells_per_block, G)."""
+  lib = load()
+  x, dout = f32(x), f32(dout)
+  R, H, W, Ci = x.shape
+  Co = int(dout.shape[3])
+  assert dout.shape[:3] == (R, H, W)
+  dw = np.empty((3, 3, Ci, Co), dtype=np.float32)
+  info = np.zeros(4, dtype=np.int32)
+  check(lib.mv_op_small_conv_wgrad(device, SMALL_WGRAD_FORMS[form], fptr(x), fptr(dout), R, H, W,
+                                   Ci, Co, fptr(dw), iptr(info)))
+  return dw, dict(form=_name_of(SMALL_WGRAD_FORMS, int(info[0])), blocks=int(info[1]),
+                  cells_per_block=int(info[2]), G=int(info[3]))
+
+
+def op_colsum(x, device=0):
+  """mv_op_colsum: x [rows, ncols] -> (column sums [ncols], slabs, narrow)."""
+  lib = load()
+  x = f32(x)
+  rows, ncols = x.shape
+  out = np.empty(ncols, dtype=np.float32)
+  info = np.zeros(2, dtype=np.int32)
+  check(lib.mv_op_colsum(device, fptr(x), rows, ncols, fptr(out), iptr(info)))
+  return out, int(info[0]), bool(info[1])
+
+
+def op_long_sum(x, scale=1.0, device=0):
+  """mv_op_long_sum: x [n] -> (scale * sum, whether the chunk stage ran)."""
+  lib = load()
+  x = f32(x).reshape(-1)
+  out = np.empty(1, dtype=np.float32)
+  ch = np.zeros(1, dtype=np.int32)
+  check(lib.mv_op_long_sum(device, fptr(x), x.size, float(scale), fptr(out), iptr(ch)))
+  return out[0], bool(ch[0])
+
+
+def op_scene_conv_bwd(x, y, dy, w, act=0, din_init=None, accumulate=False, device=0):
+  """mv_op_scene_conv_bwd: x [U, Hi, Wi, Ci], y / dy [U, Ho, Wo, Co], w [k, k, Ci, Co] -> dict of
+  dpre, din, dw, db, pad_t, pad_l, slabs, rows_per_slab."""
+  lib = load()
+  x, y, dy, w = f32(x), f32(y), f32(dy), f32(w)
+  U, Hi, Wi, Ci = x.shape
+  k, Co = int(w.shape[0]), int(w.shape[3])
+  assert y.shape == dy.shape == (U, (Hi + 1) // 2, (Wi + 1) // 2, Co)
+  init = f32(din_init) if din_init is not None else None
+  dpre, din = np.empty_like(y), np.empty_like(x)
+  dw, db = np.empty_like(w), np.empty(Co, dtype=np.float32)
+  info = np.zeros(4, dtype=np.int32)
+  check(lib.mv_op_scene_conv_bwd(device, fptr(x), fptr(y), fptr(dy), fptr(w), U, Hi, Wi, Ci, Co,
+                                 k, int(act), fptr(init), 1 if accumulate else 0, fptr(dpre),
+                                 fptr(din), fptr(dw), fptr(db), iptr(info)))
+  return dict(dpre=dpre, din=din, dw=dw, db=db, pad_t=int(info[0]), pad_l=int(info[1]),
+              slabs=int(info[2]), rows_per_slab=int(info[3]))
+
+
+def op_grid_emb_onehot_wgrad(dpre, labels, dw_init=None, accumulate=False, device=0):
+  """mv_op_grid_emb_onehot_wgrad: dpre [T, N, H, W, E], labels [N, T] -> dw [3, 3, E]."""
+  lib = load()
+  dpre, labels = f32(dpre), i32(labels)
+  T, N, H, W, E = dpre.shape
+  assert labels.shape == (N, T)
+  dw = f32(dw_init).copy() if dw_init is not None else np.zeros((3, 3, E), dtype=np.float32)
+  assert dw.shape == (3, 3, E)
+  check(lib.mv_op_grid_emb_onehot_wgrad(device, fptr(dpre), iptr(labels), N, T, H, W, E,
+                                        1 if accumulate else 0, fptr(dw)))
+  return dw
+
+
+def op_train_loss(kind, pred, scale, labels=None, soft=None, target=None, fg=None,
+                  sample_w=None, pred_lens=None, device=0):
+  """mv_op_train_loss: pred [T, N, K] (cross entropies) or [T, N, K, 2] (Huber kinds, target
+  [N, T, K, 2], fg [T, N, K]) -> dict of loss (rows [T, N] or elements), grad, loss_sum, count,
+  chunked."""
+  lib = load()
+  pred = f32(pred)
+  T, N, K = pred.shape[:3]
+  ce = TRAIN_LOSS_KINDS[kind] <= 2
+  assert pred.ndim == (3 if ce else 4)
+  opt = lambda a, conv: conv(a) if a is not None else None
+  labels, pred_lens = opt(labels, i32), opt(pred_lens, i32)
+  soft, target, fg, sample_w = opt(soft, f32), opt(target, f32), opt(fg, f32), opt(sample_w, f32)
+  assert labels is None or labels.shape == (N, T)
+  assert soft is None or soft.shape == pred.shape
+  assert target is None or target.shape == (N, T, K, 2)
+  assert fg is None or fg.shape == (T, N, K)
+  assert sample_w is None or sample_w.shape == (N,)
+  assert pred_lens is None or pred_lens.shape == (N,)
+  loss = np.empty((T, N) if ce else pred.shape, dtype=np.float32)
+  grad = np.empty_like(pred)
+  total = np.empty(1, dtype=np.float32)
+  info = np.zeros(2, dtype=np.int32)
+  check(lib.mv_op_train_loss(device, TRAIN_LOSS_KINDS[kind], fptr(pred), iptr(labels), fptr(soft),
+                             fptr(target), fptr(fg), fptr(sample_w), iptr(pred_lens), T, N, K,
+                             float(scale), fptr(loss), fptr(grad), fptr(total), iptr(info)))
+  return dict(loss=loss, grad=grad, loss_sum=total[0], count=int(info[0]), chunked=bool(info[1]))

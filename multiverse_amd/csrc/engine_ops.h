@@ -1281,6 +1281,270 @@ int mv_op_gnn_bwd(int device, const float* h, const float* scene_mean, const flo
   });
 }
 
+// ---- the helper kernels of a training step, one door each (tests/test_gpu_train_helpers.py):
+// every door uploads its operands, calls the launcher the engine calls (engine_train.h
+// launch_small_dgrad / launch_small_wgrad / launch_colsum / launch_long_sum / launch_scene_dgrad
+// / launch_scene_wgrad / launch_grid_emb_onehot_wgrad / launch_ce_loss / launch_huber_loss) and
+// reports the form that ran.  Output buffers hold kOpSentinel bytes before the launches.
+
+int mv_op_small_conv_dgrad(int device, int32_t form, const float* dout, int64_t dout_rs,
+                           const float* w, float* din, int64_t din_rs, int32_t M, int32_t H,
+                           int32_t W, int32_t Ci, int32_t Co, int32_t accumulate,
+                           int32_t* form_ran) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(dout && w && din && form_ran, "mv_op_small_conv_dgrad: NULL argument");
+    MV_REQUIRE(M >= 1 && H >= 1 && W >= 1 && Ci >= 1 && Co >= 1,
+               "mv_op_small_conv_dgrad: bad shape");
+    MV_REQUIRE(dout_rs >= (int64_t)H * W * Co && din_rs >= (int64_t)H * W * Ci,
+               "mv_op_small_conv_dgrad: a row stride is shorter than a row");
+    MV_REQUIRE(form >= 0 && form <= 3, "mv_op_small_conv_dgrad: form %d (0 = the plan's, 1 scalar, "
+               "2 dgrad4<1>, 3 dgrad4<2>)", (int)form);
+    const bool v4 = small_dgrad_vec4_ok((size_t)din_rs, M, H, W, Ci, Co);
+    MV_REQUIRE(form != 2 || (v4 && Co == 1), "mv_op_small_conv_dgrad: form dgrad4<1> needs "
+               "Ci %% 4 == 0, Co == 1 and a din row stride that is a multiple of 4");
+    MV_REQUIRE(form != 3 || (v4 && Co == 2), "mv_op_small_conv_dgrad: form dgrad4<2> needs "
+               "Ci %% 4 == 0, Co == 2 and a din row stride that is a multiple of 4");
+    const SmallDgradForm f = form == 0 ? plan_small_dgrad((size_t)din_rs, M, H, W, Ci, Co)
+                                       : (SmallDgradForm)form;
+    OpCtx ctx(device);
+    DevBuf<float> d_o, d_w, d_i;
+    ctx.up(d_o, dout, (size_t)M * dout_rs);
+    ctx.up(d_w, w, (size_t)9 * Ci * Co);
+    ctx.up(d_i, din, (size_t)M * din_rs);
+    launch_small_dgrad(ctx.stream, f, d_o.p, (size_t)dout_rs, d_w.p, d_i.p, (size_t)din_rs, M, H,
+                       W, Ci, Co, accumulate != 0);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(din, d_i, (size_t)M * din_rs);
+    *form_ran = (int32_t)f;
+  });
+}
+
+int mv_op_small_conv_wgrad(int device, int32_t form, const float* in, const float* dout,
+                           int32_t R, int32_t H, int32_t W, int32_t Ci, int32_t Co, float* dw,
+                           int32_t* info) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(in && dout && dw && info, "mv_op_small_conv_wgrad: NULL argument");
+    MV_REQUIRE(R >= 1 && H >= 1 && W >= 1 && Ci >= 1 && Co >= 1,
+               "mv_op_small_conv_wgrad: bad shape");
+    MV_REQUIRE(form >= 0 && form <= 3, "mv_op_small_conv_wgrad: form %d (0 = the plan's, 1 "
+               "small_wgrad<false>, 2 small_wgrad<true>, 3 h2g)", (int)form);
+    const SmallWgradPlan p = plan_small_wgrad(R, H, W, Ci, Co);
+    require_small_wgrad_shape(p);
+    MV_REQUIRE(p.P <= 512 || p.lds2 <= 48 * 1024, "small wgrad: LDS of the hidden2grid form");
+    MV_REQUIRE((form != 1 && form != 2) || p.P <= 512, "mv_op_small_conv_wgrad: form "
+               "small_wgrad<%s> needs Ci*Co <= 512", form == 2 ? "true" : "false");
+    MV_REQUIRE(form != 3 || ((Co == 1 || Co == 2) && p.lds2 <= 48 * 1024),
+               "mv_op_small_conv_wgrad: form h2g needs Co 1 or 2 and its slab in 48 KB of LDS");
+    const SmallWgradForm f = form == 0 ? p.form : (SmallWgradForm)form;
+    OpCtx ctx(device);
+    DevBuf<float> d_i, d_o, d_w, partial, scratch;
+    ctx.up(d_i, in, (size_t)p.cells * Ci);
+    ctx.up(d_o, dout, (size_t)p.cells * Co);
+    d_w.alloc(p.ncols); partial.alloc((size_t)p.nblk * p.ncols); scratch.alloc(64 * p.ncols);
+    HIP_CHECK(hipMemsetAsync(d_w.p, kOpSentinel, p.ncols * sizeof(float), ctx.stream));
+    launch_small_wgrad(ctx.stream, p, f, d_i.p, d_o.p, d_w.p, R, H, W, Ci, Co, partial.p,
+                       scratch.p);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(dw, d_w, p.ncols);
+    info[0] = (int32_t)f; info[1] = (int32_t)p.nblk; info[2] = p.cpb;
+    info[3] = f == SmallWgradForm::H2g ? 1 : p.G;
+  });
+}
+
+int mv_op_colsum(int device, const float* x, int64_t rows, int64_t ncols, float* out,
+                 int32_t* info) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(x && out && info, "mv_op_colsum: NULL argument");
+    MV_REQUIRE(rows >= 1 && ncols >= 1, "mv_op_colsum: bad shape");
+    OpCtx ctx(device);
+    DevBuf<float> d_x, d_o, tmp;
+    ctx.up(d_x, x, (size_t)rows * ncols);
+    d_o.alloc((size_t)ncols); tmp.alloc((size_t)1056 * ncols);
+    HIP_CHECK(hipMemsetAsync(d_o.p, kOpSentinel, (size_t)ncols * sizeof(float), ctx.stream));
+    const ColsumPlan p = launch_colsum(ctx.stream, d_x.p, (size_t)rows, (size_t)ncols, d_o.p,
+                                       tmp.p);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(out, d_o, (size_t)ncols);
+    info[0] = (int32_t)p.nslab; info[1] = p.narrow ? 1 : 0;
+  });
+}
+
+int mv_op_long_sum(int device, const float* x, int64_t n, float scale, float* out,
+                   int32_t* chunked) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(x && out && chunked, "mv_op_long_sum: NULL argument");
+    MV_REQUIRE(n >= 1, "mv_op_long_sum: bad length");
+    OpCtx ctx(device);
+    DevBuf<float> d_x, d_o, partial;
+    ctx.up(d_x, x, (size_t)n);
+    d_o.alloc(1);
+    const size_t pn = cdiv((size_t)n, mv::kSumChunk);
+    partial.alloc(pn);
+    HIP_CHECK(hipMemsetAsync(d_o.p, kOpSentinel, sizeof(float), ctx.stream));
+    const bool c = launch_long_sum(ctx.stream, d_x.p, (size_t)n, d_o.p, scale, partial.p, pn);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(out, d_o, (size_t)1);
+    *chunked = c ? 1 : 0;
+  });
+}
+
+int mv_op_scene_conv_bwd(int device, const float* in, const float* y, const float* dy,
+                         const float* w, int32_t U, int32_t Hi, int32_t Wi, int32_t Ci,
+                         int32_t Co, int32_t k, int32_t act, const float* din_init,
+                         int32_t accumulate, float* dpre, float* din, float* dw, float* db,
+                         int32_t* info) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(in && y && dy && w && dpre && din && dw && db && info,
+               "mv_op_scene_conv_bwd: NULL argument");
+    MV_REQUIRE(U >= 1 && Hi >= 1 && Wi >= 1 && Ci >= 1 && Co >= 1 && k >= 1,
+               "mv_op_scene_conv_bwd: bad shape");
+    MV_REQUIRE(act >= 0 && act <= 2, "mv_op_scene_conv_bwd: activation %d", (int)act);
+    MV_REQUIRE(!accumulate || din_init, "mv_op_scene_conv_bwd: accumulate needs din_init");
+    OpCtx ctx(device);
+    const int Ho = (Hi + 1) / 2, Wo = (Wi + 1) / 2;      // SAME, stride 2
+    const size_t nin = (size_t)U * Hi * Wi * Ci, nout = (size_t)U * Ho * Wo * Co;
+    const SceneWgradPlan p = plan_scene_wgrad(U, Ho, Ci, Co, k);
+    DevBuf<float> d_in, d_y, d_dy, d_w, d_pre, d_din, d_dw, d_db, partial;
+    ctx.up(d_in, in, nin);
+    ctx.up(d_y, y, nout);
+    ctx.up(d_dy, dy, nout);
+    ctx.up(d_w, w, p.nw);
+    if (din_init) ctx.up(d_din, din_init, nin);
+    else {
+      d_din.alloc(nin);
+      HIP_CHECK(hipMemsetAsync(d_din.p, kOpSentinel, nin * sizeof(float), ctx.stream));
+    }
+    d_pre.alloc(nout); d_dw.alloc(p.nw); d_db.alloc((size_t)Co);
+    const size_t pn = std::max((size_t)p.nslab * p.nw, (size_t)1056 * Co);
+    partial.alloc(pn);
+    HIP_CHECK(hipMemsetAsync(d_pre.p, kOpSentinel, nout * sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(d_dw.p, kOpSentinel, p.nw * sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(d_db.p, kOpSentinel, (size_t)Co * sizeof(float), ctx.stream));
+    hipLaunchKernelGGL(mv::tanh_bwd_kernel, dim3(cdiv(nout, 256)), dim3(256), 0, ctx.stream,
+                       d_dy.p, d_y.p, d_pre.p, nout, (int)act);
+    launch_scene_dgrad(ctx.stream, d_pre.p, d_w.p, d_din.p, U, Hi, Wi, Ci, Ho, Wo, Co, k,
+                       accumulate != 0);
+    launch_scene_wgrad(ctx.stream, d_in.p, d_pre.p, d_dw.p, U, Hi, Wi, Ci, Ho, Wo, Co, k,
+                       partial.p, pn);
+    launch_colsum(ctx.stream, d_pre.p, (size_t)U * Ho * Wo, (size_t)Co, d_db.p, partial.p);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(dpre, d_pre, nout);
+    ctx.down(din, d_din, nin);
+    ctx.down(dw, d_dw, p.nw);
+    ctx.down(db, d_db, (size_t)Co);
+    info[0] = scene_same_pad(Ho, k, Hi); info[1] = scene_same_pad(Wo, k, Wi);
+    info[2] = p.nslab; info[3] = p.rps;
+  });
+}
+
+int mv_op_grid_emb_onehot_wgrad(int device, const float* dpre, const int32_t* labels, int32_t N,
+                                int32_t T, int32_t H, int32_t W, int32_t E, int32_t accumulate,
+                                float* dw) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(dpre && labels && dw, "mv_op_grid_emb_onehot_wgrad: NULL argument");
+    MV_REQUIRE(N >= 1 && T >= 1 && H >= 1 && W >= 1 && E >= 32 && E % 32 == 0,
+               "mv_op_grid_emb_onehot_wgrad: bad shape (E a multiple of 32)");
+    for (size_t i = 0; i < (size_t)N * T; ++i)
+      MV_REQUIRE(labels[i] >= 0 && labels[i] < H * W, "mv_op_grid_emb_onehot_wgrad: label %d "
+                 "is not a cell of the %d x %d grid", (int)labels[i], (int)H, (int)W);
+    OpCtx ctx(device);
+    DevBuf<float> d_p, d_w;
+    DevBuf<int32_t> d_l;
+    ctx.up(d_p, dpre, (size_t)T * N * H * W * E);
+    ctx.up(d_l, labels, (size_t)N * T);
+    ctx.up(d_w, dw, (size_t)9 * E);
+    launch_grid_emb_onehot_wgrad(ctx.stream, d_p.p, d_l.p, N, T, H, W, E, d_w.p,
+                                 accumulate != 0);
+    HIP_CHECK(hipGetLastError());
+    ctx.down(dw, d_w, (size_t)9 * E);
+  });
+}
+
+// kind: 0 ce, 1 ce_soft, 2 ce_len (hard labels, or soft when given), 3 huber, 4 huber_len,
+// 5 huber_masked (with count_positive_kernel in front and masked_mean_kernel behind)
+int mv_op_train_loss(int device, int32_t kind, const float* pred, const int32_t* labels,
+                     const float* soft, const float* target, const float* fg,
+                     const float* sample_w, const int32_t* pred_lens, int32_t T, int32_t N,
+                     int32_t K, float scale, float* loss, float* grad, float* loss_sum,
+                     int32_t* info) {
+  return guarded(nullptr, [&] {
+    MV_REQUIRE(kind >= 0 && kind <= 5, "mv_op_train_loss: kind %d (0 ce, 1 ce_soft, 2 ce_len, "
+               "3 huber, 4 huber_len, 5 huber_masked)", (int)kind);
+    MV_REQUIRE(pred && loss && grad && loss_sum && info, "mv_op_train_loss: NULL argument");
+    MV_REQUIRE(T >= 1 && N >= 1 && K >= 1, "mv_op_train_loss: bad shape");
+    const bool ce = kind <= 2, lens = kind == 2 || kind == 4;
+    MV_REQUIRE(!lens || pred_lens, "mv_op_train_loss: the kind needs pred_lens");
+    MV_REQUIRE(lens || !pred_lens, "mv_op_train_loss: the kind takes no pred_lens");
+    if (lens)
+      for (int n = 0; n < N; ++n)
+        MV_REQUIRE(pred_lens[n] >= 0 && pred_lens[n] <= T, "mv_op_train_loss: pred_lens[%d] = %d "
+                   "outside [0, %d]", n, (int)pred_lens[n], (int)T);
+    const size_t rows = (size_t)T * N;
+    const bool hard = kind == 0 || (kind == 2 && !soft);
+    if (ce) {
+      MV_REQUIRE(kind != 0 || !soft, "mv_op_train_loss: ce takes labels, not soft labels");
+      MV_REQUIRE(kind != 1 || soft, "mv_op_train_loss: ce_soft needs soft labels");
+      MV_REQUIRE(!hard || labels, "mv_op_train_loss: the kind needs labels");
+      MV_REQUIRE(!sample_w || kind != 2, "mv_op_train_loss: ce_len takes no sample weights");
+      if (hard)
+        for (size_t i = 0; i < rows; ++i)
+          MV_REQUIRE(labels[i] >= 0 && labels[i] < K, "mv_op_train_loss: label %d outside "
+                     "[0, %d)", (int)labels[i], (int)K);
+    } else {
+      MV_REQUIRE(target, "mv_op_train_loss: the kind needs a target");
+      MV_REQUIRE(kind != 5 || fg, "mv_op_train_loss: huber_masked needs the foreground map");
+      MV_REQUIRE(!sample_w, "mv_op_train_loss: the Huber kinds take no sample weights");
+    }
+    OpCtx ctx(device);
+    DevBuf<float> d_pred, d_soft, d_tgt, d_fg, d_sw, d_loss, d_grad, d_sum, d_tmp, partial;
+    DevBuf<int32_t> d_lab, d_len, d_cnt;
+    const size_t nel = rows * K * (ce ? 1 : 2), nloss = ce ? rows : nel;
+    ctx.up(d_pred, pred, nel);
+    if (hard) ctx.up(d_lab, labels, rows);
+    if (ce && soft) ctx.up(d_soft, soft, nel);
+    if (!ce) ctx.up(d_tgt, target, nel);
+    if (kind == 5) ctx.up(d_fg, fg, rows * K);
+    if (sample_w) ctx.up(d_sw, sample_w, (size_t)N);
+    if (lens) ctx.up(d_len, pred_lens, (size_t)N);
+    d_loss.alloc(nloss); d_grad.alloc(nel); d_sum.alloc(1); d_tmp.alloc(1); d_cnt.alloc(1);
+    const size_t pn = cdiv(nel, mv::kSumChunk);
+    partial.alloc(pn);
+    HIP_CHECK(hipMemsetAsync(d_loss.p, kOpSentinel, nloss * sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(d_grad.p, kOpSentinel, nel * sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(d_sum.p, kOpSentinel, sizeof(float), ctx.stream));
+    HIP_CHECK(hipMemsetAsync(d_cnt.p, 0, sizeof(int32_t), ctx.stream));
+    bool chunked = false;
+    if (ce) {
+      CeLossArgs a{};
+      a.logits = d_pred.p; a.labels = hard ? d_lab.p : nullptr;
+      a.soft = soft ? d_soft.p : nullptr; a.sample_w = sample_w ? d_sw.p : nullptr;
+      a.pred_lens = lens ? d_len.p : nullptr;
+      a.loss_row = d_loss.p; a.dlogits = d_grad.p; a.loss_out = d_sum.p;
+      a.T = T; a.N = N; a.K = K; a.scale = scale;
+      launch_ce_loss(ctx.stream, a);
+    } else {
+      HuberLossArgs a{};
+      a.pred = d_pred.p; a.target = d_tgt.p;
+      a.loss_elem = d_loss.p; a.dpred = d_grad.p; a.loss_out = d_sum.p;
+      a.T = T; a.N = N; a.KP = K * 2; a.scale = scale;
+      a.sum_tmp = d_tmp.p; a.partial = partial.p; a.partial_n = pn;
+      if (kind == 5) {
+        launch_count_positive(ctx.stream, d_fg.p, rows * K, d_cnt.p);
+        a.fg = d_fg.p; a.count = d_cnt.p;
+      } else if (lens) {
+        a.pred_lens = d_len.p;
+      }
+      chunked = launch_huber_loss(ctx.stream, a);
+    }
+    HIP_CHECK(hipGetLastError());
+    ctx.down(loss, d_loss, nloss);
+    ctx.down(grad, d_grad, nel);
+    ctx.down(loss_sum, d_sum, (size_t)1);
+    ctx.down(info, d_cnt, (size_t)1);
+    info[1] = chunked ? 1 : 0;
+  });
+}
+
 // Debug probe (not part of the public header): XCC id of every workgroup of a
 // 1-D launch of `nblocks` x 256 threads -- checks the "linear id % 8 -> XCD"
 // dispatch pattern the XCD-aware block maps rely on for speed.

@@ -214,21 +214,32 @@ void train_alloc(mv_engine* e) {
   t.losses.alloc(64);
 }
 
+// The helper launches of a training step on (stream, buffers, shape): the engine's run_*
+// wrappers below and the single-kernel doors (engine_ops.h mv_op_small_conv_dgrad / _wgrad,
+// mv_op_colsum, mv_op_long_sum, mv_op_scene_conv_bwd, mv_op_grid_emb_onehot_wgrad,
+// mv_op_train_loss) call the same code, so a door runs the engine's own choice of kernel, its
+// launch geometry and its folds.
+
 // out[0] = scale * sum(in[0 .. n)), fixed order: long inputs go through per-chunk workgroups
 // first (train_kernels.h chunk_sum_kernel), the partials through the one-workgroup kernel.
-void run_long_sum(mv_engine* e, TrainState& t, const float* in, size_t n, float* out,
-                  float scale) {
+// Returns whether the chunk stage ran.
+bool launch_long_sum(hipStream_t stream, const float* in, size_t n, float* out, float scale,
+                     float* partial, size_t partial_n) {
   if (n <= 4 * (size_t)mv::kSumChunk) {
-    hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, e->stream, in, n, out,
+    hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, stream, in, n, out,
                        scale, 0);
-    return;
+    return false;
   }
   const size_t nblk = cdiv(n, mv::kSumChunk);
-  MV_REQUIRE(nblk <= t.partial.n, "internal: long-sum partials");
-  hipLaunchKernelGGL(mv::chunk_sum_kernel, dim3(nblk), dim3(256), 0, e->stream, in, n,
-                     t.partial.p);
-  hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, e->stream, t.partial.p, nblk,
+  MV_REQUIRE(nblk <= partial_n, "internal: long-sum partials");
+  hipLaunchKernelGGL(mv::chunk_sum_kernel, dim3(nblk), dim3(256), 0, stream, in, n, partial);
+  hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, stream, partial, nblk,
                      out, scale, 0);
+  return true;
+}
+void run_long_sum(mv_engine* e, TrainState& t, const float* in, size_t n, float* out,
+                  float scale) {
+  launch_long_sum(e->stream, in, n, out, scale, t.partial.p, t.partial.n);
 }
 
 // deterministic column sum of X [rows, ncols] into out [ncols]: slabs of rows are summed in
@@ -236,107 +247,273 @@ void run_long_sum(mv_engine* e, TrainState& t, const float* in, size_t n, float*
 // the result does not depend on timing).  Round 3: the fold of up to 1 024 partial rows used
 // to be ONE serial loop per column in a single workgroup per 256 columns (240 us per bias
 // gradient, 2 ms per training step); now every pass is at most 32 dependent adds.
-void run_colsum(mv_engine* e, const float* x, size_t rows, size_t ncols, float* out,
-                float* tmp /* >= 1056*ncols */) {
-  size_t nslab = std::min<size_t>(1024, (rows + 63) / 64);
-  if (nslab < 1) nslab = 1;
-  const size_t rps = (rows + nslab - 1) / nslab;
-  nslab = (rows + rps - 1) / rps;
+struct ColsumPlan {
+  size_t nslab, rps;   // slabs of rps rows (the last one may be short)
+  bool narrow;         // colsum_narrow_kernel sums the slabs (never with one slab)
+};
+ColsumPlan plan_colsum(size_t rows, size_t ncols) {
+  ColsumPlan p;
+  p.nslab = std::min<size_t>(1024, (rows + 63) / 64);
+  if (p.nslab < 1) p.nslab = 1;
+  p.rps = (rows + p.nslab - 1) / p.nslab;
+  p.nslab = (rows + p.rps - 1) / p.rps;
+  p.narrow = p.nslab > 1 && ncols <= 128 && 256 % ncols == 0;
+  return p;
+}
+ColsumPlan launch_colsum(hipStream_t stream, const float* x, size_t rows, size_t ncols,
+                         float* out, float* tmp /* >= 1056*ncols */) {
+  const ColsumPlan p = plan_colsum(rows, ncols);
+  const size_t nslab = p.nslab, rps = p.rps;
   const unsigned gy = cdiv(ncols, 256);
   if (nslab == 1) {
-    hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, gy), dim3(256), 0, e->stream, x, out,
+    hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, gy), dim3(256), 0, stream, x, out,
                        rows, ncols, rows);
-    return;
+    return p;
   }
-  if (ncols <= 128 && 256 % ncols == 0)       // narrow: all 256 threads on 1 KB runs
+  if (p.narrow)                               // narrow: all 256 threads on 1 KB runs
     hipLaunchKernelGGL(mv::colsum_narrow_kernel, dim3((unsigned)nslab), dim3(256), 0,
-                       e->stream, x, tmp, rows, (int)ncols, rps);
+                       stream, x, tmp, rows, (int)ncols, rps);
   else
     hipLaunchKernelGGL(mv::colsum_kernel, dim3((unsigned)nslab, gy), dim3(256), 0,
-                       e->stream, x, tmp, rows, ncols, rps);
+                       stream, x, tmp, rows, ncols, rps);
   // fold the nslab partial rows: tmp rows [0, nslab) -> rows [1024, 1024 + ceil(nslab/32))
   const float* cur = tmp;
   size_t n = nslab;
   float* nxt = tmp + (size_t)1024 * ncols;
   while (n > 32) {
     const size_t m = (n + 31) / 32;
-    hipLaunchKernelGGL(mv::colsum_kernel, dim3((unsigned)m, gy), dim3(256), 0, e->stream, cur,
+    hipLaunchKernelGGL(mv::colsum_kernel, dim3((unsigned)m, gy), dim3(256), 0, stream, cur,
                        nxt, n, ncols, (size_t)32);
     cur = nxt; n = m;
     nxt = (cur == tmp) ? tmp + (size_t)1024 * ncols : tmp;   // m <= 32 rows: fits either end
   }
-  hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, gy), dim3(256), 0, e->stream, cur, out, n,
+  hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, gy), dim3(256), 0, stream, cur, out, n,
                      ncols, n);
+  return p;
+}
+void run_colsum(mv_engine* e, const float* x, size_t rows, size_t ncols, float* out,
+                float* tmp /* >= 1056*ncols */) {
+  launch_colsum(e->stream, x, rows, ncols, out, tmp);
 }
 
+// dgrad of a small 3x3 conv: the kernel form by shape (Scalar for every shape; Vec4Co1 /
+// Vec4Co2: conv3x3_small_dgrad4_kernel<1> / <2>, 16-byte accesses of din and W)
+enum class SmallDgradForm : int { Plan = 0, Scalar = 1, Vec4Co1 = 2, Vec4Co2 = 3 };
+bool small_dgrad_vec4_ok(size_t din_rs, int M, int H, int W, int Ci, int Co) {
+  const size_t total = (size_t)M * H * W * Ci;
+  return (Ci % 4 == 0) && (Co == 1 || Co == 2) && (din_rs % 4 == 0) &&
+         total / 4 < 0xffffffffull;
+}
+SmallDgradForm plan_small_dgrad(size_t din_rs, int M, int H, int W, int Ci, int Co) {
+  if (!small_dgrad_vec4_ok(din_rs, M, H, W, Ci, Co)) return SmallDgradForm::Scalar;
+  return Co == 1 ? SmallDgradForm::Vec4Co1 : SmallDgradForm::Vec4Co2;
+}
+void launch_small_dgrad(hipStream_t stream, SmallDgradForm form, const float* dout,
+                        size_t dout_rs, const float* w, float* din, size_t din_rs, int M,
+                        int H, int W, int Ci, int Co, bool accumulate) {
+  const size_t total = (size_t)M * H * W * Ci;
+  if (form == SmallDgradForm::Vec4Co1)
+    hipLaunchKernelGGL(mv::conv3x3_small_dgrad4_kernel<1>, dim3(cdiv(total / 4, 256)),
+                       dim3(256), 0, stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci,
+                       accumulate ? 1 : 0);
+  else if (form == SmallDgradForm::Vec4Co2)
+    hipLaunchKernelGGL(mv::conv3x3_small_dgrad4_kernel<2>, dim3(cdiv(total / 4, 256)),
+                       dim3(256), 0, stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci,
+                       accumulate ? 1 : 0);
+  else
+    hipLaunchKernelGGL(mv::conv3x3_small_dgrad_kernel, dim3(cdiv(total, 256)), dim3(256),
+                       0, stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci, Co,
+                       accumulate ? 1 : 0);
+}
 void run_small_dgrad(mv_engine* e, const float* dout, size_t dout_rs, const float* w,
                      float* din, size_t din_rs, int M, int H, int W, int Ci, int Co,
                      bool accumulate) {
   const size_t total = (size_t)M * H * W * Ci;
-  const bool vec4 = (Ci % 4 == 0) && (Co == 1 || Co == 2) && (din_rs % 4 == 0) &&
-                    total / 4 < 0xffffffffull;
+  const SmallDgradForm form = plan_small_dgrad(din_rs, M, H, W, Ci, Co);
   launch(e, "conv3x3_small_dgrad", 2.0 * total * 9 * Co, 4.0 * total * 2, [&] {
-    if (vec4 && Co == 1)
-      hipLaunchKernelGGL(mv::conv3x3_small_dgrad4_kernel<1>, dim3(cdiv(total / 4, 256)),
-                         dim3(256), 0, e->stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci,
-                         accumulate ? 1 : 0);
-    else if (vec4)
-      hipLaunchKernelGGL(mv::conv3x3_small_dgrad4_kernel<2>, dim3(cdiv(total / 4, 256)),
-                         dim3(256), 0, e->stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci,
-                         accumulate ? 1 : 0);
-    else
-      hipLaunchKernelGGL(mv::conv3x3_small_dgrad_kernel, dim3(cdiv(total, 256)), dim3(256),
-                         0, e->stream, dout, dout_rs, w, din, din_rs, M, H, W, Ci, Co,
-                         accumulate ? 1 : 0);
+    launch_small_dgrad(e->stream, form, dout, dout_rs, w, din, din_rs, M, H, W, Ci, Co,
+                       accumulate);
   });
 }
 
-// dW [9][Ci][Co] of a small 3x3 conv over R images
+// dW [9][Ci][Co] of a small 3x3 conv over R images: per-block partial tiles, then a two-level
+// fold in a fixed order
+enum class SmallWgradForm : int { Plan = 0, WideOut = 1, WideIn = 2, H2g = 3 };
+struct SmallWgradPlan {
+  bool h2g_shape;        // hidden2grid: Ci > Co, Ci <= 512, Co 1 or 2 (may exceed Ci*Co 512)
+  long long cells, nblk;
+  int P, G, cpb, threads;
+  size_t ncols, lds, lds2;
+  SmallWgradForm form;   // what the engine launches
+};
+SmallWgradPlan plan_small_wgrad(int R, int H, int W, int Ci, int Co) {
+  SmallWgradPlan p;
+  p.h2g_shape = Ci > Co && Ci <= 512 && (Co == 1 || Co == 2);   // hidden2grid
+  p.cells = (long long)R * H * W;
+  p.P = Ci * Co;
+  p.G = std::max(1, 256 / p.P);                 // cell groups per workgroup
+  p.nblk = std::min<long long>(4096, (p.cells + 63) / 64);
+  p.cpb = (int)((p.cells + p.nblk - 1) / p.nblk);
+  p.nblk = (p.cells + p.cpb - 1) / p.cpb;
+  p.threads = ((p.P * p.G + 63) / 64) * 64;
+  p.ncols = (size_t)9 * p.P;
+  p.lds = p.G > 1 ? (size_t)p.G * 9 * p.P * sizeof(float) : 0;
+  p.lds2 = ((size_t)(p.cpb + 2 * W + 2) * Co + p.cpb) * sizeof(float);
+  p.form = (p.h2g_shape && p.G == 1 && p.lds2 <= 48 * 1024) ? SmallWgradForm::H2g
+           : Ci > Co ? SmallWgradForm::WideIn : SmallWgradForm::WideOut;
+  return p;
+}
+void require_small_wgrad_shape(const SmallWgradPlan& p) {
+  MV_REQUIRE(p.P <= 512 || p.h2g_shape, "small wgrad: Ci*Co %d > 512", p.P);
+}
+void launch_small_wgrad(hipStream_t stream, const SmallWgradPlan& p, SmallWgradForm form,
+                        const float* in, const float* dout, float* dw, int R, int H, int W,
+                        int Ci, int Co, float* partial, float* scratch) {
+  const unsigned nblk = (unsigned)p.nblk;
+  const int cpb = p.cpb, G = p.G;
+  if (form == SmallWgradForm::H2g) {
+    if (Co == 1)
+      hipLaunchKernelGGL(mv::h2g_wgrad_kernel<1>, dim3(nblk), dim3(256), p.lds2, stream, in,
+                         dout, partial, R, H, W, Ci, cpb);
+    else
+      hipLaunchKernelGGL(mv::h2g_wgrad_kernel<2>, dim3(nblk), dim3(256), p.lds2, stream, in,
+                         dout, partial, R, H, W, Ci, cpb);
+  } else if (form == SmallWgradForm::WideIn)
+    hipLaunchKernelGGL(mv::conv3x3_small_wgrad_kernel<true>, dim3(nblk), dim3(p.threads),
+                       p.lds, stream, in, dout, partial, R, H, W, Ci, Co, cpb, G);
+  else
+    hipLaunchKernelGGL(mv::conv3x3_small_wgrad_kernel<false>, dim3(nblk), dim3(p.threads),
+                       p.lds, stream, in, dout, partial, R, H, W, Ci, Co, cpb, G);
+  // two-level fold of the nblk partial rows (fixed order)
+  const size_t ncols = p.ncols;
+  const size_t rps = ((size_t)p.nblk + 63) / 64, nslab = ((size_t)p.nblk + rps - 1) / rps;
+  hipLaunchKernelGGL(mv::colsum_kernel, dim3((unsigned)nslab, cdiv(ncols, 256)), dim3(256),
+                     0, stream, partial, scratch, (size_t)p.nblk, ncols, rps);
+  hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(ncols, 256)), dim3(256), 0, stream,
+                     scratch, dw, nslab, ncols, nslab);
+}
 void run_small_wgrad(mv_engine* e, const float* in, const float* dout, float* dw, int R,
                      int H, int W, int Ci, int Co) {
   TrainState& t = TS(e);
-  const bool h2g_form = Ci > Co && Ci <= 512 && (Co == 1 || Co == 2);   // hidden2grid
-  MV_REQUIRE(Ci * Co <= 512 || h2g_form, "small wgrad: Ci*Co %d > 512", Ci * Co);
-  const long long cells = (long long)R * H * W;
-  const int P = Ci * Co;
-  const int G = std::max(1, 256 / P);                 // cell groups per workgroup
-  long long nblk = std::min<long long>(4096, (cells + 63) / 64);
-  const int cpb = (int)((cells + nblk - 1) / nblk);
-  nblk = (cells + cpb - 1) / cpb;
-  const int threads = ((P * G + 63) / 64) * 64;
-  const size_t ncols = (size_t)9 * P;
-  const size_t lds = G > 1 ? (size_t)G * 9 * P * sizeof(float) : 0;
-  MV_REQUIRE((size_t)nblk * ncols <= t.partial.n && 64 * ncols <= t.scratch.n,
+  const SmallWgradPlan p = plan_small_wgrad(R, H, W, Ci, Co);
+  require_small_wgrad_shape(p);
+  MV_REQUIRE((size_t)p.nblk * p.ncols <= t.partial.n && 64 * p.ncols <= t.scratch.n,
              "internal: small wgrad partial buffer");
   // algorithmic bytes: the input and the output gradient are each read ONCE (the nine taps
   // re-read the same cells from LDS / L1), plus the per-block partial tiles written and
   // folded.  (Rounds 1-3 counted the input nine times: a "roofline fraction" of 1.05.)
-  launch(e, "conv3x3_small_wgrad", 2.0 * cells * 9 * Ci * Co,
-         4.0 * cells * ((double)Ci + Co) + 8.0 * (double)nblk * ncols, [&] {
-    const size_t lds2 = ((size_t)(cpb + 2 * W + 2) * Co + cpb) * sizeof(float);
-    MV_REQUIRE(Ci * Co <= 512 || lds2 <= 48 * 1024, "small wgrad: LDS of the hidden2grid form");
-    if (h2g_form && G == 1 && lds2 <= 48 * 1024) {
-      if (Co == 1)
-        hipLaunchKernelGGL(mv::h2g_wgrad_kernel<1>, dim3((unsigned)nblk), dim3(256), lds2,
-                           e->stream, in, dout, t.partial.p, R, H, W, Ci, cpb);
-      else
-        hipLaunchKernelGGL(mv::h2g_wgrad_kernel<2>, dim3((unsigned)nblk), dim3(256), lds2,
-                           e->stream, in, dout, t.partial.p, R, H, W, Ci, cpb);
-    } else if (Ci > Co)
-      hipLaunchKernelGGL(mv::conv3x3_small_wgrad_kernel<true>, dim3((unsigned)nblk),
-                         dim3(threads), lds, e->stream, in, dout, t.partial.p, R, H, W, Ci,
-                         Co, cpb, G);
-    else
-      hipLaunchKernelGGL(mv::conv3x3_small_wgrad_kernel<false>, dim3((unsigned)nblk),
-                         dim3(threads), lds, e->stream, in, dout, t.partial.p, R, H, W, Ci,
-                         Co, cpb, G);
-    // two-level fold of the nblk partial rows (fixed order)
-    const size_t rps = ((size_t)nblk + 63) / 64, nslab = ((size_t)nblk + rps - 1) / rps;
-    hipLaunchKernelGGL(mv::colsum_kernel, dim3((unsigned)nslab, cdiv(ncols, 256)), dim3(256),
-                       0, e->stream, t.partial.p, t.scratch.p, (size_t)nblk, ncols, rps);
-    hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(ncols, 256)), dim3(256), 0,
-                       e->stream, t.scratch.p, dw, nslab, ncols, nslab);
+  launch(e, "conv3x3_small_wgrad", 2.0 * p.cells * 9 * Ci * Co,
+         4.0 * p.cells * ((double)Ci + Co) + 8.0 * (double)p.nblk * p.ncols, [&] {
+    MV_REQUIRE(Ci * Co <= 512 || p.lds2 <= 48 * 1024, "small wgrad: LDS of the hidden2grid form");
+    launch_small_wgrad(e->stream, p, p.form, in, dout, dw, R, H, W, Ci, Co, t.partial.p,
+                       t.scratch.p);
   });
+}
+
+// ---- the stride-2 scene stack's backward, one level
+// SAME padding before the first row / column of a stride-2 k x k conv from `in` to `out` cells
+int scene_same_pad(int out, int k, int in) { return std::max((out - 1) * 2 + k - in, 0) / 2; }
+void launch_scene_dgrad(hipStream_t stream, const float* dpre, const float* w, float* din,
+                        int U, int Hi, int Wi, int Ci, int Ho, int Wo, int Co, int k,
+                        bool accumulate) {
+  const size_t nin = (size_t)U * Hi * Wi * Ci;
+  hipLaunchKernelGGL(mv::conv_s2_dgrad_kernel, dim3(cdiv(nin, 256)), dim3(256), 0, stream,
+                     dpre, w, din, U, Hi, Wi, Ci, Ho, Wo, Co, k, scene_same_pad(Ho, k, Hi),
+                     scene_same_pad(Wo, k, Wi), accumulate ? 1 : 0);
+}
+// output rows (u, oy) in <= 64 slabs, partials folded in slab order
+struct SceneWgradPlan { int rows, rps, nslab; size_t nw; };
+SceneWgradPlan plan_scene_wgrad(int U, int Ho, int Ci, int Co, int k) {
+  SceneWgradPlan p;
+  p.rows = U * Ho; p.rps = (p.rows + 63) / 64; p.nslab = (p.rows + p.rps - 1) / p.rps;
+  p.nw = (size_t)k * k * Ci * Co;
+  return p;
+}
+SceneWgradPlan launch_scene_wgrad(hipStream_t stream, const float* in, const float* dpre,
+                                  float* dw, int U, int Hi, int Wi, int Ci, int Ho, int Wo,
+                                  int Co, int k, float* partial, size_t partial_n) {
+  const SceneWgradPlan p = plan_scene_wgrad(U, Ho, Ci, Co, k);
+  MV_REQUIRE((size_t)p.nslab * p.nw <= partial_n, "internal: scene wgrad partial buffer");
+  hipLaunchKernelGGL(mv::conv_s2_wgrad_kernel, dim3(cdiv(p.nw, 256), p.nslab), dim3(256), 0,
+                     stream, in, dpre, partial, U, Hi, Wi, Ci, Ho, Wo, Co, k,
+                     scene_same_pad(Ho, k, Hi), scene_same_pad(Wo, k, Wi), p.rps);
+  hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(p.nw, 256)), dim3(256), 0, stream,
+                     partial, dw, (size_t)p.nslab, p.nw, (size_t)p.nslab);
+  return p;
+}
+
+// dW of the class encoder's grid_emb from the 9 cells around each hot cell (kernels_misc.h)
+void launch_grid_emb_onehot_wgrad(hipStream_t stream, const float* dpre, const int32_t* labels,
+                                  int N, int T, int H, int W, int E, float* dw,
+                                  bool accumulate) {
+  hipLaunchKernelGGL(mv::grid_emb_onehot_wgrad_kernel, dim3(9, E / 32), dim3(256), 0, stream,
+                     dpre, labels, N, T, H, W, E, dw, accumulate ? 1 : 0);
+}
+
+// ---- the losses of one scale
+// foreground count of --mask_grid_regression
+void launch_count_positive(hipStream_t stream, const float* in, size_t n, int32_t* count) {
+  HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int32_t), stream));
+  hipLaunchKernelGGL(mv::count_positive_kernel, dim3(256), dim3(256), 0, stream, in, n, count);
+}
+// cross entropy of the time-major logits [T, N, K]: pred_lens -> the length-aware kernel (hard
+// labels [N][T], or soft [T*N, K] when given); else soft -> ce_soft_loss_kernel; else
+// ce_loss_kernel.  sample_w [N]: the rows scaled afterwards.  loss_out = scale * sum of the rows.
+struct CeLossArgs {
+  const float* logits; const int32_t* labels; const float* soft; const float* sample_w;
+  const int32_t* pred_lens;
+  float* loss_row; float* dlogits; float* loss_out;
+  int T, N, K; float scale;
+};
+void launch_ce_loss(hipStream_t stream, const CeLossArgs& a) {
+  const int T = a.T, N = a.N, K = a.K;
+  if (a.pred_lens)
+    hipLaunchKernelGGL(mv::ce_loss_len_kernel, dim3(T * N), dim3(64), 0, stream, a.logits,
+                       a.labels, a.soft, a.loss_row, a.dlogits, T, N, K, a.scale, a.pred_lens);
+  else if (a.soft)
+    hipLaunchKernelGGL(mv::ce_soft_loss_kernel, dim3(T * N), dim3(64), 0, stream, a.logits,
+                       a.soft, a.loss_row, a.dlogits, K, a.scale);
+  else
+    hipLaunchKernelGGL(mv::ce_loss_kernel, dim3(T * N), dim3(64), 0, stream, a.logits,
+                       a.labels, a.loss_row, a.dlogits, T, N, K, a.scale);
+  if (a.sample_w)
+    hipLaunchKernelGGL(mv::scale_rows_kernel, dim3(cdiv((size_t)T * N * K, 256)), dim3(256), 0,
+                       stream, a.loss_row, a.dlogits, a.sample_w, T * N, N, K);
+  hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, stream, a.loss_row,
+                     (size_t)T * N, a.loss_out, a.scale, 0);
+}
+// Huber of pred [T, N, KP] (time-major) against target [N, T, KP]: fg + count -> the masked
+// kernel (KP = 2 K; `scale` is the loss weight, the mean over 2 count by masked_mean_kernel);
+// else pred_lens -> the length-aware kernel; else huber_loss_kernel.  Returns whether the long
+// sum ran its chunk stage.
+struct HuberLossArgs {
+  const float* pred; const float* target; const float* fg; const int32_t* count;
+  const int32_t* pred_lens;
+  float* loss_elem; float* dpred; float* loss_out;
+  int T, N, KP; float scale;
+  float* sum_tmp;                      // masked: the un-normalised sum (one float)
+  float* partial; size_t partial_n;    // long-sum partials
+};
+bool launch_huber_loss(hipStream_t stream, const HuberLossArgs& a) {
+  const size_t nel = (size_t)a.T * a.N * a.KP;
+  if (a.fg) {
+    hipLaunchKernelGGL(mv::huber_masked_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0, stream,
+                       a.pred, a.target, a.fg, a.count, a.loss_elem, a.dpred, a.T, a.N,
+                       a.KP / 2, a.scale);
+    const bool chunked = launch_long_sum(stream, a.loss_elem, nel, a.sum_tmp, 1.0f, a.partial,
+                                         a.partial_n);
+    hipLaunchKernelGGL(mv::masked_mean_kernel, dim3(1), dim3(64), 0, stream, a.sum_tmp, a.count,
+                       a.loss_out, a.scale);
+    return chunked;
+  }
+  if (a.pred_lens)
+    hipLaunchKernelGGL(mv::huber_loss_len_kernel, dim3(cdiv(nel, 256)), dim3(256), 0, stream,
+                       a.pred, a.target, a.loss_elem, a.dpred, a.T, a.N, a.KP, a.scale,
+                       a.pred_lens);
+  else
+    hipLaunchKernelGGL(mv::huber_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0, stream,
+                       a.pred, a.target, a.loss_elem, a.dpred, a.T, a.N, a.KP, a.scale);
+  return launch_long_sum(stream, a.loss_elem, nel, a.loss_out, a.scale, a.partial, a.partial_n);
 }
 
 void run_pack(mv_engine* e, TrainChain& ch) {
@@ -612,11 +789,8 @@ void train_prepare_targets(mv_engine* e) {
       hipLaunchKernelGGL(mv::gt_class_maps_kernel, dim3(cdiv((size_t)Tp * NK, 256)), dim3(256),
                          0, e->stream, R.pred_labels.p, R.gt_cls.p, Tp, N, S.H, S.W, ks, sk);
     }
-    if (t.tc.mask_grid_regression) {
-      HIP_CHECK(hipMemsetAsync(R.fg_count.p, 0, sizeof(int32_t), e->stream));
-      hipLaunchKernelGGL(mv::count_positive_kernel, dim3(256), dim3(256), 0, e->stream,
-                         R.gt_cls.p, (size_t)Tp * NK, R.fg_count.p);
-    }
+    if (t.tc.mask_grid_regression)
+      launch_count_positive(e->stream, R.gt_cls.p, (size_t)Tp * NK, R.fg_count.p);
     if (t.tc.reg_teacher_forcing) {       // [N][Tp][K][2] -> time-major
       const size_t tot = (size_t)N * Tp * S.K * 2;
       hipLaunchKernelGGL(mv::transpose_nt_kernel, dim3(cdiv(tot, 256)), dim3(256), 0,
@@ -872,56 +1046,40 @@ void train_losses(mv_engine* e) {
     const size_t Mv = rag ? (size_t)e->tl.M : (size_t)N * Tp;
     const float cs = t.tc.grid_loss_weight / (float)Mv;
     launch(e, "ce_loss", 0, 8.0 * Tp * NK, [&] {
-      if (rag)
-        hipLaunchKernelGGL(mv::ce_loss_len_kernel, dim3(Tp * N), dim3(64), 0, e->stream,
-                           R.logits.p, R.pred_labels.p,
-                           t.tc.use_soft_grid_class ? R.gt_cls.p : (const float*)nullptr,
-                           R.loss_row.p, R.dlogits.p, Tp, N, S.K, cs, e->tl.d_pred());
-      else if (t.mix_on) {
+      CeLossArgs a{};
+      a.logits = R.logits.p; a.labels = R.pred_labels.p;
+      a.loss_row = R.loss_row.p; a.dlogits = R.dlogits.p; a.loss_out = t.losses.p + li;
+      a.T = Tp; a.N = N; a.K = S.K; a.scale = cs;
+      if (rag) {
+        a.soft = t.tc.use_soft_grid_class ? R.gt_cls.p : (const float*)nullptr;
+        a.pred_lens = e->tl.d_pred();
+      } else if (t.mix_on) {
         // mixed-up targets w * one_hot(label) + one_hot(extra view's label) * (1 - w)
         // (SimAug/code/pred_models.py:1371-1390), optionally weighted per sample (:1391-1398)
         hipLaunchKernelGGL(mv::twohot_map_kernel, dim3(cdiv((size_t)Tp * NK, 256)), dim3(256), 0,
                            e->stream, R.pred_labels.p, R.pred_labels2.p, Tp, 1, t.mix_w,
                            R.mix_cls.p, Tp, N, S.K);
-        hipLaunchKernelGGL(mv::ce_soft_loss_kernel, dim3(Tp * N), dim3(64), 0, e->stream,
-                           R.logits.p, R.mix_cls.p, R.loss_row.p, R.dlogits.p, S.K, cs);
-        if (t.mix_sw)
-          hipLaunchKernelGGL(mv::scale_rows_kernel, dim3(cdiv((size_t)Tp * NK, 256)), dim3(256),
-                             0, e->stream, R.loss_row.p, R.dlogits.p, t.sample_w.p, Tp * N, N,
-                             S.K);
-      } else if (t.tc.use_soft_grid_class)
-        hipLaunchKernelGGL(mv::ce_soft_loss_kernel, dim3(Tp * N), dim3(64), 0, e->stream,
-                           R.logits.p, R.gt_cls.p, R.loss_row.p, R.dlogits.p, S.K, cs);
-      else
-        hipLaunchKernelGGL(mv::ce_loss_kernel, dim3(Tp * N), dim3(64), 0, e->stream,
-                           R.logits.p, R.pred_labels.p, R.loss_row.p, R.dlogits.p, Tp, N,
-                           S.K, cs);
-      hipLaunchKernelGGL(mv::reduce_sum_kernel, dim3(1), dim3(256), 0, e->stream,
-                         R.loss_row.p, (size_t)Tp * N, t.losses.p + li, cs, 0);
+        a.soft = R.mix_cls.p;
+        if (t.mix_sw) a.sample_w = t.sample_w.p;
+      } else if (t.tc.use_soft_grid_class) {
+        a.soft = R.gt_cls.p;
+      }
+      launch_ce_loss(e->stream, a);
     });
     const size_t nel = (size_t)Tp * NK * 2;
     const float rs = t.tc.grid_reg_loss_weight / (float)(Mv * S.K * 2);
     launch(e, "huber_loss", 0, 16.0 * nel, [&] {
+      HuberLossArgs a{};
+      a.pred = R.regio.p + NK * 2; a.target = R.pred_reg.p;
+      a.loss_elem = R.loss_elem.p; a.dpred = R.dreg.p; a.loss_out = t.losses.p + li + 1;
+      a.T = Tp; a.N = N; a.KP = S.K * 2; a.scale = rs;
+      a.sum_tmp = t.scratch.p; a.partial = t.partial.p; a.partial_n = t.partial.n;
       if (t.tc.mask_grid_regression) {
-        hipLaunchKernelGGL(mv::huber_masked_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
-                           e->stream, R.regio.p + NK * 2, R.pred_reg.p, R.gt_cls.p,
-                           R.fg_count.p, R.loss_elem.p, R.dreg.p, Tp, N, S.K,
-                           t.tc.grid_reg_loss_weight);
-        run_long_sum(e, t, R.loss_elem.p, nel, t.scratch.p, 1.0f);
-        hipLaunchKernelGGL(mv::masked_mean_kernel, dim3(1), dim3(64), 0, e->stream,
-                           t.scratch.p, R.fg_count.p, t.losses.p + li + 1,
-                           t.tc.grid_reg_loss_weight);
+        a.fg = R.gt_cls.p; a.count = R.fg_count.p; a.scale = t.tc.grid_reg_loss_weight;
       } else if (rag) {
-        hipLaunchKernelGGL(mv::huber_loss_len_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
-                           e->stream, R.regio.p + NK * 2, R.pred_reg.p, R.loss_elem.p,
-                           R.dreg.p, Tp, N, S.K * 2, rs, e->tl.d_pred());
-        run_long_sum(e, t, R.loss_elem.p, nel, t.losses.p + li + 1, rs);
-      } else {
-        hipLaunchKernelGGL(mv::huber_loss_kernel, dim3(cdiv(nel, 256)), dim3(256), 0,
-                           e->stream, R.regio.p + NK * 2, R.pred_reg.p, R.loss_elem.p,
-                           R.dreg.p, Tp, N, S.K * 2, rs);
-        run_long_sum(e, t, R.loss_elem.p, nel, t.losses.p + li + 1, rs);
+        a.pred_lens = e->tl.d_pred();
       }
+      launch_huber_loss(e->stream, a);
     });
     li += 2;
   }
@@ -1633,9 +1791,8 @@ void train_backward(mv_engine* e) {
       });
       const bool first = !enc_emb_done;
       launch(e, "grid_emb_onehot_wgrad", 9.0 * To * N * E2, 4.0 * 9 * To * N * E2, [&] {
-        hipLaunchKernelGGL(mv::grid_emb_onehot_wgrad_kernel, dim3(9, E2 / 32), dim3(256), 0,
-                           e->stream, dx, S.labels.p, N, To, S.H, S.W, E2,
-                           grad_of(e, e->enc_emb_W), first ? 0 : 1);
+        launch_grid_emb_onehot_wgrad(e->stream, dx, S.labels.p, N, To, S.H, S.W, E2,
+                                     grad_of(e, e->enc_emb_W), !first);
       });
       if (first) {
         run_colsum(e, dx, (size_t)To * NK, E2, grad_of(e, e->enc_emb_b), t.partial.p);
@@ -1725,38 +1882,27 @@ void train_backward(mv_engine* e) {
     }
     if (i + 1 < L) {
       const int Ho2 = e->conv_h[i + 1], Wo2 = e->conv_w[i + 1];
-      const int ph = std::max((Ho2 - 1) * 2 + k - Ho, 0), pw = std::max((Wo2 - 1) * 2 + k - Wo, 0);
       launch(e, "scene_conv_dgrad", 2.0 * n * k * k * D / 4, 8.0 * n, [&] {
-        hipLaunchKernelGGL(mv::conv_s2_dgrad_kernel, dim3(cdiv(n, 256)), dim3(256), 0,
-                           e->stream, t.dpre_sc[i + 1].p, e->scene_W[i + 1]->dev.p,
-                           t.dys[i].p, U, Ho, Wo, D, Ho2, Wo2, D, k, ph / 2, pw / 2, 1);
+        launch_scene_dgrad(e->stream, t.dpre_sc[i + 1].p, e->scene_W[i + 1]->dev.p, t.dys[i].p,
+                           U, Ho, Wo, D, Ho2, Wo2, D, k, true);
       });
     }
     hipLaunchKernelGGL(mv::tanh_bwd_kernel, dim3(cdiv(n, 256)), dim3(256), 0, e->stream,
                        t.dys[i].p, e->scene_conv[i].p, t.dpre_sc[i].p, n, e->cfg.activation);
-    const int ph = std::max((Ho - 1) * 2 + k - Hi, 0), pw = std::max((Wo - 1) * 2 + k - Wi, 0);
     const size_t nw = (size_t)k * k * Ci * D;
     const float* in = i == 0 ? e->scene_feat.p : e->scene_conv[i - 1].p;
     if (i == 0 && t.want_dscene) {     // down to the input: d loss / d scene_feat
       const size_t nin = (size_t)U * Hi * Wi * Ci;
       t.dscene.alloc((size_t)c.batch_size * c.obs_len * Hi * Wi * Ci);
       launch(e, "scene_input_dgrad", 2.0 * nin * k * k * D / 4, 4.0 * (nin + n), [&] {
-        hipLaunchKernelGGL(mv::conv_s2_dgrad_kernel, dim3(cdiv(nin, 256)), dim3(256), 0,
-                           e->stream, t.dpre_sc[0].p, e->scene_W[0]->dev.p, t.dscene.p, U, Hi,
-                           Wi, Ci, Ho, Wo, D, k, ph / 2, pw / 2, 0);
+        launch_scene_dgrad(e->stream, t.dpre_sc[0].p, e->scene_W[0]->dev.p, t.dscene.p, U, Hi,
+                           Wi, Ci, Ho, Wo, D, k, false);
       });
       t.have_dscene = true;
     }
     launch(e, "scene_conv_wgrad", 2.0 * n * k * k * Ci, 4.0 * nw, [&] {
-      // output rows (u, oy) in <= 64 slabs, partials folded in slab order
-      const int rows = U * Ho, rps = (rows + 63) / 64, nslab = (rows + rps - 1) / rps;
-      MV_REQUIRE((size_t)nslab * nw <= t.partial.n, "internal: scene wgrad partial buffer");
-      hipLaunchKernelGGL(mv::conv_s2_wgrad_kernel, dim3(cdiv(nw, 256), nslab), dim3(256), 0,
-                         e->stream, in, t.dpre_sc[i].p, t.partial.p, U, Hi, Wi, Ci, Ho, Wo,
-                         D, k, ph / 2, pw / 2, rps);
-      hipLaunchKernelGGL(mv::colsum_kernel, dim3(1, cdiv(nw, 256)), dim3(256), 0, e->stream,
-                         t.partial.p, grad_of(e, e->scene_W[i]), (size_t)nslab, nw,
-                         (size_t)nslab);
+      launch_scene_wgrad(e->stream, in, t.dpre_sc[i].p, grad_of(e, e->scene_W[i]), U, Hi, Wi,
+                         Ci, Ho, Wo, D, k, t.partial.p, t.partial.n);
     });
     run_colsum(e, t.dpre_sc[i].p, (size_t)U * Ho * Wo, D, grad_of(e, e->scene_b[i]),
                t.partial.p);
